@@ -22,7 +22,9 @@ Two launch forms:
     mcpt_comm_init_rank); torch.distributed only provides the barrier and the max-over-ranks timing.
     WORLD_SIZE must equal --gpus.
 
-Also reported: the roofline of the dominant kernel (k_prep: fp64 VALU-bound light prep), the
+A plain run sets up, warms up, times the steps and prints its line; --dump-outputs DIR also writes the
+framebuffer the timed steps produced.  With --full, also reported: the roofline of the dominant kernel
+(k_prep: fp64 VALU-bound light prep) from an untimed statistics replay of the steps, the
 CPU baseline (the C oracle on a bounded stratified pixel subset, rank 0, N=1 only) and the
 relative L2 of the GPU frame against that CPU render on the same pixels and samples.
 """
@@ -111,6 +113,24 @@ def max_px_rel(g, c):
     d = np.linalg.norm((g - c).reshape(-1, 3), axis=1)
     n = np.linalg.norm(c.reshape(-1, 3), axis=1)
     return float(np.max(np.where(n > 0, d / np.maximum(n, 1e-300), np.where(d > 0, np.inf, 0.0))))
+
+
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(d, fb, seed):
+    """--dump-outputs: DIR/framebuffer.npy, the (H, W, 3) fp64 framebuffer the last timed step returned.  A
+    frame over DUMP_MAX_BYTES is written as a fixed sample of its pixels (drawn from the seed, sorted):
+    (n, 3) values, beside framebuffer_pixels.npy, their flat y*W+x indices as float64."""
+    os.makedirs(d, exist_ok=True)
+    fb = np.ascontiguousarray(fb, dtype=np.float64)
+    H, W, _ = fb.shape
+    n = DUMP_MAX_BYTES // (4 * 8)  # 3 values + 1 index per sampled pixel
+    if fb.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(seed).choice(H * W, size=n, replace=False))
+        np.save(os.path.join(d, "framebuffer_pixels.npy"), idx.astype(np.float64))
+        fb = fb.reshape(-1, 3)[idx]
+    np.save(os.path.join(d, "framebuffer.npy"), fb)
 
 
 def host_cpu_model():
@@ -227,9 +247,16 @@ def main():
                     help="CPU baseline budget: the full-spp subset runs if it fits, else fewer spp, extrapolated")
     ap.add_argument("--cpu-single-seconds", type=float, default=20.0,
                     help="budget of the single-thread CPU baseline leg (spp reduced to fit; rate per sample)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline and L2 check")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the untimed statistics replay with the "
+                         "rooflines it feeds, and (1 GPU) the CPU baseline with the L2 check against it.  Without it a "
+                         "run sets up, warms up, times the steps and prints its line (those fields null)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last of them returned -- the fp64 framebuffer holding "
+                         "the samples of all timed steps -- as DIR/framebuffer.npy (rank 0)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and L2 check")
     ap.add_argument("--no-replay", action="store_true",
-                    help="skip the untimed statistics replay (PMC passes: the profile then holds only the warmup and "
+                    help="with --full: skip the untimed statistics replay (PMC passes: the profile then holds only the warmup and "
                          "timed steps' kernel instances; the line has no traversal roofline, whose events it counts)")
     ap.add_argument("--fresh-pdf", action="store_true",
                     help="MIS with the node's own light pdf (MCPT_RENDER_FRESH_PDF) instead of the reference's stale one")
@@ -247,6 +274,8 @@ def main():
                          "NCCL-API library (tests/collshim/libmcpt_collshim.so, host shared memory) instead of RCCL, ranks "
                          "share GPUs round-robin and torch.distributed uses gloo")
     args = ap.parse_args()
+    if not args.full:  # a plain run: nothing beyond the warmup and the timed steps
+        args.no_cpu = args.no_replay = True
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -527,6 +556,8 @@ def main():
         cpu["gpu_over_host_threads"] = round(value / cpu["multi_thread_value"], 1)
     if args.out:
         mcpt.write_bmp(args.out, mcpt.tone_map(fb.cpu().numpy()))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, fb.cpu().numpy(), args.seed)
     line = {
         "metric": SCENES[args.scene][0], "value": round(value, 4), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True,

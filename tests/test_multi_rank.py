@@ -256,7 +256,7 @@ def test_bench_two_ranks_under_torchrun(tmp_path):
     out = tmp_path / "bench.log"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1",
-           "--warmup", "1", "--spp-per-step", "8", "--no-cpu", "--collective-lib", SHIM]
+           "--warmup", "1", "--spp-per-step", "8", "--full", "--no-cpu", "--collective-lib", SHIM]
     with open(out, "w") as f:
         rc = subprocess.run(cmd, stdout=f, stderr=subprocess.STDOUT, timeout=300,
                             env=dict(os.environ, MCPT_COLLSHIM_TIMEOUT="90")).returncode
@@ -277,7 +277,7 @@ def test_bench_plain_launch_uses_n_gpus(tmp_path):
     collective shim (--collective-lib); the line must say n_gpus 2 and count both shards' samples."""
     out = tmp_path / "bench_plain.log"
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-           "--spp-per-step", "8", "--no-cpu", "--collective-lib", SHIM]
+           "--spp-per-step", "8", "--full", "--no-cpu", "--collective-lib", SHIM]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["MCPT_COLLSHIM_TIMEOUT"] = "90"
     with open(out, "w") as f:

@@ -9,7 +9,7 @@ VARIANTS=${VARIANTS:-A B}
 for r in $(seq "$ROUNDS"); do
     for v in $VARIANTS; do
         err=$(mktemp)
-        out=$(MCPT_LIB_PATH=ab/lib$v.so timeout -k 10 200 python bench.py --no-cpu "$@" 2>"$err" | grep '^{') || exit 1
+        out=$(MCPT_LIB_PATH=ab/lib$v.so timeout -k 10 200 python bench.py --full --no-cpu "$@" 2>"$err" | grep '^{') || exit 1
         # the exact pick's listed nodes over the timed steps, from the rank-0 totals log line
         exact=$(grep -o '"prep_exact_nodes": [0-9]*' "$err" | tail -1 | grep -o '[0-9]*$')
         rm -f "$err"

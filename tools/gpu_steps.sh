@@ -4,7 +4,8 @@
 # going after an ordinary failure (e.g. a failing test, exit 1) so later measurements still run.
 #   tools/gpu_steps.sh "300:name:cmd ..." "600:name2:cmd2 ..."
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
-mkdir -p gpurun_out
+OUT=${OUT:-profile_out}  # logs go to $OUT/<name>.log
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 status=0
 for spec in "$@"; do
@@ -14,10 +15,10 @@ for spec in "$@"; do
     cmd=${rest#*:}
     echo "=== [$name] limit ${limit}s: $cmd"
     start=$(date +%s)
-    timeout -k 10 "$limit" bash -c "$cmd" > "gpurun_out/$name.log" 2>&1
+    timeout -k 10 "$limit" bash -c "$cmd" > "$OUT/$name.log" 2>&1
     rc=$?
     echo "=== [$name] exit $rc after $(( $(date +%s) - start ))s"
-    tail -n 25 "gpurun_out/$name.log"
+    tail -n 25 "$OUT/$name.log"
     if [ $rc -ne 0 ]; then status=$rc; fi
     case $rc in
         124|134|137|139) echo "=== stopping: fatal exit $rc"; exit $rc ;;
