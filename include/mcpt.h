@@ -23,7 +23,9 @@
 extern "C" {
 #endif
 
-#define MCPT_VERSION 20200 /* 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
+#define MCPT_VERSION 20300 /* 2.3.0: adaptive sampling (mcpt_adaptive_opts, mcpt_render_adaptive and its _device
+                               * form); no existing struct changes;
+                               * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
                                * an older header is refused by struct_size instead of having its smaller
@@ -249,6 +251,48 @@ int mcpt_render(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opt
  * such buffers are rejected with MCPT_E_INVALID. */
 int mcpt_render_device(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* opts,
                        double* dev_out_rgb, mcpt_stats* stats);
+
+/* Adaptive sampling (no counterpart in the reference, which gives every pixel the same spp, main.cpp:567):
+ * the frame is rendered in passes, each active pixel's noise is estimated after every pass, and pixels at or
+ * below the threshold stop being sampled.  Sample k of a pixel draws the counter-RNG numbers of a plain
+ * render's sample k, so the result can be reproduced from plain renders.
+ *   passes   pass 0 renders global sample indices [0, min_spp) of every pixel, each later pass the next
+ *            pass_spp indices of the active pixels only; the last pass is cut at max_spp.  A pass [a, b) is
+ *            split at h = a + (b - a) / 2 (integer division): samples [a, h) are summed into A, samples
+ *            [h, b) into B (raw fp64 sums).
+ *   noise    after a pass, for each pixel active in it, with n its sample count: I = (A + B) / n,
+ *            Ah = 2 A / n, num = sum_c |I_c - Ah_c|, e = num / sqrt(sum_c I_c) if num > 0, else 0 (Dammertz
+ *            et al. 2010, "A Hierarchical Automatic Stopping Condition for Monte Carlo Global Illumination",
+ *            with the half buffer taken from the first half of each pass).
+ *   active   U = active and e > threshold; next active = active and dilate(U, radius), the dilation over
+ *            the (2 radius + 1)^2 square clipped at the frame's border.  A pixel that leaves never returns.
+ *            The passes end when no pixel is active or the count reaches max_spp.
+ * Single device only: a device list or a communicator is refused. */
+typedef struct {
+    uint32_t struct_size; /* sizeof(mcpt_adaptive_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
+    int32_t min_spp;      /* samples of pass 0: even, >= 2 */
+    int32_t pass_spp;     /* samples of each later pass: even, >= 2 */
+    int32_t max_spp;      /* the cap: >= min_spp */
+    double threshold;     /* tau >= 0: a pixel with e <= tau has converged */
+    int32_t radius;       /* 0..4: an unconverged pixel keeps its neighbours within this distance active */
+} mcpt_adaptive_opts;
+/* zero-fills *opts and sets struct_size, min_spp = 16, pass_spp = 16, max_spp = 1024, threshold = 0.05,
+ * radius = 1 (a pixel whose first samples are all black has e = 0; its neighbours keep it sampled) */
+void mcpt_adaptive_opts_init(mcpt_adaptive_opts* opts);
+/* Renders adaptively and ADDS (A + B) / count per pixel into out_rgb (as mcpt_render adds its weighted sum);
+ * count (int32 per pixel: samples taken) and noise (double per pixel: the last e computed for it) are
+ * overwritten; either may be NULL.  `base` supplies mode, seed, device, accel, flags, progress,
+ * samples_per_launch and queue_factor; its spp, sample_begin and sample_end must be left as
+ * mcpt_render_opts_init set them, and num_devices / comm must be unset (MCPT_E_INVALID otherwise).
+ * stats: summed over the passes; camera_samples is the sum of the count map, prep_cache_points is counted
+ * once (the root-point cache is built once per call). */
+int mcpt_render_adaptive(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* base,
+                         const mcpt_adaptive_opts* adaptive, double* out_rgb, int32_t* count, double* noise,
+                         mcpt_stats* stats);
+/* same with the three maps in DEVICE memory (coarse-grained, on base->device; see mcpt_render_device) */
+int mcpt_render_adaptive_device(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* base,
+                                const mcpt_adaptive_opts* adaptive, double* dev_out_rgb, int32_t* dev_count,
+                                double* dev_noise, mcpt_stats* stats);
 
 /* Myobj::cal_scene_boundingbox(eye) + Myobj::meshing(n0) (Myobj.cpp:78-162): build the scene's
  * uniform grid (box of every vertex and `eye`; cell edge = largest extent / n0^(1/3)) for

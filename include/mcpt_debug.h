@@ -95,6 +95,11 @@ int mcpt_debug_bvh8_check(mcpt_scene* scene, int32_t light_only, int64_t out[6])
 // outside an ancestor slot's box, a quantized slot box not containing its fp32 box, a bad index), depth}.
 int mcpt_debug_bvh4_check(mcpt_scene* scene, int32_t light_only, int64_t out[6]);
 
+/* diagnostics: the last active-pixel list the scene's most recent adaptive render built on `device` (-1 = current)
+ * -- the pixels sampled by its last pass, or the list built after pass 0 when max_spp = min_spp + pass_spp.
+ * *n = its length (0: no list was built); up to `cap` pixel indices are copied to `pixels`. */
+int mcpt_debug_adaptive_active(mcpt_scene* scene, int32_t device, int32_t* pixels, int32_t cap, int32_t* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,7 @@ import os
 
 import numpy as np
 
-__all__ = ["Scene", "Camera", "Comm", "render", "render_device", "closest_hit", "light_prep", "primary_hits",
+__all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_adaptive", "render_adaptive_device", "closest_hit", "light_prep", "primary_hits",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -26,7 +26,7 @@ MODES = {"mis": MODE_MIS, "brdf": MODE_BRDF, "shade": MODE_SHADE, "shade_area": 
 ACCEL_BVH, ACCEL_GRID = 0, 1  # mcpt_render_opts.accel: BVH, or the reference's uniform grid (Myobj.cpp:78-162)
 HIT_LIGHT_ONLY, HIT_GRID = 1, 2  # mcpt_closest_hit flags
 DEFAULT_SEED = 20240430
-MCPT_VERSION = 20200  # include/mcpt.h MCPT_VERSION this mirror is written against
+MCPT_VERSION = 20300  # include/mcpt.h MCPT_VERSION this mirror is written against
 COMM_ID_BYTES = 128  # MCPT_COMM_ID_BYTES
 STATS_MAX_DEVICES = 16  # MCPT_STATS_MAX_DEVICES
 
@@ -72,6 +72,12 @@ DEBUG_NO_EXACT_DEFER = 1 << 23  # k_prep_exact recomputes same-launch duplicate 
 DEBUG_HIT_CW8 = 1 << 8  # mcpt_closest_hit: trace through the 8-wide trees
 
 
+class AdaptiveOpts(C.Structure):
+    """mcpt_adaptive_opts: the adaptive stopping rule's parameters (include/mcpt.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("min_spp", C.c_int32), ("pass_spp", C.c_int32), ("max_spp", C.c_int32),
+                ("threshold", C.c_double), ("radius", C.c_int32)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 
 
@@ -103,10 +109,12 @@ _lib = None
 EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_create", "mcpt_scene_destroy",
            "mcpt_scene_counts", "mcpt_scene_accel_bytes", "mcpt_scene_arrays", "mcpt_scene_camera", "mcpt_scene_meshing", "mcpt_scene_grid_info",
            "mcpt_render_opts_init", "mcpt_render", "mcpt_render_device",
+           "mcpt_adaptive_opts_init", "mcpt_render_adaptive", "mcpt_render_adaptive_device",
            "mcpt_closest_hit", "mcpt_light_prep", "mcpt_primary_hits", "mcpt_tone_map",
            "mcpt_write_bmp", "mcpt_comm_unique_id", "mcpt_comm_init_rank", "mcpt_comm_destroy"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
-                 "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check"]  # include/mcpt_debug.h
+                 "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
+                 "mcpt_debug_adaptive_active"]  # include/mcpt_debug.h
 
 
 def lib():
@@ -146,6 +154,14 @@ def lib():
         L.mcpt_render_opts_init.restype = None
         L.mcpt_render.argtypes = [P, C.POINTER(Camera), C.POINTER(RenderOpts), dp, C.POINTER(Stats)]
         L.mcpt_render_device.argtypes = [P, C.POINTER(Camera), C.POINTER(RenderOpts), C.c_void_p, C.POINTER(Stats)]
+        if hasattr(L, "mcpt_render_adaptive"):  # ABI 2.3 (an older build timed through MCPT_LIB_PATH lacks it)
+            L.mcpt_adaptive_opts_init.argtypes = [C.POINTER(AdaptiveOpts)]
+            L.mcpt_adaptive_opts_init.restype = None
+            L.mcpt_render_adaptive.argtypes = [P, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(AdaptiveOpts), dp,
+                                               C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+            L.mcpt_render_adaptive_device.argtypes = [P, C.POINTER(Camera), C.POINTER(RenderOpts),
+                                                      C.POINTER(AdaptiveOpts), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.POINTER(Stats)]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -157,7 +173,8 @@ def lib():
                "mcpt_debug_light_literal": [P, dp, dp, dp],
                "mcpt_debug_set_collective_lib": [C.c_char_p],
                "mcpt_debug_bvh8_check": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
-               "mcpt_debug_bvh4_check": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")]}
+               "mcpt_debug_bvh4_check": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
+               "mcpt_debug_adaptive_active": [P, I, ip, I, C.POINTER(I)]}
         for name, argt in dbg.items():
             if hasattr(L, name):
                 getattr(L, name).argtypes = argt
@@ -341,6 +358,71 @@ def render_device(scene, camera, spp, dev_ptr, mode="mis", seed=DEFAULT_SEED, sa
               devices, comm)
     _check(lib().mcpt_render_device(scene.h, C.byref(camera), C.byref(o), C.c_void_p(int(dev_ptr)), C.byref(st)))
     return st
+
+
+def _adaptive_opts(max_spp, threshold, min_spp, pass_spp, radius):
+    a = AdaptiveOpts()
+    lib().mcpt_adaptive_opts_init(C.byref(a))
+    a.max_spp, a.threshold, a.radius = int(max_spp), float(threshold), int(radius)
+    if min_spp is not None:
+        a.min_spp = int(min_spp)
+    if pass_spp is not None:
+        a.pass_spp = int(pass_spp)
+    return a
+
+
+def _adaptive_base(mode, seed, device, samples_per_launch, queue_factor, progress, accel, flags):
+    o = _opts(0, mode, seed, None, device, samples_per_launch, queue_factor, progress, accel, flags)
+    d = RenderOpts()
+    lib().mcpt_render_opts_init(C.byref(d))
+    o.spp = d.spp  # left at its default: the sample counts come from the adaptive options
+    return o
+
+
+def render_adaptive(scene, camera, max_spp, threshold, min_spp=None, pass_spp=None, radius=1, mode="mis",
+                    seed=DEFAULT_SEED, out=None, device=None, samples_per_launch=0, queue_factor=0, progress=None,
+                    accel="bvh", flags=0):
+    """Adaptive sampling (mcpt_render_adaptive, include/mcpt.h): render in passes of pass_spp samples after
+    the first min_spp (library defaults: 16 each), estimate each active pixel's noise e after every pass and
+    stop sampling the pixels with e <= threshold whose neighbours within `radius` have converged too; no pixel
+    takes more than max_spp.  Returns (image, count, noise, Stats): the H x W x 3 mean radiance ADDED into
+    `out` (zeros if None), the int32 H x W samples taken and the H x W last noise estimate.  Single device."""
+    if out is None:
+        out = np.zeros((camera.height, camera.width, 3))
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (camera.height, camera.width, 3)
+    count = np.zeros((camera.height, camera.width), np.int32)
+    noise = np.zeros((camera.height, camera.width))
+    st = Stats()
+    o = _adaptive_base(mode, seed, device, samples_per_launch, queue_factor, progress, accel, flags)
+    a = _adaptive_opts(max_spp, threshold, min_spp, pass_spp, radius)
+    _check(lib().mcpt_render_adaptive(scene.h, C.byref(camera), C.byref(o), C.byref(a), out.reshape(-1),
+                                      count.ctypes.data_as(C.c_void_p), noise.ctypes.data_as(C.c_void_p), C.byref(st)))
+    return out, count, noise, st
+
+
+def render_adaptive_device(scene, camera, max_spp, threshold, dev_ptr, count_ptr=None, noise_ptr=None, min_spp=None,
+                           pass_spp=None, radius=1, mode="mis", seed=DEFAULT_SEED, device=None, samples_per_launch=0,
+                           queue_factor=0, progress=None, accel="bvh", flags=0):
+    """render_adaptive into device buffers (e.g. torch CUDA tensors' data_ptr()): dev_ptr H*W*3 float64
+    (added into), count_ptr H*W int32 and noise_ptr H*W float64 (overwritten; either may be None)."""
+    st = Stats()
+    o = _adaptive_base(mode, seed, device, samples_per_launch, queue_factor, progress, accel, flags)
+    a = _adaptive_opts(max_spp, threshold, min_spp, pass_spp, radius)
+    _check(lib().mcpt_render_adaptive_device(
+        scene.h, C.byref(camera), C.byref(o), C.byref(a), C.c_void_p(int(dev_ptr)),
+        None if count_ptr is None else C.c_void_p(int(count_ptr)),
+        None if noise_ptr is None else C.c_void_p(int(noise_ptr)), C.byref(st)))
+    return st
+
+
+def debug_adaptive_active(scene, device=-1):
+    """Diagnostics: the last active-pixel list the scene's most recent adaptive render built
+    (include/mcpt_debug.h), as an int32 array of pixel indices."""
+    n = C.c_int32()
+    _check(lib().mcpt_debug_adaptive_active(scene.h, int(device), np.zeros(1, np.int32), 0, C.byref(n)))
+    px = np.zeros(max(n.value, 1), np.int32)
+    _check(lib().mcpt_debug_adaptive_active(scene.h, int(device), px, n.value, C.byref(n)))
+    return px[:n.value]
 
 
 def closest_hit(scene, ro, rd, exclude=None, light_only=False, grid=False, wide=False):

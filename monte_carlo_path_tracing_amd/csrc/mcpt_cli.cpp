@@ -7,6 +7,11 @@
 //   mcpt_render --scene scenes/veach-mis/veach-mis [--width 1280 --height 720] [--spp 10]
 //               [--mode mis|brdf|shade|shade-area] [--seed 20240430] [--out test.bmp] [--hdr out.pfm] [--progress]
 //               [--grid] [--devices 0,1,2,3,4,5,6,7] [--precision fp64|fp32]
+//               [--adaptive TAU [--min-spp N] [--pass-spp N] [--radius R] [--count-out count.bmp]]
+//   --adaptive TAU renders adaptively (mcpt_render_adaptive): passes of --pass-spp samples after the first
+//   --min-spp (default 16 each), a pixel stops once its noise estimate is at most TAU and so are its
+//   neighbours' within --radius (default 1); --spp is the cap.  Prints the mean spp and the share of pixels at
+//   the cap; --count-out writes the per-pixel sample count as a grey BMP (white = the cap).  One device.
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -60,6 +65,25 @@ int render(mcpt_scene* scene, const mcpt_camera& cam, int spp, int mode, uint64_
     return mcpt_render(scene, &cam, &o, hdr.data(), st);
 }
 
+// the adaptive form of render(): --spp is the cap; the count map comes back too
+int render_adaptive(mcpt_scene* scene, const mcpt_camera& cam, const mcpt_adaptive_opts& ad, int mode, uint64_t seed,
+                    bool progress, bool grid, int flags, std::vector<double>& hdr, std::vector<int32_t>& count, mcpt_stats* st) {
+    hdr.assign(3ull * cam.width * cam.height, 0.0);
+    count.assign((size_t)cam.width * cam.height, 0);
+    mcpt_render_opts o;
+    mcpt_render_opts_init(&o);
+    o.mode = mode;
+    o.seed = seed;
+    o.accel = grid ? MCPT_ACCEL_GRID : MCPT_ACCEL_BVH;
+    o.flags = flags;
+    int last = -10;
+    if (progress) {
+        o.progress = print_progress;
+        o.progress_user = &last;
+    }
+    return mcpt_render_adaptive(scene, &cam, &o, &ad, hdr.data(), count.data(), nullptr, st);
+}
+
 bool write_pfm(const char* path, const std::vector<double>& hdr, int W, int H) {
     FILE* f = std::fopen(path, "wb");
     if (!f) return false;
@@ -83,6 +107,10 @@ int main(int argc, char** argv) {
     bool xml_cam = false, progress = false, grid = false;
     int flags = 0;
     std::vector<int32_t> devices;
+    bool adaptive = false;
+    mcpt_adaptive_opts ad;
+    mcpt_adaptive_opts_init(&ad);
+    std::string count_out;
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -121,6 +149,14 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (!std::strcmp(argv[a], "--adaptive")) {
+            adaptive = true;
+            ad.threshold = std::atof(next());
+        }
+        else if (!std::strcmp(argv[a], "--min-spp")) ad.min_spp = std::atoi(next());
+        else if (!std::strcmp(argv[a], "--pass-spp")) ad.pass_spp = std::atoi(next());
+        else if (!std::strcmp(argv[a], "--radius")) ad.radius = std::atoi(next());
+        else if (!std::strcmp(argv[a], "--count-out")) count_out = next();
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -158,8 +194,19 @@ int main(int argc, char** argv) {
     cam.height = H;
     std::vector<double> hdr;
     mcpt_stats st{};
+    std::vector<int32_t> count;
+    if (adaptive && !devices.empty()) {
+        std::fprintf(stderr, "--adaptive renders on one device; drop --devices\n");
+        return 2;
+    }
+    if (!adaptive && !count_out.empty()) {
+        std::fprintf(stderr, "--count-out needs --adaptive\n");
+        return 2;
+    }
+    ad.max_spp = spp;
     const auto t0 = std::chrono::steady_clock::now();
-    if (render(scene, cam, spp, mode, seed, progress, grid, flags, devices, hdr, &st) != MCPT_OK) {
+    if ((adaptive ? render_adaptive(scene, cam, ad, mode, seed, progress, grid, flags, hdr, count, &st)
+                  : render(scene, cam, spp, mode, seed, progress, grid, flags, devices, hdr, &st)) != MCPT_OK) {
         std::fprintf(stderr, "render failed: %s\n", mcpt_last_error());
         return 1;
     }
@@ -173,6 +220,22 @@ int main(int argc, char** argv) {
                     st.device_setup_seconds, st.reduce_seconds);
         for (int u = 0; u < st.devices_used && u < MCPT_STATS_MAX_DEVICES; u++) std::printf(" %.3f", st.device_seconds[u]);
         std::printf(" s\n");
+    }
+    if (adaptive) {
+        size_t capped = 0;
+        for (int32_t c : count) capped += c >= spp;
+        std::printf("  adaptive (threshold %g, min %d, pass %d, radius %d): mean %.2f spp of at most %d, %.1f%% of the pixels "
+                    "at the cap\n", ad.threshold, ad.min_spp, ad.pass_spp, ad.radius, (double)st.camera_samples / count.size(),
+                    spp, 100.0 * capped / count.size());
+        if (!count_out.empty()) {  // grey: 255 = the cap
+            std::vector<uint8_t> grey(3 * count.size());
+            for (size_t k = 0; k < count.size(); k++)
+                grey[3 * k] = grey[3 * k + 1] = grey[3 * k + 2] = (uint8_t)(255ll * count[k] / spp);
+            if (mcpt_write_bmp(count_out.c_str(), grey.data(), W, H) != MCPT_OK) {
+                std::fprintf(stderr, "%s\n", mcpt_last_error());
+                return 1;
+            }
+        }
     }
     std::vector<uint8_t> rgb8(hdr.size());
     mcpt_tone_map(hdr.data(), W, H, 380.0, 0.25, rgb8.data());  // main.cpp:583

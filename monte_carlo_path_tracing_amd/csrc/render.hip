@@ -21,6 +21,8 @@
 //                                       light + BRDF samples, their closest hits, MIS weights and the
 //                                       children's entry checks -> next generation's queue
 //   k_extend_brdf      lane per node  : the BRDF-only vertex in one kernel
+//   k_adaptive_error / _mark / _compact / _finalize : adaptive sampling -- per-pixel noise after a pass,
+//                                       the next ascending active-pixel list (k_roots_t's pixels), the result
 //
 // A node's value is the sum over its subtree's emitter hits of (throughput x emit); contributions
 // are accumulated straight into an fp64 framebuffer with hardware fp64 atomics.
@@ -785,6 +787,13 @@ struct Queue {
 #ifndef MCPT_BAND_DIAG
 #define MCPT_BAND_DIAG 0
 #endif
+// 1: every render prints to stderr how many wavefront runs it made, the time of their drains (from the end
+// of the generation that took a run's last roots to the run's end) and, adaptive, the time of the adaptive
+// kernels -- the host clock read where the stream is idle, with extra waits: not for timed comparisons
+// (tools/adaptive_bench.py reads the line)
+#ifndef MCPT_ADAPTIVE_DIAG
+#define MCPT_ADAPTIVE_DIAG 0
+#endif
 #ifndef MCPT_EXACT_PICK
 #define MCPT_EXACT_PICK 1
 #endif
@@ -1067,8 +1076,13 @@ __device__ inline void root_of(long long rg, int npx, int s0, int group, int nsa
 constexpr int kRootsPT = MCPT_ROOTS_PT;
 // lite (BRDF-only with P.root_pnw): the entries' point, normal, wo and throughput are not written
 // (k_extend_brdf reads them from the root table)
+// ACTIVE (adaptive sampling's later passes): the roots run over the `npx` entries of the ascending pixel list
+// `active` instead of the frame, and root_of's pixel is the index into it.  A template parameter, so the
+// plain instance (active unused) is the kernel it was.
+template <bool ACTIVE>
 __global__ __launch_bounds__(256) void k_roots_t(Params P, const int* __restrict__ hit_f, int npx, int s0, long long rbase,
-                                                 int nroots, Queue q, int group, int nsamp, RootTab rt, int lite) {
+                                                 int nroots, Queue q, int group, int nsamp, RootTab rt, int lite,
+                                                 const int* __restrict__ active) {
     __shared__ unsigned s_w[kRootsPT][4];
     __shared__ unsigned s_base;
     const int lane = lane_id(), wid = threadIdx.x >> 6;
@@ -1082,6 +1096,7 @@ __global__ __launch_bounds__(256) void k_roots_t(Params P, const int* __restrict
         px[j] = 0, sm[j] = 0;
         if (r < nroots) {
             root_of(rbase + r, npx, s0, group, nsamp, &px[j], &sm[j]);
+            if (ACTIVE) px[j] = active[px[j]];
             const int kind = rt.kind[px[j]];
             if (kind >= 0) {  // emitter: its emission (main.cpp:411-412 with throughput 1)
                 double* fb = P.fb + 3 * (size_t)px[j];
@@ -1151,6 +1166,95 @@ __global__ __launch_bounds__(256) void k_queue_move(Queue src, int sb, Queue dst
     dst.sample[d] = src.sample[s];
     dst.node[d] = src.node[s];
     dst.par[d] = src.par[s];
+}
+
+// --------------------------------------------------------------------------------------------
+// Adaptive sampling (mcpt_render_adaptive): after every pass the noise of each active
+// pixel is estimated from two unweighted fp64 sums -- A over the first half of every pass's samples, B
+// over the second -- and pixels below the threshold leave the active list for good.
+// Per-pixel state bytes: 0 not active, 1 active, 2 active and above the threshold.
+// --------------------------------------------------------------------------------------------
+
+// Dammertz et al. 2010 with the half buffer from the passes' first halves: I = (A + B) / n, Ah = 2 A / n,
+// e = sum_c |I_c - Ah_c| / sqrt(sum_c I_c) (0 when the numerator is 0).  One lane per active pixel
+// (active == nullptr: every pixel of the frame); writes the pixel's noise, count and state.
+__global__ __launch_bounds__(256) void k_adaptive_error(const int* __restrict__ active, int nactive,
+                                                        const double* __restrict__ A, const double* __restrict__ B, int n,
+                                                        double tau, double* __restrict__ noise, int* __restrict__ count,
+                                                        unsigned char* __restrict__ state) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nactive) return;
+    const int p = active ? active[idx] : idx;
+    double num = 0, sum = 0;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const double a = A[3 * (size_t)p + c], b = B[3 * (size_t)p + c];
+        const double I = (a + b) / n, Ah = 2 * a / n;
+        num += fabs(I - Ah);
+        sum += I;
+    }
+    const double e = num > 0 ? num / sqrt(sum) : 0.0;
+    noise[p] = e;
+    count[p] = n;
+    state[p] = e > tau ? 2 : 1;
+}
+
+// next_active = active AND dilate(above threshold, r): the (2r+1)^2 square clipped at the frame's border.
+// One lane per pixel of the frame; writes the next state byte (1 / 0) of every pixel and the number of
+// survivors of each 256-pixel block, from which k_adaptive_compact places them (no atomics: the list's
+// order is the pixel order).
+__global__ __launch_bounds__(256) void k_adaptive_mark(const unsigned char* __restrict__ cur, unsigned char* __restrict__ nxt,
+                                                       int W, int H, int r, unsigned* __restrict__ block_cnt) {
+    __shared__ unsigned s_cnt[4];
+    const int p = blockIdx.x * 256 + (int)threadIdx.x, npx = W * H;
+    bool keep = false;
+    if (p < npx && cur[p]) {
+        const int y = p / W, x = p - y * W;
+        const int y0 = max(y - r, 0), y1 = min(y + r, H - 1), x0 = max(x - r, 0), x1 = min(x + r, W - 1);
+        for (int yy = y0; yy <= y1; yy++)
+            for (int xx = x0; xx <= x1; xx++) keep |= cur[yy * W + xx] == 2;
+    }
+    if (p < npx) nxt[p] = keep ? 1 : 0;
+    const uint64_t m = __ballot(keep);
+    if (lane_id() == 0) s_cnt[threadIdx.x >> 6] = (unsigned)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// The surviving pixels in ascending order: a block's base is the sum of the earlier blocks' counts (each
+// block adds them up itself: blocks^2 / 2 word reads in all, 1.8 M for 800x600), a wave's offset the sum of
+// the block's earlier waves, a lane's rank the set bits below it in the wave's ballot -- the wave-aggregated
+// append of block_append with the atomic replaced by the prefix.  The last block writes the total.
+__global__ __launch_bounds__(256) void k_adaptive_compact(const unsigned char* __restrict__ state, int npx,
+                                                          const unsigned* __restrict__ block_cnt, int* __restrict__ list,
+                                                          unsigned* __restrict__ total) {
+    __shared__ unsigned s_part[4], s_cnt[4];
+    const int lane = lane_id(), wid = threadIdx.x >> 6;
+    const int p = blockIdx.x * 256 + (int)threadIdx.x;
+    unsigned part = 0;
+    for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) part += block_cnt[b];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) part += __shfl_down(part, d);
+    const bool keep = p < npx && state[p];
+    const uint64_t m = __ballot(keep);
+    if (lane == 0) s_part[wid] = part, s_cnt[wid] = (unsigned)__popcll(m);
+    __syncthreads();
+    unsigned base = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    for (int w = 0; w < wid; w++) base += s_cnt[w];
+    if (keep) {
+        const unsigned rk = __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+        const unsigned slot = base + rk;
+        if (slot < (unsigned)npx) list[slot] = p;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) *total = base + (unsigned)__popcll(m);
+}
+
+// out += (A + B) / count, the way a plain render adds its weighted sum
+__global__ __launch_bounds__(256) void k_adaptive_finalize(double* __restrict__ out, const double* __restrict__ A,
+                                                           const double* __restrict__ B, const int* __restrict__ count, int npx) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= 3 * (size_t)npx) return;
+    out[i] += (A[i] + B[i]) / count[i / 3];
 }
 
 // root shading points of the pixels whose primary hit is a front-facing non-emitter (the nodes
@@ -4258,6 +4362,10 @@ struct DeviceState {
     DevBuf exact, exact_scr, slack;  // exact pick: list, k_prep_exact's scratch, per-node slack
     DevBuf lit_slot, lit_pool;        // exact pick: roots' literal sums per pixel (RootLit)
     DevBuf sc_cum, sc_wsum, sc_last;  // small-table root-point cache (SmallCache)
+    // adaptive sampling: half sums A / B, active lists and state bytes (ping-pong), per-block survivor counts
+    // (+ the total), the library's own count / noise maps
+    DevBuf ad_acc[2], ad_list[2], ad_state[2], ad_blk, ad_count, ad_noise;
+    int ad_last_list = -1, ad_last_n = 0;  // the last active list built (mcpt_debug_adaptive_active)
     int spill_cap = 0;  // nodes the spill stack qs holds (grown on demand)
     bool bvh8_tried = false;  // ensure_bvh8 ran on this device
     DevBuf g_start, g_tri;  // the scene's uniform grid (MCPT_ACCEL_GRID), version grid_version
@@ -4955,9 +5063,20 @@ int validate_render(const mcpt_render_opts* o) {
     return MCPT_OK;
 }
 
-// the wavefront render into a device framebuffer already resident on D's device
+// an adaptive call (mcpt_render_adaptive): the rule's parameters and where the count / noise maps go
+// (device memory on D's device; nullptr: the library's own maps)
+struct AdaptiveRun {
+    mcpt_adaptive_opts a;
+    int* count;
+    double* noise;
+};
+
+// the wavefront render into a device framebuffer already resident on D's device.  The per-call setup
+// (allocations, primary hits, root table, root-point cache) runs once; the wavefront loop runs once over
+// [s0, s1) for a plain render, or twice per pass (the halves A and B) for an adaptive one (ad != nullptr:
+// o->spp is the cap, the statistics are summed over the passes).
 int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt_render_opts* o,
-                     double* dfb, mcpt_stats* stats) {
+                     double* dfb, mcpt_stats* stats, const AdaptiveRun* ad = nullptr) {
     const CamFrame cf = cam_setup(*cam);
     const int W = cam->width, H = cam->height, npx = W * H;
     const int s0 = (o->sample_begin == 0 && o->sample_end == 0) ? 0 : o->sample_begin;
@@ -4984,8 +5103,9 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
     // sample-major otherwise (Veach: the root-point cache's per-pixel reads spread; -3% minor)
     const uint64_t accel = (uint64_t)(D.d.nbvh4 + D.d.nlbvh4) * sizeof(BvhNode4) +
                            (uint64_t)(sc->bvh.leaf_facets.size() + sc->lbvh.leaf_facets.size()) * 3 * sizeof(float4);
-    const int nminor = (MCPT_ROOT_MINOR > 0 || (MCPT_ROOT_MINOR < 0 && accel > (4ull << 20))) ? s1 - s0
-                                                                                              : std::min(MCPT_ROOT_GROUP, s1 - s0);
+    const auto minor_of = [&](int nsamp) {  // the group of a run of nsamp samples
+        return (MCPT_ROOT_MINOR > 0 || (MCPT_ROOT_MINOR < 0 && accel > (4ull << 20))) ? nsamp : std::min(MCPT_ROOT_GROUP, nsamp);
+    };
     const int qf = o->queue_factor > 0 ? o->queue_factor : 2;
     // default working set: MCPT_WORKING_SET nodes (48 Mi: fewer, larger generations amortise each
     // launch's tail -- measured +6% Veach, +21% Cornell-1M over 4 Mi), but no more than the call's
@@ -5037,7 +5157,7 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
     Params P;
     P.S = D.d;
     P.seed = o->seed;
-    P.inv_spp = 1.0 / o->spp;
+    P.inv_spp = ad ? 1.0 : 1.0 / o->spp;  // adaptive: raw sums (P.fb is set per half)
     P.fb = dfb;
     P.stats = (unsigned long long*)D.stats.p;
     P.mode = o->mode;
@@ -5134,6 +5254,16 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
     // (round 6: k_rays_persistent handing the combine its hit points instead of (beta, gamma) was measured slower,
     // C5 -2..-6%, shade-area -9%: profiles/round6_ab_hit_points.txt)
     const bool rays_cw8 = rays_pers && (MCPT_RAYS_CW8 || (o->flags & MCPT_DEBUG_RAYS_CW8)) && D.d.bvh8 && D.d.lbvh8;
+    const int nblk = (npx + 255) / 256;  // adaptive: blocks of k_adaptive_mark / k_adaptive_compact
+    if (ad) {
+        for (int k = 0; k < 2; k++)
+            if ((rc = ensure(D.ad_acc[k], 24ull * npx)) || (rc = ensure(D.ad_list[k], 4ull * npx)) ||
+                (rc = ensure(D.ad_state[k], (size_t)npx)))
+                return rc;
+        if ((rc = ensure(D.ad_blk, 4ull * (nblk + 1))) || (rc = ensure(D.ad_count, 4ull * npx)) ||
+            (rc = ensure(D.ad_noise, 8ull * npx)))
+            return rc;
+    }
     // every buffer is allocated above (first-call hipMalloc of the cache is not device work); the
     // timed region (seconds, HIP events) starts at the primary-hit kernel
     HIP_OK(hipMemsetAsync(D.stats.p, 0, kStatBytes, st));
@@ -5195,296 +5325,399 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
             HIP_OK(hipMemsetAsync(rl.slot + 16, 0xff, 4ull * npx, st));
         }
     }
-    Queue* cur = &qa;
-    Queue* nxt = &qb;
-    HIP_OK(hipMemsetAsync(cur->count, 0, 4, st));
-    long long rnext = 0;
-    // Slicing: an MIS node has up to 2 children (shade / BRDF: 1), so a generation of at most `slice`
-    // nodes always fits its children into nxt.  A larger generation (supercritical trees, e.g. occluded
-    // lights: 2 x RR 0.6 = 1.2 children per node) parks its excess on a spill stack in HBM (grown on
-    // demand) and takes it back, last in first out, before fresh roots -- so deep subtrees drain
-    // first and the stack stays bounded by ~depth x slice.  The image does not depend on the order.
-    const int branch = o->mode == MCPT_MODE_MIS ? 2 : 1;
-    const int slice = cap / branch;
-    const int fill = std::min(target, slice);  // refill / pop up to this many nodes per generation
-    Queue qs{};
-    long long spill_n = 0;
-    uint64_t spilled = 0;
-    auto grow_spill = [&](long long need) -> int {
-        if (need <= D.spill_cap && qs.p) return MCPT_OK;
-        if (need > (1ll << 30)) {
-            set_error("spill stack beyond 2^30 nodes");
-            return MCPT_E_DEVICE;
-        }
-        const int ncap = (int)std::min<long long>(std::max<long long>(need, 2ll * D.spill_cap), 1ll << 30);
-        DevBuf nb[14];
-        Queue nq;
-        int r;
-        if ((r = alloc_queue(nb, ncap, nq))) return r;
-        if (spill_n > 0 && qs.p)
-            hipLaunchKernelGGL(k_queue_move, dim3((unsigned)((spill_n + 255) / 256)), dim3(256), 0, st, qs, 0, nq, 0, (int)spill_n);
-        HIP_OK(hipStreamSynchronize(st));
-        for (int k = 0; k < 14; k++) {
-            if (D.qs[k].p) HIP_OK(hipFree(D.qs[k].p));
-            D.qs[k] = nb[k];
-        }
-        D.spill_cap = ncap;
-        qs = nq;
-        return MCPT_OK;
+    uint64_t spilled = 0, roots_total = 0;
+#if MCPT_ADAPTIVE_DIAG
+    int diag_runs = 0;
+    double diag_drain_ms = 0, diag_kernel_ms = 0;
+    const auto diag_now = [] { return std::chrono::steady_clock::now(); };
+    const auto diag_ms = [](std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1) {
+        return std::chrono::duration<double, std::milli>(t1 - t0).count();
     };
-    if (D.spill_cap > 0) {  // the stack of an earlier call (empty)
-        int r;
-        if ((r = alloc_queue(D.qs, D.spill_cap, qs))) return r;
-    }
-    auto read_count = [&](unsigned* out) -> int {  // cur's node count; fails on a queue overflow
-        HIP_OK(hipMemcpyAsync(D.pinned_count, cur->count, 4, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipMemcpyAsync(D.pinned_count + 2, (char*)D.stats.p + 32, 8, hipMemcpyDeviceToHost, st));
-        if (stale) HIP_OK(hipMemcpyAsync(D.pinned_count + 16, T.ctrl, kCtrlBytes, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        if (*(unsigned long long*)(D.pinned_count + 2)) {
-            set_error("wavefront queue overflow (capacity %d); raise queue_factor", cap);
-            return MCPT_E_OVERFLOW;
+#endif
+    // The wavefront loop: samples [a, b) of the pixels active[0, nact) (nullptr: the frame's nact = npx
+    // pixels) are traced to the end of their trees and added into P.fb with weight P.inv_spp.  The setup above
+    // holds for every run: the root table and the root-point cache are keyed by pixel.
+    auto wavefront = [&](int a, int b, const int* active, int nact) -> int {
+        const long long R = (long long)(b - a) * nact;
+        const int nminor = minor_of(b - a);
+        roots_total += (uint64_t)R;
+        Queue* cur = &qa;
+        Queue* nxt = &qb;
+        HIP_OK(hipMemsetAsync(cur->count, 0, 4, st));
+        long long rnext = 0;
+        // Slicing: an MIS node has up to 2 children (shade / BRDF: 1), so a generation of at most `slice`
+        // nodes always fits its children into nxt.  A larger generation (supercritical trees, e.g. occluded
+        // lights: 2 x RR 0.6 = 1.2 children per node) parks its excess on a spill stack in HBM (grown on
+        // demand) and takes it back, last in first out, before fresh roots -- so deep subtrees drain
+        // first and the stack stays bounded by ~depth x slice.  The image does not depend on the order.
+        const int branch = o->mode == MCPT_MODE_MIS ? 2 : 1;
+        const int slice = cap / branch;
+        const int fill = std::min(target, slice);  // refill / pop up to this many nodes per generation
+        Queue qs{};
+        long long spill_n = 0;
+        auto grow_spill = [&](long long need) -> int {
+            if (need <= D.spill_cap && qs.p) return MCPT_OK;
+            if (need > (1ll << 30)) {
+                set_error("spill stack beyond 2^30 nodes");
+                return MCPT_E_DEVICE;
+            }
+            const int ncap = (int)std::min<long long>(std::max<long long>(need, 2ll * D.spill_cap), 1ll << 30);
+            DevBuf nb[14];
+            Queue nq;
+            int r;
+            if ((r = alloc_queue(nb, ncap, nq))) return r;
+            if (spill_n > 0 && qs.p)
+                hipLaunchKernelGGL(k_queue_move, dim3((unsigned)((spill_n + 255) / 256)), dim3(256), 0, st, qs, 0, nq, 0, (int)spill_n);
+            HIP_OK(hipStreamSynchronize(st));
+            for (int k = 0; k < 14; k++) {
+                if (D.qs[k].p) HIP_OK(hipFree(D.qs[k].p));
+                D.qs[k] = nb[k];
+            }
+            D.spill_cap = ncap;
+            qs = nq;
+            return MCPT_OK;
+        };
+        if (D.spill_cap > 0) {  // the stack of an earlier call (empty)
+            int r;
+            if ((r = alloc_queue(D.qs, D.spill_cap, qs))) return r;
         }
-        *out = std::min<unsigned>(D.pinned_count[0], (unsigned)cap);
-        return MCPT_OK;
-    };
-    while (true) {
-        unsigned n = 0;
-        if ((rc = read_count(&n))) return rc;
-        if (n > (unsigned)slice) {  // push the excess children onto the spill stack
-            const int m = (int)n - slice;
-            if ((rc = grow_spill(spill_n + m))) return rc;
-            hipLaunchKernelGGL(k_queue_move, dim3((m + 255) / 256), dim3(256), 0, st, *cur, slice, qs, (int)spill_n, m);
-            HIP_OK(hipGetLastError());
-            spill_n += m;
-            spilled += (uint64_t)m;
-            n = (unsigned)slice;
-            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)cur->count, (int)n, 1, st));
-        } else if (spill_n > 0 && n < (unsigned)fill) {  // pop spilled children before new roots
-            const int m = (int)std::min<long long>((long long)fill - n, spill_n);
-            spill_n -= m;
-            hipLaunchKernelGGL(k_queue_move, dim3((m + 255) / 256), dim3(256), 0, st, qs, (int)spill_n, *cur, (int)n, m);
-            HIP_OK(hipGetLastError());
-            n += (unsigned)m;
-            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)cur->count, (int)n, 1, st));
-        }
-        const unsigned n_children = n;  // [0, n_children) children, [n_children, n) fresh roots
-        if (rnext < R && n < (unsigned)fill) {  // refill with roots (appended through node_entry)
-            const int m = (int)std::min<long long>((long long)fill - n, R - rnext);
-            hipLaunchKernelGGL(k_roots_t, dim3((m + 256 * kRootsPT - 1) / (256 * kRootsPT)), dim3(256), 0, st, P,
-                               (const int*)D.hit_f.p, npx, s0, rnext, m, *cur, std::max(1, nminor), s1 - s0, rtab,
-                               P.root_pnw ? 1 : 0);
-            HIP_OK(hipGetLastError());
-            rnext += m;
+        auto read_count = [&](unsigned* out) -> int {  // cur's node count; fails on a queue overflow
+            HIP_OK(hipMemcpyAsync(D.pinned_count, cur->count, 4, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(D.pinned_count + 2, (char*)D.stats.p + 32, 8, hipMemcpyDeviceToHost, st));
+            if (stale) HIP_OK(hipMemcpyAsync(D.pinned_count + 16, T.ctrl, kCtrlBytes, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            if (*(unsigned long long*)(D.pinned_count + 2)) {
+                set_error("wavefront queue overflow (capacity %d); raise queue_factor", cap);
+                return MCPT_E_OVERFLOW;
+            }
+            *out = std::min<unsigned>(D.pinned_count[0], (unsigned)cap);
+            return MCPT_OK;
+        };
+#if MCPT_ADAPTIVE_DIAG
+        bool diag_draining = false;
+        auto diag_t0 = diag_now();
+#endif
+        while (true) {
+            unsigned n = 0;
             if ((rc = read_count(&n))) return rc;
-        }
-        if (n == 0) {
-            if (rnext >= R && spill_n == 0) break;
-            continue;  // every root of the refill terminated at entry: refill again
-        }
-        if (stale) {  // a shard serves at most ceil(blocks / 32) workgroups of 256 nodes per generation
-            const unsigned per_shard = ((n + 255) / 256 + kSlotShards - 1) / kSlotShards * 256;
-            unsigned bump = 0;
-            for (int sh = 0; sh < kSlotShards; sh++) bump = std::max(bump, hctrl[16 * sh]);
-            if (bump + per_shard > (unsigned)T.rcap) {
-                const long long nr = std::max<long long>(2ll * T.rcap, (long long)bump + per_shard + 4096);
-                if (nr * kSlotShards > (1ll << 30)) {
-                    set_error("MIS reduction slot pool beyond 2^30 slots");
-                    return MCPT_E_DEVICE;
+#if MCPT_ADAPTIVE_DIAG
+            if (rnext >= R && !diag_draining) diag_draining = true, diag_t0 = diag_now();  // the stream is idle here
+#endif
+            if (n > (unsigned)slice) {  // push the excess children onto the spill stack
+                const int m = (int)n - slice;
+                if ((rc = grow_spill(spill_n + m))) return rc;
+                hipLaunchKernelGGL(k_queue_move, dim3((m + 255) / 256), dim3(256), 0, st, *cur, slice, qs, (int)spill_n, m);
+                HIP_OK(hipGetLastError());
+                spill_n += m;
+                spilled += (uint64_t)m;
+                n = (unsigned)slice;
+                HIP_OK(hipMemsetD32Async((hipDeviceptr_t)cur->count, (int)n, 1, st));
+            } else if (spill_n > 0 && n < (unsigned)fill) {  // pop spilled children before new roots
+                const int m = (int)std::min<long long>((long long)fill - n, spill_n);
+                spill_n -= m;
+                hipLaunchKernelGGL(k_queue_move, dim3((m + 255) / 256), dim3(256), 0, st, qs, (int)spill_n, *cur, (int)n, m);
+                HIP_OK(hipGetLastError());
+                n += (unsigned)m;
+                HIP_OK(hipMemsetD32Async((hipDeviceptr_t)cur->count, (int)n, 1, st));
+            }
+            const unsigned n_children = n;  // [0, n_children) children, [n_children, n) fresh roots
+            if (rnext < R && n < (unsigned)fill) {  // refill with roots (appended through node_entry)
+                const int m = (int)std::min<long long>((long long)fill - n, R - rnext);
+                hipLaunchKernelGGL(active ? k_roots_t<true> : k_roots_t<false>, dim3((m + 256 * kRootsPT - 1) / (256 * kRootsPT)),
+                                   dim3(256), 0, st, P, (const int*)D.hit_f.p, nact, a, rnext, m, *cur, std::max(1, nminor), b - a,
+                                   rtab, P.root_pnw ? 1 : 0, active);
+                HIP_OK(hipGetLastError());
+                rnext += m;
+                if ((rc = read_count(&n))) return rc;
+            }
+            if (n == 0) {
+                if (rnext >= R && spill_n == 0) break;
+                continue;  // every root of the refill terminated at entry: refill again
+            }
+            if (stale) {  // a shard serves at most ceil(blocks / 32) workgroups of 256 nodes per generation
+                const unsigned per_shard = ((n + 255) / 256 + kSlotShards - 1) / kSlotShards * 256;
+                unsigned bump = 0;
+                for (int sh = 0; sh < kSlotShards; sh++) bump = std::max(bump, hctrl[16 * sh]);
+                if (bump + per_shard > (unsigned)T.rcap) {
+                    const long long nr = std::max<long long>(2ll * T.rcap, (long long)bump + per_shard + 4096);
+                    if (nr * kSlotShards > (1ll << 30)) {
+                        set_error("MIS reduction slot pool beyond 2^30 slots");
+                        return MCPT_E_DEVICE;
+                    }
+                    if ((rc = alloc_slots(D.sl, (int)nr, T, st, true, rp, hctrl))) return rc;
                 }
-                if ((rc = alloc_slots(D.sl, (int)nr, T, st, true, rp, hctrl))) return rc;
             }
-        }
-        gens++;
-        nodes_total += (uint64_t)n;
-        const int ni = (int)n;
-        // prep_seconds / prep_launches time the full light-prep kernel (k_prep_pk2) launches only
-        bool timed = false;
-        if (needs_prep) {
-            PrepCache cx{};  // the children's full prep: no cache, the picks' slack
-            int nmask = 0;   // nodes [0, nmask) have candidate words (k_prep_exact)
-            int root_off = INT_MAX;  // nodes [root_off, ni) are roots with a cached candidate list
-            cx.slack = slack;
-            cx.maybe = maybe_list;
-            if (exact_pick) {
-                HIP_OK(hipMemsetAsync(exact_list, 0, 4, st));
-                HIP_OK(hipMemsetAsync(maybe_list, 0, 4, st));
-            }
-            if (pc.use || small_use) {  // children: full prep; roots: pick from the root-point cache
-                const int nc = (int)n_children, nr = ni - nc;
-                if (nc > 0) {
-                    // MCPT_DEBUG_FUSED_CULL (A/B): the cheap stages inside k_prep_pk2, wave per node (variant 8)
-                    uint64_t* cmasks = (o->flags & MCPT_DEBUG_FUSED_CULL) ? nullptr : masks;
-                    nmask = prep_writes_masks(D.d, cmasks) ? nc : 0;
+            gens++;
+            nodes_total += (uint64_t)n;
+            const int ni = (int)n;
+            // prep_seconds / prep_launches time the full light-prep kernel (k_prep_pk2) launches only
+            bool timed = false;
+            if (needs_prep) {
+                PrepCache cx{};  // the children's full prep: no cache, the picks' slack
+                int nmask = 0;   // nodes [0, nmask) have candidate words (k_prep_exact)
+                int root_off = INT_MAX;  // nodes [root_off, ni) are roots with a cached candidate list
+                cx.slack = slack;
+                cx.maybe = maybe_list;
+                if (exact_pick) {
+                    HIP_OK(hipMemsetAsync(exact_list, 0, 4, st));
+                    HIP_OK(hipMemsetAsync(maybe_list, 0, 4, st));
+                }
+                if (pc.use || small_use) {  // children: full prep; roots: pick from the root-point cache
+                    const int nc = (int)n_children, nr = ni - nc;
+                    if (nc > 0) {
+                        // MCPT_DEBUG_FUSED_CULL (A/B): the cheap stages inside k_prep_pk2, wave per node (variant 8)
+                        uint64_t* cmasks = (o->flags & MCPT_DEBUG_FUSED_CULL) ? nullptr : masks;
+                        nmask = prep_writes_masks(D.d, cmasks) ? nc : 0;
+                        HIP_OK(hipEventRecord(D.evp0, st));
+                        HIP_OK(launch_prep(-1, D.d, o->seed, nc, cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr,
+                                           cur->wsum, cur->pick, nullptr, P.stats, (unsigned*)D.work.p, st, cx, cmasks,
+                                           count_c1, fp32, corder));
+                        HIP_OK(hipEventRecord(D.evp1, st));
+                        timed = true;
+                    }
+                    // the cached roots are counted here (nr is known): the pick kernels' per-wave atomics on
+                    // one statistics word serialised at ~88 per us -- 2.3 of k_prep_lane_pick's 2.5 ms per C5 launch
+                    if (nr > 0) cached_roots += (uint64_t)nr;
+                    if (nr > 0 && small_use) {
+                        hipLaunchKernelGGL(k_prep_lane_pick, dim3((nr + 255) / 256), dim3(256), 0, st, D.d, o->seed, nr,
+                                           cur->pixel + nc, cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc,
+                                           nullptr, scache);
+                        HIP_OK(hipGetLastError());
+                    } else if (nr > 0) {
+                        root_off = nc;
+                        PrepCache pr = pc;
+                        pr.exact = exact_list;
+                        pr.exact_off = nc;
+                        if (MCPT_PICK_GROUPS && nchunks <= 64) {  // 16 lanes per root
+                            const int blocks = std::max(1, std::min((nr + 16 * kPickSlots - 1) / (16 * kPickSlots), 8192));
+                            hipLaunchKernelGGL(k_prep_pick_g, dim3(blocks), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
+                                               cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr,
+                                               nchunks, pr);
+                        } else {
+                            const int blocks = std::max(1, std::min((nr + 4 * kPickNodes - 1) / (4 * kPickNodes), 8192));
+                            hipLaunchKernelGGL(k_prep_pick, dim3(blocks), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
+                                               cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr,
+                                               nchunks, pr);
+                        }
+                        HIP_OK(hipGetLastError());
+                    }
+                } else {
+                    nmask = prep_writes_masks(D.d, masks) ? ni : 0;
                     HIP_OK(hipEventRecord(D.evp0, st));
-                    HIP_OK(launch_prep(-1, D.d, o->seed, nc, cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr,
-                                       cur->wsum, cur->pick, nullptr, P.stats, (unsigned*)D.work.p, st, cx, cmasks,
+                    HIP_OK(launch_prep(-1, D.d, o->seed, ni, cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr,
+                                       cur->wsum, cur->pick, nullptr, P.stats, (unsigned*)D.work.p, st, cx, masks,
                                        count_c1, fp32, corder));
                     HIP_OK(hipEventRecord(D.evp1, st));
                     timed = true;
                 }
-                // the cached roots are counted here (nr is known): the pick kernels' per-wave atomics on
-                // one statistics word serialised at ~88 per us -- 2.3 of k_prep_lane_pick's 2.5 ms per C5 launch
-                if (nr > 0) cached_roots += (uint64_t)nr;
-                if (nr > 0 && small_use) {
-                    hipLaunchKernelGGL(k_prep_lane_pick, dim3((nr + 255) / 256), dim3(256), 0, st, D.d, o->seed, nr,
-                                       cur->pixel + nc, cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc,
-                                       nullptr, scache);
-                    HIP_OK(hipGetLastError());
-                } else if (nr > 0) {
-                    root_off = nc;
-                    PrepCache pr = pc;
-                    pr.exact = exact_list;
-                    pr.exact_off = nc;
-                    if (MCPT_PICK_GROUPS && nchunks <= 64) {  // 16 lanes per root
-                        const int blocks = std::max(1, std::min((nr + 16 * kPickSlots - 1) / (16 * kPickSlots), 8192));
-                        hipLaunchKernelGGL(k_prep_pick_g, dim3(blocks), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
-                                           cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr,
-                                           nchunks, pr);
-                    } else {
-                        const int blocks = std::max(1, std::min((nr + 4 * kPickNodes - 1) / (4 * kPickNodes), 8192));
-                        hipLaunchKernelGGL(k_prep_pick, dim3(blocks), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
-                                           cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr,
-                                           nchunks, pr);
-                    }
+                prep_launches += timed;
+                if (exact_pick) {  // the band's nodes: the reference's literal prep and pick
+                    hipLaunchKernelGGL(k_prep_band, dim3(kBandBlocks), dim3(256), 0, st, D.d, maybe_list, slack, cur->p, cur->cap,
+                                       masks, nmask, nchunks, exact_list, P.stats);
+                    // launch ids 2g and 2g + 1 (generation g): the follow-up launch reads what the first one stored
+                    const int lid = (int)std::min<uint64_t>(2 * gens, 2046);
+                    int* defer = MCPT_EXACT_DEFER && rl.slot && !(o->flags & MCPT_DEBUG_NO_EXACT_DEFER) ? maybe_list
+                                                                                                        : nullptr;  // k_prep_band has consumed it
+                    if (defer) HIP_OK(hipMemsetAsync(defer, 0, 4, st));
+                    hipLaunchKernelGGL(k_prep_exact, dim3(exact_blocks(D.d.NL)), dim3(kExactBlock), 0, st, D.d, o->seed, exact_list,
+                                       cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr, cur->wsum, cur->pick,
+                                       nullptr, P.stats, exact_scr, masks, nmask, nchunks, pc.use ? pc.lst : nullptr,
+                                       pc.use ? pc.info : nullptr, pc.lstride, root_off,
+                                       RootLit{rl.slot, rl.pool, rl.cap, rl.stride, lid}, defer);
+                    if (defer)  // the deferred roots (counted above already: no stats)
+                        hipLaunchKernelGGL(k_prep_exact, dim3(exact_blocks(D.d.NL)), dim3(kExactBlock), 0, st, D.d, o->seed, defer,
+                                           cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr, cur->wsum,
+                                           cur->pick, nullptr, nullptr, exact_scr, masks, nmask, nchunks, pc.use ? pc.lst : nullptr,
+                                           pc.use ? pc.info : nullptr, pc.lstride, root_off,
+                                           RootLit{rl.slot, rl.pool, rl.cap, rl.stride, lid + 1}, nullptr);
                     HIP_OK(hipGetLastError());
                 }
-            } else {
-                nmask = prep_writes_masks(D.d, masks) ? ni : 0;
-                HIP_OK(hipEventRecord(D.evp0, st));
-                HIP_OK(launch_prep(-1, D.d, o->seed, ni, cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr,
-                                   cur->wsum, cur->pick, nullptr, P.stats, (unsigned*)D.work.p, st, cx, masks,
-                                   count_c1, fp32, corder));
-                HIP_OK(hipEventRecord(D.evp1, st));
-                timed = true;
             }
-            prep_launches += timed;
-            if (exact_pick) {  // the band's nodes: the reference's literal prep and pick
-                hipLaunchKernelGGL(k_prep_band, dim3(kBandBlocks), dim3(256), 0, st, D.d, maybe_list, slack, cur->p, cur->cap,
-                                   masks, nmask, nchunks, exact_list, P.stats);
-                // launch ids 2g and 2g + 1 (generation g): the follow-up launch reads what the first one stored
-                const int lid = (int)std::min<uint64_t>(2 * gens, 2046);
-                int* defer = MCPT_EXACT_DEFER && rl.slot && !(o->flags & MCPT_DEBUG_NO_EXACT_DEFER) ? maybe_list
-                                                                                                    : nullptr;  // k_prep_band has consumed it
-                if (defer) HIP_OK(hipMemsetAsync(defer, 0, 4, st));
-                hipLaunchKernelGGL(k_prep_exact, dim3(exact_blocks(D.d.NL)), dim3(kExactBlock), 0, st, D.d, o->seed, exact_list,
-                                   cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr, cur->wsum, cur->pick,
-                                   nullptr, P.stats, exact_scr, masks, nmask, nchunks, pc.use ? pc.lst : nullptr,
-                                   pc.use ? pc.info : nullptr, pc.lstride, root_off,
-                                   RootLit{rl.slot, rl.pool, rl.cap, rl.stride, lid}, defer);
-                if (defer)  // the deferred roots (counted above already: no stats)
-                    hipLaunchKernelGGL(k_prep_exact, dim3(exact_blocks(D.d.NL)), dim3(kExactBlock), 0, st, D.d, o->seed, defer,
-                                       cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr, cur->wsum,
-                                       cur->pick, nullptr, nullptr, exact_scr, masks, nmask, nchunks, pc.use ? pc.lst : nullptr,
-                                       pc.use ? pc.info : nullptr, pc.lstride, root_off,
-                                       RootLit{rl.slot, rl.pool, rl.cap, rl.stride, lid + 1}, nullptr);
-                HIP_OK(hipGetLastError());
-            }
-        }
-        HIP_OK(hipMemsetAsync(nxt->count, 0, 4, st));
-        const dim3 g256((ni + 255) / 256), b256(256);
-        unsigned long long* tcnt = P.stats + 8;  // node visits, triangle tests (MCPT_DEBUG_COUNT_TRAVERSAL)
-    auto launch_rays = [&](int first_set, int nsets, int seeded) {
-        // shade() with uniform-area light points: its shadow and bounce rays run 4% faster on the refilling
-        // persistent waves even on the small stand-in (shade_area 2 104-2 126 -> 2 185-2 191 Msamples/s, same
-        // binary, profiles/round5_ab_persistent_veach.txt); MIS and shade() are slower there (-1%, -1%)
-        if (rays_pers) {
-            unsigned* pool = (unsigned*)D.work.p + 8;
-            (void)hipMemsetAsync(pool, 0, sizeof(unsigned), st);
-            const long long items = (long long)nsets * ni;
-            const int blocks = (int)std::max<long long>(1, std::min<long long>((items + kRayBlock - 1) / kRayBlock, 2048));
-            if (rays_cw8) {
-                if (count_trav)
-                    hipLaunchKernelGGL(k_rays_cw8<true>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux, first_set, nsets,
-                                       pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
+            HIP_OK(hipMemsetAsync(nxt->count, 0, 4, st));
+            const dim3 g256((ni + 255) / 256), b256(256);
+            unsigned long long* tcnt = P.stats + 8;  // node visits, triangle tests (MCPT_DEBUG_COUNT_TRAVERSAL)
+        auto launch_rays = [&](int first_set, int nsets, int seeded) {
+            // shade() with uniform-area light points: its shadow and bounce rays run 4% faster on the refilling
+            // persistent waves even on the small stand-in (shade_area 2 104-2 126 -> 2 185-2 191 Msamples/s, same
+            // binary, profiles/round5_ab_persistent_veach.txt); MIS and shade() are slower there (-1%, -1%)
+            if (rays_pers) {
+                unsigned* pool = (unsigned*)D.work.p + 8;
+                (void)hipMemsetAsync(pool, 0, sizeof(unsigned), st);
+                const long long items = (long long)nsets * ni;
+                const int blocks = (int)std::max<long long>(1, std::min<long long>((items + kRayBlock - 1) / kRayBlock, 2048));
+                if (rays_cw8) {
+                    if (count_trav)
+                        hipLaunchKernelGGL(k_rays_cw8<true>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux, first_set, nsets,
+                                           pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
+                    else
+                        hipLaunchKernelGGL(k_rays_cw8<false>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux, first_set, nsets,
+                                           pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
+                } else if (count_trav)
+                    hipLaunchKernelGGL(k_rays_persistent<true>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux,
+                                       first_set, nsets, pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
                 else
-                    hipLaunchKernelGGL(k_rays_cw8<false>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux, first_set, nsets,
-                                       pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
-            } else if (count_trav)
-                hipLaunchKernelGGL(k_rays_persistent<true>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux,
-                                   first_set, nsets, pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
-            else
-                hipLaunchKernelGGL(k_rays_persistent<false>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux,
-                                   first_set, nsets, pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
-        } else {
-            hipLaunchKernelGGL(K_MIS_RAYS, dim3((ni + kRayBlock - 1) / kRayBlock, nsets), dim3(kRayBlock), 0, st, D.d,
-                               *cur, ni, aux, first_set, tcnt, MCPT_SEED_LIGHT ? seeded : 0,
-                               o->mode == MCPT_MODE_MIS ? 0 : 1);
-        }
-    };
-        // trace_seconds: HIP events around the traversal kernel (k_mis_rays; BRDF-only: k_extend_brdf)
-        if (!fused && o->mode == MCPT_MODE_MIS) {
-            hipLaunchKernelGGL(stale ? k_mis_gen<true> : k_mis_gen<false>, g256, b256, 0, st, P, *cur, ni, aux);
-            HIP_OK(hipEventRecord(D.evr0, st));
-            launch_rays(0, 3, 1);
-            HIP_OK(hipEventRecord(D.evr1, st));
-            hipLaunchKernelGGL(stale ? k_mis_combine<true> : k_mis_combine<false>, g256, b256, 0, st, P, *cur, ni, aux,
-                               *nxt, T, rp);
-            if (stale) {  // one level of the bottom-up reduction per generation
-                hipLaunchKernelGGL(k_mis_complete, dim3(32, kSlotShards), dim3(256), 0, st, P, T, rp);
-                hipLaunchKernelGGL(k_slot_fixup, dim3(1), dim3(kSlotShards), 0, st, T, rp);
-                rp ^= 1;
+                    hipLaunchKernelGGL(k_rays_persistent<false>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux,
+                                       first_set, nsets, pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
+            } else {
+                hipLaunchKernelGGL(K_MIS_RAYS, dim3((ni + kRayBlock - 1) / kRayBlock, nsets), dim3(kRayBlock), 0, st, D.d,
+                                   *cur, ni, aux, first_set, tcnt, MCPT_SEED_LIGHT ? seeded : 0,
+                                   o->mode == MCPT_MODE_MIS ? 0 : 1);
             }
-        } else if (!fused && (o->mode == MCPT_MODE_SHADE || o->mode == MCPT_MODE_SHADE_AREA)) {
-            hipLaunchKernelGGL(k_shade_gen, g256, b256, 0, st, P, *cur, ni, aux);
-            HIP_OK(hipEventRecord(D.evr0, st));
-            launch_rays(0, 2, 1);
-            HIP_OK(hipEventRecord(D.evr1, st));
-            hipLaunchKernelGGL(k_shade_combine, g256, b256, 0, st, P, *cur, ni, aux, *nxt);
-        } else if (!fused) {
-            hipLaunchKernelGGL(k_brdf_gen, g256, b256, 0, st, P, *cur, ni, aux);
-            HIP_OK(hipEventRecord(D.evr0, st));
-            launch_rays(1, 1, 0);
-            HIP_OK(hipEventRecord(D.evr1, st));
-            hipLaunchKernelGGL(k_brdf_combine, g256, b256, 0, st, P, *cur, ni, aux, *nxt);
-        } else {
-            HIP_OK(hipEventRecord(D.evr0, st));
-            hipLaunchKernelGGL(count_trav ? k_extend_brdf<true> : k_extend_brdf<false>, dim3((ni + kBrdfBlock - 1) / kBrdfBlock),
-                               dim3(kBrdfBlock), 0, st, P, *cur, ni, *nxt);
-            HIP_OK(hipEventRecord(D.evr1, st));
+        };
+            // trace_seconds: HIP events around the traversal kernel (k_mis_rays; BRDF-only: k_extend_brdf)
+            if (!fused && o->mode == MCPT_MODE_MIS) {
+                hipLaunchKernelGGL(stale ? k_mis_gen<true> : k_mis_gen<false>, g256, b256, 0, st, P, *cur, ni, aux);
+                HIP_OK(hipEventRecord(D.evr0, st));
+                launch_rays(0, 3, 1);
+                HIP_OK(hipEventRecord(D.evr1, st));
+                hipLaunchKernelGGL(stale ? k_mis_combine<true> : k_mis_combine<false>, g256, b256, 0, st, P, *cur, ni, aux,
+                                   *nxt, T, rp);
+                if (stale) {  // one level of the bottom-up reduction per generation
+                    hipLaunchKernelGGL(k_mis_complete, dim3(32, kSlotShards), dim3(256), 0, st, P, T, rp);
+                    hipLaunchKernelGGL(k_slot_fixup, dim3(1), dim3(kSlotShards), 0, st, T, rp);
+                    rp ^= 1;
+                }
+            } else if (!fused && (o->mode == MCPT_MODE_SHADE || o->mode == MCPT_MODE_SHADE_AREA)) {
+                hipLaunchKernelGGL(k_shade_gen, g256, b256, 0, st, P, *cur, ni, aux);
+                HIP_OK(hipEventRecord(D.evr0, st));
+                launch_rays(0, 2, 1);
+                HIP_OK(hipEventRecord(D.evr1, st));
+                hipLaunchKernelGGL(k_shade_combine, g256, b256, 0, st, P, *cur, ni, aux, *nxt);
+            } else if (!fused) {
+                hipLaunchKernelGGL(k_brdf_gen, g256, b256, 0, st, P, *cur, ni, aux);
+                HIP_OK(hipEventRecord(D.evr0, st));
+                launch_rays(1, 1, 0);
+                HIP_OK(hipEventRecord(D.evr1, st));
+                hipLaunchKernelGGL(k_brdf_combine, g256, b256, 0, st, P, *cur, ni, aux, *nxt);
+            } else {
+                HIP_OK(hipEventRecord(D.evr0, st));
+                hipLaunchKernelGGL(count_trav ? k_extend_brdf<true> : k_extend_brdf<false>, dim3((ni + kBrdfBlock - 1) / kBrdfBlock),
+                                   dim3(kBrdfBlock), 0, st, P, *cur, ni, *nxt);
+                HIP_OK(hipEventRecord(D.evr1, st));
+            }
+            HIP_OK(hipGetLastError());
+            trace_launches++;
+            if (timed) {
+                float ms = 0;
+                HIP_OK(hipEventSynchronize(D.evp1));
+                HIP_OK(hipEventElapsedTime(&ms, D.evp0, D.evp1));
+                prep_ms += ms;
+            }
+            {
+                float ms = 0;
+                HIP_OK(hipEventSynchronize(D.evr1));
+                HIP_OK(hipEventElapsedTime(&ms, D.evr0, D.evr1));
+                trace_ms += ms;
+            }
+            std::swap(cur, nxt);
+            // (an adaptive call reports the samples of all its runs so far against the cap's total)
+            if (o->progress && o->progress(o->progress_user, roots_total - (uint64_t)(R - rnext), (uint64_t)(s1 - s0) * npx)) {
+                HIP_OK(hipStreamSynchronize(st));
+                set_error("render cancelled by the progress callback after %lld of %lld camera samples", rnext, R);
+                return MCPT_E_CANCELLED;
+            }
         }
-        HIP_OK(hipGetLastError());
-        trace_launches++;
-        if (timed) {
-            float ms = 0;
-            HIP_OK(hipEventSynchronize(D.evp1));
-            HIP_OK(hipEventElapsedTime(&ms, D.evp0, D.evp1));
-            prep_ms += ms;
-        }
-        {
-            float ms = 0;
-            HIP_OK(hipEventSynchronize(D.evr1));
-            HIP_OK(hipEventElapsedTime(&ms, D.evr0, D.evr1));
-            trace_ms += ms;
-        }
-        std::swap(cur, nxt);
-        if (o->progress && o->progress(o->progress_user, (uint64_t)rnext, (uint64_t)R)) {
+        while (stale) {  // drain the reduction: the trees' remaining levels up to their roots
+            HIP_OK(hipMemcpyAsync(D.pinned_count + 16, T.ctrl, kCtrlBytes, hipMemcpyDeviceToHost, st));
             HIP_OK(hipStreamSynchronize(st));
-            set_error("render cancelled by the progress callback after %lld of %lld camera samples", rnext, R);
-            return MCPT_E_CANCELLED;
+            unsigned pending = 0;
+            for (int sh = 0; sh < kSlotShards; sh++) pending += hctrl[16 * sh + 4 + rp];
+            if (pending == 0) break;
+            hipLaunchKernelGGL(k_mis_complete, dim3(32, kSlotShards), dim3(256), 0, st, P, T, rp);
+            hipLaunchKernelGGL(k_slot_fixup, dim3(1), dim3(kSlotShards), 0, st, T, rp);
+            rp ^= 1;
         }
-    }
-    while (stale) {  // drain the reduction: the trees' remaining levels up to their roots
-        HIP_OK(hipMemcpyAsync(D.pinned_count + 16, T.ctrl, kCtrlBytes, hipMemcpyDeviceToHost, st));
+#if MCPT_ADAPTIVE_DIAG
         HIP_OK(hipStreamSynchronize(st));
-        unsigned pending = 0;
-        for (int sh = 0; sh < kSlotShards; sh++) pending += hctrl[16 * sh + 4 + rp];
-        if (pending == 0) break;
-        hipLaunchKernelGGL(k_mis_complete, dim3(32, kSlotShards), dim3(256), 0, st, P, T, rp);
-        hipLaunchKernelGGL(k_slot_fixup, dim3(1), dim3(kSlotShards), 0, st, T, rp);
-        rp ^= 1;
+        diag_runs++;
+        if (diag_draining) diag_drain_ms += diag_ms(diag_t0, diag_now());
+#endif
+        return MCPT_OK;
+    };
+    if (!ad) {
+        if ((rc = wavefront(s0, s1, nullptr, npx))) return rc;
+    } else {
+        // Adaptive passes (include/mcpt.h, mcpt_adaptive_opts): pass 0 renders samples [0, min_spp) of every
+        // pixel, each later pass the next pass_spp (cut at the cap) of the active pixels; the first half of a
+        // pass adds into A, the second into B.  After a pass k_adaptive_error rates the active pixels and
+        // k_adaptive_mark / k_adaptive_compact build the next ascending list.
+        const mcpt_adaptive_opts& ao = ad->a;
+        double* acc[2] = {(double*)D.ad_acc[0].p, (double*)D.ad_acc[1].p};
+        int* count = ad->count ? ad->count : (int*)D.ad_count.p;
+        double* noise = ad->noise ? ad->noise : (double*)D.ad_noise.p;
+        unsigned* blk = (unsigned*)D.ad_blk.p;
+        HIP_OK(hipMemsetAsync(acc[0], 0, 24ull * npx, st));
+        HIP_OK(hipMemsetAsync(acc[1], 0, 24ull * npx, st));
+        const int* active = nullptr;  // pass 0: the whole frame
+        int nact = npx, n = 0, li = 0;
+        D.ad_last_list = -1, D.ad_last_n = 0;
+        for (int pass = 0; nact > 0 && n < ao.max_spp; pass++) {
+            const int pa = n, pb = std::min(n + (pass == 0 ? ao.min_spp : ao.pass_spp), ao.max_spp), ph = pa + (pb - pa) / 2;
+            const int cut[3] = {pa, ph, pb};
+            for (int half = 0; half < 2; half++) {
+                if (cut[half + 1] == cut[half]) continue;  // a one-sample last pass: all of it in B
+                if (stale && (pass > 0 || half > 0)) {  // an empty slot pool, as alloc_slots left it for the first run
+                    HIP_OK(hipMemsetAsync(T.ctrl, 0, kCtrlBytes, st));
+                    rp = 0;
+                }
+                P.fb = acc[half];
+                if ((rc = wavefront(cut[half], cut[half + 1], active, nact))) return rc;
+            }
+            n = pb;
+            unsigned char* state = (unsigned char*)D.ad_state[li].p;
+#if MCPT_ADAPTIVE_DIAG
+            const auto diag_k0 = diag_now();  // the stream is idle (the run's last read_count)
+#endif
+            hipLaunchKernelGGL(k_adaptive_error, dim3((nact + 255) / 256), dim3(256), 0, st, active, nact, acc[0], acc[1], n,
+                               ao.threshold, noise, count, state);
+            HIP_OK(hipGetLastError());
+#if MCPT_ADAPTIVE_DIAG
+            if (n >= ao.max_spp) {
+                HIP_OK(hipStreamSynchronize(st));
+                diag_kernel_ms += diag_ms(diag_k0, diag_now());
+            }
+#endif
+            if (n >= ao.max_spp) break;
+            unsigned char* state_next = (unsigned char*)D.ad_state[li ^ 1].p;
+            int* list = (int*)D.ad_list[li].p;  // not the list this pass read (ad_list[li ^ 1], or none)
+            hipLaunchKernelGGL(k_adaptive_mark, dim3(nblk), dim3(256), 0, st, state, state_next, W, H, ao.radius, blk);
+            hipLaunchKernelGGL(k_adaptive_compact, dim3(nblk), dim3(256), 0, st, state_next, npx, blk, list, blk + nblk);
+            HIP_OK(hipGetLastError());
+            HIP_OK(hipMemcpyAsync(D.pinned_count, blk + nblk, 4, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            nact = (int)std::min<unsigned>(D.pinned_count[0], (unsigned)npx);
+#if MCPT_ADAPTIVE_DIAG
+            diag_kernel_ms += diag_ms(diag_k0, diag_now());
+#endif
+            active = list;
+            D.ad_last_list = li, D.ad_last_n = nact;
+            li ^= 1;
+        }
+#if MCPT_ADAPTIVE_DIAG
+        const auto diag_f0 = diag_now();
+#endif
+        hipLaunchKernelGGL(k_adaptive_finalize, dim3((3 * npx + 255) / 256), dim3(256), 0, st, dfb, acc[0], acc[1], count, npx);
+        HIP_OK(hipGetLastError());
+#if MCPT_ADAPTIVE_DIAG
+        HIP_OK(hipStreamSynchronize(st));
+        diag_kernel_ms += diag_ms(diag_f0, diag_now());
+#endif
     }
     HIP_OK(hipEventRecord(D.ev1, st));
     HIP_OK(hipEventSynchronize(D.ev1));
     float ms = 0;
     HIP_OK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
+#if MCPT_ADAPTIVE_DIAG
+    fprintf(stderr, "adaptive diag: runs %d drain_ms %.3f adaptive_kernels_ms %.3f total_ms %.3f\n", diag_runs, diag_drain_ms,
+            diag_kernel_ms, (double)ms);
+#endif
     if (stats) {
         unsigned long long hs[kStatBytes / 8] = {0};
         HIP_OK(hipMemcpy(hs, D.stats.p, kStatBytes, hipMemcpyDeviceToHost));
         for (int k = 1; k <= kStatShards; k++) hs[2] += hs[16 * k], hs[3] += hs[16 * k + 1];  // ray_stats shards
         stats->seconds = ms * 1e-3;
         stats->device_seconds[0] = stats->seconds;
-        stats->camera_samples = (uint64_t)(s1 - s0) * npx;
+        stats->camera_samples = roots_total;  // plain: (s1 - s0) * npx; adaptive: the sum of the count map
         stats->light_evals_survived = hs[1];
         stats->rays = hs[2];
         stats->light_rays = hs[3];
@@ -5561,19 +5794,19 @@ int check_opts(const mcpt_render_opts* o) {
 
 // the caller's framebuffer must be device memory of `device` (fp64 hardware atomics are lost on
 // host / managed memory, and a host pointer the runtime does not know would fault the GPU)
-int check_device_buffer(const void* p, int device) {
+int check_device_buffer(const void* p, int device, const char* name = "dev_out_rgb") {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();
-        set_error("dev_out_rgb is not coarse-grained device memory (unknown to the HIP runtime)");
+        set_error("%s is not coarse-grained device memory (unknown to the HIP runtime)", name);
         return MCPT_E_INVALID;
     }
     if (a.type != hipMemoryTypeDevice || a.isManaged) {
-        set_error("dev_out_rgb is not coarse-grained device memory (memory type %d, managed %d)", (int)a.type, a.isManaged);
+        set_error("%s is not coarse-grained device memory (memory type %d, managed %d)", name, (int)a.type, a.isManaged);
         return MCPT_E_INVALID;
     }
     if (a.device != device) {
-        set_error("dev_out_rgb lives on device %d, the render's root device is %d", a.device, device);
+        set_error("%s lives on device %d, the render's root device is %d", name, a.device, device);
         return MCPT_E_INVALID;
     }
     return MCPT_OK;
@@ -6114,7 +6347,9 @@ void mcpt_scene_destroy(mcpt_scene* sc) {
         std::vector<DevBuf*> bufs = {&D->hit_f, &D->hit_tbg, &D->fb, &D->rank_fb, &D->stats, &D->work, &D->cache_bt, &D->cache_lst,
                                      &D->cache_info, &D->cache_w, &D->masks, &D->g_start, &D->g_tri, &D->root_pnw,
                                      &D->root_kind, &D->exact, &D->exact_scr, &D->slack, &D->lit_slot, &D->lit_pool,
-                                     &D->sc_cum, &D->sc_wsum, &D->sc_last, &D->cull_keys, &D->cull_order, &D->cull_count};
+                                     &D->sc_cum, &D->sc_wsum, &D->sc_last, &D->cull_keys, &D->cull_order, &D->cull_count,
+                                     &D->ad_acc[0], &D->ad_acc[1], &D->ad_list[0], &D->ad_list[1], &D->ad_state[0],
+                                     &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise};
         for (int k = 0; k < 14; k++) bufs.insert(bufs.end(), {&D->qa[k], &D->qb[k], &D->qs[k]});
         for (int k = 0; k < 9; k++) bufs.push_back(&D->aux[k]);
         for (int k = 0; k < 13; k++) bufs.push_back(&D->sl[k]);
@@ -6260,6 +6495,113 @@ static int render_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render
     if (rank != 0) return MCPT_OK;  // the job total lands on rank 0; this rank's out_rgb is unchanged
     HIP_OK(hipMemcpyAsync(out_rgb, D->fb.p, n * sizeof(double), hipMemcpyDeviceToHost, D->stream));
     HIP_OK(hipStreamSynchronize(D->stream));
+    return MCPT_OK;
+}
+
+void mcpt_adaptive_opts_init(mcpt_adaptive_opts* a) {
+    if (!a) return;
+    std::memset((void*)a, 0, sizeof *a);
+    a->struct_size = sizeof *a;
+    a->min_spp = 16;
+    a->pass_spp = 16;
+    a->max_spp = 1024;
+    a->threshold = 0.05;
+    a->radius = 1;
+}
+
+// the checks of an adaptive call that need no device; *ok = base with spp = the cap
+static int check_adaptive(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* base, const mcpt_adaptive_opts* a,
+                          const void* out, mcpt_render_opts* ok) {
+    if (!sc || !base || !a || !out) {
+        set_error("null argument");
+        return MCPT_E_INVALID;
+    }
+    if (base->struct_size == sizeof(mcpt_render_opts) && (base->num_devices > 0 || base->comm)) {
+        set_error("adaptive render is single-device: a device list or a communicator is not supported");
+        return MCPT_E_INVALID;
+    }
+    int rc;
+    if ((rc = check_opts(base)) || (rc = validate_camera(cam))) return rc;
+    if (a->struct_size != sizeof(mcpt_adaptive_opts)) {
+        set_error("mcpt_adaptive_opts.struct_size is %u, this library expects %zu (use mcpt_adaptive_opts_init / the "
+                  "mcpt.h of MCPT_VERSION %d)", a->struct_size, sizeof(mcpt_adaptive_opts), MCPT_VERSION);
+        return MCPT_E_INVALID;
+    }
+    mcpt_render_opts def;
+    mcpt_render_opts_init(&def);
+    if (base->spp != def.spp || base->sample_begin != 0 || base->sample_end != 0) {
+        set_error("adaptive render: spp, sample_begin and sample_end of the base options must be left at their defaults "
+                  "(spp %d, range [%d,%d)); the sample counts come from mcpt_adaptive_opts", base->spp, base->sample_begin,
+                  base->sample_end);
+        return MCPT_E_INVALID;
+    }
+    if (a->min_spp < 2 || (a->min_spp & 1) || a->pass_spp < 2 || (a->pass_spp & 1) || a->max_spp < a->min_spp ||
+        !(a->threshold >= 0) || a->radius < 0 || a->radius > 4) {
+        set_error("invalid adaptive options (min_spp %d and pass_spp %d must be even and >= 2, max_spp %d >= min_spp, "
+                  "threshold %g >= 0, radius %d in 0..4)", a->min_spp, a->pass_spp, a->max_spp, a->threshold, a->radius);
+        return MCPT_E_INVALID;
+    }
+    *ok = *base;
+    ok->spp = a->max_spp;
+    return validate_render(ok);
+}
+
+int mcpt_render_adaptive_device(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* base,
+                                const mcpt_adaptive_opts* a, double* dev_out, int32_t* dev_count, double* dev_noise,
+                                mcpt_stats* stats) {
+    mcpt_render_opts ok;
+    int rc;
+    if ((rc = check_adaptive(sc, cam, base, a, dev_out, &ok))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    if ((rc = get_device_state(sc, ok.device, &D))) return rc;
+    if ((rc = check_device_buffer(dev_out, D->device)) ||
+        (dev_count && (rc = check_device_buffer(dev_count, D->device, "dev_count"))) ||
+        (dev_noise && (rc = check_device_buffer(dev_noise, D->device, "dev_noise"))))
+        return rc;
+    // the caller's buffers may still be written by work on other streams (e.g. torch's)
+    HIP_OK(hipDeviceSynchronize());
+    const AdaptiveRun ad{*a, dev_count, dev_noise};
+    mcpt_stats st{};
+    if ((rc = render_on_device(sc, *D, cam, &ok, dev_out, &st, &ad))) return rc;
+    copy_stats(base, st, stats);
+    return MCPT_OK;
+}
+
+int mcpt_render_adaptive(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* base, const mcpt_adaptive_opts* a,
+                         double* out_rgb, int32_t* count, double* noise, mcpt_stats* stats) {
+    mcpt_render_opts ok;
+    int rc;
+    if ((rc = check_adaptive(sc, cam, base, a, out_rgb, &ok))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    if ((rc = get_device_state(sc, ok.device, &D))) return rc;
+    const size_t npx = (size_t)cam->width * cam->height;
+    if ((rc = ensure(D->fb, 3 * npx * sizeof(double)))) return rc;
+    HIP_OK(hipMemcpyAsync(D->fb.p, out_rgb, 3 * npx * sizeof(double), hipMemcpyHostToDevice, D->stream));
+    const AdaptiveRun ad{*a, nullptr, nullptr};  // the library's own count / noise maps
+    mcpt_stats st{};
+    if ((rc = render_on_device(sc, *D, cam, &ok, (double*)D->fb.p, &st, &ad))) return rc;
+    HIP_OK(hipMemcpyAsync(out_rgb, D->fb.p, 3 * npx * sizeof(double), hipMemcpyDeviceToHost, D->stream));
+    if (count) HIP_OK(hipMemcpyAsync(count, D->ad_count.p, npx * sizeof(int32_t), hipMemcpyDeviceToHost, D->stream));
+    if (noise) HIP_OK(hipMemcpyAsync(noise, D->ad_noise.p, npx * sizeof(double), hipMemcpyDeviceToHost, D->stream));
+    HIP_OK(hipStreamSynchronize(D->stream));
+    copy_stats(base, st, stats);
+    return MCPT_OK;
+}
+
+int mcpt_debug_adaptive_active(mcpt_scene* sc, int32_t device, int32_t* pixels, int32_t cap, int32_t* n) {
+    if (!sc || !n || cap < 0 || (cap > 0 && !pixels)) {
+        set_error("null argument");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    int rc;
+    if ((rc = get_device_state(sc, device, &D))) return rc;
+    *n = D->ad_last_list < 0 ? 0 : D->ad_last_n;
+    const int m = std::min<int>(*n, cap);
+    if (m > 0) HIP_OK(hipMemcpy(pixels, D->ad_list[D->ad_last_list].p, 4ull * m, hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
 
