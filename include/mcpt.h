@@ -24,7 +24,10 @@ extern "C" {
 #endif
 
 #define MCPT_VERSION 20300 /* 2.3.0: adaptive sampling (mcpt_adaptive_opts, mcpt_render_adaptive and its _device
-                               * form); no existing struct changes;
+                               * form); no existing struct changes; added since under the same number (additions
+                               * only: bind them when present): primary-hit AOVs (mcpt_aov_buffers,
+                               * mcpt_render_aovs and its _device form) and the variance-guided a-trous denoiser
+                               * (mcpt_denoise_opts, mcpt_denoise and its _device form, mcpt_variance_from_noise);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -293,6 +296,83 @@ int mcpt_render_adaptive(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_r
 int mcpt_render_adaptive_device(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* base,
                                 const mcpt_adaptive_opts* adaptive, double* dev_out_rgb, int32_t* dev_count,
                                 double* dev_noise, mcpt_stats* stats);
+
+/* Primary-hit feature buffers (AOVs; no counterpart in the reference): what the first hit of every pixel's
+ * camera ray looks like, for filters that must not blur across geometry.  Row 0 = top image row.  For a pixel
+ * whose primary ray hits facet f at (beta, gamma), exactly as mcpt_primary_hits reports it:
+ *   position  height*width*3: the interpolated hit point (main.cpp:406)
+ *   normal    height*width*3: the normalised interpolation of f's vertex normals (main.cpp:407); NOT flipped
+ *             for a back face
+ *   depth     height*width:   the Euclidean distance from the primary ray's origin (the pulled-back eye) to
+ *             position
+ *   albedo    height*width*3: Kd + Ks of f's material per channel (the floats widened to double, then added)
+ * A miss writes 0 to all four; depth == 0 is the miss marker (a hit has depth > 0).  Any pointer may be NULL. */
+typedef struct {
+    double *albedo, *normal, *position, *depth;
+} mcpt_aov_buffers;
+/* Fills the host arrays of *out.  opts supplies device and accel only (every other field is ignored); a
+ * device list or a communicator is MCPT_E_INVALID.  Runs the per-call setup of a render (primary hits, root
+ * table) and one kernel that writes the maps; no sample is traced. */
+int mcpt_render_aovs(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* opts,
+                     const mcpt_aov_buffers* out);
+/* same with the arrays in DEVICE memory (coarse-grained, on opts->device; see mcpt_render_device) */
+int mcpt_render_aovs_device(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* opts,
+                            const mcpt_aov_buffers* dev_out);
+
+/* Variance-guided edge-avoiding a-trous wavelet filter (Dammertz et al. 2010, "Edge-Avoiding A-Trous Wavelet
+ * Transform for fast Global Illumination Filtering", with the luminance edge-stopping function scaled by the
+ * local standard deviation as in Schied et al. 2017, "Spatiotemporal Variance-Guided Filtering"), on one
+ * frame, in fp64 throughout.  Inputs: the colour C_0 (height*width*3), an optional per-pixel variance V_0 of
+ * the pixel's mean luminance (height*width) and the four guides of an mcpt_aov_buffers: N normal, X position,
+ * rho albedo and depth.  With hit(p) = depth_p > 0, h = (1/16, 1/4, 3/8, 1/4, 1/16) indexed by d + 2 and
+ * eps = 1e-10, iteration i = 0 .. iterations - 1 with step s = 2^i computes for every pixel p
+ *   l(p)     = (C_i(p).r + C_i(p).g + C_i(p).b) / 3
+ *   Vg(p)    = the 3x3 Gaussian (1/4, 1/2, 1/4)^2 of V_i around p; taps outside the frame are dropped and the
+ *              remaining weights renormalised (sum of weight * V_i over the sum of the weights)
+ *   sigma(p) = sigma_color * sqrt(max(Vg(p), 0)) + eps
+ *   taps     q = p + s * (dx, dy) for dx, dy in [-2, 2]; taps outside the frame are skipped
+ *   geo(p,q) = w_n * w_x * w_a when both p and q hit, 1 when both miss, 0 when exactly one hits, with
+ *              w_n = max(0, N_p . N_q)^sigma_normal
+ *              w_x = exp(-|N_p . (X_q - X_p)| / (sigma_plane * depth_p))
+ *              w_a = exp(-|rho_p - rho_q|^2 / sigma_albedo^2)
+ *   w        = h(dx) * h(dy) * geo(p, q) * exp(-|l(p) - l(q)| / sigma(p))
+ *   C_{i+1}(p) = sum_q w C_i(q) / sum_q w
+ *   V_{i+1}(p) = sum_q w^2 V_i(q) / (sum_q w)^2          (the centre tap, w = 9/64, keeps sum_q w > 0)
+ * The results are out = C_K and out_variance = V_K, K = iterations; both are overwritten, not added to.
+ * When variance is NULL, V_0 is a two-pass spatial estimate over the clipped 5x5 window at step 1:
+ *   u(q) = h(dx) * h(dy) * geo(p, q),  m = sum_q u l(q) / sum_q u,  V_0(p) = sum_q u (l(q) - m)^2 / sum_q u
+ * (the one-pass form m2 - m1^2 cancels, and the square root that follows amplifies its error).
+ * The filter is normalised, hence biased: it trades variance for blur, smears highlights far brighter than
+ * their surroundings when their variance is large, and without a supplied variance it treats an emitter's
+ * edge as noise.  Single device. */
+typedef struct {
+    uint32_t struct_size;  /* sizeof(mcpt_denoise_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
+    int32_t iterations;    /* 1..8, default 5: iteration i uses step 2^i */
+    double sigma_color;    /* default 4: luminance edge-stopping, in standard deviations */
+    double sigma_normal;   /* default 128: exponent of the normal weight */
+    double sigma_plane;    /* default 0.01: distance from p's tangent plane, relative to depth_p */
+    double sigma_albedo;   /* default 0.1: albedo distance (RGB Euclidean) */
+    int32_t device;        /* HIP device ordinal (-1 = current) */
+} mcpt_denoise_opts;
+/* zero-fills *opts and sets struct_size and the defaults above (device = -1) */
+void mcpt_denoise_opts_init(mcpt_denoise_opts* opts);
+/* Host arrays in, host arrays out.  guides: all four arrays are required.  variance (height*width) may be
+ * NULL (the spatial estimate), out_variance (height*width) and device_seconds (device time of the filter's
+ * kernels, HIP events) may be NULL.  Refused with MCPT_E_INVALID before any device work: a struct_size
+ * mismatch, iterations outside 1..8, a sigma that is not finite or not > 0, width or height < 1, a NULL
+ * colour, output or guide array, out (or out_variance) aliasing an input array. */
+int mcpt_denoise(const mcpt_denoise_opts* opts, int32_t width, int32_t height, const double* color,
+                 const double* variance, const mcpt_aov_buffers* guides, double* out, double* out_variance,
+                 double* device_seconds);
+/* same with every array in DEVICE memory on opts->device (device_seconds stays a host pointer) */
+int mcpt_denoise_device(const mcpt_denoise_opts* opts, int32_t width, int32_t height, const double* dev_color,
+                        const double* dev_variance, const mcpt_aov_buffers* dev_guides, double* dev_out,
+                        double* dev_out_variance, double* device_seconds);
+/* Host helper: the adaptive render's outputs (image I = rgb, noise e) as V_0 = (e * sqrt(sum_c I_c) / 3)^2 per
+ * pixel (0 where sum_c I_c <= 0): the squared mean absolute channel difference between I and the rescaled
+ * first half buffer Ah (e sqrt(sum I) = sum_c |I_c - Ah_c|), a one-sample estimate of the variance of the
+ * pixel's mean luminance.  rgb height*width*3, noise and variance height*width. */
+int mcpt_variance_from_noise(int32_t width, int32_t height, const double* rgb, const double* noise, double* variance);
 
 /* Myobj::cal_scene_boundingbox(eye) + Myobj::meshing(n0) (Myobj.cpp:78-162): build the scene's
  * uniform grid (box of every vertex and `eye`; cell edge = largest extent / n0^(1/3)) for

@@ -16,6 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_adaptive", "render_adaptive_device", "closest_hit", "light_prep", "primary_hits",
+           "AovBuffers", "DenoiseOpts", "render_aovs", "render_aovs_device", "denoise", "denoise_device", "variance_from_noise",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -78,6 +79,18 @@ class AdaptiveOpts(C.Structure):
                 ("threshold", C.c_double), ("radius", C.c_int32)]
 
 
+class AovBuffers(C.Structure):
+    """mcpt_aov_buffers: the four primary-hit maps (include/mcpt.h); any pointer may be NULL where allowed."""
+    _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p)]
+
+
+class DenoiseOpts(C.Structure):
+    """mcpt_denoise_opts: the a-trous filter's parameters (include/mcpt.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("sigma_color", C.c_double),
+                ("sigma_normal", C.c_double), ("sigma_plane", C.c_double), ("sigma_albedo", C.c_double),
+                ("device", C.c_int32)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 
 
@@ -110,7 +123,8 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_scene_counts", "mcpt_scene_accel_bytes", "mcpt_scene_arrays", "mcpt_scene_camera", "mcpt_scene_meshing", "mcpt_scene_grid_info",
            "mcpt_render_opts_init", "mcpt_render", "mcpt_render_device",
            "mcpt_adaptive_opts_init", "mcpt_render_adaptive", "mcpt_render_adaptive_device",
-           "mcpt_closest_hit", "mcpt_light_prep", "mcpt_primary_hits", "mcpt_tone_map",
+           "mcpt_render_aovs", "mcpt_render_aovs_device", "mcpt_denoise_opts_init", "mcpt_denoise", "mcpt_denoise_device",
+           "mcpt_variance_from_noise", "mcpt_closest_hit", "mcpt_light_prep", "mcpt_primary_hits", "mcpt_tone_map",
            "mcpt_write_bmp", "mcpt_comm_unique_id", "mcpt_comm_init_rank", "mcpt_comm_destroy"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
@@ -162,6 +176,14 @@ def lib():
             L.mcpt_render_adaptive_device.argtypes = [P, C.POINTER(Camera), C.POINTER(RenderOpts),
                                                       C.POINTER(AdaptiveOpts), C.c_void_p, C.c_void_p, C.c_void_p,
                                                       C.POINTER(Stats)]
+        if hasattr(L, "mcpt_denoise"):  # added under ABI 2.3 (an older build timed through MCPT_LIB_PATH lacks them)
+            L.mcpt_render_aovs.argtypes = [P, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(AovBuffers)]
+            L.mcpt_render_aovs_device.argtypes = L.mcpt_render_aovs.argtypes
+            L.mcpt_denoise_opts_init.argtypes = [C.POINTER(DenoiseOpts)]
+            L.mcpt_denoise_opts_init.restype = None
+            L.mcpt_denoise.argtypes = [C.POINTER(DenoiseOpts), I, I, P, P, C.POINTER(AovBuffers), P, P, C.POINTER(D)]
+            L.mcpt_denoise_device.argtypes = L.mcpt_denoise.argtypes
+            L.mcpt_variance_from_noise.argtypes = [I, I, dp, dp, dp]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -413,6 +435,87 @@ def render_adaptive_device(scene, camera, max_spp, threshold, dev_ptr, count_ptr
         None if count_ptr is None else C.c_void_p(int(count_ptr)),
         None if noise_ptr is None else C.c_void_p(int(noise_ptr)), C.byref(st)))
     return st
+
+
+def _aov_opts(device, accel):
+    return _opts(1, "mis", DEFAULT_SEED, None, device, 0, 0, accel=accel)
+
+
+def render_aovs(scene, camera, device=None, accel="bvh"):
+    """Primary-hit feature buffers (mcpt_render_aovs, include/mcpt.h): dict of albedo (Kd + Ks), normal (shading
+    normal, not flipped), position (H x W x 3 each) and depth (H x W, distance from the pulled-back eye; 0 marks a
+    miss, whose other maps are 0 too)."""
+    H, W = camera.height, camera.width
+    a = dict(albedo=np.zeros((H, W, 3)), normal=np.zeros((H, W, 3)), position=np.zeros((H, W, 3)), depth=np.zeros((H, W)))
+    b = AovBuffers(*[a[k].ctypes.data for k in ("albedo", "normal", "position", "depth")])
+    o = _aov_opts(device, accel)
+    _check(lib().mcpt_render_aovs(scene.h, C.byref(camera), C.byref(o), C.byref(b)))
+    return a
+
+
+def render_aovs_device(scene, camera, albedo_ptr=None, normal_ptr=None, position_ptr=None, depth_ptr=None, device=None,
+                       accel="bvh"):
+    """render_aovs into device buffers (e.g. torch CUDA float64 tensors' data_ptr()): H*W*3 doubles each, depth
+    H*W; any may be None."""
+    b = AovBuffers(*[None if p is None else int(p) for p in (albedo_ptr, normal_ptr, position_ptr, depth_ptr)])
+    o = _aov_opts(device, accel)
+    _check(lib().mcpt_render_aovs_device(scene.h, C.byref(camera), C.byref(o), C.byref(b)))
+
+
+def _denoise_opts(iterations, sigma_color, sigma_normal, sigma_plane, sigma_albedo, device):
+    o = DenoiseOpts()
+    lib().mcpt_denoise_opts_init(C.byref(o))
+    for k, v in (("sigma_color", sigma_color), ("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane),
+                 ("sigma_albedo", sigma_albedo)):
+        if v is not None:
+            setattr(o, k, float(v))
+    if iterations is not None:
+        o.iterations = int(iterations)
+    o.device = -1 if device is None else int(device)
+    return o
+
+
+def denoise(color, aovs, variance=None, iterations=None, sigma_color=None, sigma_normal=None, sigma_plane=None,
+            sigma_albedo=None, device=None):
+    """Variance-guided a-trous filter (mcpt_denoise; include/mcpt.h states the rule).  color H x W x 3, aovs the
+    dict of render_aovs (all four maps), variance H x W (of the pixel's mean luminance, e.g. variance_from_noise)
+    or None for the filter's own spatial estimate; None parameters take the library defaults (5 iterations,
+    sigmas 4 / 128 / 0.01 / 0.1).  Returns (out, out_variance, device seconds)."""
+    color = _d(color)
+    H, W = color.shape[:2]
+    assert color.shape == (H, W, 3)
+    g = {k: _d(aovs[k], (H, W) if k == "depth" else (H, W, 3)) for k in ("albedo", "normal", "position", "depth")}
+    b = AovBuffers(*[g[k].ctypes.data for k in ("albedo", "normal", "position", "depth")])
+    var = None if variance is None else _d(variance, (H, W))
+    out, out_var, sec = np.zeros((H, W, 3)), np.zeros((H, W)), C.c_double()
+    o = _denoise_opts(iterations, sigma_color, sigma_normal, sigma_plane, sigma_albedo, device)
+    _check(lib().mcpt_denoise(C.byref(o), W, H, color.ctypes.data, None if var is None else var.ctypes.data, C.byref(b),
+                              out.ctypes.data, out_var.ctypes.data, C.byref(sec)))
+    return out, out_var, sec.value
+
+
+def denoise_device(width, height, color_ptr, aov_ptrs, out_ptr, variance_ptr=None, out_variance_ptr=None, iterations=None,
+                   sigma_color=None, sigma_normal=None, sigma_plane=None, sigma_albedo=None, device=None):
+    """denoise over device buffers (e.g. torch CUDA float64 tensors' data_ptr()): aov_ptrs is a dict of the four
+    guides' pointers; variance_ptr and out_variance_ptr may be None.  Returns the device seconds."""
+    b = AovBuffers(*[int(aov_ptrs[k]) for k in ("albedo", "normal", "position", "depth")])
+    sec = C.c_double()
+    o = _denoise_opts(iterations, sigma_color, sigma_normal, sigma_plane, sigma_albedo, device)
+    _check(lib().mcpt_denoise_device(
+        C.byref(o), int(width), int(height), C.c_void_p(int(color_ptr)),
+        None if variance_ptr is None else C.c_void_p(int(variance_ptr)), C.byref(b), C.c_void_p(int(out_ptr)),
+        None if out_variance_ptr is None else C.c_void_p(int(out_variance_ptr)), C.byref(sec)))
+    return sec.value
+
+
+def variance_from_noise(img, noise):
+    """mcpt_variance_from_noise: render_adaptive's image and noise map as the variance of each pixel's mean
+    luminance, V = (e sqrt(sum_c I_c) / 3)^2 -- the denoiser's `variance` input."""
+    img = _d(img)
+    H, W = img.shape[:2]
+    var = np.zeros((H, W))
+    _check(lib().mcpt_variance_from_noise(W, H, img.reshape(-1), _d(noise, (H, W)).reshape(-1), var.reshape(-1)))
+    return var
 
 
 def debug_adaptive_active(scene, device=-1):

@@ -12,6 +12,11 @@
 //   --min-spp (default 16 each), a pixel stops once its noise estimate is at most TAU and so are its
 //   neighbours' within --radius (default 1); --spp is the cap.  Prints the mean spp and the share of pixels at
 //   the cap; --count-out writes the per-pixel sample count as a grey BMP (white = the cap).  One device.
+//               [--denoise [--denoise-iterations K] [--denoise-sigma-color S]] [--aov-out PREFIX]
+//   --denoise filters the frame with the variance-guided a-trous filter (mcpt_denoise) guided by the primary-hit
+//   AOVs (mcpt_render_aovs); --out and --hdr then carry the denoised frame.  With --adaptive the variance comes
+//   from the adaptive render's noise map (mcpt_variance_from_noise), else from the filter's spatial estimate.
+//   --aov-out PREFIX writes PREFIX_albedo.pfm, PREFIX_normal.pfm (PF) and PREFIX_depth.pfm (Pf).
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -67,9 +72,11 @@ int render(mcpt_scene* scene, const mcpt_camera& cam, int spp, int mode, uint64_
 
 // the adaptive form of render(): --spp is the cap; the count map comes back too
 int render_adaptive(mcpt_scene* scene, const mcpt_camera& cam, const mcpt_adaptive_opts& ad, int mode, uint64_t seed,
-                    bool progress, bool grid, int flags, std::vector<double>& hdr, std::vector<int32_t>& count, mcpt_stats* st) {
+                    bool progress, bool grid, int flags, std::vector<double>& hdr, std::vector<int32_t>& count,
+                    std::vector<double>& noise, mcpt_stats* st) {
     hdr.assign(3ull * cam.width * cam.height, 0.0);
     count.assign((size_t)cam.width * cam.height, 0);
+    noise.assign((size_t)cam.width * cam.height, 0.0);
     mcpt_render_opts o;
     mcpt_render_opts_init(&o);
     o.mode = mode;
@@ -81,16 +88,17 @@ int render_adaptive(mcpt_scene* scene, const mcpt_camera& cam, const mcpt_adapti
         o.progress = print_progress;
         o.progress_user = &last;
     }
-    return mcpt_render_adaptive(scene, &cam, &o, &ad, hdr.data(), count.data(), nullptr, st);
+    return mcpt_render_adaptive(scene, &cam, &o, &ad, hdr.data(), count.data(), noise.data(), st);
 }
 
-bool write_pfm(const char* path, const std::vector<double>& hdr, int W, int H) {
+// channels: 3 (PF) or 1 (Pf)
+bool write_pfm(const char* path, const std::vector<double>& hdr, int W, int H, int channels = 3) {
     FILE* f = std::fopen(path, "wb");
     if (!f) return false;
-    std::fprintf(f, "PF\n%d %d\n-1.0\n", W, H);
-    std::vector<float> row(3ull * W);
+    std::fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", W, H);
+    std::vector<float> row((size_t)channels * W);
     for (int i = H - 1; i >= 0; i--) {  // PFM is bottom-up
-        for (int k = 0; k < 3 * W; k++) row[k] = static_cast<float>(hdr[3ull * i * W + k]);
+        for (int k = 0; k < channels * W; k++) row[k] = static_cast<float>(hdr[(size_t)channels * i * W + k]);
         std::fwrite(row.data(), sizeof(float), row.size(), f);
     }
     std::fclose(f);
@@ -110,7 +118,10 @@ int main(int argc, char** argv) {
     bool adaptive = false;
     mcpt_adaptive_opts ad;
     mcpt_adaptive_opts_init(&ad);
-    std::string count_out;
+    std::string count_out, aov_out;
+    bool denoise = false;
+    mcpt_denoise_opts dn;
+    mcpt_denoise_opts_init(&dn);
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -157,6 +168,10 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--pass-spp")) ad.pass_spp = std::atoi(next());
         else if (!std::strcmp(argv[a], "--radius")) ad.radius = std::atoi(next());
         else if (!std::strcmp(argv[a], "--count-out")) count_out = next();
+        else if (!std::strcmp(argv[a], "--denoise")) denoise = true;
+        else if (!std::strcmp(argv[a], "--denoise-iterations")) dn.iterations = std::atoi(next());
+        else if (!std::strcmp(argv[a], "--denoise-sigma-color")) dn.sigma_color = std::atof(next());
+        else if (!std::strcmp(argv[a], "--aov-out")) aov_out = next();
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -195,6 +210,7 @@ int main(int argc, char** argv) {
     std::vector<double> hdr;
     mcpt_stats st{};
     std::vector<int32_t> count;
+    std::vector<double> noise;
     if (adaptive && !devices.empty()) {
         std::fprintf(stderr, "--adaptive renders on one device; drop --devices\n");
         return 2;
@@ -205,7 +221,7 @@ int main(int argc, char** argv) {
     }
     ad.max_spp = spp;
     const auto t0 = std::chrono::steady_clock::now();
-    if ((adaptive ? render_adaptive(scene, cam, ad, mode, seed, progress, grid, flags, hdr, count, &st)
+    if ((adaptive ? render_adaptive(scene, cam, ad, mode, seed, progress, grid, flags, hdr, count, noise, &st)
                   : render(scene, cam, spp, mode, seed, progress, grid, flags, devices, hdr, &st)) != MCPT_OK) {
         std::fprintf(stderr, "render failed: %s\n", mcpt_last_error());
         return 1;
@@ -235,6 +251,41 @@ int main(int argc, char** argv) {
                 std::fprintf(stderr, "%s\n", mcpt_last_error());
                 return 1;
             }
+        }
+    }
+    if (denoise || !aov_out.empty()) {
+        const size_t npx = (size_t)W * H;
+        std::vector<double> albedo(3 * npx), normal(3 * npx), position(3 * npx), depth(npx);
+        const mcpt_aov_buffers aov{albedo.data(), normal.data(), position.data(), depth.data()};
+        mcpt_render_opts ao;
+        mcpt_render_opts_init(&ao);
+        ao.accel = grid ? MCPT_ACCEL_GRID : MCPT_ACCEL_BVH;
+        if (mcpt_render_aovs(scene, &cam, &ao, &aov) != MCPT_OK) {
+            std::fprintf(stderr, "AOV render failed: %s\n", mcpt_last_error());
+            return 1;
+        }
+        if (!aov_out.empty() && !(write_pfm((aov_out + "_albedo.pfm").c_str(), albedo, W, H) &&
+                                  write_pfm((aov_out + "_normal.pfm").c_str(), normal, W, H) &&
+                                  write_pfm((aov_out + "_depth.pfm").c_str(), depth, W, H, 1))) {
+            std::fprintf(stderr, "cannot write %s_{albedo,normal,depth}.pfm\n", aov_out.c_str());
+            return 1;
+        }
+        if (denoise) {
+            // adaptive: the noise map as the variance of the pixel's mean luminance; else the spatial estimate
+            std::vector<double> variance, filtered(3 * npx);
+            if (adaptive) {
+                variance.resize(npx);
+                mcpt_variance_from_noise(W, H, hdr.data(), noise.data(), variance.data());
+            }
+            double dsec = 0;
+            if (mcpt_denoise(&dn, W, H, hdr.data(), adaptive ? variance.data() : nullptr, &aov, filtered.data(), nullptr,
+                             &dsec) != MCPT_OK) {
+                std::fprintf(stderr, "denoise failed: %s\n", mcpt_last_error());
+                return 1;
+            }
+            hdr.swap(filtered);
+            std::printf("  denoised: %d iterations, sigma_color %g, variance from %s, %.3f ms device\n", dn.iterations,
+                        dn.sigma_color, adaptive ? "the adaptive noise map" : "the spatial estimate", dsec * 1e3);
         }
     }
     std::vector<uint8_t> rgb8(hdr.size());

@@ -1039,6 +1039,30 @@ __global__ __launch_bounds__(256) void k_root_table(DScene S, CamFrame cam, cons
     rt.kind[px] = kind;
 }
 
+// Primary-hit feature buffers (mcpt_render_aovs) from the primary hits and the root table: position and
+// normal are node_point's (the table holds them for back faces too), depth the distance from the eye, albedo
+// Kd + Ks of the facet's material; a miss writes 0 everywhere.  Any output may be null.
+__global__ __launch_bounds__(256) void k_aovs(DScene S, CamFrame cam, const int* hit_f, const double* pnw, mcpt_aov_buffers o) {
+    const int px = blockIdx.x * blockDim.x + threadIdx.x;
+    if (px >= cam.W * cam.H) return;
+    const int f = hit_f[px];
+    d3 p = mk3(0, 0, 0), N = mk3(0, 0, 0), a = mk3(0, 0, 0);
+    double depth = 0.0;
+    if (f >= 0) {
+        const double* r = pnw + 9 * (size_t)px;
+        p = mk3(r[0], r[1], r[2]);
+        N = mk3(r[3], r[4], r[5]);
+        depth = norm2(sub(p, cam.eye));
+        const float* m = S.mtl + 7 * S.tri_mat[f];
+        a = mk3((double)m[0] + (double)m[3], (double)m[1] + (double)m[4], (double)m[2] + (double)m[5]);
+    }
+    const size_t k = 3 * (size_t)px;
+    if (o.albedo) o.albedo[k] = a.x, o.albedo[k + 1] = a.y, o.albedo[k + 2] = a.z;
+    if (o.normal) o.normal[k] = N.x, o.normal[k + 1] = N.y, o.normal[k + 2] = N.z;
+    if (o.position) o.position[k] = p.x, o.position[k + 1] = p.y, o.position[k + 2] = p.z;
+    if (o.depth) o.depth[px] = depth;
+}
+
 // pixel and sample of root rg (the call's root index; order above)
 __device__ inline void root_of(long long rg, int npx, int s0, int group, int nsamp, int* pixel, int* sample) {
     const long long full = (long long)(nsamp / group) * group * npx;  // roots in whole blocks
@@ -4366,6 +4390,7 @@ struct DeviceState {
     // (+ the total), the library's own count / noise maps
     DevBuf ad_acc[2], ad_list[2], ad_state[2], ad_blk, ad_count, ad_noise;
     int ad_last_list = -1, ad_last_n = 0;  // the last active list built (mcpt_debug_adaptive_active)
+    DevBuf aov;  // mcpt_render_aovs: the four maps of a host call (10 doubles per pixel)
     int spill_cap = 0;  // nodes the spill stack qs holds (grown on demand)
     bool bvh8_tried = false;  // ensure_bvh8 ran on this device
     DevBuf g_start, g_tri;  // the scene's uniform grid (MCPT_ACCEL_GRID), version grid_version
@@ -6349,7 +6374,7 @@ void mcpt_scene_destroy(mcpt_scene* sc) {
                                      &D->root_kind, &D->exact, &D->exact_scr, &D->slack, &D->lit_slot, &D->lit_pool,
                                      &D->sc_cum, &D->sc_wsum, &D->sc_last, &D->cull_keys, &D->cull_order, &D->cull_count,
                                      &D->ad_acc[0], &D->ad_acc[1], &D->ad_list[0], &D->ad_list[1], &D->ad_state[0],
-                                     &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise};
+                                     &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise, &D->aov};
         for (int k = 0; k < 14; k++) bufs.insert(bufs.end(), {&D->qa[k], &D->qb[k], &D->qs[k]});
         for (int k = 0; k < 9; k++) bufs.push_back(&D->aux[k]);
         for (int k = 0; k < 13; k++) bufs.push_back(&D->sl[k]);
@@ -6588,6 +6613,82 @@ int mcpt_render_adaptive(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_rend
     HIP_OK(hipStreamSynchronize(D->stream));
     copy_stats(base, st, stats);
     return MCPT_OK;
+}
+
+// mcpt_render_aovs / _device: the per-call setup of a render (k_primary, k_root_table) and k_aovs.  host: the
+// maps go through D.aov and are copied out; else `out` holds device pointers and k_aovs writes them directly.
+static int render_aovs_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o, const mcpt_aov_buffers* out,
+                            bool host) {
+    if (!sc || !o || !out) {
+        set_error("null argument");
+        return MCPT_E_INVALID;
+    }
+    if (o->struct_size == sizeof(mcpt_render_opts) && (o->num_devices > 0 || o->comm)) {
+        set_error("mcpt_render_aovs is single-device: a device list or a communicator is not supported");
+        return MCPT_E_INVALID;
+    }
+    int rc;
+    if ((rc = check_opts(o)) || (rc = validate_camera(cam))) return rc;
+    if (o->accel != MCPT_ACCEL_BVH && o->accel != MCPT_ACCEL_GRID) {
+        set_error("invalid accel %d", o->accel);
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    if ((rc = get_device_state(sc, o->device, &D))) return rc;
+    const CamFrame cf = cam_setup(*cam);
+    const size_t npx = (size_t)cam->width * cam->height;
+    const bool grid = o->accel == MCPT_ACCEL_GRID;
+    if (grid) {
+        const double eye[3] = {cf.eye.x, cf.eye.y, cf.eye.z};
+        if ((rc = use_grid(sc, *D, eye, 100000))) return rc;
+    }
+    if ((rc = ensure(D->hit_f, 4 * npx)) || (rc = ensure(D->hit_tbg, 24 * npx)) || (rc = ensure(D->root_pnw, 72 * npx)) ||
+        (rc = ensure(D->root_kind, 4 * npx)))
+        return rc;
+    mcpt_aov_buffers dev = *out;
+    if (host) {
+        if ((rc = ensure(D->aov, 80 * npx))) return rc;
+        double* b = (double*)D->aov.p;
+        dev = mcpt_aov_buffers{out->albedo ? b : nullptr, out->normal ? b + 3 * npx : nullptr,
+                               out->position ? b + 6 * npx : nullptr, out->depth ? b + 9 * npx : nullptr};
+    } else {
+        if ((dev.albedo && (rc = check_device_buffer(dev.albedo, D->device, "dev_out.albedo"))) ||
+            (dev.normal && (rc = check_device_buffer(dev.normal, D->device, "dev_out.normal"))) ||
+            (dev.position && (rc = check_device_buffer(dev.position, D->device, "dev_out.position"))) ||
+            (dev.depth && (rc = check_device_buffer(dev.depth, D->device, "dev_out.depth"))))
+            return rc;
+        // the caller's buffers may still be written by work on other streams (e.g. torch's)
+        HIP_OK(hipDeviceSynchronize());
+    }
+    const hipStream_t st = D->stream;
+    const int n = (int)npx;
+    hipLaunchKernelGGL(grid ? k_primary<true> : k_primary<false>, dim3((n + kTraceBlock - 1) / kTraceBlock), dim3(kTraceBlock),
+                       0, st, D->d, cf, (int*)D->hit_f.p, (double*)D->hit_tbg.p);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_root_table, dim3((n + 255) / 256), dim3(256), 0, st, D->d, cf, (const int*)D->hit_f.p,
+                       (const double*)D->hit_tbg.p, RootTab{(double*)D->root_pnw.p, (int*)D->root_kind.p});
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_aovs, dim3((n + 255) / 256), dim3(256), 0, st, D->d, cf, (const int*)D->hit_f.p,
+                       (const double*)D->root_pnw.p, dev);
+    HIP_OK(hipGetLastError());
+    if (host) {
+        if (out->albedo) HIP_OK(hipMemcpyAsync(out->albedo, dev.albedo, 24 * npx, hipMemcpyDeviceToHost, st));
+        if (out->normal) HIP_OK(hipMemcpyAsync(out->normal, dev.normal, 24 * npx, hipMemcpyDeviceToHost, st));
+        if (out->position) HIP_OK(hipMemcpyAsync(out->position, dev.position, 24 * npx, hipMemcpyDeviceToHost, st));
+        if (out->depth) HIP_OK(hipMemcpyAsync(out->depth, dev.depth, 8 * npx, hipMemcpyDeviceToHost, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    return MCPT_OK;
+}
+
+int mcpt_render_aovs(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o, const mcpt_aov_buffers* out) {
+    return render_aovs_impl(sc, cam, o, out, true);
+}
+
+int mcpt_render_aovs_device(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o,
+                            const mcpt_aov_buffers* dev_out) {
+    return render_aovs_impl(sc, cam, o, dev_out, false);
 }
 
 int mcpt_debug_adaptive_active(mcpt_scene* sc, int32_t device, int32_t* pixels, int32_t cap, int32_t* n) {
