@@ -28,6 +28,8 @@ extern "C" {
                                * only: bind them when present): primary-hit AOVs (mcpt_aov_buffers,
                                * mcpt_render_aovs and its _device form) and the variance-guided a-trous denoiser
                                * (mcpt_denoise_opts, mcpt_denoise and its _device form, mcpt_variance_from_noise);
+                               * temporal accumulation (mcpt_temporal_opts, mcpt_temporal_accumulate and its
+                               * _device form, mcpt_camera_orbit);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -373,6 +375,81 @@ int mcpt_denoise_device(const mcpt_denoise_opts* opts, int32_t width, int32_t he
  * first half buffer Ah (e sqrt(sum I) = sum_c |I_c - Ah_c|), a one-sample estimate of the variance of the
  * pixel's mean luminance.  rgb height*width*3, noise and variance height*width. */
 int mcpt_variance_from_noise(int32_t width, int32_t height, const double* rgb, const double* noise, double* variance);
+
+/* Temporal accumulation: the other half of Schied et al. 2017 (SVGF).  The scene is static, so the world position
+ * of a pixel's primary hit is projected into the PREVIOUS frame's camera, the previous frame's accumulated colour
+ * and luminance moments are gathered there (bilinear, every tap's geometry checked), blended with the current
+ * frame, and a per-pixel variance of the accumulated luminance comes out for mcpt_denoise.  fp64 throughout.
+ * Inputs for a frame of width w, height h: the current colour C (h*w*3), the current guides (N normal, X position,
+ * depth; albedo is read by the spatial estimate only) and, optionally, the previous state: its camera cam', its
+ * guides N', X', depth' (its albedo is ignored), its colour history Hc' (h*w*3) and its moments Hm' (h*w*4,
+ * interleaved (m1, m2, n, g)).
+ *   frame    of cam', as the renderer builds it (main.cpp:507-510): wv = lookat - eye, the pulled-back eye
+ *            E = eye - wv * (dist_scale - 1), Nc = wv / |wv|, V = (Nc x up) / |Nc x up|, U = (V x Nc) / |V x Nc|,
+ *            S = wlen / pixellen with wlen = |wv * dist_scale| and pixellen = tan(fovy / 360) * wlen / (h / 2)
+ * For each pixel p = (i, j) (row, column), with l = (C.r + C.g + C.b) / 3:
+ *   source   when depth_p > 0: d = X_p - E, a = d . U, b = d . V, c = d . Nc; when also c > 0:
+ *            y = (h - 1) / 2 - S * a / c, x = (w - 1) / 2 + S * b / c (the inverse of the camera ray's direction).
+ *            p has NO source when depth_p == 0, or c <= 0, or !(y > -1 && y < h && x > -1 && x < w)
+ *   taps     i0 = floor(y), j0 = floor(x), fy = y - i0, fx = x - j0; q = (i0 + di, j0 + dj) for (di, dj) = (0, 0),
+ *            (0, 1), (1, 0), (1, 1) in this order, with b_q = (di ? fy : 1 - fy) * (dj ? fx : 1 - fx).  A tap is
+ *            valid when it lies inside the frame, depth'_q > 0, n'_q > 0, N_p . N'_q >= normal_min and
+ *            |N_p . (X'_q - X_p)| <= plane_max * depth_p (a surface point keeps its world position, so the
+ *            plane distance is taken in world space)
+ *   history  Wsum = sum of b_q over the valid taps; p has history when it has a source and Wsum >= min_weight;
+ *            then (Hc, m1', m2', n', g') = (sum of b_q * the tap's values) / Wsum, n' and g' as doubles
+ *   blend    with history: n = min(n' + 1, max_history), A = max(alpha, 1 / n), out_color = (1 - A) Hc + A C,
+ *            m1 = (1 - A) m1' + A l, m2 = (1 - A) m2' + A l^2, g = (1 - A)^2 g' + A^2;
+ *            without (and whenever no previous state is given): out_color = C, (m1, m2, n, g) = (l, l^2, 1, 1).
+ *            g is the sum of the squared blend weights: one frame's variance times g is the variance of the
+ *            blended value (g = 1 / n while the blend is an arithmetic mean)
+ *   variance when n > variance_min_history - 0.5 and g < 1: V = max(0, m2 - m1^2) * g / (1 - g), the empirical
+ *            per-frame luminance variance with the small-sample correction, scaled to the accumulated value;
+ *            otherwise V is the spatial estimate V_0 of mcpt_denoise above, word for word (u-weighted, two passes
+ *            over the clipped 5x5 at step 1), of out_color with the current guides and this call's sigma_normal,
+ *            sigma_plane and sigma_albedo.  The - 0.5 keeps the decision away from the integers n takes in a
+ *            static sequence; g < 1 fails only for alpha = 1, where nothing is accumulated.
+ * out_color (h*w*3), out_moments (h*w*4) and out_variance (h*w, optional) are overwritten.  The history is the
+ * caller's: feed out_color / out_moments of one call as prev_color / prev_moments of the next (two sets of buffers,
+ * swapped; an output may not alias an input).  The filtered colour is NOT fed back, miss pixels keep no history,
+ * the geometry must not move.  Single device. */
+typedef struct {
+    uint32_t struct_size;  /* sizeof(mcpt_temporal_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
+    int32_t max_history;   /* default 64, >= 1: the cap of the history length n */
+    int32_t variance_min_history; /* default 4, >= 2: with a shorter history the variance is the spatial estimate */
+    int32_t device;        /* HIP device ordinal (-1 = current) */
+    double alpha;          /* default 0.1, in (0, 1]: the smallest weight of the current frame */
+    double normal_min;     /* default 0.9, finite: a tap needs N_p . N'_q >= normal_min */
+    double plane_max;      /* default 0.02, finite and > 0: and lies within plane_max * depth_p of p's tangent plane */
+    double min_weight;     /* default 0.01, in (0, 1]: the least bilinear weight of the valid taps */
+    double sigma_normal;   /* default 128 */
+    double sigma_plane;    /* default 0.01    the spatial estimate's geo(p, q), as in mcpt_denoise_opts */
+    double sigma_albedo;   /* default 0.1 */
+} mcpt_temporal_opts;
+/* zero-fills *opts and sets struct_size and the defaults above (device = -1) */
+void mcpt_temporal_opts_init(mcpt_temporal_opts* opts);
+/* Host arrays in, host arrays out.  guides: all four arrays are required.  The previous state -- prev_cam,
+ * prev_guides (normal, position and depth required), prev_color, prev_moments -- is given whole or not at all
+ * (all NULL: every pixel starts a history); prev_cam's width and height must equal width and height.
+ * out_variance and device_seconds (device time of the kernels, HIP events) may be NULL.  Refused with
+ * MCPT_E_INVALID before any device work: a struct_size mismatch, an option outside the range above (sigmas:
+ * finite and > 0), width or height < 1, a NULL required array, a partial previous state, a previous camera of
+ * another size, an output aliasing an input or another output. */
+int mcpt_temporal_accumulate(const mcpt_temporal_opts* opts, const mcpt_camera* prev_cam, int32_t width, int32_t height,
+                             const double* color, const mcpt_aov_buffers* guides, const mcpt_aov_buffers* prev_guides,
+                             const double* prev_color, const double* prev_moments, double* out_color,
+                             double* out_moments, double* out_variance, double* device_seconds);
+/* same with every array in DEVICE memory on opts->device (prev_cam and device_seconds stay host pointers) */
+int mcpt_temporal_accumulate_device(const mcpt_temporal_opts* opts, const mcpt_camera* prev_cam, int32_t width,
+                                    int32_t height, const double* dev_color, const mcpt_aov_buffers* dev_guides,
+                                    const mcpt_aov_buffers* dev_prev_guides, const double* dev_prev_color,
+                                    const double* dev_prev_moments, double* dev_out_color, double* dev_out_moments,
+                                    double* dev_out_variance, double* device_seconds);
+/* Host helper: *out = *in with eye rotated by `degrees` about the axis through lookat along k = up / |up|
+ * (Rodrigues, right-handed): with v = eye - lookat, t = degrees * pi / 180 and vp = v - k (k . v),
+ * eye' = eye + (k x v) sin t - vp (1 - cos t); 0 degrees returns eye bit for bit.  MCPT_E_INVALID for a NULL
+ * pointer, a degrees that is not finite or an up of length 0.  in and out may be the same struct. */
+int mcpt_camera_orbit(const mcpt_camera* in, double degrees, mcpt_camera* out);
 
 /* Myobj::cal_scene_boundingbox(eye) + Myobj::meshing(n0) (Myobj.cpp:78-162): build the scene's
  * uniform grid (box of every vertex and `eye`; cell edge = largest extent / n0^(1/3)) for

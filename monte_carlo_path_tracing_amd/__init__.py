@@ -17,6 +17,7 @@ import numpy as np
 
 __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_adaptive", "render_adaptive_device", "closest_hit", "light_prep", "primary_hits",
            "AovBuffers", "DenoiseOpts", "render_aovs", "render_aovs_device", "denoise", "denoise_device", "variance_from_noise",
+           "TemporalOpts", "TemporalAccumulator", "temporal_accumulate", "temporal_accumulate_device", "camera_orbit",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -91,6 +92,14 @@ class DenoiseOpts(C.Structure):
                 ("device", C.c_int32)]
 
 
+class TemporalOpts(C.Structure):
+    """mcpt_temporal_opts: the temporal accumulation's parameters (include/mcpt.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("max_history", C.c_int32), ("variance_min_history", C.c_int32),
+                ("device", C.c_int32), ("alpha", C.c_double), ("normal_min", C.c_double), ("plane_max", C.c_double),
+                ("min_weight", C.c_double), ("sigma_normal", C.c_double), ("sigma_plane", C.c_double),
+                ("sigma_albedo", C.c_double)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 
 
@@ -124,7 +133,8 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_render_opts_init", "mcpt_render", "mcpt_render_device",
            "mcpt_adaptive_opts_init", "mcpt_render_adaptive", "mcpt_render_adaptive_device",
            "mcpt_render_aovs", "mcpt_render_aovs_device", "mcpt_denoise_opts_init", "mcpt_denoise", "mcpt_denoise_device",
-           "mcpt_variance_from_noise", "mcpt_closest_hit", "mcpt_light_prep", "mcpt_primary_hits", "mcpt_tone_map",
+           "mcpt_variance_from_noise", "mcpt_temporal_opts_init", "mcpt_temporal_accumulate",
+           "mcpt_temporal_accumulate_device", "mcpt_camera_orbit", "mcpt_closest_hit", "mcpt_light_prep", "mcpt_primary_hits", "mcpt_tone_map",
            "mcpt_write_bmp", "mcpt_comm_unique_id", "mcpt_comm_init_rank", "mcpt_comm_destroy"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
@@ -184,6 +194,13 @@ def lib():
             L.mcpt_denoise.argtypes = [C.POINTER(DenoiseOpts), I, I, P, P, C.POINTER(AovBuffers), P, P, C.POINTER(D)]
             L.mcpt_denoise_device.argtypes = L.mcpt_denoise.argtypes
             L.mcpt_variance_from_noise.argtypes = [I, I, dp, dp, dp]
+        if hasattr(L, "mcpt_temporal_accumulate"):  # added under ABI 2.3 as well
+            L.mcpt_temporal_opts_init.argtypes = [C.POINTER(TemporalOpts)]
+            L.mcpt_temporal_opts_init.restype = None
+            L.mcpt_temporal_accumulate.argtypes = [C.POINTER(TemporalOpts), C.POINTER(Camera), I, I, P, C.POINTER(AovBuffers),
+                                                   C.POINTER(AovBuffers), P, P, P, P, P, C.POINTER(D)]
+            L.mcpt_temporal_accumulate_device.argtypes = L.mcpt_temporal_accumulate.argtypes
+            L.mcpt_camera_orbit.argtypes = [C.POINTER(Camera), D, C.POINTER(Camera)]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -516,6 +533,101 @@ def variance_from_noise(img, noise):
     var = np.zeros((H, W))
     _check(lib().mcpt_variance_from_noise(W, H, img.reshape(-1), _d(noise, (H, W)).reshape(-1), var.reshape(-1)))
     return var
+
+
+def camera_orbit(camera, degrees):
+    """mcpt_camera_orbit: a copy of `camera` with its eye rotated by `degrees` about the axis through lookat along
+    up (the CLI's --orbit builds its cameras with the same function, so both are bit-identical)."""
+    out = Camera()
+    _check(lib().mcpt_camera_orbit(C.byref(camera), float(degrees), C.byref(out)))
+    return out
+
+
+TEMPORAL_OPTS = ("alpha", "max_history", "normal_min", "plane_max", "min_weight", "variance_min_history", "sigma_normal",
+                 "sigma_plane", "sigma_albedo", "device")
+
+
+def _temporal_opts(opts):
+    o = TemporalOpts()
+    lib().mcpt_temporal_opts_init(C.byref(o))
+    for k, v in opts.items():
+        if k not in TEMPORAL_OPTS:
+            raise TypeError("unknown temporal option %r (one of %s)" % (k, ", ".join(TEMPORAL_OPTS)))
+        if v is not None:
+            setattr(o, k, type(getattr(o, k))(v))
+    return o
+
+
+def temporal_accumulate(color, aovs, prev=None, **opts):
+    """Temporal accumulation (mcpt_temporal_accumulate; include/mcpt.h states the rule).  color H x W x 3 and aovs
+    (the dict of render_aovs) are the current frame; prev is None (every pixel starts a history) or the previous
+    state (camera, aovs, colour, moments): that frame's Camera and guides and the colour and moments this function
+    returned for it.  opts: the fields of TemporalOpts (alpha, max_history, normal_min, plane_max, min_weight,
+    variance_min_history, sigma_normal, sigma_plane, sigma_albedo, device); None or absent = the library default.
+    Returns (colour H x W x 3, moments H x W x 4 of (m1, m2, n, g), variance H x W of the accumulated luminance --
+    the `variance` input of denoise -- and the device seconds)."""
+    color = _d(color)
+    H, W = color.shape[:2]
+    assert color.shape == (H, W, 3)
+    keys = ("albedo", "normal", "position", "depth")
+    g = {k: _d(aovs[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys}
+    b = AovBuffers(*[g[k].ctypes.data for k in keys])
+    pc = pb = pcol = pmom = None
+    if prev is not None:
+        pcam, paov, pcol, pmom = prev
+        pg = {k: _d(paov[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys[1:]}
+        pb = AovBuffers(None, *[pg[k].ctypes.data for k in keys[1:]])
+        pcol, pmom = _d(pcol, (H, W, 3)), _d(pmom, (H, W, 4))
+        pc = C.byref(pcam)
+    out, mom, var, sec = np.zeros((H, W, 3)), np.zeros((H, W, 4)), np.zeros((H, W)), C.c_double()
+    o = _temporal_opts(opts)
+    _check(lib().mcpt_temporal_accumulate(
+        C.byref(o), pc, W, H, color.ctypes.data, C.byref(b), None if pb is None else C.byref(pb),
+        None if pcol is None else pcol.ctypes.data, None if pmom is None else pmom.ctypes.data, out.ctypes.data,
+        mom.ctypes.data, var.ctypes.data, C.byref(sec)))
+    return out, mom, var, sec.value
+
+
+def temporal_accumulate_device(width, height, color_ptr, aov_ptrs, out_color_ptr, out_moments_ptr, out_variance_ptr=None,
+                               prev=None, **opts):
+    """temporal_accumulate over device buffers (e.g. torch CUDA float64 tensors' data_ptr()): aov_ptrs is a dict of
+    the four guides' pointers; prev is None or (camera, dict of the previous normal / position / depth pointers,
+    previous colour pointer, previous moments pointer); out_variance_ptr may be None.  Returns the device seconds."""
+    b = AovBuffers(*[int(aov_ptrs[k]) for k in ("albedo", "normal", "position", "depth")])
+    pc = pb = pcol = pmom = None
+    if prev is not None:
+        pcam, paov, pcol, pmom = prev
+        pb = AovBuffers(None, *[int(paov[k]) for k in ("normal", "position", "depth")])
+        pc, pcol, pmom = C.byref(pcam), C.c_void_p(int(pcol)), C.c_void_p(int(pmom))
+    sec = C.c_double()
+    o = _temporal_opts(opts)
+    _check(lib().mcpt_temporal_accumulate_device(
+        C.byref(o), pc, int(width), int(height), C.c_void_p(int(color_ptr)), C.byref(b), None if pb is None else C.byref(pb),
+        pcol, pmom, C.c_void_p(int(out_color_ptr)), C.c_void_p(int(out_moments_ptr)),
+        None if out_variance_ptr is None else C.c_void_p(int(out_variance_ptr)), C.byref(sec)))
+    return sec.value
+
+
+class TemporalAccumulator:
+    """The history of a frame sequence over a static scene: push(camera, color, aovs) accumulates one frame onto
+    what the earlier pushes left and returns (accumulated colour, variance of its luminance); the unfiltered
+    accumulated colour is the history (denoise the returned frame, not the history).  opts as temporal_accumulate.
+    After a push: `moments` (H x W x 4), `seconds` (device time) and `kept` (share of pixels that kept a history)."""
+
+    def __init__(self, **opts):
+        self.opts = opts
+        self.reset()
+
+    def reset(self):
+        self.state, self.moments, self.seconds, self.kept = None, None, 0.0, 0.0
+
+    def push(self, camera, color, aovs):
+        cam = Camera.from_buffer_copy(camera)
+        keep = {k: np.array(aovs[k], dtype=np.float64) for k in ("albedo", "normal", "position", "depth")}
+        out, mom, var, self.seconds = temporal_accumulate(color, keep, self.state, **self.opts)
+        self.state, self.moments = (cam, keep, out, mom), mom
+        self.kept = float((mom[..., 2] > 1.5).mean())
+        return out, var
 
 
 def debug_adaptive_active(scene, device=-1):

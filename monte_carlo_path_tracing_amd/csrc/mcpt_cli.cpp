@@ -17,6 +17,13 @@
 //   AOVs (mcpt_render_aovs); --out and --hdr then carry the denoised frame.  With --adaptive the variance comes
 //   from the adaptive render's noise map (mcpt_variance_from_noise), else from the filter's spatial estimate.
 //   --aov-out PREFIX writes PREFIX_albedo.pfm, PREFIX_normal.pfm (PF) and PREFIX_depth.pfm (Pf).
+//               [--frames N --orbit DEG [--temporal-alpha A]]
+//   --frames N renders a sequence with temporal accumulation (mcpt_temporal_accumulate): frame k uses the camera
+//   orbited by k * DEG degrees about the up axis through lookat (mcpt_camera_orbit) and seed + k (with the counter
+//   RNG the same seed would repeat the same noise), and is accumulated onto the reprojected history of frame k - 1.
+//   With --denoise the accumulated colour and its temporal variance feed mcpt_denoise; the unfiltered accumulated
+//   colour stays the history.  --out, --hdr and --aov-out gain _%04d (the frame) before the extension; one line per
+//   frame reports the share of pixels that kept their history.  Not with --adaptive.
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -105,6 +112,103 @@ bool write_pfm(const char* path, const std::vector<double>& hdr, int W, int H, i
     return true;
 }
 
+// "out.bmp", 7 -> "out_0007.bmp" (no extension: appended)
+std::string frame_path(const std::string& path, int k) {
+    char tag[16];
+    std::snprintf(tag, sizeof tag, "_%04d", k);
+    const size_t dot = path.rfind('.'), slash = path.find_last_of('/');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return path + tag;
+    return path.substr(0, dot) + tag + path.substr(dot);
+}
+
+struct SequenceArgs {
+    int frames, spp, mode, flags;
+    double orbit;
+    uint64_t seed;
+    bool progress, grid, denoise;
+    std::string out, hdr_out, aov_out;
+};
+
+// --frames: render, accumulate (and filter) frame after frame; the history ping-pongs between two sets of buffers
+int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceArgs& a, const std::vector<int32_t>& devices,
+                    const mcpt_temporal_opts& tp, const mcpt_denoise_opts& dn) {
+    const int W = cam0.width, H = cam0.height;
+    const size_t npx = (size_t)W * H;
+    struct Frame {
+        mcpt_camera cam;
+        std::vector<double> albedo, normal, position, depth, color, moments;
+    } fr[2];
+    for (auto& f : fr) {
+        f.albedo.resize(3 * npx), f.normal.resize(3 * npx), f.position.resize(3 * npx), f.depth.resize(npx);
+        f.color.resize(3 * npx), f.moments.resize(4 * npx);
+    }
+    std::vector<double> hdr, variance(npx), filtered(3 * npx);
+    for (int k = 0; k < a.frames; k++) {
+        Frame &cur = fr[k & 1], &prev = fr[(k & 1) ^ 1];
+        if (mcpt_camera_orbit(&cam0, k * a.orbit, &cur.cam) != MCPT_OK) {
+            std::fprintf(stderr, "%s\n", mcpt_last_error());
+            return 1;
+        }
+        mcpt_stats st{};
+        if (render(scene, cur.cam, a.spp, a.mode, a.seed + k, a.progress, a.grid, a.flags, devices, hdr, &st) != MCPT_OK) {
+            std::fprintf(stderr, "render failed: %s\n", mcpt_last_error());
+            return 1;
+        }
+        const mcpt_aov_buffers aov{cur.albedo.data(), cur.normal.data(), cur.position.data(), cur.depth.data()};
+        const mcpt_aov_buffers paov{prev.albedo.data(), prev.normal.data(), prev.position.data(), prev.depth.data()};
+        mcpt_render_opts ao;
+        mcpt_render_opts_init(&ao);
+        ao.accel = a.grid ? MCPT_ACCEL_GRID : MCPT_ACCEL_BVH;
+        if (mcpt_render_aovs(scene, &cur.cam, &ao, &aov) != MCPT_OK) {
+            std::fprintf(stderr, "AOV render failed: %s\n", mcpt_last_error());
+            return 1;
+        }
+        double tsec = 0;
+        if (mcpt_temporal_accumulate(&tp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov, k ? &paov : nullptr,
+                                     k ? prev.color.data() : nullptr, k ? prev.moments.data() : nullptr, cur.color.data(),
+                                     cur.moments.data(), variance.data(), &tsec) != MCPT_OK) {
+            std::fprintf(stderr, "temporal accumulation failed: %s\n", mcpt_last_error());
+            return 1;
+        }
+        size_t kept = 0;
+        double nsum = 0;
+        for (size_t p = 0; p < npx; p++) kept += cur.moments[4 * p + 2] > 1.5, nsum += cur.moments[4 * p + 2];
+        std::printf("frame %d: orbit %g deg, seed %llu, %.3f s render, %.3f ms accumulate, %.1f%% of the pixels kept their "
+                    "history (mean length %.2f)\n", k, k * a.orbit, (unsigned long long)(a.seed + k), st.seconds, tsec * 1e3,
+                    100.0 * kept / npx, nsum / npx);
+        const std::vector<double>* shown = &cur.color;
+        if (a.denoise) {
+            double dsec = 0;
+            if (mcpt_denoise(&dn, W, H, cur.color.data(), variance.data(), &aov, filtered.data(), nullptr, &dsec) != MCPT_OK) {
+                std::fprintf(stderr, "denoise failed: %s\n", mcpt_last_error());
+                return 1;
+            }
+            std::printf("  denoised: %d iterations, sigma_color %g, variance from the temporal moments, %.3f ms device\n",
+                        dn.iterations, dn.sigma_color, dsec * 1e3);
+            shown = &filtered;
+        }
+        if (!a.aov_out.empty()) {
+            const std::string pre = frame_path(a.aov_out, k);
+            if (!(write_pfm((pre + "_albedo.pfm").c_str(), cur.albedo, W, H) && write_pfm((pre + "_normal.pfm").c_str(), cur.normal, W, H) &&
+                  write_pfm((pre + "_depth.pfm").c_str(), cur.depth, W, H, 1))) {
+                std::fprintf(stderr, "cannot write %s_{albedo,normal,depth}.pfm\n", pre.c_str());
+                return 1;
+            }
+        }
+        std::vector<uint8_t> rgb8(shown->size());
+        mcpt_tone_map(shown->data(), W, H, 380.0, 0.25, rgb8.data());  // main.cpp:583
+        if (mcpt_write_bmp(frame_path(a.out, k).c_str(), rgb8.data(), W, H) != MCPT_OK) {
+            std::fprintf(stderr, "%s\n", mcpt_last_error());
+            return 1;
+        }
+        if (!a.hdr_out.empty() && !write_pfm(frame_path(a.hdr_out, k).c_str(), *shown, W, H)) {
+            std::fprintf(stderr, "cannot write %s\n", frame_path(a.hdr_out, k).c_str());
+            return 1;
+        }
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -122,6 +226,11 @@ int main(int argc, char** argv) {
     bool denoise = false;
     mcpt_denoise_opts dn;
     mcpt_denoise_opts_init(&dn);
+    int frames = 0;
+    double orbit = 0.0;
+    bool sequence_flag = false;  // --orbit or --temporal-alpha seen
+    mcpt_temporal_opts tp;
+    mcpt_temporal_opts_init(&tp);
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -172,6 +281,15 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--denoise-iterations")) dn.iterations = std::atoi(next());
         else if (!std::strcmp(argv[a], "--denoise-sigma-color")) dn.sigma_color = std::atof(next());
         else if (!std::strcmp(argv[a], "--aov-out")) aov_out = next();
+        else if (!std::strcmp(argv[a], "--frames")) {
+            frames = std::atoi(next());
+            if (frames < 1) {
+                std::fprintf(stderr, "--frames needs a count >= 1\n");
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[a], "--orbit")) orbit = std::atof(next()), sequence_flag = true;
+        else if (!std::strcmp(argv[a], "--temporal-alpha")) tp.alpha = std::atof(next()), sequence_flag = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -218,6 +336,20 @@ int main(int argc, char** argv) {
     if (!adaptive && !count_out.empty()) {
         std::fprintf(stderr, "--count-out needs --adaptive\n");
         return 2;
+    }
+    if (sequence_flag && frames == 0) {
+        std::fprintf(stderr, "--orbit and --temporal-alpha need --frames\n");
+        return 2;
+    }
+    if (frames > 0) {
+        if (adaptive) {
+            std::fprintf(stderr, "--frames accumulates plain renders; drop --adaptive\n");
+            return 2;
+        }
+        const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out};
+        const int rc = render_sequence(scene, cam, sa, devices, tp, dn);
+        mcpt_scene_destroy(scene);
+        return rc;
     }
     ad.max_spp = spp;
     const auto t0 = std::chrono::steady_clock::now();
