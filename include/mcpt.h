@@ -29,7 +29,8 @@ extern "C" {
                                * mcpt_render_aovs and its _device form) and the variance-guided a-trous denoiser
                                * (mcpt_denoise_opts, mcpt_denoise and its _device form, mcpt_variance_from_noise);
                                * temporal accumulation (mcpt_temporal_opts, mcpt_temporal_accumulate and its
-                               * _device form, mcpt_camera_orbit);
+                               * _device form, mcpt_camera_orbit); its history clamping
+                               * (mcpt_temporal_clamp_opts, mcpt_temporal_accumulate_clamped and its _device form);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -445,6 +446,62 @@ int mcpt_temporal_accumulate_device(const mcpt_temporal_opts* opts, const mcpt_c
                                     const mcpt_aov_buffers* dev_prev_guides, const double* dev_prev_color,
                                     const double* dev_prev_moments, double* dev_out_color, double* dev_out_moments,
                                     double* dev_out_variance, double* device_seconds);
+
+/* Temporal accumulation with history clamping (opt-in; mcpt_temporal_accumulate above is unchanged).  The long
+ * history ghosts view-dependent shading once the camera moves: the reprojected surface point is the same, its
+ * radiance towards the new camera is not.  The remedy of the SVGF descendants (variance clipping against a fast
+ * history, as in ReLAX): keep a second history Hf that forgets within a few frames, and clamp the long one per pixel
+ * and channel to mean +- sigma * standard deviation of the fast history over a small window.  The state gains the
+ * fast history (h*w*3): prev_fast in, out_fast out.
+ * Everything of mcpt_temporal_accumulate's rule up to and including `blend` is unchanged; call its results S (the
+ * colour) and (m1, m2, n, g).  Then, for each pixel p:
+ *   fast     gathered from prev_fast with the same taps, validity tests, b_q and Wsum as Hc; with history:
+ *            A_f = max(alpha_fast, 1 / n) with the same n, F = (1 - A_f) Hf + A_f C; without: F = C.  out_fast = F:
+ *            what mcpt_temporal_accumulate returns as colour for alpha = alpha_fast, prev_color = prev_fast and
+ *            the same prev_moments, bit for bit
+ *   box      only when p has history (which implies depth_p > 0): over the taps q of the clipped
+ *            (2 radius + 1)^2 window around p with depth_q > 0 (the current depth), rows top to bottom, columns
+ *            left to right, k of them, per channel c: mu_c = (sum of F_q,c) / k, then
+ *            sd_c = sqrt((sum of (F_q,c - mu_c)^2) / k), lo_c = mu_c - sigma * sd_c, hi_c = mu_c + sigma * sd_c.
+ *            Two passes, not sum x^2 - (sum x)^2 / k, for the reason given for V_0 above
+ *   clamp    out_color_c = min(max(S_c, lo_c), hi_c).  With l_S = (S.r + S.g + S.b) / 3 and l_out the same of
+ *            out_color: shift = l_out - l_S, m1 <- m1 + shift, m2 <- m2 + (m1_new^2 - m1_old^2) (the central moment
+ *            m2 - m1^2 is kept), n and g unchanged.  Without history: out_color = C, moments (l, l^2, 1, 1), shift 0
+ *   variance as in mcpt_temporal_accumulate, from the clamped out_color and the corrected moments: the temporal
+ *            formula where it applies, otherwise V_0 of the clamped out_color
+ * out_shift (h*w, optional) is the shift per pixel, 0 where nothing moved: a continuous quantity, so two
+ * implementations can be compared without a discrete "was clamped" decision.  sigma = 0 replaces the history by the
+ * window's mean; a large sigma clamps nothing except where the window's deviation is 0 (a single hit tap).  The
+ * clamped colour is the history of the next call, and so is out_fast.  It costs accuracy where there is nothing to
+ * fix: on a static camera the box cuts into the long history's converged values. */
+typedef struct {
+    uint32_t struct_size; /* sizeof(mcpt_temporal_clamp_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
+    int32_t radius;       /* default 2, 1..3: the (2 radius + 1)^2 window of the fast history */
+    double alpha_fast;    /* default 0.5, in (0, 1]: the smallest weight of the current frame in the fast history */
+    double sigma;         /* default 2, finite and >= 0: the box is mean +- sigma * standard deviation, per channel */
+} mcpt_temporal_clamp_opts;
+/* zero-fills *clamp and sets struct_size and the defaults above */
+void mcpt_temporal_clamp_opts_init(mcpt_temporal_clamp_opts* clamp);
+/* As mcpt_temporal_accumulate, with prev_fast (part of the previous state: given with it or not at all), out_fast
+ * (required) and out_shift (may be NULL).  Refused with MCPT_E_INVALID before any device work: everything
+ * mcpt_temporal_accumulate refuses, a NULL clamp, a clamp struct_size mismatch, a radius, alpha_fast or sigma outside
+ * the ranges above, a NULL out_fast, a previous state without prev_fast or prev_fast alone, out_fast or out_shift
+ * aliasing an input or another output (and an output aliasing prev_fast). */
+int mcpt_temporal_accumulate_clamped(const mcpt_temporal_opts* opts, const mcpt_temporal_clamp_opts* clamp,
+                                     const mcpt_camera* prev_cam, int32_t width, int32_t height, const double* color,
+                                     const mcpt_aov_buffers* guides, const mcpt_aov_buffers* prev_guides,
+                                     const double* prev_color, const double* prev_moments, const double* prev_fast,
+                                     double* out_color, double* out_moments, double* out_fast, double* out_variance,
+                                     double* out_shift, double* device_seconds);
+/* same with every array in DEVICE memory on opts->device (opts, clamp, prev_cam and device_seconds stay host pointers) */
+int mcpt_temporal_accumulate_clamped_device(const mcpt_temporal_opts* opts, const mcpt_temporal_clamp_opts* clamp,
+                                            const mcpt_camera* prev_cam, int32_t width, int32_t height,
+                                            const double* dev_color, const mcpt_aov_buffers* dev_guides,
+                                            const mcpt_aov_buffers* dev_prev_guides, const double* dev_prev_color,
+                                            const double* dev_prev_moments, const double* dev_prev_fast,
+                                            double* dev_out_color, double* dev_out_moments, double* dev_out_fast,
+                                            double* dev_out_variance, double* dev_out_shift, double* device_seconds);
+
 /* Host helper: *out = *in with eye rotated by `degrees` about the axis through lookat along k = up / |up|
  * (Rodrigues, right-handed): with v = eye - lookat, t = degrees * pi / 180 and vp = v - k (k . v),
  * eye' = eye + (k x v) sin t - vp (1 - cos t); 0 degrees returns eye bit for bit.  MCPT_E_INVALID for a NULL

@@ -18,6 +18,7 @@ import numpy as np
 __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_adaptive", "render_adaptive_device", "closest_hit", "light_prep", "primary_hits",
            "AovBuffers", "DenoiseOpts", "render_aovs", "render_aovs_device", "denoise", "denoise_device", "variance_from_noise",
            "TemporalOpts", "TemporalAccumulator", "temporal_accumulate", "temporal_accumulate_device", "camera_orbit",
+           "TemporalClampOpts", "temporal_accumulate_clamped", "temporal_accumulate_clamped_device",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -100,6 +101,11 @@ class TemporalOpts(C.Structure):
                 ("sigma_albedo", C.c_double)]
 
 
+class TemporalClampOpts(C.Structure):
+    """mcpt_temporal_clamp_opts: the history clamp's parameters (include/mcpt.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("alpha_fast", C.c_double), ("sigma", C.c_double)]
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 
 
@@ -134,7 +140,8 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_adaptive_opts_init", "mcpt_render_adaptive", "mcpt_render_adaptive_device",
            "mcpt_render_aovs", "mcpt_render_aovs_device", "mcpt_denoise_opts_init", "mcpt_denoise", "mcpt_denoise_device",
            "mcpt_variance_from_noise", "mcpt_temporal_opts_init", "mcpt_temporal_accumulate",
-           "mcpt_temporal_accumulate_device", "mcpt_camera_orbit", "mcpt_closest_hit", "mcpt_light_prep", "mcpt_primary_hits", "mcpt_tone_map",
+           "mcpt_temporal_accumulate_device", "mcpt_temporal_clamp_opts_init", "mcpt_temporal_accumulate_clamped",
+           "mcpt_temporal_accumulate_clamped_device", "mcpt_camera_orbit", "mcpt_closest_hit", "mcpt_light_prep", "mcpt_primary_hits", "mcpt_tone_map",
            "mcpt_write_bmp", "mcpt_comm_unique_id", "mcpt_comm_init_rank", "mcpt_comm_destroy"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
@@ -201,6 +208,13 @@ def lib():
                                                    C.POINTER(AovBuffers), P, P, P, P, P, C.POINTER(D)]
             L.mcpt_temporal_accumulate_device.argtypes = L.mcpt_temporal_accumulate.argtypes
             L.mcpt_camera_orbit.argtypes = [C.POINTER(Camera), D, C.POINTER(Camera)]
+        if hasattr(L, "mcpt_temporal_accumulate_clamped"):  # and so is the history clamp
+            L.mcpt_temporal_clamp_opts_init.argtypes = [C.POINTER(TemporalClampOpts)]
+            L.mcpt_temporal_clamp_opts_init.restype = None
+            L.mcpt_temporal_accumulate_clamped.argtypes = [C.POINTER(TemporalOpts), C.POINTER(TemporalClampOpts), C.POINTER(Camera),
+                                                           I, I, P, C.POINTER(AovBuffers), C.POINTER(AovBuffers), P, P, P, P, P,
+                                                           P, P, P, C.POINTER(D)]
+            L.mcpt_temporal_accumulate_clamped_device.argtypes = L.mcpt_temporal_accumulate_clamped.argtypes
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -608,24 +622,105 @@ def temporal_accumulate_device(width, height, color_ptr, aov_ptrs, out_color_ptr
     return sec.value
 
 
+CLAMP_OPTS = ("radius", "alpha_fast", "sigma")
+
+
+def _clamp_opts(clamp):
+    """clamp: None or True (the library defaults) or a dict of radius / alpha_fast / sigma"""
+    c = TemporalClampOpts()
+    lib().mcpt_temporal_clamp_opts_init(C.byref(c))
+    for k, v in ({} if clamp is None or clamp is True else dict(clamp)).items():
+        if k not in CLAMP_OPTS:
+            raise TypeError("unknown clamp option %r (one of %s)" % (k, ", ".join(CLAMP_OPTS)))
+        if v is not None:
+            setattr(c, k, type(getattr(c, k))(v))
+    return c
+
+
+def temporal_accumulate_clamped(color, aovs, prev=None, clamp=None, **opts):
+    """temporal_accumulate with history clamping (mcpt_temporal_accumulate_clamped; include/mcpt.h states the rule).
+    prev is None or (camera, aovs, colour, moments, fast): the previous frame's Camera and guides and the colour,
+    moments and fast history this function returned for it.  clamp: None or True for the library defaults, or a dict
+    of radius, alpha_fast, sigma.  opts as temporal_accumulate.  Returns (colour H x W x 3, moments H x W x 4, fast
+    history H x W x 3, variance H x W, shift H x W -- how far the clamp moved each pixel's luminance, 0 where it did
+    not -- and the device seconds)."""
+    color = _d(color)
+    H, W = color.shape[:2]
+    assert color.shape == (H, W, 3)
+    keys = ("albedo", "normal", "position", "depth")
+    g = {k: _d(aovs[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys}
+    b = AovBuffers(*[g[k].ctypes.data for k in keys])
+    pc = pb = pcol = pmom = pfast = None
+    if prev is not None:
+        pcam, paov, pcol, pmom, pfast = prev
+        pg = {k: _d(paov[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys[1:]}
+        pb = AovBuffers(None, *[pg[k].ctypes.data for k in keys[1:]])
+        pcol, pmom, pfast = _d(pcol, (H, W, 3)), _d(pmom, (H, W, 4)), _d(pfast, (H, W, 3))
+        pc = C.byref(pcam)
+    out, mom, fast, var, shift = np.zeros((H, W, 3)), np.zeros((H, W, 4)), np.zeros((H, W, 3)), np.zeros((H, W)), np.zeros((H, W))
+    sec = C.c_double()
+    o, c = _temporal_opts(opts), _clamp_opts(clamp)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _check(lib().mcpt_temporal_accumulate_clamped(
+        C.byref(o), C.byref(c), pc, W, H, color.ctypes.data, C.byref(b), None if pb is None else C.byref(pb), ptr(pcol),
+        ptr(pmom), ptr(pfast), out.ctypes.data, mom.ctypes.data, fast.ctypes.data, var.ctypes.data, shift.ctypes.data,
+        C.byref(sec)))
+    return out, mom, fast, var, shift, sec.value
+
+
+def temporal_accumulate_clamped_device(width, height, color_ptr, aov_ptrs, out_color_ptr, out_moments_ptr, out_fast_ptr,
+                                       out_variance_ptr=None, out_shift_ptr=None, prev=None, clamp=None, **opts):
+    """temporal_accumulate_clamped over device buffers, as temporal_accumulate_device: prev is None or (camera, dict of
+    the previous normal / position / depth pointers, previous colour, moments and fast-history pointers);
+    out_variance_ptr and out_shift_ptr may be None.  Returns the device seconds."""
+    b = AovBuffers(*[int(aov_ptrs[k]) for k in ("albedo", "normal", "position", "depth")])
+    pc = pb = pcol = pmom = pfast = None
+    if prev is not None:
+        pcam, paov, pcol, pmom, pfast = prev
+        pb = AovBuffers(None, *[int(paov[k]) for k in ("normal", "position", "depth")])
+        pc, pcol, pmom, pfast = C.byref(pcam), C.c_void_p(int(pcol)), C.c_void_p(int(pmom)), C.c_void_p(int(pfast))
+    sec = C.c_double()
+    o, c = _temporal_opts(opts), _clamp_opts(clamp)
+    opt = lambda p: None if p is None else C.c_void_p(int(p))
+    _check(lib().mcpt_temporal_accumulate_clamped_device(
+        C.byref(o), C.byref(c), pc, int(width), int(height), C.c_void_p(int(color_ptr)), C.byref(b),
+        None if pb is None else C.byref(pb), pcol, pmom, pfast, C.c_void_p(int(out_color_ptr)),
+        C.c_void_p(int(out_moments_ptr)), C.c_void_p(int(out_fast_ptr)), opt(out_variance_ptr), opt(out_shift_ptr),
+        C.byref(sec)))
+    return sec.value
+
+
 class TemporalAccumulator:
     """The history of a frame sequence over a static scene: push(camera, color, aovs) accumulates one frame onto
     what the earlier pushes left and returns (accumulated colour, variance of its luminance); the unfiltered
     accumulated colour is the history (denoise the returned frame, not the history).  opts as temporal_accumulate.
-    After a push: `moments` (H x W x 4), `seconds` (device time) and `kept` (share of pixels that kept a history)."""
+    After a push: `moments` (H x W x 4), `seconds` (device time) and `kept` (share of pixels that kept a history).
+    clamp: None (the default: plain accumulation), True or a dict of radius / alpha_fast / sigma for history clamping
+    (temporal_accumulate_clamped); then a push also leaves `fast` (the fast history), `shift` and `clamped`, the share
+    of pixels with shift != 0."""
 
-    def __init__(self, **opts):
-        self.opts = opts
+    def __init__(self, clamp=None, **opts):
+        if clamp is False:
+            clamp = None
+        self.clamp, self.opts = clamp, opts
         self.reset()
 
     def reset(self):
         self.state, self.moments, self.seconds, self.kept = None, None, 0.0, 0.0
+        self.fast, self.shift, self.clamped = None, None, 0.0
 
     def push(self, camera, color, aovs):
         cam = Camera.from_buffer_copy(camera)
         keep = {k: np.array(aovs[k], dtype=np.float64) for k in ("albedo", "normal", "position", "depth")}
-        out, mom, var, self.seconds = temporal_accumulate(color, keep, self.state, **self.opts)
-        self.state, self.moments = (cam, keep, out, mom), mom
+        if self.clamp is None:
+            out, mom, var, self.seconds = temporal_accumulate(color, keep, self.state, **self.opts)
+            self.state = (cam, keep, out, mom)
+        else:
+            out, mom, self.fast, var, self.shift, self.seconds = temporal_accumulate_clamped(color, keep, self.state, self.clamp,
+                                                                                             **self.opts)
+            self.state = (cam, keep, out, mom, self.fast)
+            self.clamped = float((self.shift != 0).mean())
+        self.moments = mom
         self.kept = float((mom[..., 2] > 1.5).mean())
         return out, var
 

@@ -17,13 +17,17 @@
 //   AOVs (mcpt_render_aovs); --out and --hdr then carry the denoised frame.  With --adaptive the variance comes
 //   from the adaptive render's noise map (mcpt_variance_from_noise), else from the filter's spatial estimate.
 //   --aov-out PREFIX writes PREFIX_albedo.pfm, PREFIX_normal.pfm (PF) and PREFIX_depth.pfm (Pf).
-//               [--frames N --orbit DEG [--temporal-alpha A]]
+//               [--frames N --orbit DEG [--temporal-alpha A] [--history-clamp K [--clamp-radius R] [--clamp-alpha-fast A]]]
 //   --frames N renders a sequence with temporal accumulation (mcpt_temporal_accumulate): frame k uses the camera
 //   orbited by k * DEG degrees about the up axis through lookat (mcpt_camera_orbit) and seed + k (with the counter
 //   RNG the same seed would repeat the same noise), and is accumulated onto the reprojected history of frame k - 1.
 //   With --denoise the accumulated colour and its temporal variance feed mcpt_denoise; the unfiltered accumulated
 //   colour stays the history.  --out, --hdr and --aov-out gain _%04d (the frame) before the extension; one line per
 //   frame reports the share of pixels that kept their history.  Not with --adaptive.
+//   --history-clamp K accumulates with mcpt_temporal_accumulate_clamped: the history is clamped to mean +- K standard
+//   deviations of a fast history (weight of the current frame >= A, default 0.5) over the (2 R + 1)^2 window (default
+//   R = 2), which removes the ghosts of view-dependent shading at larger steps and costs a little on a static camera;
+//   the frame's line then ends with the share of pixels the clamp moved.
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -131,18 +135,19 @@ struct SequenceArgs {
 
 // --frames: render, accumulate (and filter) frame after frame; the history ping-pongs between two sets of buffers
 int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceArgs& a, const std::vector<int32_t>& devices,
-                    const mcpt_temporal_opts& tp, const mcpt_denoise_opts& dn) {
+                    const mcpt_temporal_opts& tp, const mcpt_temporal_clamp_opts* clamp, const mcpt_denoise_opts& dn) {
     const int W = cam0.width, H = cam0.height;
     const size_t npx = (size_t)W * H;
     struct Frame {
         mcpt_camera cam;
-        std::vector<double> albedo, normal, position, depth, color, moments;
+        std::vector<double> albedo, normal, position, depth, color, moments, fast;
     } fr[2];
     for (auto& f : fr) {
         f.albedo.resize(3 * npx), f.normal.resize(3 * npx), f.position.resize(3 * npx), f.depth.resize(npx);
         f.color.resize(3 * npx), f.moments.resize(4 * npx);
+        if (clamp) f.fast.resize(3 * npx);
     }
-    std::vector<double> hdr, variance(npx), filtered(3 * npx);
+    std::vector<double> hdr, variance(npx), filtered(3 * npx), shift(clamp ? npx : 0);
     for (int k = 0; k < a.frames; k++) {
         Frame &cur = fr[k & 1], &prev = fr[(k & 1) ^ 1];
         if (mcpt_camera_orbit(&cam0, k * a.orbit, &cur.cam) != MCPT_OK) {
@@ -164,9 +169,15 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
             return 1;
         }
         double tsec = 0;
-        if (mcpt_temporal_accumulate(&tp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov, k ? &paov : nullptr,
-                                     k ? prev.color.data() : nullptr, k ? prev.moments.data() : nullptr, cur.color.data(),
-                                     cur.moments.data(), variance.data(), &tsec) != MCPT_OK) {
+        const int rc = clamp ? mcpt_temporal_accumulate_clamped(&tp, clamp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov,
+                                                                k ? &paov : nullptr, k ? prev.color.data() : nullptr,
+                                                                k ? prev.moments.data() : nullptr, k ? prev.fast.data() : nullptr,
+                                                                cur.color.data(), cur.moments.data(), cur.fast.data(),
+                                                                variance.data(), shift.data(), &tsec)
+                             : mcpt_temporal_accumulate(&tp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov, k ? &paov : nullptr,
+                                                        k ? prev.color.data() : nullptr, k ? prev.moments.data() : nullptr,
+                                                        cur.color.data(), cur.moments.data(), variance.data(), &tsec);
+        if (rc != MCPT_OK) {
             std::fprintf(stderr, "temporal accumulation failed: %s\n", mcpt_last_error());
             return 1;
         }
@@ -174,8 +185,14 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
         double nsum = 0;
         for (size_t p = 0; p < npx; p++) kept += cur.moments[4 * p + 2] > 1.5, nsum += cur.moments[4 * p + 2];
         std::printf("frame %d: orbit %g deg, seed %llu, %.3f s render, %.3f ms accumulate, %.1f%% of the pixels kept their "
-                    "history (mean length %.2f)\n", k, k * a.orbit, (unsigned long long)(a.seed + k), st.seconds, tsec * 1e3,
+                    "history (mean length %.2f)", k, k * a.orbit, (unsigned long long)(a.seed + k), st.seconds, tsec * 1e3,
                     100.0 * kept / npx, nsum / npx);
+        if (clamp) {
+            size_t moved = 0;
+            for (size_t p = 0; p < npx; p++) moved += shift[p] != 0;
+            std::printf(", the clamp moved %.1f%% of the pixels", 100.0 * moved / npx);
+        }
+        std::printf("\n");
         const std::vector<double>* shown = &cur.color;
         if (a.denoise) {
             double dsec = 0;
@@ -228,9 +245,12 @@ int main(int argc, char** argv) {
     mcpt_denoise_opts_init(&dn);
     int frames = 0;
     double orbit = 0.0;
-    bool sequence_flag = false;  // --orbit or --temporal-alpha seen
+    bool sequence_flag = false;  // --orbit, --temporal-alpha or a clamp option seen
     mcpt_temporal_opts tp;
     mcpt_temporal_opts_init(&tp);
+    bool history_clamp = false, clamp_flag = false;  // --history-clamp seen; --clamp-radius or --clamp-alpha-fast seen
+    mcpt_temporal_clamp_opts tc;
+    mcpt_temporal_clamp_opts_init(&tc);
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -290,6 +310,9 @@ int main(int argc, char** argv) {
         }
         else if (!std::strcmp(argv[a], "--orbit")) orbit = std::atof(next()), sequence_flag = true;
         else if (!std::strcmp(argv[a], "--temporal-alpha")) tp.alpha = std::atof(next()), sequence_flag = true;
+        else if (!std::strcmp(argv[a], "--history-clamp")) tc.sigma = std::atof(next()), history_clamp = sequence_flag = true;
+        else if (!std::strcmp(argv[a], "--clamp-radius")) tc.radius = std::atoi(next()), clamp_flag = sequence_flag = true;
+        else if (!std::strcmp(argv[a], "--clamp-alpha-fast")) tc.alpha_fast = std::atof(next()), clamp_flag = sequence_flag = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -338,7 +361,7 @@ int main(int argc, char** argv) {
         return 2;
     }
     if (sequence_flag && frames == 0) {
-        std::fprintf(stderr, "--orbit and --temporal-alpha need --frames\n");
+        std::fprintf(stderr, "--orbit, --temporal-alpha and --history-clamp need --frames\n");
         return 2;
     }
     if (frames > 0) {
@@ -347,7 +370,11 @@ int main(int argc, char** argv) {
             return 2;
         }
         const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out};
-        const int rc = render_sequence(scene, cam, sa, devices, tp, dn);
+        if (clamp_flag && !history_clamp) {
+            std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
+            return 2;
+        }
+        const int rc = render_sequence(scene, cam, sa, devices, tp, history_clamp ? &tc : nullptr, dn);
         mcpt_scene_destroy(scene);
         return rc;
     }

@@ -1,8 +1,14 @@
-// Temporal accumulation for gfx950 (mcpt_temporal_accumulate, include/mcpt.h states the rule in full) and the
-// host helper mcpt_camera_orbit.  No counterpart in the reference.
+// Temporal accumulation for gfx950 (mcpt_temporal_accumulate and mcpt_temporal_accumulate_clamped, include/mcpt.h
+// states both rules in full) and the host helper mcpt_camera_orbit.  No counterpart in the reference.
 //
 //   k_temporal_accumulate  lane per pixel : reproject, gather the four taps of the previous history, blend,
-//                                           and the temporal variance where the history is long enough
+//                                           and the temporal variance where the history is long enough; the
+//                                           <true> instantiation (the clamped call) gathers and blends the fast
+//                                           history with the same taps and leaves the variance to the clamp
+//   k_temporal_clamp       lane per pixel : (the clamped call) mean and standard deviation of the fast history over
+//                                           the hit taps of the clipped window (an LDS tile), two passes; clamps
+//                                           the blended colour in place, corrects the moments, writes the shift
+//                                           and the temporal variance; lanes without history leave early
 //   k_temporal_spatial     lane per pixel : V_0 of the a-trous filter on the blended colour, only in lanes whose
 //                                           history is short (the others leave at once)
 //
@@ -10,9 +16,10 @@
 // rounding (tests/test_temporal.py).  A block is 64 x 4 pixels as in denoise.hip: the centre's loads and the
 // stores are consecutive across a wave; the four gathers follow the reprojection, which keeps neighbours
 // together under a camera move.  The centre's guides stay in registers for the four taps.  Plain loads and
-// stores only: no atomics, no LDS.  Per pixel the first kernel reads 10 doubles of its own (colour, normal,
-// position, depth), up to 4 x 14 of the previous frame (depth, moments, normal, position, colour; neighbouring
-// lanes share them in cache) and writes 8: about 0.5 KB.
+// stores only: no atomics, and no LDS outside k_temporal_clamp.  Per pixel the first kernel reads 10 doubles of
+// its own (colour, normal, position, depth), up to 4 x 14 of the previous frame (depth, moments, normal, position,
+// colour; neighbouring lanes share them in cache) and writes 8: about 0.5 KB (the clamped call: 4 x 3 more read
+// and 4 more written).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -37,10 +44,16 @@ struct TpParams {
     const double *C, *N, *X, *depth;        // the current frame
     const double *pN, *pX, *pdepth, *pC, *pM;  // the previous state
     double *outC, *outM, *outV;
+    // the clamped call only
+    int radius;
+    double alpha_fast, sigma;
+    const double* pF;
+    double *outF, *outS;  // outS: k_temporal_accumulate<true> leaves "has a history" (1 or 0), k_temporal_clamp the shift
 };
 
 __device__ inline bool temporal_variance_applies(const TpParams& P, double n, double g) { return n > P.var_n && g < 1.0; }
 
+template <bool FAST>
 __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
     const int x = blockIdx.x * kBx + threadIdx.x, y = blockIdx.y * kBy + threadIdx.y;
     if (x >= P.W || y >= P.H) return;
@@ -49,6 +62,7 @@ __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
     const double l = (c0 + c1 + c2) / 3.0;
     const double depth = P.depth[p];
     double wsum = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0, m1 = 0.0, m2 = 0.0, hn = 0.0, hg = 0.0;
+    double f0 = 0.0, f1 = 0.0, f2 = 0.0;  // FAST: the fast history's gather
     bool source = false;
     if (P.has_prev && depth > 0) {
         const double N0 = P.N[3 * p], N1 = P.N[3 * p + 1], N2 = P.N[3 * p + 2];
@@ -84,12 +98,18 @@ __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
                     m2 += bq * P.pM[4 * q + 1];
                     hn += bq * P.pM[4 * q + 2];
                     hg += bq * P.pM[4 * q + 3];
+                    if (FAST) {
+                        f0 += bq * P.pF[3 * q];
+                        f1 += bq * P.pF[3 * q + 1];
+                        f2 += bq * P.pF[3 * q + 2];
+                    }
                 }
             }
         }
     }
     double o0 = c0, o1 = c1, o2 = c2, om1 = l, om2 = l * l, on = 1.0, og = 1.0;
-    if (source && wsum >= P.min_weight) {
+    const bool history = source && wsum >= P.min_weight;
+    if (history) {
         on = fmin(hn / wsum + 1.0, P.max_history);
         const double A = fmax(P.alpha, 1.0 / on), B = 1.0 - A;
         o0 = B * (h0 / wsum) + A * c0;
@@ -101,6 +121,78 @@ __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
     }
     P.outC[3 * p] = o0, P.outC[3 * p + 1] = o1, P.outC[3 * p + 2] = o2;
     P.outM[4 * p] = om1, P.outM[4 * p + 1] = om2, P.outM[4 * p + 2] = on, P.outM[4 * p + 3] = og;
+    if (FAST) {  // the variance waits for the clamped colour and the corrected moments (k_temporal_clamp)
+        double F0 = c0, F1 = c1, F2 = c2;
+        if (history) {
+            const double A = fmax(P.alpha_fast, 1.0 / on), B = 1.0 - A;
+            F0 = B * (f0 / wsum) + A * c0;
+            F1 = B * (f1 / wsum) + A * c1;
+            F2 = B * (f2 / wsum) + A * c2;
+        }
+        P.outF[3 * p] = F0, P.outF[3 * p + 1] = F1, P.outF[3 * p + 2] = F2;
+        P.outS[p] = history ? 1.0 : 0.0;
+        return;
+    }
+    if (P.outV && temporal_variance_applies(P, on, og)) P.outV[p] = fmax(0.0, om2 - om1 * om1) * og / (1.0 - og);
+}
+
+// The clamp of the clamped call, in place on outC / outM after k_temporal_accumulate<true>: neighbours are read from
+// outF and depth only, which no lane of this kernel writes.  The block first copies its (64 + 2 r) x (4 + 2 r) window
+// of outF and depth into LDS: four planes (F.r, F.g, F.b, depth), so consecutive lanes read consecutive doubles;
+// 22 KB at the largest radius, which leaves seven blocks to a CU.  Pixels outside the frame enter as misses.  On
+// the MI355X the tile beat direct global reads of the window.  Each tap is read twice (mean, then
+// deviations) instead of held in up to 3 * 49 registers.
+constexpr int kClampRmax = 3, kTw = kBx + 2 * kClampRmax, kTh = kBy + 2 * kClampRmax, kPlane = kTw * kTh;
+
+__global__ __launch_bounds__(kBx* kBy) void k_temporal_clamp(TpParams P) {
+    __shared__ double tile[4 * kPlane];
+    const int x = blockIdx.x * kBx + threadIdx.x, y = blockIdx.y * kBy + threadIdx.y;
+    const int bx0 = blockIdx.x * kBx - P.radius, by0 = blockIdx.y * kBy - P.radius;
+    const int tw = kBx + 2 * P.radius, th = kBy + 2 * P.radius;
+    for (int t = threadIdx.y * kBx + threadIdx.x; t < tw * th; t += kBx * kBy) {
+        const int ty = t / tw, tx = t - ty * tw, gx = bx0 + tx, gy = by0 + ty;
+        double d = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        if (gx >= 0 && gx < P.W && gy >= 0 && gy < P.H) {
+            const size_t q = (size_t)gy * P.W + gx;
+            d = P.depth[q], a0 = P.outF[3 * q], a1 = P.outF[3 * q + 1], a2 = P.outF[3 * q + 2];
+        }
+        const int e = ty * kTw + tx;
+        tile[e] = a0, tile[kPlane + e] = a1, tile[2 * kPlane + e] = a2, tile[3 * kPlane + e] = d;
+    }
+    __syncthreads();
+    if (x >= P.W || y >= P.H) return;
+    const size_t p = (size_t)y * P.W + x;
+    if (P.outS[p] == 0.0) return;  // no history: colour, moments and a shift of 0 are already in place
+    const int y0 = max(y - P.radius, 0) - by0, y1 = min(y + P.radius, P.H - 1) - by0;  // the clipped window, in the tile
+    const int x0 = max(x - P.radius, 0) - bx0, x1 = min(x + P.radius, P.W - 1) - bx0;
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, cnt = 0.0;
+    for (int ty = y0; ty <= y1; ty++)
+        for (int tx = x0; tx <= x1; tx++) {
+            const int e = ty * kTw + tx;
+            if (!(tile[3 * kPlane + e] > 0)) continue;
+            cnt += 1.0;
+            s0 += tile[e], s1 += tile[kPlane + e], s2 += tile[2 * kPlane + e];
+        }
+    const double mu0 = s0 / cnt, mu1 = s1 / cnt, mu2 = s2 / cnt;  // cnt >= 1: p itself is a hit
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0;
+    for (int ty = y0; ty <= y1; ty++)
+        for (int tx = x0; tx <= x1; tx++) {
+            const int e = ty * kTw + tx;
+            if (!(tile[3 * kPlane + e] > 0)) continue;
+            const double e0 = tile[e] - mu0, e1 = tile[kPlane + e] - mu1, e2 = tile[2 * kPlane + e] - mu2;
+            v0 += e0 * e0, v1 += e1 * e1, v2 += e2 * e2;
+        }
+    const double w0 = P.sigma * sqrt(v0 / cnt), w1 = P.sigma * sqrt(v1 / cnt), w2 = P.sigma * sqrt(v2 / cnt);
+    const double S0 = P.outC[3 * p], S1 = P.outC[3 * p + 1], S2 = P.outC[3 * p + 2];
+    const double o0 = fmin(fmax(S0, mu0 - w0), mu0 + w0);
+    const double o1 = fmin(fmax(S1, mu1 - w1), mu1 + w1);
+    const double o2 = fmin(fmax(S2, mu2 - w2), mu2 + w2);
+    const double shift = (o0 + o1 + o2) / 3.0 - (S0 + S1 + S2) / 3.0;
+    const double m1 = P.outM[4 * p], om1 = m1 + shift, om2 = P.outM[4 * p + 1] + (om1 * om1 - m1 * m1);
+    const double on = P.outM[4 * p + 2], og = P.outM[4 * p + 3];
+    P.outC[3 * p] = o0, P.outC[3 * p + 1] = o1, P.outC[3 * p + 2] = o2;
+    P.outM[4 * p] = om1, P.outM[4 * p + 1] = om2;
+    P.outS[p] = shift;
     if (P.outV && temporal_variance_applies(P, on, og)) P.outV[p] = fmax(0.0, om2 - om1 * om1) * og / (1.0 - og);
 }
 
@@ -122,10 +214,17 @@ bool overlap(const Range& a, const Range& b) {
     return a.p && b.p && (uintptr_t)a.p < (uintptr_t)(b.p + b.n) && (uintptr_t)b.p < (uintptr_t)(a.p + a.n);
 }
 
+// the clamped call's extra arguments (clamp == nullptr: the plain call, the other three are NULL)
+struct ClampArgs {
+    const mcpt_temporal_clamp_opts* clamp;
+    const double* pfast;
+    double *outf, *outs;
+};
+
 // every check a call makes before it touches a device; *has_prev: the previous state is given
 int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* color, const mcpt_aov_buffers* g,
                const mcpt_aov_buffers* pg, const double* pcol, const double* pmom, const double* out, const double* outm,
-               const double* outv, bool* has_prev) {
+               const double* outv, bool* has_prev, bool clamped = false, const ClampArgs& ca = ClampArgs{}) {
     if (!o) {
         set_error("null mcpt_temporal_opts");
         return MCPT_E_INVALID;
@@ -165,12 +264,41 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
             set_error("invalid temporal options: %s %g must be finite and > 0", s.name, s.v);
             return MCPT_E_INVALID;
         }
+    if (clamped) {
+        const mcpt_temporal_clamp_opts* c = ca.clamp;
+        if (!c) {
+            set_error("null mcpt_temporal_clamp_opts (clamp)");
+            return MCPT_E_INVALID;
+        }
+        if (c->struct_size != sizeof(mcpt_temporal_clamp_opts)) {
+            set_error("mcpt_temporal_clamp_opts.struct_size is %u, this library expects %zu (use "
+                      "mcpt_temporal_clamp_opts_init / the mcpt.h of MCPT_VERSION %d)", c->struct_size,
+                      sizeof(mcpt_temporal_clamp_opts), MCPT_VERSION);
+            return MCPT_E_INVALID;
+        }
+        if (c->radius < 1 || c->radius > 3) {
+            set_error("invalid clamp options: radius %d is outside 1..3", c->radius);
+            return MCPT_E_INVALID;
+        }
+        if (!(c->alpha_fast > 0 && c->alpha_fast <= 1)) {
+            set_error("invalid clamp options: alpha_fast %g is outside (0, 1]", c->alpha_fast);
+            return MCPT_E_INVALID;
+        }
+        if (!std::isfinite(c->sigma) || !(c->sigma >= 0)) {
+            set_error("invalid clamp options: sigma %g must be finite and >= 0", c->sigma);
+            return MCPT_E_INVALID;
+        }
+    }
     if (W < 1 || H < 1 || (long long)W * H > (1ll << 28)) {
         set_error("invalid frame size: width %d, height %d", W, H);
         return MCPT_E_INVALID;
     }
     if (!color || !out || !outm) {
         set_error("null argument: %s", !color ? "color" : !out ? "out_color" : "out_moments");
+        return MCPT_E_INVALID;
+    }
+    if (clamped && !ca.outf) {
+        set_error("null argument: out_fast");
         return MCPT_E_INVALID;
     }
     if (!g || !g->albedo || !g->normal || !g->position || !g->depth) {
@@ -184,6 +312,12 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
         set_error("partial previous state: %s is NULL while %s is given (pass prev_cam, prev_guides, prev_color and "
                   "prev_moments, or none of them)", !pc ? "prev_cam" : !pg ? "prev_guides" : !pcol ? "prev_color" : "prev_moments",
                   pc ? "prev_cam" : pg ? "prev_guides" : pcol ? "prev_color" : "prev_moments");
+        return MCPT_E_INVALID;
+    }
+    if (clamped && *has_prev != (ca.pfast != nullptr)) {
+        set_error("partial previous state: prev_fast is %s (the fast history belongs to the previous state: pass it with "
+                  "prev_cam, prev_guides, prev_color and prev_moments, or none of them)",
+                  ca.pfast ? "given while the rest of the previous state is NULL" : "NULL while the rest of the previous state is given");
         return MCPT_E_INVALID;
     }
     if (*has_prev) {
@@ -209,8 +343,10 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
                          {"prev_guides.position", *has_prev ? pg->position : nullptr, 3 * npx},
                          {"prev_guides.depth", *has_prev ? pg->depth : nullptr, npx},
                          {"prev_color", pcol, 3 * npx},
-                         {"prev_moments", pmom, 4 * npx}},
-                outs[] = {{"out_color", out, 3 * npx}, {"out_moments", outm, 4 * npx}, {"out_variance", outv, npx}};
+                         {"prev_moments", pmom, 4 * npx},
+                         {"prev_fast", ca.pfast, 3 * npx}},
+                outs[] = {{"out_color", out, 3 * npx}, {"out_moments", outm, 4 * npx}, {"out_variance", outv, npx},
+                          {"out_fast", ca.outf, 3 * npx}, {"out_shift", ca.outs, npx}};  // NULL: overlaps nothing
     for (const auto& w : outs)
         for (const auto& r : ins)
             if (overlap(w, r)) {
@@ -218,8 +354,8 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
                           w.name, r.name);
                 return MCPT_E_INVALID;
             }
-    for (int a = 0; a < 3; a++)
-        for (int b = a + 1; b < 3; b++)
+    for (int a = 0; a < 5; a++)
+        for (int b = a + 1; b < 5; b++)
             if (overlap(outs[a], outs[b])) {
                 set_error("%s is aliasing %s", outs[a].name, outs[b].name);
                 return MCPT_E_INVALID;
@@ -227,10 +363,10 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
     return MCPT_OK;
 }
 
-// both kernels over device arrays
+// the kernels over device arrays; ca (the clamped call): its device arrays, outs never NULL
 int run_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* dC, const mcpt_aov_buffers* g,
                    const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut, double* dOutM,
-                   double* dOutV, Scratch& S, double* seconds) {
+                   double* dOutV, Scratch& S, double* seconds, const ClampArgs* ca = nullptr) {
     TpParams P{};
     P.W = W, P.H = H;
     P.has_prev = pc != nullptr;
@@ -246,12 +382,22 @@ int run_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, in
     P.min_weight = o->min_weight, P.var_n = o->variance_min_history - 0.5;
     P.C = dC, P.N = g->normal, P.X = g->position, P.depth = g->depth;
     P.outC = dOut, P.outM = dOutM, P.outV = dOutV;
+    if (ca) {
+        P.radius = ca->clamp->radius, P.alpha_fast = ca->clamp->alpha_fast, P.sigma = ca->clamp->sigma;
+        P.pF = ca->pfast, P.outF = ca->outf, P.outS = ca->outs;
+    }
     const DnParams D{W, H, 0.0, o->sigma_normal, o->sigma_plane, o->sigma_albedo, g->albedo, g->normal, g->position, g->depth};
     const dim3 grid((W + kBx - 1) / kBx, (H + kBy - 1) / kBy), block(kBx, kBy);
     DN_HIP_OK(hipEventCreate(&S.e0));
     DN_HIP_OK(hipEventCreate(&S.e1));
     DN_HIP_OK(hipEventRecord(S.e0, nullptr));
-    hipLaunchKernelGGL(k_temporal_accumulate, grid, block, 0, nullptr, P);
+    if (ca) {
+        hipLaunchKernelGGL(k_temporal_accumulate<true>, grid, block, 0, nullptr, P);
+        DN_HIP_OK(hipGetLastError());
+        if (P.has_prev) hipLaunchKernelGGL(k_temporal_clamp, grid, block, 0, nullptr, P);  // else no pixel has a history
+    } else {
+        hipLaunchKernelGGL(k_temporal_accumulate<false>, grid, block, 0, nullptr, P);
+    }
     DN_HIP_OK(hipGetLastError());
     if (dOutV) {
         hipLaunchKernelGGL(k_temporal_spatial, grid, block, 0, nullptr, P, D);
@@ -285,12 +431,14 @@ void mcpt_temporal_opts_init(mcpt_temporal_opts* o) {
     o->sigma_albedo = 0.1;
 }
 
-int mcpt_temporal_accumulate_device(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* dC,
-                                    const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM,
-                                    double* dOut, double* dOutM, double* dOutV, double* seconds) {
+// both device forms; ca: the clamped call's arguments, nullptr for the plain call
+static int accumulate_device(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* dC,
+                             const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM,
+                             double* dOut, double* dOutM, double* dOutV, double* seconds, const ClampArgs* ca) {
     int rc;
     bool has_prev = false;
-    if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev))) return rc;
+    if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev, ca != nullptr, ca ? *ca : ClampArgs{})))
+        return rc;
     Scratch S;
     int device;
     if ((rc = select_device(o->device, S, &device))) return rc;
@@ -307,23 +455,38 @@ int mcpt_temporal_accumulate_device(const mcpt_temporal_opts* o, const mcpt_came
                      (rc = check_device_array(dpC, device, "dev_prev_color")) ||
                      (rc = check_device_array(dpM, device, "dev_prev_moments"))))
         return rc;
+    ClampArgs dca{};
+    if (ca) {
+        if ((rc = check_device_array(ca->outf, device, "dev_out_fast")) ||
+            (ca->outs && (rc = check_device_array(ca->outs, device, "dev_out_shift"))) ||
+            (has_prev && (rc = check_device_array(ca->pfast, device, "dev_prev_fast"))))
+            return rc;
+        dca = *ca;
+        if (!dca.outs) {  // the kernels pass "has a history" through it
+            DN_HIP_OK(hipMalloc(&S.p, (size_t)W * H * sizeof(double)));
+            dca.outs = S.p;
+        }
+    }
     // the caller's arrays may still be written by work on other streams (e.g. torch's)
     DN_HIP_OK(hipDeviceSynchronize());
-    return run_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, S, seconds);
+    return run_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, S, seconds, ca ? &dca : nullptr);
 }
 
-int mcpt_temporal_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* color,
-                             const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* pcol, const double* pmom,
-                             double* out, double* outm, double* outv, double* seconds) {
+// both host forms
+static int accumulate_host(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* color,
+                           const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* pcol, const double* pmom,
+                           double* out, double* outm, double* outv, double* seconds, const ClampArgs* ca) {
     int rc;
     bool has_prev = false;
-    if ((rc = check_call(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, &has_prev))) return rc;
+    if ((rc = check_call(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, &has_prev, ca != nullptr, ca ? *ca : ClampArgs{})))
+        return rc;
     Scratch S;
     int device;
     if ((rc = select_device(o->device, S, &device))) return rc;
     const size_t npx = (size_t)W * H, B = sizeof(double);
-    // colour 3, guides 3 + 3 + 3 + 1, out colour 3, moments 4, variance 1, then the previous state 3 + 3 + 1 + 3 + 4
-    DN_HIP_OK(hipMalloc(&S.p, (has_prev ? 35 : 21) * npx * B));
+    // colour 3, guides 3 + 3 + 3 + 1, out colour 3, moments 4, variance 1, then the previous state 3 + 3 + 1 + 3 + 4,
+    // then the clamped call's fast history 3, shift 1 and previous fast history 3
+    DN_HIP_OK(hipMalloc(&S.p, ((has_prev ? 35 : 21) + (ca ? 7 : 0)) * npx * B));
     double* dC = S.p;
     const mcpt_aov_buffers dg{dC + 3 * npx, dC + 6 * npx, dC + 9 * npx, dC + 12 * npx};
     double* dOut = dC + 13 * npx;
@@ -345,13 +508,65 @@ int mcpt_temporal_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc,
         DN_HIP_OK(hipMemcpy(dpC, pcol, 3 * npx * B, hipMemcpyHostToDevice));
         DN_HIP_OK(hipMemcpy(dpM, pmom, 4 * npx * B, hipMemcpyHostToDevice));
     }
+    ClampArgs dca{};
+    if (ca) {
+        dca.clamp = ca->clamp;
+        dca.outf = S.p + (has_prev ? 35 : 21) * npx, dca.outs = dca.outf + 3 * npx;
+        if (has_prev) {
+            double* dpF = dca.outs + npx;
+            DN_HIP_OK(hipMemcpy(dpF, ca->pfast, 3 * npx * B, hipMemcpyHostToDevice));
+            dca.pfast = dpF;
+        }
+    }
     if ((rc = run_accumulate(o, has_prev ? pc : nullptr, W, H, dC, &dg, &dpg, dpC, dpM, dOut, dOutM, outv ? dOutV : nullptr, S,
-                             seconds)))
+                             seconds, ca ? &dca : nullptr)))
         return rc;
+    if (ca) {
+        DN_HIP_OK(hipMemcpy(ca->outf, dca.outf, 3 * npx * B, hipMemcpyDeviceToHost));
+        if (ca->outs) DN_HIP_OK(hipMemcpy(ca->outs, dca.outs, npx * B, hipMemcpyDeviceToHost));
+    }
     DN_HIP_OK(hipMemcpy(out, dOut, 3 * npx * B, hipMemcpyDeviceToHost));
     DN_HIP_OK(hipMemcpy(outm, dOutM, 4 * npx * B, hipMemcpyDeviceToHost));
     if (outv) DN_HIP_OK(hipMemcpy(outv, dOutV, npx * B, hipMemcpyDeviceToHost));
     return MCPT_OK;
+}
+
+int mcpt_temporal_accumulate_device(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* dC,
+                                    const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM,
+                                    double* dOut, double* dOutM, double* dOutV, double* seconds) {
+    return accumulate_device(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, seconds, nullptr);
+}
+
+int mcpt_temporal_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* color,
+                             const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* pcol, const double* pmom,
+                             double* out, double* outm, double* outv, double* seconds) {
+    return accumulate_host(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, seconds, nullptr);
+}
+
+void mcpt_temporal_clamp_opts_init(mcpt_temporal_clamp_opts* c) {
+    if (!c) return;
+    std::memset((void*)c, 0, sizeof *c);
+    c->struct_size = sizeof *c;
+    c->radius = 2;
+    c->alpha_fast = 0.5;
+    c->sigma = 2.0;
+}
+
+int mcpt_temporal_accumulate_clamped_device(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, const mcpt_camera* pc,
+                                            int32_t W, int32_t H, const double* dC, const mcpt_aov_buffers* g,
+                                            const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, const double* dpF,
+                                            double* dOut, double* dOutM, double* dOutF, double* dOutV, double* dOutS,
+                                            double* seconds) {
+    const ClampArgs ca{clamp, dpF, dOutF, dOutS};
+    return accumulate_device(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, seconds, &ca);
+}
+
+int mcpt_temporal_accumulate_clamped(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, const mcpt_camera* pc,
+                                     int32_t W, int32_t H, const double* color, const mcpt_aov_buffers* g,
+                                     const mcpt_aov_buffers* pg, const double* pcol, const double* pmom, const double* pfast,
+                                     double* out, double* outm, double* outf, double* outv, double* outs, double* seconds) {
+    const ClampArgs ca{clamp, pfast, outf, outs};
+    return accumulate_host(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, seconds, &ca);
 }
 
 int mcpt_camera_orbit(const mcpt_camera* in, double degrees, mcpt_camera* out) {
