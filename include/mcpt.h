@@ -31,6 +31,9 @@ extern "C" {
                                * temporal accumulation (mcpt_temporal_opts, mcpt_temporal_accumulate and its
                                * _device form, mcpt_camera_orbit); its history clamping
                                * (mcpt_temporal_clamp_opts, mcpt_temporal_accumulate_clamped and its _device form);
+                               * the device-resident frame sequence (mcpt_sequence, mcpt_sequence_opts,
+                               * mcpt_sequence_info, the mcpt_sequence_* functions, mcpt_tone_map_device and
+                               * mcpt_frame_stats_device);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -535,6 +538,93 @@ int mcpt_primary_hits(mcpt_scene* scene, const mcpt_camera* cam, int32_t* facet,
 int mcpt_tone_map(const double* rgb, int32_t width, int32_t height, double max_radiance, double gamma,
                   uint8_t* out_rgb8);
 int mcpt_write_bmp(const char* path, const uint8_t* rgb8, int32_t width, int32_t height);
+/* mcpt_tone_map over DEVICE memory on `device` (-1 = current): dev_rgb height*width*3 doubles, dev_rgb8 as many
+ * bytes.  The same rule value by value: A = pow(max_radiance, -gamma) on the host, r = A * pow(v, gamma) and
+ * x = floor(r * 255 + 0.5) on the device; the level is 0 when !(x >= -2^31 && x < 2^31) (NaN, infinities and huge
+ * values: the reference's x86 out-of-range conversion), else x clamped to 0..255.  The device's pow is not the
+ * host's, so a value whose 255 r + 0.5 lies within 1e-9 * max(1, |255 r + 0.5|) of an integer may come out one
+ * level off mcpt_tone_map's; every other value is the same byte.  Refused with MCPT_E_INVALID before any device
+ * work: a NULL pointer, width or height < 1, a max_radiance or gamma that is not finite or not > 0. */
+int mcpt_tone_map_device(const double* dev_rgb, int32_t width, int32_t height, double max_radiance, double gamma,
+                         uint8_t* dev_rgb8, int32_t device);
+
+/* What a frame sequence prints about its history, reduced on the device: over the moments (height*width*4, (m1, m2,
+ * n, g) of mcpt_temporal_accumulate) *kept = the pixels with n > 1.5 and *history_sum = the sum of n over the pixels
+ * with n > 0; over the optional shift map (height*width, mcpt_temporal_accumulate_clamped's) *moved = the pixels with
+ * shift != 0 (0 when dev_shift is NULL).  Any output may be NULL.  Deterministic: per-block partial sums in a fixed
+ * lane and wave order, then one pass over the partials in index order -- no floating-point atomics, so two runs
+ * give the same bits and the counts are exact.  MCPT_E_INVALID before any device work for a NULL dev_moments or a
+ * width or height < 1. */
+int mcpt_frame_stats_device(const double* dev_moments, const double* dev_shift, int32_t width, int32_t height,
+                            int32_t device, uint64_t* kept, double* history_sum, uint64_t* moved);
+
+/* A frame sequence resident on one device: render, AOVs, temporal accumulation, statistics, filter and tone map of
+ * every frame run on buffers the handle allocated once in mcpt_sequence_create; per frame only the 8-bit image (when
+ * asked for) and a few dozen bytes of statistics cross to the host.  The stages are the existing device forms
+ * (mcpt_render_device, mcpt_render_aovs_device, the rules of mcpt_temporal_accumulate[_clamped] and mcpt_denoise)
+ * and mcpt_tone_map_device, so every buffer holds what those calls would have produced from the same inputs.  The
+ * history is the unfiltered accumulated colour; the filtered colour is not fed back.  One device, no adaptive
+ * sampling.  The scene must outlive the handle; one call at a time per handle. */
+typedef struct mcpt_sequence mcpt_sequence;
+typedef struct {
+    uint32_t struct_size; /* sizeof(mcpt_sequence_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
+    int32_t width, height;
+    int32_t spp;          /* samples per pixel of every frame, >= 1 */
+    int32_t denoise;      /* 0: show the accumulated colour; 1: filter it (mcpt_denoise's rule) */
+    int32_t clamp;        /* 0: mcpt_temporal_accumulate's rule; 1: mcpt_temporal_accumulate_clamped's */
+    double tone_max, tone_gamma; /* defaults 380, 0.25 (main.cpp:583): finite and > 0 */
+    uint32_t info_size;   /* sizeof(mcpt_sequence_info) of the caller's header (mcpt_sequence_opts_init sets it): a
+                           * frame writes at most this many bytes of its info */
+} mcpt_sequence_opts;
+/* zero-fills *opts and sets struct_size, info_size, spp = 1, denoise = 1, clamp = 0 and the tone map's defaults;
+ * width and height are the caller's to set */
+void mcpt_sequence_opts_init(mcpt_sequence_opts* opts);
+/* `base` supplies mode, device, accel, flags, samples_per_launch, queue_factor and progress, as for
+ * mcpt_render_adaptive: its spp, sample_begin and sample_end must be left as mcpt_render_opts_init set them (the
+ * samples come from opts->spp, the seed from each frame) and a device list or a communicator is refused.  temporal
+ * is required; clamp is required when opts->clamp, denoise when opts->denoise (otherwise they are ignored); the
+ * device fields of the stage options are ignored, base->device is the sequence's.  Refused with MCPT_E_INVALID
+ * before any device work: a NULL argument, a struct_size mismatch of any struct, the conditions above, spp < 1,
+ * width or height < 1, a tone_max or tone_gamma that is not finite or not > 0, a mode or accel that does not exist
+ * and everything the stage option structs' own calls refuse.  Allocates every buffer of a frame (MCPT_E_DEVICE when
+ * that fails). */
+int mcpt_sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, const mcpt_sequence_opts* opts,
+                         const mcpt_temporal_opts* temporal, const mcpt_temporal_clamp_opts* clamp,
+                         const mcpt_denoise_opts* denoise, mcpt_sequence** out);
+typedef struct {
+    /* device time (HIP events).  render: mcpt_stats.seconds of the frame's render; aov: the window of
+     * mcpt_render_aovs_device; temporal: the accumulation's kernels and the statistics reduction; denoise: the
+     * filter's kernels (0 without denoise); tonemap: the tone map's kernel */
+    double render_seconds, aov_seconds, temporal_seconds, denoise_seconds, tonemap_seconds;
+    double kept;          /* share of the pixels with a history length n > 1.5 */
+    double mean_history;  /* (sum of n over the pixels with n > 0) / (width * height) */
+    double clamped;       /* share of the pixels the clamp moved (shift != 0); 0 without clamp */
+    uint64_t frame_index; /* frames since create or the last reset, this one not counted: 0 starts every history */
+} mcpt_sequence_info;
+/* One frame: zero the raw buffer, render [0, spp) with `seed` into it, write the AOVs, accumulate onto the previous
+ * frame's state (none on the first frame and after a reset), reduce the statistics, filter (if denoise), tone-map
+ * the shown frame (the filtered colour if denoise, else the accumulated one) and, when out_rgb8 is not NULL, copy
+ * its height*width*3 bytes to the host; then the two sets of history buffers swap.  The stages after the AOVs go to
+ * the null stream and the frame ends with one synchronisation.  info and stats (the render's; base->stats_size
+ * bytes) may be NULL.  MCPT_E_INVALID before any device work: a NULL handle or camera, an invalid camera, a camera
+ * whose width or height is not the handle's.  A failed frame leaves the history as it was (the buffers of the last
+ * frame are then no longer readable until the next frame succeeds). */
+int mcpt_sequence_frame(mcpt_sequence* seq, const mcpt_camera* cam, uint64_t seed, uint8_t* out_rgb8,
+                        mcpt_sequence_info* info, mcpt_stats* stats);
+/* the last frame's buffers: RAW the render (h*w*3), ACCUMULATED (h*w*3), MOMENTS (h*w*4), VARIANCE (h*w), FILTERED
+ * (h*w*3; with denoise), FAST (h*w*3) and SHIFT (h*w) (with clamp), RGB8 (h*w*3 bytes; mcpt_sequence_device_buffer
+ * only) */
+enum { MCPT_SEQ_RAW = 0, MCPT_SEQ_ACCUMULATED = 1, MCPT_SEQ_MOMENTS = 2, MCPT_SEQ_VARIANCE = 3, MCPT_SEQ_FILTERED = 4,
+       MCPT_SEQ_FAST = 5, MCPT_SEQ_SHIFT = 6, MCPT_SEQ_RGB8 = 7 };
+/* copies one of them to the host.  MCPT_E_INVALID: a NULL argument, an unknown selector (RGB8 included), FAST or
+ * SHIFT without clamp, FILTERED without denoise, no frame since create / reset / a failed frame */
+int mcpt_sequence_read(mcpt_sequence* seq, int32_t what, double* host_out);
+/* the device pointer of one of them (on the sequence's device), valid until the next frame, reset or destroy; the
+ * same refusals, RGB8 allowed */
+int mcpt_sequence_device_buffer(mcpt_sequence* seq, int32_t what, const void** dev_ptr);
+/* the next frame starts every history (as the first frame did); the buffers stay allocated */
+int mcpt_sequence_reset(mcpt_sequence* seq);
+void mcpt_sequence_destroy(mcpt_sequence* seq);
 
 /* Multi-process communicator (see mcpt_comm above): ncclGetUniqueId / ncclCommInitRank /
  * ncclCommDestroy.  device -1 = the current device. */

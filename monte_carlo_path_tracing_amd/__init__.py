@@ -19,6 +19,7 @@ __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_adaptiv
            "AovBuffers", "DenoiseOpts", "render_aovs", "render_aovs_device", "denoise", "denoise_device", "variance_from_noise",
            "TemporalOpts", "TemporalAccumulator", "temporal_accumulate", "temporal_accumulate_device", "camera_orbit",
            "TemporalClampOpts", "temporal_accumulate_clamped", "temporal_accumulate_clamped_device",
+           "SequenceOpts", "SequenceInfo", "FrameSequence", "tone_map_device", "frame_stats_device",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -106,6 +107,28 @@ class TemporalClampOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("alpha_fast", C.c_double), ("sigma", C.c_double)]
 
 
+class SequenceOpts(C.Structure):
+    """mcpt_sequence_opts: what a device-resident frame sequence is created with (include/mcpt.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32),
+                ("denoise", C.c_int32), ("clamp", C.c_int32), ("tone_max", C.c_double), ("tone_gamma", C.c_double),
+                ("info_size", C.c_uint32)]
+
+
+class SequenceInfo(C.Structure):
+    """mcpt_sequence_info: the stage device times and the history statistics of one frame (include/mcpt.h)."""
+    _fields_ = [("render_seconds", C.c_double), ("aov_seconds", C.c_double), ("temporal_seconds", C.c_double),
+                ("denoise_seconds", C.c_double), ("tonemap_seconds", C.c_double), ("kept", C.c_double),
+                ("mean_history", C.c_double), ("clamped", C.c_double), ("frame_index", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# mcpt_sequence_read / _device_buffer selectors: name -> (MCPT_SEQ_*, trailing shape)
+SEQ_BUFFERS = {"raw": (0, (3,)), "accumulated": (1, (3,)), "moments": (2, (4,)), "variance": (3, ()), "filtered": (4, (3,)),
+               "fast": (5, (3,)), "shift": (6, ()), "rgb8": (7, (3,))}
+
+
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
 
 
@@ -142,7 +165,10 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_variance_from_noise", "mcpt_temporal_opts_init", "mcpt_temporal_accumulate",
            "mcpt_temporal_accumulate_device", "mcpt_temporal_clamp_opts_init", "mcpt_temporal_accumulate_clamped",
            "mcpt_temporal_accumulate_clamped_device", "mcpt_camera_orbit", "mcpt_closest_hit", "mcpt_light_prep", "mcpt_primary_hits", "mcpt_tone_map",
-           "mcpt_write_bmp", "mcpt_comm_unique_id", "mcpt_comm_init_rank", "mcpt_comm_destroy"]
+           "mcpt_write_bmp", "mcpt_comm_unique_id", "mcpt_comm_init_rank", "mcpt_comm_destroy",
+           "mcpt_tone_map_device", "mcpt_frame_stats_device", "mcpt_sequence_opts_init", "mcpt_sequence_create",
+           "mcpt_sequence_frame", "mcpt_sequence_read", "mcpt_sequence_device_buffer", "mcpt_sequence_reset",
+           "mcpt_sequence_destroy"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active"]  # include/mcpt_debug.h
@@ -215,6 +241,19 @@ def lib():
                                                            I, I, P, C.POINTER(AovBuffers), C.POINTER(AovBuffers), P, P, P, P, P,
                                                            P, P, P, C.POINTER(D)]
             L.mcpt_temporal_accumulate_clamped_device.argtypes = L.mcpt_temporal_accumulate_clamped.argtypes
+        if hasattr(L, "mcpt_sequence_create"):  # and the device-resident frame sequence
+            L.mcpt_tone_map_device.argtypes = [P, I, I, D, D, P, I]
+            L.mcpt_frame_stats_device.argtypes = [P, P, I, I, I, C.POINTER(C.c_uint64), C.POINTER(D), C.POINTER(C.c_uint64)]
+            L.mcpt_sequence_opts_init.argtypes = [C.POINTER(SequenceOpts)]
+            L.mcpt_sequence_opts_init.restype = None
+            L.mcpt_sequence_create.argtypes = [P, C.POINTER(RenderOpts), C.POINTER(SequenceOpts), C.POINTER(TemporalOpts),
+                                               C.POINTER(TemporalClampOpts), C.POINTER(DenoiseOpts), C.POINTER(P)]
+            L.mcpt_sequence_frame.argtypes = [P, C.POINTER(Camera), C.c_uint64, P, C.POINTER(SequenceInfo), C.POINTER(Stats)]
+            L.mcpt_sequence_read.argtypes = [P, I, P]
+            L.mcpt_sequence_device_buffer.argtypes = [P, I, C.POINTER(P)]
+            L.mcpt_sequence_reset.argtypes = [P]
+            L.mcpt_sequence_destroy.argtypes = [P]
+            L.mcpt_sequence_destroy.restype = None
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -723,6 +762,107 @@ class TemporalAccumulator:
         self.moments = mom
         self.kept = float((mom[..., 2] > 1.5).mean())
         return out, var
+
+
+DENOISE_OPTS = ("iterations", "sigma_color", "sigma_normal", "sigma_plane", "sigma_albedo")
+
+
+class FrameSequence:
+    """A frame sequence resident on one device (mcpt_sequence; include/mcpt.h states the contract): every frame is
+    rendered, accumulated onto the reprojected history, filtered (denoise=True) and tone-mapped on buffers allocated
+    once here, and only the 8-bit frame and a few statistics come back.  The same kernels as render / render_aovs /
+    TemporalAccumulator / denoise ran on the same inputs, so read() returns what that host pipeline computes.
+    clamp: None or False (plain accumulation), True or a dict of radius / alpha_fast / sigma (history clamping).
+    denoise: False, True (the filter's defaults) or a dict of iterations / sigma_color / sigma_normal / sigma_plane /
+    sigma_albedo.  temporal_opts: the fields of TemporalOpts, as for temporal_accumulate (device excepted).
+    After a frame: `info` (SequenceInfo: stage device times, kept, mean_history, clamped) and `stats` (the render's)."""
+
+    def __init__(self, scene, width, height, spp, mode="mis", denoise=True, clamp=None, device=None, accel="bvh", flags=0,
+                 tone_max=None, tone_gamma=None, **temporal_opts):
+        self.h = None
+        self._destroy = lib().mcpt_sequence_destroy
+        if clamp is False:
+            clamp = None
+        base = _adaptive_base(mode, DEFAULT_SEED, device, 0, 0, None, accel, flags)
+        o = SequenceOpts()
+        lib().mcpt_sequence_opts_init(C.byref(o))
+        o.width, o.height, o.spp = int(width), int(height), int(spp)
+        o.denoise, o.clamp = int(bool(denoise)), int(clamp is not None)
+        if tone_max is not None:
+            o.tone_max = float(tone_max)
+        if tone_gamma is not None:
+            o.tone_gamma = float(tone_gamma)
+        tp = _temporal_opts(temporal_opts)
+        tc = _clamp_opts(clamp) if clamp is not None else None
+        dn = None
+        if denoise:
+            d = denoise if isinstance(denoise, dict) else {}
+            unknown = set(d) - set(DENOISE_OPTS)
+            if unknown:
+                raise TypeError("unknown denoise option %r (one of %s)" % (sorted(unknown)[0], ", ".join(DENOISE_OPTS)))
+            dn = _denoise_opts(*[d.get(k) for k in DENOISE_OPTS], device)
+        h = C.c_void_p()
+        _check(lib().mcpt_sequence_create(scene.h, C.byref(base), C.byref(o), C.byref(tp), None if tc is None else C.byref(tc),
+                                          None if dn is None else C.byref(dn), C.byref(h)))
+        self.h, self.scene = h, scene  # the scene must outlive the handle
+        self.width, self.height, self.spp, self.denoise, self.clamp = o.width, o.height, o.spp, bool(denoise), clamp
+        self.info, self.stats = None, None
+
+    def frame(self, camera, seed=DEFAULT_SEED, readback=True):
+        """One frame with `camera` (of the sequence's size) and `seed`; returns the tone-mapped H x W x 3 uint8 frame,
+        or None with readback=False (the frame then stays on the device: device_buffer("rgb8"))."""
+        out = np.zeros((self.height, self.width, 3), np.uint8) if readback else None
+        info, st = SequenceInfo(), Stats()
+        _check(lib().mcpt_sequence_frame(self.h, C.byref(camera), int(seed), None if out is None else out.ctypes.data,
+                                         C.byref(info), C.byref(st)))
+        self.info, self.stats = info, st
+        return out
+
+    def read(self, name):
+        """The last frame's buffer `name` as a float64 array: raw, accumulated, filtered, fast (H x W x 3), moments
+        (H x W x 4), variance, shift (H x W)."""
+        what, tail = SEQ_BUFFERS.get(name, (-1, ()))
+        out = np.zeros((self.height, self.width) + tail)
+        _check(lib().mcpt_sequence_read(self.h, what, out.ctypes.data))
+        return out
+
+    def device_buffer(self, name):
+        """The device pointer (int) of the last frame's buffer `name` (read()'s names and rgb8), valid until the next
+        frame, reset or close."""
+        p = C.c_void_p()
+        _check(lib().mcpt_sequence_device_buffer(self.h, SEQ_BUFFERS.get(name, (-1, ()))[0], C.byref(p)))
+        return p.value
+
+    def reset(self):
+        """The next frame starts every history."""
+        _check(lib().mcpt_sequence_reset(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
+def tone_map_device(ptr, width, height, out_ptr, max_radiance=380.0, gamma=0.25, device=None):
+    """mcpt_tone_map_device: tone_map over device memory -- ptr H*W*3 float64, out_ptr H*W*3 uint8 (e.g. torch CUDA
+    tensors' data_ptr()).  A value whose 255 r + 0.5 is within 1e-9 relative of an integer may differ from tone_map by
+    one level (the device's pow is not the host's)."""
+    _check(lib().mcpt_tone_map_device(None if ptr is None else C.c_void_p(int(ptr)), int(width), int(height),
+                                      float(max_radiance), float(gamma), None if out_ptr is None else C.c_void_p(int(out_ptr)),
+                                      -1 if device is None else int(device)))
+
+
+def frame_stats_device(moments_ptr, width, height, shift_ptr=None, device=None):
+    """mcpt_frame_stats_device over device memory: moments_ptr H*W*4 float64, shift_ptr H*W float64 or None.  Returns
+    (pixels with n > 1.5, sum of n over the pixels with n > 0, pixels with shift != 0), reduced in a fixed order."""
+    kept, moved, nsum = C.c_uint64(), C.c_uint64(), C.c_double()
+    _check(lib().mcpt_frame_stats_device(None if moments_ptr is None else C.c_void_p(int(moments_ptr)),
+                                         None if shift_ptr is None else C.c_void_p(int(shift_ptr)), int(width), int(height),
+                                         -1 if device is None else int(device), C.byref(kept), C.byref(nsum), C.byref(moved)))
+    return kept.value, nsum.value, moved.value
 
 
 def debug_adaptive_active(scene, device=-1):

@@ -83,9 +83,8 @@ __global__ __launch_bounds__(kBx* kBy) void k_atrous(DnParams P, const double* C
     Vout[p] = sv / (sw * sw);
 }
 
-// every check a call makes before it touches a device
-int check_call(const mcpt_denoise_opts* o, int W, int H, const double* color, const double* variance,
-               const mcpt_aov_buffers* g, const double* out, const double* out_variance) {
+// the option struct's checks; mcpt::denoise_check_opts is this function
+int check_opts(const mcpt_denoise_opts* o) {
     if (!o) {
         set_error("null mcpt_denoise_opts");
         return MCPT_E_INVALID;
@@ -109,6 +108,14 @@ int check_call(const mcpt_denoise_opts* o, int W, int H, const double* color, co
             set_error("invalid denoise options: %s %g must be finite and > 0", s.name, s.v);
             return MCPT_E_INVALID;
         }
+    return MCPT_OK;
+}
+
+// every check a call makes before it touches a device
+int check_call(const mcpt_denoise_opts* o, int W, int H, const double* color, const double* variance,
+               const mcpt_aov_buffers* g, const double* out, const double* out_variance) {
+    int orc;
+    if ((orc = check_opts(o))) return orc;
     if (W < 1 || H < 1 || (long long)W * H > (1ll << 28)) {
         set_error("invalid frame size: width %d, height %d", W, H);
         return MCPT_E_INVALID;
@@ -144,18 +151,15 @@ int check_call(const mcpt_denoise_opts* o, int W, int H, const double* color, co
     return MCPT_OK;
 }
 
-// the filter over device arrays; tmp holds 8 npx doubles (two colour + variance buffers)
-int run_filter(const mcpt_denoise_opts* o, int W, int H, const double* dC, const double* dV, const mcpt_aov_buffers* g,
-               double* dOut, double* dOutV, double* tmp, Scratch& S, double* seconds) {
+// the filter over device arrays, enqueued on the null stream; tmp holds 8 npx doubles (two colour + variance buffers)
+int enqueue_filter(const mcpt_denoise_opts* o, int W, int H, const double* dC, const double* dV, const mcpt_aov_buffers* g,
+                   double* dOut, double* dOutV, double* tmp) {
     const size_t npx = (size_t)W * H;
     double* bufC[2] = {tmp, tmp + 3 * npx};
     double* bufV[2] = {tmp + 6 * npx, tmp + 7 * npx};
     const DnParams P{W, H, o->sigma_color, o->sigma_normal, o->sigma_plane, o->sigma_albedo, g->albedo, g->normal, g->position, g->depth};
     const dim3 grid((W + kBx - 1) / kBx, (H + kBy - 1) / kBy), block(kBx, kBy);
     const int K = o->iterations;
-    DN_HIP_OK(hipEventCreate(&S.e0));
-    DN_HIP_OK(hipEventCreate(&S.e1));
-    DN_HIP_OK(hipEventRecord(S.e0, nullptr));
     const double *srcC = dC, *srcV = dV;
     if (!srcV) {  // iteration 0 writes buffer 0, so the estimate goes to buffer 1
         hipLaunchKernelGGL(k_spatial_variance, grid, block, 0, nullptr, P, dC, bufV[1]);
@@ -170,6 +174,17 @@ int run_filter(const mcpt_denoise_opts* o, int W, int H, const double* dC, const
         DN_HIP_OK(hipGetLastError());
         srcC = dstC, srcV = dstV;
     }
+    return MCPT_OK;
+}
+
+// the same, timed with two events and waited for
+int run_filter(const mcpt_denoise_opts* o, int W, int H, const double* dC, const double* dV, const mcpt_aov_buffers* g,
+               double* dOut, double* dOutV, double* tmp, Scratch& S, double* seconds) {
+    int rc;
+    DN_HIP_OK(hipEventCreate(&S.e0));
+    DN_HIP_OK(hipEventCreate(&S.e1));
+    DN_HIP_OK(hipEventRecord(S.e0, nullptr));
+    if ((rc = enqueue_filter(o, W, H, dC, dV, g, dOut, dOutV, tmp))) return rc;
     DN_HIP_OK(hipEventRecord(S.e1, nullptr));
     DN_HIP_OK(hipEventSynchronize(S.e1));
     float ms = 0;
@@ -179,6 +194,24 @@ int run_filter(const mcpt_denoise_opts* o, int W, int H, const double* dC, const
 }
 
 }  // namespace
+
+// mcpt_internal.h: the filter for a caller that owns every buffer (sequence.hip)
+namespace mcpt {
+
+int denoise_check_opts(const mcpt_denoise_opts* o) { return check_opts(o); }
+
+int denoise_enqueue(const mcpt_denoise_opts* o, int32_t W, int32_t H, const double* dC, const double* dV,
+                    const mcpt_aov_buffers* g, double* dOut, double* dOutV, double* tmp) {
+    int rc;
+    if ((rc = check_call(o, W, H, dC, dV, g, dOut, dOutV))) return rc;
+    if (!tmp) {
+        set_error("null argument: the filter's scratch");
+        return MCPT_E_INVALID;
+    }
+    return enqueue_filter(o, W, H, dC, dV, g, dOut, dOutV, tmp);
+}
+
+}  // namespace mcpt
 
 extern "C" {
 

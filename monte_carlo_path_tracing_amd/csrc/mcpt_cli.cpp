@@ -28,6 +28,11 @@
 //   deviations of a fast history (weight of the current frame >= A, default 0.5) over the (2 R + 1)^2 window (default
 //   R = 2), which removes the ghosts of view-dependent shading at larger steps and costs a little on a static camera;
 //   the frame's line then ends with the share of pixels the clamp moved.
+//               [--device-sequence]
+//   --device-sequence (with --frames) runs the same sequence through mcpt_sequence: every stage, the tone map
+//   included, works on device buffers allocated once, and per frame only the 8-bit image (and the HDR frame, when
+//   --hdr asks for it) comes back.  The files and the lines printed are those of the default path.  One device; not
+//   with --aov-out (the handle does not hand out the guides).
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -226,6 +231,70 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
     return 0;
 }
 
+// --frames --device-sequence: the same sequence through mcpt_sequence; the lines and files of render_sequence
+int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceArgs& a, const mcpt_temporal_opts& tp,
+                           const mcpt_temporal_clamp_opts* clamp, const mcpt_denoise_opts& dn) {
+    const int W = cam0.width, H = cam0.height;
+    const size_t npx = (size_t)W * H;
+    mcpt_render_opts base;
+    mcpt_render_opts_init(&base);
+    base.mode = a.mode;
+    base.accel = a.grid ? MCPT_ACCEL_GRID : MCPT_ACCEL_BVH;
+    base.flags = a.flags;
+    int last = -10;
+    if (a.progress) {
+        base.progress = print_progress;
+        base.progress_user = &last;
+    }
+    mcpt_sequence_opts so;
+    mcpt_sequence_opts_init(&so);
+    so.width = W, so.height = H, so.spp = a.spp;
+    so.denoise = a.denoise, so.clamp = clamp != nullptr;
+    mcpt_sequence* seq = nullptr;
+    if (mcpt_sequence_create(scene, &base, &so, &tp, clamp, a.denoise ? &dn : nullptr, &seq) != MCPT_OK) {
+        std::fprintf(stderr, "sequence setup failed: %s\n", mcpt_last_error());
+        return 1;
+    }
+    std::vector<uint8_t> rgb8(3 * npx);
+    std::vector<double> shown;
+    int rc = 0;
+    for (int k = 0; k < a.frames && !rc; k++) {
+        mcpt_camera cam;
+        mcpt_sequence_info fi{};
+        last = -10;
+        if (mcpt_camera_orbit(&cam0, k * a.orbit, &cam) != MCPT_OK ||
+            mcpt_sequence_frame(seq, &cam, a.seed + k, rgb8.data(), &fi, nullptr) != MCPT_OK) {
+            std::fprintf(stderr, "frame %d failed: %s\n", k, mcpt_last_error());
+            rc = 1;
+            break;
+        }
+        std::printf("frame %d: orbit %g deg, seed %llu, %.3f s render, %.3f ms accumulate, %.1f%% of the pixels kept their "
+                    "history (mean length %.2f)", k, k * a.orbit, (unsigned long long)(a.seed + k), fi.render_seconds,
+                    fi.temporal_seconds * 1e3, 100.0 * fi.kept, fi.mean_history);
+        if (clamp) std::printf(", the clamp moved %.1f%% of the pixels", 100.0 * fi.clamped);
+        std::printf("\n");
+        if (a.denoise)
+            std::printf("  denoised: %d iterations, sigma_color %g, variance from the temporal moments, %.3f ms device\n",
+                        dn.iterations, dn.sigma_color, fi.denoise_seconds * 1e3);
+        if (mcpt_write_bmp(frame_path(a.out, k).c_str(), rgb8.data(), W, H) != MCPT_OK) {
+            std::fprintf(stderr, "%s\n", mcpt_last_error());
+            rc = 1;
+        }
+        if (!rc && !a.hdr_out.empty()) {
+            shown.resize(3 * npx);
+            if (mcpt_sequence_read(seq, a.denoise ? MCPT_SEQ_FILTERED : MCPT_SEQ_ACCUMULATED, shown.data()) != MCPT_OK) {
+                std::fprintf(stderr, "%s\n", mcpt_last_error());
+                rc = 1;
+            } else if (!write_pfm(frame_path(a.hdr_out, k).c_str(), shown, W, H)) {
+                std::fprintf(stderr, "cannot write %s\n", frame_path(a.hdr_out, k).c_str());
+                rc = 1;
+            }
+        }
+    }
+    mcpt_sequence_destroy(seq);
+    return rc;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -249,6 +318,7 @@ int main(int argc, char** argv) {
     mcpt_temporal_opts tp;
     mcpt_temporal_opts_init(&tp);
     bool history_clamp = false, clamp_flag = false;  // --history-clamp seen; --clamp-radius or --clamp-alpha-fast seen
+    bool device_sequence = false;
     mcpt_temporal_clamp_opts tc;
     mcpt_temporal_clamp_opts_init(&tc);
     for (int a = 1; a < argc; a++) {
@@ -313,6 +383,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--history-clamp")) tc.sigma = std::atof(next()), history_clamp = sequence_flag = true;
         else if (!std::strcmp(argv[a], "--clamp-radius")) tc.radius = std::atoi(next()), clamp_flag = sequence_flag = true;
         else if (!std::strcmp(argv[a], "--clamp-alpha-fast")) tc.alpha_fast = std::atof(next()), clamp_flag = sequence_flag = true;
+        else if (!std::strcmp(argv[a], "--device-sequence")) device_sequence = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -326,6 +397,24 @@ int main(int argc, char** argv) {
         }
         else {
             std::fprintf(stderr, "unknown option %s\n", argv[a]);
+            return 2;
+        }
+    }
+    if (device_sequence) {  // refused before anything is loaded
+        if (frames == 0) {
+            std::fprintf(stderr, "--device-sequence needs --frames\n");
+            return 2;
+        }
+        if (adaptive) {
+            std::fprintf(stderr, "--device-sequence runs plain renders; drop --adaptive\n");
+            return 2;
+        }
+        if (!aov_out.empty()) {
+            std::fprintf(stderr, "--device-sequence keeps the guides on the device; drop --aov-out\n");
+            return 2;
+        }
+        if (!devices.empty()) {
+            std::fprintf(stderr, "--device-sequence runs on one device; drop --devices\n");
             return 2;
         }
     }
@@ -374,7 +463,8 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
             return 2;
         }
-        const int rc = render_sequence(scene, cam, sa, devices, tp, history_clamp ? &tc : nullptr, dn);
+        const int rc = device_sequence ? render_sequence_device(scene, cam, sa, tp, history_clamp ? &tc : nullptr, dn)
+                                       : render_sequence(scene, cam, sa, devices, tp, history_clamp ? &tc : nullptr, dn);
         mcpt_scene_destroy(scene);
         return rc;
     }

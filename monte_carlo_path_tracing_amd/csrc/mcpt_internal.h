@@ -128,4 +128,25 @@ Grid build_grid(const HostScene& s, const double eye[3], int n0);
 
 void set_error(const char* fmt, ...);
 
+// temporal.hip / denoise.hip -- the accumulation and the filter for a caller that owns every buffer, scratch
+// included (the frame sequence, sequence.hip).  Not exported.  Both make every check of their public device forms
+// that needs no device, then only enqueue their kernels on the null stream of the CURRENT device: no allocation,
+// no pointer query, no event and no synchronisation.  The public functions run the same kernels on the same
+// arguments, so the results are theirs bit for bit.
+struct TemporalClampIo {  // the clamped rule's extra arguments
+    const mcpt_temporal_clamp_opts* clamp;
+    const double* prev_fast;  // part of the previous state
+    double* out_fast;
+    double* out_shift;  // required here: the kernels pass "has a history" through it (the public form's scratch)
+};
+int temporal_check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, bool clamped);
+// io == nullptr: mcpt_temporal_accumulate's rule, else mcpt_temporal_accumulate_clamped's
+int temporal_enqueue(const mcpt_temporal_opts* o, const mcpt_camera* prev_cam, int32_t W, int32_t H, const double* dC,
+                     const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut,
+                     double* dOutM, double* dOutV, const TemporalClampIo* io);
+int denoise_check_opts(const mcpt_denoise_opts* o);
+// tmp: 8 * W * H doubles of scratch (two colour + variance buffers)
+int denoise_enqueue(const mcpt_denoise_opts* o, int32_t W, int32_t H, const double* dC, const double* dV,
+                    const mcpt_aov_buffers* g, double* dOut, double* dOutV, double* tmp);
+
 }  // namespace mcpt

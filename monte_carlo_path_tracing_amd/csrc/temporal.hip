@@ -221,10 +221,8 @@ struct ClampArgs {
     double *outf, *outs;
 };
 
-// every check a call makes before it touches a device; *has_prev: the previous state is given
-int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* color, const mcpt_aov_buffers* g,
-               const mcpt_aov_buffers* pg, const double* pcol, const double* pmom, const double* out, const double* outm,
-               const double* outv, bool* has_prev, bool clamped = false, const ClampArgs& ca = ClampArgs{}) {
+// the option structs' checks (c is looked at only when clamped); mcpt::temporal_check_opts is this function
+int check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* c, bool clamped) {
     if (!o) {
         set_error("null mcpt_temporal_opts");
         return MCPT_E_INVALID;
@@ -265,7 +263,6 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
             return MCPT_E_INVALID;
         }
     if (clamped) {
-        const mcpt_temporal_clamp_opts* c = ca.clamp;
         if (!c) {
             set_error("null mcpt_temporal_clamp_opts (clamp)");
             return MCPT_E_INVALID;
@@ -289,6 +286,15 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
             return MCPT_E_INVALID;
         }
     }
+    return MCPT_OK;
+}
+
+// every check a call makes before it touches a device; *has_prev: the previous state is given
+int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* color, const mcpt_aov_buffers* g,
+               const mcpt_aov_buffers* pg, const double* pcol, const double* pmom, const double* out, const double* outm,
+               const double* outv, bool* has_prev, bool clamped = false, const ClampArgs& ca = ClampArgs{}) {
+    int orc;
+    if ((orc = check_opts(o, ca.clamp, clamped))) return orc;
     if (W < 1 || H < 1 || (long long)W * H > (1ll << 28)) {
         set_error("invalid frame size: width %d, height %d", W, H);
         return MCPT_E_INVALID;
@@ -363,10 +369,10 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
     return MCPT_OK;
 }
 
-// the kernels over device arrays; ca (the clamped call): its device arrays, outs never NULL
-int run_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* dC, const mcpt_aov_buffers* g,
-                   const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut, double* dOutM,
-                   double* dOutV, Scratch& S, double* seconds, const ClampArgs* ca = nullptr) {
+// the kernels over device arrays, enqueued on the null stream; ca (the clamped call): its device arrays, outs never NULL
+int enqueue_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* dC, const mcpt_aov_buffers* g,
+                       const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut, double* dOutM,
+                       double* dOutV, const ClampArgs* ca) {
     TpParams P{};
     P.W = W, P.H = H;
     P.has_prev = pc != nullptr;
@@ -388,9 +394,6 @@ int run_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, in
     }
     const DnParams D{W, H, 0.0, o->sigma_normal, o->sigma_plane, o->sigma_albedo, g->albedo, g->normal, g->position, g->depth};
     const dim3 grid((W + kBx - 1) / kBx, (H + kBy - 1) / kBy), block(kBx, kBy);
-    DN_HIP_OK(hipEventCreate(&S.e0));
-    DN_HIP_OK(hipEventCreate(&S.e1));
-    DN_HIP_OK(hipEventRecord(S.e0, nullptr));
     if (ca) {
         hipLaunchKernelGGL(k_temporal_accumulate<true>, grid, block, 0, nullptr, P);
         DN_HIP_OK(hipGetLastError());
@@ -403,6 +406,18 @@ int run_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, in
         hipLaunchKernelGGL(k_temporal_spatial, grid, block, 0, nullptr, P, D);
         DN_HIP_OK(hipGetLastError());
     }
+    return MCPT_OK;
+}
+
+// the same, timed with two events and waited for
+int run_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* dC, const mcpt_aov_buffers* g,
+                   const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut, double* dOutM,
+                   double* dOutV, Scratch& S, double* seconds, const ClampArgs* ca = nullptr) {
+    int rc;
+    DN_HIP_OK(hipEventCreate(&S.e0));
+    DN_HIP_OK(hipEventCreate(&S.e1));
+    DN_HIP_OK(hipEventRecord(S.e0, nullptr));
+    if ((rc = enqueue_accumulate(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, ca))) return rc;
     DN_HIP_OK(hipEventRecord(S.e1, nullptr));
     DN_HIP_OK(hipEventSynchronize(S.e1));
     float ms = 0;
@@ -412,6 +427,29 @@ int run_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, in
 }
 
 }  // namespace
+
+// mcpt_internal.h: the accumulation for a caller that owns every buffer (sequence.hip)
+namespace mcpt {
+
+int temporal_check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, bool clamped) {
+    return check_opts(o, clamp, clamped);
+}
+
+int temporal_enqueue(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* dC,
+                     const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut,
+                     double* dOutM, double* dOutV, const TemporalClampIo* io) {
+    int rc;
+    bool has_prev = false;
+    const ClampArgs ca = io ? ClampArgs{io->clamp, io->prev_fast, io->out_fast, io->out_shift} : ClampArgs{};
+    if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev, io != nullptr, ca))) return rc;
+    if (io && !io->out_shift) {  // the kernels pass "has a history" through it: the caller's scratch
+        set_error("null argument: out_shift (required by the caller-owned form)");
+        return MCPT_E_INVALID;
+    }
+    return enqueue_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, io ? &ca : nullptr);
+}
+
+}  // namespace mcpt
 
 extern "C" {
 
