@@ -33,7 +33,9 @@ extern "C" {
                                * (mcpt_temporal_clamp_opts, mcpt_temporal_accumulate_clamped and its _device form);
                                * the device-resident frame sequence (mcpt_sequence, mcpt_sequence_opts,
                                * mcpt_sequence_info, the mcpt_sequence_* functions, mcpt_tone_map_device and
-                               * mcpt_frame_stats_device);
+                               * mcpt_frame_stats_device); radiance along caller-supplied rays and pixel jitter
+                               * (mcpt_render_rays and its _device form, mcpt_camera_rays, the flag
+                               * MCPT_RENDER_PIXEL_JITTER);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -174,6 +176,20 @@ enum { MCPT_RENDER_FRESH_PDF = 2 };
  * light triangles (the split prep); cheap culls, pick, sampling, pdf and shading stay fp64. */
 enum { MCPT_RENDER_PRECISION_FP32 = 4 };
 
+/* mcpt_render_opts.flags: anti-aliasing (opt-in; no counterpart in the reference, whose samples all go through the
+ * pixel's centre, main.cpp:563-564).  Sample k of pixel p = i * width + j shoots its camera ray through
+ * (i + dy, j + dx) instead of (i, j): dy = u(key, 0) - 0.5 and dx = u(key, 1) - 0.5 with key the counter RNG's key of
+ * (seed, pixel p, sample k, node 0) -- a stream no shading node uses (node ids start at 1) -- so every sample lies in
+ * its pixel's square and the frame is the scene under a box pixel filter.  The direction is the camera's formula
+ * (main.cpp:563-564) at the fractional coordinates; mcpt_camera_rays returns these rays.  Everything after the primary
+ * hit is unchanged, a sample's ray depends on (seed, p, k) only, so sample ranges, device lists and communicators
+ * split a jittered frame as they split a plain one.  The primary hit is traced per sample and no root shares a light
+ * prep: mcpt_stats.prep_cached_nodes and prep_cache_points are 0 and the render is slower (README.md gives the
+ * measured cost).  Accepted by mcpt_render, mcpt_render_device and (through base->flags) mcpt_sequence_create;
+ * MCPT_E_INVALID before any device work together with MCPT_ACCEL_GRID and in mcpt_render_adaptive[_device] and
+ * mcpt_render_rays[_device].  mcpt_render_aovs ignores it like every other flag: the AOVs stay at the pixel centres. */
+enum { MCPT_RENDER_PIXEL_JITTER = 8 };
+
 /* zero-fills *opts and sets struct_size, stats_size, device = -1, seed = 20240430, spp = 10 (main.cpp:567),
  * mode = MCPT_MODE_MIS */
 void mcpt_render_opts_init(mcpt_render_opts* opts);
@@ -261,6 +277,31 @@ int mcpt_render(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opt
 int mcpt_render_device(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* opts,
                        double* dev_out_rgb, mcpt_stats* stats);
 
+/* Radiance along caller-supplied rays (no counterpart in the reference, whose only rays are its camera's): ray r
+ * starts at origin[3r..] and runs along dir[3r..] (n*3 doubles each), both used as given -- dir is NOT normalised and
+ * the first node's outgoing direction is -dir, so pass unit directions for the reference's shading.  The call ADDS
+ * sum_k L_k / spp over the samples k in [sample_begin, sample_end) of ray r into out_rgb[3r..] (n*3 doubles), as
+ * mcpt_render does per pixel; sample k of ray r draws the counter-RNG numbers of (seed, pixel = r, sample = k), so
+ * the rays of an n-pixel frame give that frame's image.  A ray with a non-finite component or a zero direction is a
+ * miss (adds nothing).  opts supplies spp, the sample range, mode, seed, device, flags, samples_per_launch,
+ * queue_factor and progress.  The closest hit is traced per sample over the BVH and every root takes the full light
+ * prep (prep_cached_nodes = prep_cache_points = 0); stats->camera_samples = n * (sample_end - sample_begin).
+ * MCPT_E_INVALID before any device work: n < 1, a NULL array, a device list or a communicator, MCPT_ACCEL_GRID,
+ * MCPT_RENDER_PIXEL_JITTER and everything mcpt_render refuses in opts. */
+int mcpt_render_rays(mcpt_scene* scene, const mcpt_render_opts* opts, int32_t n, const double* origin, const double* dir,
+                     double* out_rgb, mcpt_stats* stats);
+/* same with the three arrays in DEVICE memory (coarse-grained, on opts->device; see mcpt_render_device) */
+int mcpt_render_rays_device(mcpt_scene* scene, const mcpt_render_opts* opts, int32_t n, const double* dev_origin,
+                            const double* dev_dir, double* dev_out_rgb, mcpt_stats* stats);
+/* The camera's height*width rays for sample index `sample`, row 0 = top image row, to host arrays (height*width*3
+ * doubles each): origin = the pulled-back eye, dir = the unit direction through the pixel's centre (jitter = 0;
+ * `seed` and `sample` are then unused) or through MCPT_RENDER_PIXEL_JITTER's offset for (seed, pixel, sample)
+ * (jitter = 1).  Computed on `device` (-1 = current) by the function the render's root kernel calls, so these are
+ * the render's rays bit for bit: mcpt_render_rays over them reproduces mcpt_render.  MCPT_E_INVALID before any device
+ * work: a NULL pointer, an invalid camera, sample < 0, jitter outside 0 and 1. */
+int mcpt_camera_rays(const mcpt_camera* cam, uint64_t seed, int32_t sample, int32_t jitter, int32_t device,
+                     double* origin, double* dir);
+
 /* Adaptive sampling (no counterpart in the reference, which gives every pixel the same spp, main.cpp:567):
  * the frame is rendered in passes, each active pixel's noise is estimated after every pass, and pixels at or
  * below the threshold stop being sampled.  Sample k of a pixel draws the counter-RNG numbers of a plain
@@ -276,7 +317,7 @@ int mcpt_render_device(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_ren
  *   active   U = active and e > threshold; next active = active and dilate(U, radius), the dilation over
  *            the (2 radius + 1)^2 square clipped at the frame's border.  A pixel that leaves never returns.
  *            The passes end when no pixel is active or the count reaches max_spp.
- * Single device only: a device list or a communicator is refused. */
+ * Single device only: a device list or a communicator is refused, and so is MCPT_RENDER_PIXEL_JITTER. */
 typedef struct {
     uint32_t struct_size; /* sizeof(mcpt_adaptive_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
     int32_t min_spp;      /* samples of pass 0: even, >= 2 */

@@ -15,7 +15,8 @@ import os
 
 import numpy as np
 
-__all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_adaptive", "render_adaptive_device", "closest_hit", "light_prep", "primary_hits",
+__all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_rays", "render_rays_device", "camera_rays", "RENDER_PIXEL_JITTER",
+           "render_adaptive", "render_adaptive_device", "closest_hit", "light_prep", "primary_hits",
            "AovBuffers", "DenoiseOpts", "render_aovs", "render_aovs_device", "denoise", "denoise_device", "variance_from_noise",
            "TemporalOpts", "TemporalAccumulator", "temporal_accumulate", "temporal_accumulate_device", "camera_orbit",
            "TemporalClampOpts", "temporal_accumulate_clamped", "temporal_accumulate_clamped_device",
@@ -67,6 +68,7 @@ class RenderOpts(C.Structure):
 RENDER_NO_BACKFACE_STATS = 1  # mcpt_render_opts.flags (include/mcpt.h)
 RENDER_FRESH_PDF = 2  # shade_with_mis: the node's own light pdf instead of the reference's stale one
 RENDER_PRECISION_FP32 = 4  # opt-in FP32_STABLE light prep (packed-fp32 weights, fp64 sums); default FP64_LIGHT
+RENDER_PIXEL_JITTER = 8  # opt-in anti-aliasing: every sample's camera ray through its own sub-pixel offset (box filter)
 DEBUG_SPLIT_BRDF, DEBUG_NO_ROOT_CACHE, DEBUG_COUNT_TRAVERSAL = 1 << 16, 1 << 17, 1 << 18  # include/mcpt_debug.h
 DEBUG_SHARD_RANKS = 1 << 19  # device lists: every entry its own communicator rank (tests/collshim)
 DEBUG_RAYS_PERSIST = 1 << 20  # MIS / shade ray sets through the persistent refilling traversal on every scene
@@ -160,6 +162,7 @@ _lib = None
 EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_create", "mcpt_scene_destroy",
            "mcpt_scene_counts", "mcpt_scene_accel_bytes", "mcpt_scene_arrays", "mcpt_scene_camera", "mcpt_scene_meshing", "mcpt_scene_grid_info",
            "mcpt_render_opts_init", "mcpt_render", "mcpt_render_device",
+           "mcpt_render_rays", "mcpt_render_rays_device", "mcpt_camera_rays",
            "mcpt_adaptive_opts_init", "mcpt_render_adaptive", "mcpt_render_adaptive_device",
            "mcpt_render_aovs", "mcpt_render_aovs_device", "mcpt_denoise_opts_init", "mcpt_denoise", "mcpt_denoise_device",
            "mcpt_variance_from_noise", "mcpt_temporal_opts_init", "mcpt_temporal_accumulate",
@@ -254,6 +257,10 @@ def lib():
             L.mcpt_sequence_reset.argtypes = [P]
             L.mcpt_sequence_destroy.argtypes = [P]
             L.mcpt_sequence_destroy.restype = None
+        if hasattr(L, "mcpt_render_rays"):  # and the radiance along caller-supplied rays
+            L.mcpt_render_rays.argtypes = [P, C.POINTER(RenderOpts), I, P, P, P, C.POINTER(Stats)]
+            L.mcpt_render_rays_device.argtypes = L.mcpt_render_rays.argtypes
+            L.mcpt_camera_rays.argtypes = [C.POINTER(Camera), C.c_uint64, I, I, I, P, P]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -452,6 +459,47 @@ def render_device(scene, camera, spp, dev_ptr, mode="mis", seed=DEFAULT_SEED, sa
     return st
 
 
+def render_rays(scene, origin, dir, spp, mode="mis", seed=DEFAULT_SEED, sample_range=None, out=None, device=None,
+                samples_per_launch=0, queue_factor=0, progress=None, flags=0):
+    """Radiance along caller-supplied rays (mcpt_render_rays, include/mcpt.h): origin and dir are n x 3, used as given
+    (dir is not normalised).  Returns (n x 3 fp64 radiance, Stats): sum_k L_k / spp over the samples k in
+    `sample_range` (default all) ADDED into `out` (zeros if None); sample k of ray r draws the random numbers of
+    (seed, pixel r, sample k).  The seam for other camera models: camera_rays gives this renderer's own rays.
+    Single device, BVH only."""
+    origin, dir = _d(origin, (-1, 3)), _d(dir, (-1, 3))
+    n = origin.shape[0]
+    assert dir.shape == (n, 3)
+    if out is None:
+        out = np.zeros((n, 3))
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (n, 3)
+    st = Stats()
+    o = _opts(spp, mode, seed, sample_range, device, samples_per_launch, queue_factor, progress, "bvh", flags)
+    _check(lib().mcpt_render_rays(scene.h, C.byref(o), n, origin.ctypes.data, dir.ctypes.data, out.ctypes.data, C.byref(st)))
+    return out, st
+
+
+def render_rays_device(scene, n, origin_ptr, dir_ptr, spp, dev_ptr, mode="mis", seed=DEFAULT_SEED, sample_range=None,
+                       device=None, samples_per_launch=0, queue_factor=0, progress=None, flags=0):
+    """render_rays over device buffers of n*3 doubles each (e.g. torch.float64 CUDA tensors' data_ptr()): the
+    radiance is accumulated into dev_ptr.  Returns the Stats."""
+    st = Stats()
+    o = _opts(spp, mode, seed, sample_range, device, samples_per_launch, queue_factor, progress, "bvh", flags)
+    opt = lambda p: None if p is None else C.c_void_p(int(p))
+    _check(lib().mcpt_render_rays_device(scene.h, C.byref(o), int(n), opt(origin_ptr), opt(dir_ptr), opt(dev_ptr), C.byref(st)))
+    return st
+
+
+def camera_rays(camera, seed=DEFAULT_SEED, sample=0, jitter=False, device=None):
+    """mcpt_camera_rays: the camera's rays for sample index `sample` as (origin, dir), H*W x 3 each in pixel order:
+    through the pixel centres, or (jitter=True) the rays a render with RENDER_PIXEL_JITTER shoots for (seed, sample) --
+    computed on the device by the function the render itself calls."""
+    n = camera.width * camera.height
+    origin, dir = np.zeros((n, 3)), np.zeros((n, 3))
+    _check(lib().mcpt_camera_rays(C.byref(camera), int(seed), int(sample), int(jitter), -1 if device is None else int(device),
+                                  origin.ctypes.data, dir.ctypes.data))
+    return origin, dir
+
+
 def _adaptive_opts(max_spp, threshold, min_spp, pass_spp, radius):
     a = AdaptiveOpts()
     lib().mcpt_adaptive_opts_init(C.byref(a))
@@ -507,18 +555,19 @@ def render_adaptive_device(scene, camera, max_spp, threshold, dev_ptr, count_ptr
     return st
 
 
-def _aov_opts(device, accel):
-    return _opts(1, "mis", DEFAULT_SEED, None, device, 0, 0, accel=accel)
+def _aov_opts(device, accel, flags=0):
+    return _opts(1, "mis", DEFAULT_SEED, None, device, 0, 0, accel=accel, flags=flags)
 
 
-def render_aovs(scene, camera, device=None, accel="bvh"):
+def render_aovs(scene, camera, device=None, accel="bvh", flags=0):
     """Primary-hit feature buffers (mcpt_render_aovs, include/mcpt.h): dict of albedo (Kd + Ks), normal (shading
     normal, not flipped), position (H x W x 3 each) and depth (H x W, distance from the pulled-back eye; 0 marks a
-    miss, whose other maps are 0 too)."""
+    miss, whose other maps are 0 too).  flags are ignored by the library (RENDER_PIXEL_JITTER too: the AOVs stay at
+    the pixel centres); the keyword only lets a caller hand over a render's options unchanged."""
     H, W = camera.height, camera.width
     a = dict(albedo=np.zeros((H, W, 3)), normal=np.zeros((H, W, 3)), position=np.zeros((H, W, 3)), depth=np.zeros((H, W)))
     b = AovBuffers(*[a[k].ctypes.data for k in ("albedo", "normal", "position", "depth")])
-    o = _aov_opts(device, accel)
+    o = _aov_opts(device, accel, flags)
     _check(lib().mcpt_render_aovs(scene.h, C.byref(camera), C.byref(o), C.byref(b)))
     return a
 

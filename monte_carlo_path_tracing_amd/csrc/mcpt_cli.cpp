@@ -6,7 +6,10 @@
 //
 //   mcpt_render --scene scenes/veach-mis/veach-mis [--width 1280 --height 720] [--spp 10]
 //               [--mode mis|brdf|shade|shade-area] [--seed 20240430] [--out test.bmp] [--hdr out.pfm] [--progress]
-//               [--grid] [--devices 0,1,2,3,4,5,6,7] [--precision fp64|fp32]
+//               [--grid] [--devices 0,1,2,3,4,5,6,7] [--precision fp64|fp32] [--jitter]
+//   --jitter anti-aliases (MCPT_RENDER_PIXEL_JITTER): every sample's camera ray goes through its own point of the
+//   pixel's square instead of the centre (a box pixel filter); slower, the primary hit is traced per sample.  Works
+//   with --frames, --orbit, --denoise, --history-clamp, --device-sequence and --devices; not with --adaptive or --grid.
 //               [--adaptive TAU [--min-spp N] [--pass-spp N] [--radius R] [--count-out count.bmp]]
 //   --adaptive TAU renders adaptively (mcpt_render_adaptive): passes of --pass-spp samples after the first
 //   --min-spp (default 16 each), a pixel stops once its noise estimate is at most TAU and so are its
@@ -351,6 +354,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--xml-camera")) xml_cam = true;
         else if (!std::strcmp(argv[a], "--progress")) progress = true;
         else if (!std::strcmp(argv[a], "--grid")) grid = true;
+        else if (!std::strcmp(argv[a], "--jitter")) flags |= MCPT_RENDER_PIXEL_JITTER;
         else if (!std::strcmp(argv[a], "--precision")) {
             const char* v = next();
             if (!std::strcmp(v, "fp32")) flags |= MCPT_RENDER_PRECISION_FP32;
@@ -397,6 +401,16 @@ int main(int argc, char** argv) {
         }
         else {
             std::fprintf(stderr, "unknown option %s\n", argv[a]);
+            return 2;
+        }
+    }
+    if (flags & MCPT_RENDER_PIXEL_JITTER) {  // refused before anything is loaded
+        if (adaptive) {
+            std::fprintf(stderr, "--jitter needs plain renders; drop --adaptive\n");
+            return 2;
+        }
+        if (grid) {
+            std::fprintf(stderr, "--jitter traces its camera rays over the BVH; drop --grid\n");
             return 2;
         }
     }

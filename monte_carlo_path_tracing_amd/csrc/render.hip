@@ -123,6 +123,12 @@ __device__ inline d3 cam_dir(const CamFrame& f, int i, int j) {  // main.cpp:563
     d3 delta = mk3(-f.pixellen * (i - (f.H - 1) / 2.0), f.pixellen * (j - (f.W - 1) / 2.0), 0);
     return normalized(cols_mul(f.U, f.V, f.N, add(delta, mk3(0, 0, f.wlen))));
 }
+// cam_dir at fractional pixel coordinates (row y, column x), operation for operation: cam_dir_at(f, i, j) is
+// cam_dir(f, i, j) bit for bit (the int -> double conversions are exact)
+__device__ inline d3 cam_dir_at(const CamFrame& f, double y, double x) {
+    d3 delta = mk3(-f.pixellen * (y - (f.H - 1) / 2.0), f.pixellen * (x - (f.W - 1) / 2.0), 0);
+    return normalized(cols_mul(f.U, f.V, f.N, add(delta, mk3(0, 0, f.wlen))));
+}
 
 // ============================================================================================
 // BVH traversal: fp32 slab tests on conservatively enlarged boxes (prune only), fp64 reference
@@ -344,7 +350,7 @@ __device__ inline Hit trace4_ww(const BvhNode4* __restrict__ nodes, const float4
     constexpr int kDone = 0x7fffffff;
     Hit best{-1, DBL_MAX, 0, 0};
     if (isnan(rd.x) || isnan(rd.y) || isnan(rd.z)) return best;  // reference: UB (Myobj.cpp:463-468)
-    int spill[kStack - kLds];
+    int spill[kLds < kStack ? kStack - kLds : 1];  // kLds == kStack (k_roots_rays): never indexed, no scratch
     auto inv = [](double d) {
         float f = (float)d;
         if (fabsf(f) < 1e-30f) f = copysignf(1e-30f, f);
@@ -387,13 +393,13 @@ __device__ inline Hit trace4_ww(const BvhNode4* __restrict__ nodes, const float4
     int sp = 0;
     auto push = [&](int v) {
         if (sp < kLds) lds[sp * stride] = v;
-        else if (sp < kStack) spill[sp - kLds] = v;
+        else if (kLds < kStack && sp < kStack) spill[sp - kLds] = v;
         sp = sp < kStack ? sp + 1 : sp;
     };
     auto pop = [&]() -> int {
         if (sp == 0) return kDone;
         --sp;
-        return sp < kLds ? lds[sp * stride] : spill[sp - kLds];
+        return (kLds >= kStack || sp < kLds) ? lds[sp * stride] : spill[sp - kLds];
     };
     int node = 0;
     int leaf = 0;
@@ -1138,6 +1144,148 @@ __global__ __launch_bounds__(256) void k_roots_t(Params P, const int* __restrict
         q.node[slot] = 1;
         q.par[slot] = -1;
     }
+}
+
+// --------------------------------------------------------------------------------------------
+// Roots from rays (mcpt_render_rays, MCPT_RENDER_PIXEL_JITTER): a path starts from an arbitrary
+// ray per (index, sample) instead of from the per-pixel tables, so k_primary, k_root_table and the root-point
+// caches do not run and every root takes the full light prep (as under MCPT_DEBUG_NO_ROOT_CACHE).
+// --------------------------------------------------------------------------------------------
+// where a call's roots come from when not from the per-pixel tables
+struct RayRoots {
+    const double* origin;  // supplied rays: [n][3] origins and directions in device memory (used as given)
+    const double* dir;
+    int n;                 // supplied rays: their number (the "frame" is n x 1)
+    int jitter;            // 1: the camera's rays through per-sample sub-pixel offsets (origin / dir unused)
+};
+
+// the camera ray of pixel p for sample k: through the pixel's centre, or (jitter) through the centre displaced by
+// (dy, dx) in [-0.5, 0.5)^2, drawn from the counter RNG's node 0 of (seed, p, k) -- node ids start at 1, so this
+// stream is free.  The one definition both k_roots_rays and mcpt_camera_rays use.
+__device__ inline d3 pixel_ray_dir(const CamFrame& f, uint64_t seed, int p, int k, bool jitter) {
+    const int i = p / f.W, j = p % f.W;
+    if (!jitter) return cam_dir_at(f, i, j);
+    const uint64_t key = counter_key(seed, (uint64_t)p, (uint64_t)k, 0);
+    const double dy = counter_u(key, 0) - 0.5, dx = counter_u(key, 1) - 0.5;
+    return cam_dir_at(f, i + dy, j + dx);
+}
+
+// a ray the traversal must not see: a non-finite component or a zero direction (a miss)
+__device__ inline bool ray_ok(d3 ro, d3 rd) {
+    return isfinite(ro.x) && isfinite(ro.y) && isfinite(ro.z) && isfinite(rd.x) && isfinite(rd.y) && isfinite(rd.z) &&
+           (rd.x != 0 || rd.y != 0 || rd.z != 0);
+}
+
+// kRayRootsPT roots per thread, in root_of's order, with k_roots_t's append: a 256-thread block takes 256 x
+// kRayRootsPT roots with ONE atomic on the queue counter (measured against one root per thread and an atomic per
+// 256 roots: BRDF-only jitter 79.1 -> 77.0 ms per 1024-spp frame, MIS unchanged); sub-batch j
+// (roots base + 256 j + thread) is compacted in order and placed after sub-batches < j, so the queue order equals the
+// root order and every store is coalesced.
+// Phase 1, per sub-batch: the ray, the closest hit over the BVH (k_primary<false>'s traversal) and entry_eval for
+// node 1 with throughput 1 -- back face nothing, emitter its emission into the framebuffer, else the RR draw
+// (MIS / BRDF; shade() pushes unconditionally).  The loop is not unrolled (one copy of the traversal); what a
+// pushed root needs after the barrier -- index, sample, facet, (beta, gamma), wo -- is kept in registers by
+// constant-index selects.  Phase 2: node_point again for the pushed roots (the same function on the same inputs: the
+// same bits) and the full queue entry.
+// The whole kStack-entry traversal stack lives in LDS (48 KiB per block), so trace4_ww's private overflow is empty:
+// the kernel uses no scratch.
+#ifndef MCPT_RAY_ROOTS_PT
+#define MCPT_RAY_ROOTS_PT 4
+#endif
+constexpr int kRayRootsPT = MCPT_RAY_ROOTS_PT;
+__global__ __launch_bounds__(256) void k_roots_rays(Params P, CamFrame cam, RayRoots rr, int npx, int s0, long long rbase,
+                                                    int nroots, Queue q, int group, int nsamp) {
+    __shared__ int stack[kStack * 256];
+    __shared__ unsigned s_w[kRayRootsPT][4];
+    __shared__ unsigned s_base;
+    const int lane = lane_id(), wid = threadIdx.x >> 6;
+    const int base = blockIdx.x * 256 * kRayRootsPT;
+    int px[kRayRootsPT], sm[kRayRootsPT], hf[kRayRootsPT];
+    double hb[kRayRootsPT], hg[kRayRootsPT];
+    d3 wo[kRayRootsPT];
+    uint64_t wm[kRayRootsPT];
+#pragma unroll
+    for (int k = 0; k < kRayRootsPT; k++)
+        px[k] = 0, sm[k] = 0, hf[k] = -1, hb[k] = 0, hg[k] = 0, wo[k] = mk3(0, 0, 0), wm[k] = 0;
+#pragma unroll 1
+    for (int j = 0; j < kRayRootsPT; j++) {
+        const int r = base + 256 * j + (int)threadIdx.x;
+        int p = 0, s = 0;
+        d3 w = mk3(0, 0, 0);
+        Hit h{-1, 0, 0, 0};
+        bool want = false;
+        if (r < nroots) {
+            root_of(rbase + r, npx, s0, group, nsamp, &p, &s);
+            d3 ro, rd;
+            if (rr.jitter) {
+                ro = cam.eye;
+                rd = pixel_ray_dir(cam, P.seed, p, s, true);
+            } else {
+                ro = mk3(rr.origin[3 * (size_t)p], rr.origin[3 * (size_t)p + 1], rr.origin[3 * (size_t)p + 2]);
+                rd = mk3(rr.dir[3 * (size_t)p], rr.dir[3 * (size_t)p + 1], rr.dir[3 * (size_t)p + 2]);
+            }
+            if (ray_ok(ro, rd)) {
+                h = trace4_ww<kStack>(P.S.bvh4, P.S.leaf_v, ro, rd, -1, stack + threadIdx.x, 256);
+                w = mul(rd, -1);
+            }
+            const Entry e = entry_eval(P, h.f >= 0, h.f, h.beta, h.gamma, w, p, s, 1);
+            if (e.kind == 1) {  // emitter: its emission (main.cpp:411-412 with throughput 1)
+                double* fb = P.fb + 3 * (size_t)p;
+                unsafeAtomicAdd(fb + 0, P.S.light_rad[3 * e.li + 0] * P.inv_spp);
+                unsafeAtomicAdd(fb + 1, P.S.light_rad[3 * e.li + 1] * P.inv_spp);
+                unsafeAtomicAdd(fb + 2, P.S.light_rad[3 * e.li + 2] * P.inv_spp);
+            }
+            want = e.kind == 2;
+        }
+        const uint64_t m = __ballot(want);
+        if (lane == 0) s_w[j][wid] = (unsigned)__popcll(m);
+#pragma unroll
+        for (int k = 0; k < kRayRootsPT; k++)
+            if (k == j) px[k] = p, sm[k] = s, hf[k] = h.f, hb[k] = h.beta, hg[k] = h.gamma, wo[k] = w, wm[k] = m;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned run = 0;
+        for (int j = 0; j < kRayRootsPT; j++)
+            for (int w = 0; w < 4; w++) {
+                const unsigned c = s_w[j][w];
+                s_w[j][w] = run;
+                run += c;
+            }
+        s_base = run ? atomicAdd(q.count, run) : 0u;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < kRayRootsPT; j++) {
+        if (!((wm[j] >> lane) & 1)) continue;
+        const unsigned rk = __builtin_amdgcn_mbcnt_hi((unsigned)(wm[j] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)wm[j], 0u));
+        const size_t slot = (size_t)s_base + s_w[j][wid] + rk;
+        if (slot >= (size_t)q.cap) {
+            atomicOr((unsigned long long*)(P.stats + 4), 1ull);
+            continue;
+        }
+        d3 pt, N;
+        node_point(P.S, hf[j], hb[j], hg[j], &pt, &N);
+        st3(q.p, q.cap, slot, pt);
+        st3(q.n, q.cap, slot, N);
+        st3(q.wo, q.cap, slot, wo[j]);
+        st3(q.tp, q.cap, slot, mk3(1, 1, 1));
+        q.f[slot] = hf[j];
+        q.pixel[slot] = px[j];
+        q.sample[slot] = sm[j];
+        q.node[slot] = 1;
+        q.par[slot] = -1;
+    }
+}
+
+// mcpt_camera_rays: the rays k_roots_rays shades for sample k of every pixel (jitter) or the pixel-centre rays
+__global__ __launch_bounds__(256) void k_camera_rays(CamFrame cam, uint64_t seed, int k, int jitter, double* origin,
+                                                     double* dir) {
+    const int p = blockIdx.x * 256 + (int)threadIdx.x;
+    if (p >= cam.W * cam.H) return;
+    const d3 rd = pixel_ray_dir(cam, seed, p, k, jitter != 0);
+    origin[3 * (size_t)p] = cam.eye.x, origin[3 * (size_t)p + 1] = cam.eye.y, origin[3 * (size_t)p + 2] = cam.eye.z;
+    dir[3 * (size_t)p] = rd.x, dir[3 * (size_t)p + 1] = rd.y, dir[3 * (size_t)p + 2] = rd.z;
 }
 
 // moves nodes [sb, sb + m) of src to [db, db + m) of dst (every field a generation carries into the
@@ -4360,6 +4508,7 @@ struct DeviceState {
     DevBuf ad_acc[2], ad_list[2], ad_state[2], ad_blk, ad_count, ad_noise;
     int ad_last_list = -1, ad_last_n = 0;  // the last active list built (mcpt_debug_adaptive_active)
     DevBuf aov;  // mcpt_render_aovs: the four maps of a host call (10 doubles per pixel)
+    DevBuf ray_o, ray_d;  // mcpt_render_rays: a host call's origins and directions
     int spill_cap = 0;  // nodes the spill stack qs holds (grown on demand)
     bool bvh8_tried = false;  // ensure_bvh8 ran on this device
     DevBuf g_start, g_tri;  // the scene's uniform grid (MCPT_ACCEL_GRID), version grid_version
@@ -5038,6 +5187,15 @@ int ensure_bvh8(mcpt_scene* sc, DeviceState* D) {
     return MCPT_OK;
 }
 
+// MCPT_RENDER_PIXEL_JITTER traces its roots over the BVH only (needs no device: the entry points call it first)
+int check_jitter(const mcpt_render_opts* o) {
+    if ((o->flags & MCPT_RENDER_PIXEL_JITTER) && o->accel == MCPT_ACCEL_GRID) {
+        set_error("MCPT_RENDER_PIXEL_JITTER is not supported with MCPT_ACCEL_GRID (the jittered roots are traced over the BVH)");
+        return MCPT_E_INVALID;
+    }
+    return MCPT_OK;
+}
+
 int validate_render(const mcpt_render_opts* o) {
     const int s0 = (o->sample_begin == 0 && o->sample_end == 0) ? 0 : o->sample_begin;
     const int s1 = (o->sample_begin == 0 && o->sample_end == 0) ? o->spp : o->sample_end;
@@ -5048,13 +5206,13 @@ int validate_render(const mcpt_render_opts* o) {
         return MCPT_E_INVALID;
     }
     if (o->flags & ~(MCPT_RENDER_NO_BACKFACE_STATS | MCPT_RENDER_FRESH_PDF | MCPT_RENDER_PRECISION_FP32 |
-                     MCPT_DEBUG_SPLIT_BRDF | MCPT_DEBUG_NO_ROOT_CACHE | MCPT_DEBUG_COUNT_TRAVERSAL |
+                     MCPT_RENDER_PIXEL_JITTER | MCPT_DEBUG_SPLIT_BRDF | MCPT_DEBUG_NO_ROOT_CACHE | MCPT_DEBUG_COUNT_TRAVERSAL |
                      MCPT_DEBUG_SHARD_RANKS | MCPT_DEBUG_RAYS_PERSIST | MCPT_DEBUG_RAYS_CW8 | MCPT_DEBUG_FUSED_CULL |
                      MCPT_DEBUG_NO_EXACT_DEFER)) {
         set_error("unknown mcpt_render_opts.flags bits 0x%x", (unsigned)o->flags);
         return MCPT_E_INVALID;
     }
-    return MCPT_OK;
+    return check_jitter(o);
 }
 
 // an adaptive call (mcpt_render_adaptive): the rule's parameters and where the count / noise maps go
@@ -5069,10 +5227,15 @@ struct AdaptiveRun {
 // (allocations, primary hits, root table, root-point cache) runs once; the wavefront loop runs once over
 // [s0, s1) for a plain render, or twice per pass (the halves A and B) for an adaptive one (ad != nullptr:
 // o->spp is the cap, the statistics are summed over the passes).
+// rays != nullptr (mcpt_render_rays): the roots are the supplied rays, the "frame" is rays->n x 1 and cam is unused;
+// MCPT_RENDER_PIXEL_JITTER: the roots are the camera's jittered rays.  Either way k_roots_rays makes the roots and the
+// per-pixel setup (primary hits, root table, root-point caches, RootLit pool) is skipped.
 int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt_render_opts* o,
-                     double* dfb, mcpt_stats* stats, const AdaptiveRun* ad = nullptr) {
-    const CamFrame cf = cam_setup(*cam);
-    const int W = cam->width, H = cam->height, npx = W * H;
+                     double* dfb, mcpt_stats* stats, const AdaptiveRun* ad = nullptr, const RayRoots* rays = nullptr) {
+    const CamFrame cf = rays ? CamFrame{} : cam_setup(*cam);
+    const int W = rays ? rays->n : cam->width, H = rays ? 1 : cam->height, npx = W * H;
+    const RayRoots rr = rays ? *rays : RayRoots{nullptr, nullptr, 0, (o->flags & MCPT_RENDER_PIXEL_JITTER) ? 1 : 0};
+    const bool ray_roots = rays || rr.jitter;
     const int s0 = (o->sample_begin == 0 && o->sample_end == 0) ? 0 : o->sample_begin;
     const int s1 = (o->sample_begin == 0 && o->sample_end == 0) ? o->spp : o->sample_end;
     {
@@ -5082,6 +5245,10 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
     // MCPT_ACCEL_GRID: the reference's uniform grid over the scene and this camera's eye, n0 =
     // 100000 (main.cpp:501-504), built here unless the scene already holds that grid
     const bool grid = o->accel == MCPT_ACCEL_GRID;
+    if (ray_roots && (grid || ad)) {
+        set_error("roots from rays are not supported with %s", grid ? "MCPT_ACCEL_GRID" : "adaptive sampling");
+        return MCPT_E_INVALID;
+    }
     if (grid) {
         const double eye[3] = {cf.eye.x, cf.eye.y, cf.eye.z};
         int rg;
@@ -5123,10 +5290,10 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
     const int target = (int)std::max<long long>(target_ll, 1);
     const int cap = (int)std::min<long long>((long long)qf * target + 1024, (1ll << 30));
     int rc;
-    if ((rc = ensure(D.hit_f, 4ull * npx)) || (rc = ensure(D.hit_tbg, 24ull * npx)) ||
-        (rc = ensure(D.root_pnw, 72ull * npx)) || (rc = ensure(D.root_kind, 4ull * npx)) || (rc = ensure(D.stats, kStatBytes)) ||
-        (rc = ensure(D.work, 256)))
+    if (!ray_roots && ((rc = ensure(D.hit_f, 4ull * npx)) || (rc = ensure(D.hit_tbg, 24ull * npx)) ||
+                       (rc = ensure(D.root_pnw, 72ull * npx)) || (rc = ensure(D.root_kind, 4ull * npx))))
         return rc;
+    if ((rc = ensure(D.stats, kStatBytes)) || (rc = ensure(D.work, 256))) return rc;
     Queue qa, qb;
     if ((rc = alloc_queue(D.qa, cap, qa)) || (rc = alloc_queue(D.qb, cap, qb))) return rc;
     // extension kernels: MIS and shade split into gen / rays / combine (measured faster), BRDF-only
@@ -5203,7 +5370,7 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
     HIP_OK(hipMemGetInfo(&free_b, &total_b));
     const size_t held = D.cache_bt.bytes + D.cache_lst.bytes + D.cache_info.bytes + D.cache_w.bytes;
     const size_t budget = free_b + held > (16ull << 30) ? free_b + held - (16ull << 30) : 0;
-    const bool no_cache = (o->flags & MCPT_DEBUG_NO_ROOT_CACHE) != 0;  // A/B switch
+    const bool no_cache = ray_roots || (o->flags & MCPT_DEBUG_NO_ROOT_CACHE) != 0;  // the flag: A/B switch
     if (needs_prep && s1 - s0 >= 2 && cache_bytes <= budget && !no_cache && D.d.NL > kSmallNL &&
         prep_list_wave_bytes(nchunks) * 4 <= kPrepListMaxLds && D.d.NL <= 65535) {
         if ((rc = ensure(D.cache_bt, (size_t)npx * nchunks * 8)) || (rc = ensure(D.cache_lst, (size_t)npx * lstride * 2)) ||
@@ -5262,14 +5429,16 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
     // timed region (seconds, HIP events) starts at the primary-hit kernel
     HIP_OK(hipMemsetAsync(D.stats.p, 0, kStatBytes, st));
     HIP_OK(hipEventRecord(D.ev0, st));
-    hipLaunchKernelGGL(grid ? k_primary<true> : k_primary<false>, dim3((npx + kTraceBlock - 1) / kTraceBlock), dim3(kTraceBlock),
-                       0, st, D.d, cf, (int*)D.hit_f.p, (double*)D.hit_tbg.p);
-    HIP_OK(hipGetLastError());
     RootTab rtab{(double*)D.root_pnw.p, (int*)D.root_kind.p};
-    hipLaunchKernelGGL(k_root_table, dim3((npx + 255) / 256), dim3(256), 0, st, D.d, cf, (const int*)D.hit_f.p,
-                       (const double*)D.hit_tbg.p, rtab);
-    HIP_OK(hipGetLastError());
-    if (fused) P.root_pnw = rtab.pnw;  // BRDF-only: lite root entries (Params::root_pnw)
+    if (!ray_roots) {
+        hipLaunchKernelGGL(grid ? k_primary<true> : k_primary<false>, dim3((npx + kTraceBlock - 1) / kTraceBlock),
+                           dim3(kTraceBlock), 0, st, D.d, cf, (int*)D.hit_f.p, (double*)D.hit_tbg.p);
+        HIP_OK(hipGetLastError());
+        hipLaunchKernelGGL(k_root_table, dim3((npx + 255) / 256), dim3(256), 0, st, D.d, cf, (const int*)D.hit_f.p,
+                           (const double*)D.hit_tbg.p, rtab);
+        HIP_OK(hipGetLastError());
+        if (fused) P.root_pnw = rtab.pnw;  // BRDF-only: lite root entries (Params::root_pnw)
+    }
     if (pc.use || small_use) {
         HIP_OK(hipMemsetAsync(qb.count, 0, 4, st));
         hipLaunchKernelGGL(k_root_points, dim3((npx + 255) / 256), dim3(256), 0, st, D.d, cf, (const int*)D.hit_f.p,
@@ -5417,9 +5586,14 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
             const unsigned n_children = n;  // [0, n_children) children, [n_children, n) fresh roots
             if (rnext < R && n < (unsigned)fill) {  // refill with roots (appended through node_entry)
                 const int m = (int)std::min<long long>((long long)fill - n, R - rnext);
-                hipLaunchKernelGGL(active ? k_roots_t<true> : k_roots_t<false>, dim3((m + 256 * kRootsPT - 1) / (256 * kRootsPT)),
-                                   dim3(256), 0, st, P, (const int*)D.hit_f.p, nact, a, rnext, m, *cur, std::max(1, nminor), b - a,
-                                   rtab, P.root_pnw ? 1 : 0, active);
+                if (ray_roots)
+                    hipLaunchKernelGGL(k_roots_rays, dim3((m + 256 * kRayRootsPT - 1) / (256 * kRayRootsPT)), dim3(256), 0, st, P,
+                                       cf, rr, nact, a, rnext, m, *cur, std::max(1, nminor), b - a);
+                else
+                    hipLaunchKernelGGL(active ? k_roots_t<true> : k_roots_t<false>,
+                                       dim3((m + 256 * kRootsPT - 1) / (256 * kRootsPT)), dim3(256), 0, st, P,
+                                       (const int*)D.hit_f.p, nact, a, rnext, m, *cur, std::max(1, nminor), b - a, rtab,
+                                       P.root_pnw ? 1 : 0, active);
                 HIP_OK(hipGetLastError());
                 rnext += m;
                 if ((rc = read_count(&n))) return rc;
@@ -6439,7 +6613,7 @@ static int render_device_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt
         return MCPT_E_INVALID;
     }
     int rc;
-    if ((rc = check_opts(o)) || (rc = validate_camera(cam))) return rc;
+    if ((rc = check_opts(o)) || (rc = validate_camera(cam)) || (rc = check_jitter(o))) return rc;
     std::lock_guard<std::mutex> lk(sc->mu);
     if (o->num_devices > 0) {
         if ((rc = check_device_buffer(dev_out, o->devices[0]))) return rc;
@@ -6466,7 +6640,7 @@ static int render_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render
         return MCPT_E_INVALID;
     }
     int rc;
-    if ((rc = check_opts(o)) || (rc = validate_camera(cam))) return rc;
+    if ((rc = check_opts(o)) || (rc = validate_camera(cam)) || (rc = check_jitter(o))) return rc;
     std::lock_guard<std::mutex> lk(sc->mu);
     if (o->num_devices > 0) return render_multi(sc, cam, o, nullptr, out_rgb, stats);
     int device = o->device;
@@ -6489,6 +6663,114 @@ static int render_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render
     if (rank != 0) return MCPT_OK;  // the job total lands on rank 0; this rank's out_rgb is unchanged
     HIP_OK(hipMemcpyAsync(out_rgb, D->fb.p, n * sizeof(double), hipMemcpyDeviceToHost, D->stream));
     HIP_OK(hipStreamSynchronize(D->stream));
+    return MCPT_OK;
+}
+
+// the checks of mcpt_render_rays[_device] that need no device
+static int check_render_rays(mcpt_scene* sc, const mcpt_render_opts* o, int32_t n, const double* origin, const double* dir,
+                             const double* out) {
+    if (!sc || !o || !origin || !dir || !out) {
+        set_error("mcpt_render_rays: null argument: %s", !sc ? "scene" : !o ? "opts" : !origin ? "origin" : !dir ? "dir" : "out_rgb");
+        return MCPT_E_INVALID;
+    }
+    if (o->struct_size == sizeof(mcpt_render_opts) && (o->num_devices > 0 || o->comm)) {
+        set_error("mcpt_render_rays is single-device: a device list or a communicator is not supported");
+        return MCPT_E_INVALID;
+    }
+    int rc;
+    if ((rc = check_opts(o))) return rc;
+    if (n < 1) {
+        set_error("mcpt_render_rays: n = %d rays (must be >= 1)", n);
+        return MCPT_E_INVALID;
+    }
+    if (o->accel == MCPT_ACCEL_GRID) {
+        set_error("mcpt_render_rays: MCPT_ACCEL_GRID is not supported (the rays are traced over the BVH)");
+        return MCPT_E_INVALID;
+    }
+    if (o->flags & MCPT_RENDER_PIXEL_JITTER) {
+        set_error("mcpt_render_rays: MCPT_RENDER_PIXEL_JITTER is not supported (the rays are the caller's)");
+        return MCPT_E_INVALID;
+    }
+    return validate_render(o);
+}
+
+int mcpt_render_rays_device(mcpt_scene* sc, const mcpt_render_opts* o, int32_t n, const double* dev_origin,
+                            const double* dev_dir, double* dev_out, mcpt_stats* stats) {
+    int rc;
+    if ((rc = check_render_rays(sc, o, n, dev_origin, dev_dir, dev_out))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    if ((rc = get_device_state(sc, o->device, &D))) return rc;
+    if ((rc = check_device_buffer(dev_out, D->device)) || (rc = check_device_buffer(dev_origin, D->device, "dev_origin")) ||
+        (rc = check_device_buffer(dev_dir, D->device, "dev_dir")))
+        return rc;
+    // the caller's buffers may still be written by work on other streams (e.g. torch's)
+    HIP_OK(hipDeviceSynchronize());
+    const RayRoots rr{dev_origin, dev_dir, n, 0};
+    mcpt_stats st{};
+    if ((rc = render_on_device(sc, *D, nullptr, o, dev_out, &st, nullptr, &rr))) return rc;
+    copy_stats(o, st, stats);
+    return MCPT_OK;
+}
+
+int mcpt_render_rays(mcpt_scene* sc, const mcpt_render_opts* o, int32_t n, const double* origin, const double* dir,
+                     double* out_rgb, mcpt_stats* stats) {
+    int rc;
+    if ((rc = check_render_rays(sc, o, n, origin, dir, out_rgb))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    if ((rc = get_device_state(sc, o->device, &D))) return rc;
+    const size_t bytes = 3 * (size_t)n * sizeof(double);
+    if ((rc = ensure(D->fb, bytes)) || (rc = ensure(D->ray_o, bytes)) || (rc = ensure(D->ray_d, bytes))) return rc;
+    HIP_OK(hipMemcpyAsync(D->fb.p, out_rgb, bytes, hipMemcpyHostToDevice, D->stream));
+    HIP_OK(hipMemcpyAsync(D->ray_o.p, origin, bytes, hipMemcpyHostToDevice, D->stream));
+    HIP_OK(hipMemcpyAsync(D->ray_d.p, dir, bytes, hipMemcpyHostToDevice, D->stream));
+    const RayRoots rr{(const double*)D->ray_o.p, (const double*)D->ray_d.p, n, 0};
+    mcpt_stats st{};
+    if ((rc = render_on_device(sc, *D, nullptr, o, (double*)D->fb.p, &st, nullptr, &rr))) return rc;
+    HIP_OK(hipMemcpyAsync(out_rgb, D->fb.p, bytes, hipMemcpyDeviceToHost, D->stream));
+    HIP_OK(hipStreamSynchronize(D->stream));
+    copy_stats(o, st, stats);
+    return MCPT_OK;
+}
+
+int mcpt_camera_rays(const mcpt_camera* cam, uint64_t seed, int32_t sample, int32_t jitter, int32_t device, double* origin,
+                     double* dir) {
+    if (!cam || !origin || !dir) {
+        set_error("mcpt_camera_rays: null argument: %s", !cam ? "cam" : !origin ? "origin" : "dir");
+        return MCPT_E_INVALID;
+    }
+    int rc;
+    if ((rc = validate_camera(cam))) return rc;
+    if (sample < 0 || (jitter != 0 && jitter != 1)) {
+        set_error("mcpt_camera_rays: sample %d must be >= 0 and jitter %d must be 0 or 1", sample, jitter);
+        return MCPT_E_INVALID;
+    }
+    struct Restore {  // the caller's current device
+        int prev = -1;
+        ~Restore() {
+            if (prev >= 0) (void)hipSetDevice(prev);
+        }
+    } restore;
+    if (device >= 0) {
+        HIP_OK(hipGetDevice(&restore.prev));
+        HIP_OK(hipSetDevice(device));
+    }
+    const CamFrame cf = cam_setup(*cam);
+    const int npx = cam->width * cam->height;
+    const size_t bytes = 3 * (size_t)npx * sizeof(double);
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() {
+            if (p) (void)hipFree(p);
+        }
+    } buf;
+    HIP_OK(hipMalloc(&buf.p, 2 * bytes));
+    double* d = (double*)buf.p;
+    hipLaunchKernelGGL(k_camera_rays, dim3((npx + 255) / 256), dim3(256), 0, 0, cf, seed, sample, jitter, d, d + 3 * (size_t)npx);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpy(origin, d, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dir, d + 3 * (size_t)npx, bytes, hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
 
@@ -6516,6 +6798,10 @@ static int check_adaptive(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_ren
     }
     int rc;
     if ((rc = check_opts(base)) || (rc = validate_camera(cam))) return rc;
+    if (base->flags & MCPT_RENDER_PIXEL_JITTER) {
+        set_error("adaptive render: MCPT_RENDER_PIXEL_JITTER is not supported (the passes' roots come from the per-pixel tables)");
+        return MCPT_E_INVALID;
+    }
     if (a->struct_size != sizeof(mcpt_adaptive_opts)) {
         set_error("mcpt_adaptive_opts.struct_size is %u, this library expects %zu (use mcpt_adaptive_opts_init / the "
                   "mcpt.h of MCPT_VERSION %d)", a->struct_size, sizeof(mcpt_adaptive_opts), MCPT_VERSION);

@@ -358,6 +358,10 @@ int mcpt_sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, const 
         set_error("invalid render options (mode %d, accel %d)", base->mode, base->accel);
         return MCPT_E_INVALID;
     }
+    if ((base->flags & MCPT_RENDER_PIXEL_JITTER) && base->accel == MCPT_ACCEL_GRID) {
+        set_error("MCPT_RENDER_PIXEL_JITTER is not supported with MCPT_ACCEL_GRID (the jittered roots are traced over the BVH)");
+        return MCPT_E_INVALID;
+    }
     if (o->spp < 1) {
         set_error("invalid sequence options: spp %d must be >= 1", o->spp);
         return MCPT_E_INVALID;
