@@ -1290,7 +1290,7 @@ __global__ __launch_bounds__(256) void k_camera_rays(CamFrame cam, uint64_t seed
 
 // moves nodes [sb, sb + m) of src to [db, db + m) of dst (every field a generation carries into the
 // next: point, normal, wo, throughput, facet, pixel, sample, node id) -- the spill stack's push and
-// pop when a generation is larger than its children buffer can take (render_on_device)
+// pop when a generation is larger than its children buffer can take (WavefrontRun::balance_spill)
 __global__ __launch_bounds__(256) void k_queue_move(Queue src, int sb, Queue dst, int db, int m) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= m) return;
@@ -5196,9 +5196,16 @@ int check_jitter(const mcpt_render_opts* o) {
     return MCPT_OK;
 }
 
+// [s0, s1) of the whole job (0,0 = [0, spp))
+void job_range(const mcpt_render_opts* o, int* s0, int* s1) {
+    const bool all = o->sample_begin == 0 && o->sample_end == 0;
+    *s0 = all ? 0 : o->sample_begin;
+    *s1 = all ? o->spp : o->sample_end;
+}
+
 int validate_render(const mcpt_render_opts* o) {
-    const int s0 = (o->sample_begin == 0 && o->sample_end == 0) ? 0 : o->sample_begin;
-    const int s1 = (o->sample_begin == 0 && o->sample_end == 0) ? o->spp : o->sample_end;
+    int s0, s1;
+    job_range(o, &s0, &s1);
     if (o->spp <= 0 || s0 < 0 || s1 < s0 || s1 > o->spp ||
         (o->mode != MCPT_MODE_MIS && o->mode != MCPT_MODE_BRDF && o->mode != MCPT_MODE_SHADE && o->mode != MCPT_MODE_SHADE_AREA) ||
         (o->accel != MCPT_ACCEL_BVH && o->accel != MCPT_ACCEL_GRID)) {
@@ -5223,51 +5230,70 @@ struct AdaptiveRun {
     double* noise;
 };
 
-// the wavefront render into a device framebuffer already resident on D's device.  The per-call setup
-// (allocations, primary hits, root table, root-point cache) runs once; the wavefront loop runs once over
-// [s0, s1) for a plain render, or twice per pass (the halves A and B) for an adaptive one (ad != nullptr:
-// o->spp is the cap, the statistics are summed over the passes).
-// rays != nullptr (mcpt_render_rays): the roots are the supplied rays, the "frame" is rays->n x 1 and cam is unused;
-// MCPT_RENDER_PIXEL_JITTER: the roots are the camera's jittered rays.  Either way k_roots_rays makes the roots and the
-// per-pixel setup (primary hits, root table, root-point caches, RootLit pool) is skipped.
-int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt_render_opts* o,
-                     double* dfb, mcpt_stats* stats, const AdaptiveRun* ad = nullptr, const RayRoots* rays = nullptr) {
-    const CamFrame cf = rays ? CamFrame{} : cam_setup(*cam);
-    const int W = rays ? rays->n : cam->width, H = rays ? 1 : cam->height, npx = W * H;
-    const RayRoots rr = rays ? *rays : RayRoots{nullptr, nullptr, 0, (o->flags & MCPT_RENDER_PIXEL_JITTER) ? 1 : 0};
-    const bool ray_roots = rays || rr.jitter;
-    const int s0 = (o->sample_begin == 0 && o->sample_end == 0) ? 0 : o->sample_begin;
-    const int s1 = (o->sample_begin == 0 && o->sample_end == 0) ? o->spp : o->sample_end;
-    {
-        const int rv = validate_render(o);
-        if (rv) return rv;
+// ---- the render driver: plan -> bound buffers -> primary tables -> root caches -> run (plain or adaptive) ->
+// statistics (render_on_device, at the end of this section, reads in that order) ----
+
+// What a call decides once, before it touches a buffer (make_plan); nothing changes it afterwards.
+struct RenderPlan {
+    CamFrame cf{};  // the camera's frame (unused with caller-supplied rays)
+    RayRoots rr{};  // where the roots' rays come from when ray_roots: the caller's rays, or the camera's jittered ones
+    int W = 0, H = 0, npx = 0, s0 = 0, s1 = 0;
+    bool grid = false;        // MCPT_ACCEL_GRID
+    bool ray_roots = false;   // k_roots_rays makes the roots: no per-pixel tables, no root caches
+    bool needs_prep = false;  // the O(N_L) light prep runs: shade_with_mis, and shade() with the spherical sampler
+    bool fused = false;       // BRDF-only: k_extend_brdf (the grid runs split)
+    bool split_brdf = false;
+    bool stale = false;  // shade_with_mis reduces its trees bottom-up to evaluate the BRDF branch's light pdf with the
+                         // reference's (stale) sampler state, unless MCPT_RENDER_FRESH_PDF asks for the node's own
+    bool count_trav = false, count_c1 = false, fp32 = false;
+    bool exact_pick = false;  // nodes inside the ambiguity band go to k_prep_exact
+    bool rays_pers = false;   // the MIS / shade ray sets take the persistent refilling waves
+    bool want_cw8 = false;    // ... over the 8-wide trees, where the device has them (Bound::rays_cw8)
+    bool no_cache = false;    // no root-point cache: roots from rays, or the A/B switch MCPT_DEBUG_NO_ROOT_CACHE
+    int qf = 0, target = 0, cap = 0;  // queue factor, nodes per generation, queue capacity
+    int nchunks = 0, lstride = 0;     // the light table's 64-triangle chunks; a cache row's candidate-list stride
+    uint64_t accel = 0;               // bytes of the acceleration structures the rays walk
+    // root order: sample-minor when the acceleration structures exceed an XCD's 4 MiB L2 (the
+    // secondary rays of consecutive roots then share their origin and top-down paths: C5 +10%),
+    // sample-major otherwise (Veach: the root-point cache's per-pixel reads spread; -3% minor)
+    int minor_of(int nsamp) const {  // the group of a run of nsamp samples
+        return (MCPT_ROOT_MINOR > 0 || (MCPT_ROOT_MINOR < 0 && accel > (4ull << 20))) ? nsamp : std::min(MCPT_ROOT_GROUP, nsamp);
     }
+};
+
+// validates the call and fills the plan.  rays != nullptr (mcpt_render_rays): the roots are the supplied rays, the
+// "frame" is rays->n x 1 and cam is unused; MCPT_RENDER_PIXEL_JITTER: the roots are the camera's jittered rays.
+int make_plan(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt_render_opts* o, bool adaptive,
+              const RayRoots* rays, RenderPlan* out) {
+    RenderPlan& p = *out;
+    int rc;
+    if ((rc = validate_render(o))) return rc;
+    p.cf = rays ? CamFrame{} : cam_setup(*cam);
+    p.W = rays ? rays->n : cam->width, p.H = rays ? 1 : cam->height, p.npx = p.W * p.H;
+    p.rr = rays ? *rays : RayRoots{nullptr, nullptr, 0, (o->flags & MCPT_RENDER_PIXEL_JITTER) ? 1 : 0};
+    p.ray_roots = rays || p.rr.jitter;
+    job_range(o, &p.s0, &p.s1);
     // MCPT_ACCEL_GRID: the reference's uniform grid over the scene and this camera's eye, n0 =
     // 100000 (main.cpp:501-504), built here unless the scene already holds that grid
-    const bool grid = o->accel == MCPT_ACCEL_GRID;
-    if (ray_roots && (grid || ad)) {
-        set_error("roots from rays are not supported with %s", grid ? "MCPT_ACCEL_GRID" : "adaptive sampling");
+    p.grid = o->accel == MCPT_ACCEL_GRID;
+    if (p.ray_roots && (p.grid || adaptive)) {
+        set_error("roots from rays are not supported with %s", p.grid ? "MCPT_ACCEL_GRID" : "adaptive sampling");
         return MCPT_E_INVALID;
     }
-    if (grid) {
-        const double eye[3] = {cf.eye.x, cf.eye.y, cf.eye.z};
-        int rg;
-        if ((rg = use_grid(sc, D, eye, 100000))) return rg;
+    if (p.grid) {
+        const double eye[3] = {p.cf.eye.x, p.cf.eye.y, p.cf.eye.z};
+        if ((rc = use_grid(sc, D, eye, 100000))) return rc;
     }
     // Path regeneration (wavefront with refill): before every generation the current queue is
     // topped up with fresh camera samples (roots) to `target` nodes, so every prep/extend launch
     // is large until the final drain; roots are taken in global order r = (sample - s0) * npx +
     // pixel.  samples_per_launch (if set) sets target = samples_per_launch * npx.
-    const long long R = (long long)(s1 - s0) * npx;
-    // root order: sample-minor when the acceleration structures exceed an XCD's 4 MiB L2 (the
-    // secondary rays of consecutive roots then share their origin and top-down paths: C5 +10%),
-    // sample-major otherwise (Veach: the root-point cache's per-pixel reads spread; -3% minor)
-    const uint64_t accel = (uint64_t)(D.d.nbvh4 + D.d.nlbvh4) * sizeof(BvhNode4) +
-                           (uint64_t)(sc->bvh.leaf_facets.size() + sc->lbvh.leaf_facets.size()) * 3 * sizeof(float4);
-    const auto minor_of = [&](int nsamp) {  // the group of a run of nsamp samples
-        return (MCPT_ROOT_MINOR > 0 || (MCPT_ROOT_MINOR < 0 && accel > (4ull << 20))) ? nsamp : std::min(MCPT_ROOT_GROUP, nsamp);
-    };
-    const int qf = o->queue_factor > 0 ? o->queue_factor : 2;
+    const long long R = (long long)(p.s1 - p.s0) * p.npx;
+    p.accel = (uint64_t)(D.d.nbvh4 + D.d.nlbvh4) * sizeof(BvhNode4) +
+              (uint64_t)(sc->bvh.leaf_facets.size() + sc->lbvh.leaf_facets.size()) * 3 * sizeof(float4);
+    p.qf = o->queue_factor > 0 ? o->queue_factor : 2;
+    p.nchunks = prep_chunks(D.d.NL);
+    p.lstride = 64 * p.nchunks;
     // default working set: MCPT_WORKING_SET nodes (48 Mi: fewer, larger generations amortise each
     // launch's tail -- measured +6% Veach, +21% Cornell-1M over 4 Mi), but no more than the call's
     // camera samples (a small render holds all its roots at once) and no more than half the free
@@ -5277,288 +5303,600 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
     for (int k = 0; k < 9; k++) ws_held += D.aux[k].bytes;
     for (int k = 0; k < 13; k++) ws_held += D.sl[k].bytes;
     HIP_OK(hipMemGetInfo(&ws_free, &ws_total));
-    const size_t ws_node_bytes = 2 * 132 + 152 + 8 * (size_t)mask_stride(prep_chunks(D.d.NL)) + 280;  // queues aux words slots
-    const long long ws_mem = (long long)((ws_free + ws_held) / 2 / ((size_t)qf * ws_node_bytes));
+    const size_t ws_node_bytes = 2 * 132 + 152 + 8 * (size_t)mask_stride(p.nchunks) + 280;  // queues aux words slots
+    const long long ws_mem = (long long)((ws_free + ws_held) / 2 / ((size_t)p.qf * ws_node_bytes));
     const long long target_ll =
         o->samples_per_launch > 0
-            ? (long long)o->samples_per_launch * npx
+            ? (long long)o->samples_per_launch * p.npx
             : std::min<long long>({(long long)MCPT_WORKING_SET, std::max<long long>(R, 1024), std::max<long long>(ws_mem, 1 << 20)});
     if (target_ll > (1ll << 29)) {
         set_error("batch too large");
         return MCPT_E_INVALID;
     }
-    const int target = (int)std::max<long long>(target_ll, 1);
-    const int cap = (int)std::min<long long>((long long)qf * target + 1024, (1ll << 30));
-    int rc;
-    if (!ray_roots && ((rc = ensure(D.hit_f, 4ull * npx)) || (rc = ensure(D.hit_tbg, 24ull * npx)) ||
-                       (rc = ensure(D.root_pnw, 72ull * npx)) || (rc = ensure(D.root_kind, 4ull * npx))))
-        return rc;
-    if ((rc = ensure(D.stats, kStatBytes)) || (rc = ensure(D.work, 256))) return rc;
-    Queue qa, qb;
-    if ((rc = alloc_queue(D.qa, cap, qa)) || (rc = alloc_queue(D.qb, cap, qb))) return rc;
-    // extension kernels: MIS and shade split into gen / rays / combine (measured faster), BRDF-only
-    // keeps the single kernel (one ray per node; measured faster).  A/B switches:
-    const bool count_trav = (o->flags & MCPT_DEBUG_COUNT_TRAVERSAL) != 0;
-#define K_MIS_RAYS (grid ? k_mis_rays<true> : count_trav ? k_mis_rays<false, true> : k_mis_rays<false>)
-
-    const bool split_brdf = (o->flags & MCPT_DEBUG_SPLIT_BRDF) != 0;
-    // the O(N_L) light prep runs for shade_with_mis and for shade() with the spherical sampler
-    const bool needs_prep = o->mode == MCPT_MODE_MIS || o->mode == MCPT_MODE_SHADE;
-    const bool fused = !grid && o->mode == MCPT_MODE_BRDF && !split_brdf;  // BRDF-only: k_extend_brdf (the grid runs split)
-    Aux aux{};
-    if (!fused && (rc = alloc_aux(D.aux, cap, aux))) return rc;
-    // shade_with_mis reduces its trees bottom-up to evaluate the BRDF branch's light pdf with the
-    // reference's (stale) sampler state, unless MCPT_RENDER_FRESH_PDF asks for the node's own
-    const bool stale = o->mode == MCPT_MODE_MIS && !(o->flags & MCPT_RENDER_FRESH_PDF);
-    Slots T{};
-    int rp = 0;  // ready list being filled
-    const unsigned* hctrl = D.pinned_count + 16;  // slot control words, read back with the queue count
-    hipStream_t st = D.stream;
-    if (stale && (rc = alloc_slots(D.sl, std::max(cap, 1 << 16) / kSlotShards + 1, T, st, false, 0, nullptr))) return rc;
-    Params P;
-    P.S = D.d;
-    P.seed = o->seed;
-    P.inv_spp = ad ? 1.0 : 1.0 / o->spp;  // adaptive: raw sums (P.fb is set per half)
-    P.fb = dfb;
-    P.stats = (unsigned long long*)D.stats.p;
-    P.mode = o->mode;
-    P.root_pnw = nullptr;
-    const int nchunks = prep_chunks(D.d.NL);
-    const size_t prep_lds = prep_lds_bytes(nchunks);
-    if (prep_lds > 160 * 1024) {
+    p.target = (int)std::max<long long>(target_ll, 1);
+    p.cap = (int)std::min<long long>((long long)p.qf * p.target + 1024, (1ll << 30));
+    if (prep_lds_bytes(p.nchunks) > 160 * 1024) {
         set_error("too many light triangles for the LDS chunk table (%d)", D.d.NL);
         return MCPT_E_SCENE;
     }
-    const bool count_c1 = !(o->flags & MCPT_RENDER_NO_BACKFACE_STATS);
-    const bool fp32 = (o->flags & MCPT_RENDER_PRECISION_FP32) != 0;
-    double prep_ms = 0, trace_ms = 0, cache_ms = 0;
-    uint64_t gens = 0, prep_launches = 0, nodes_total = 0, cache_points = 0, trace_launches = 0, cached_roots = 0;
-    // candidate words of the split light prep (k_prep_cull -> k_prep_pk2<mask-in>): per node and chunk
-    uint64_t* masks = nullptr;
+    // extension kernels: MIS and shade split into gen / rays / combine (measured faster), BRDF-only
+    // keeps the single kernel (one ray per node; measured faster).  A/B switches:
+    p.count_trav = (o->flags & MCPT_DEBUG_COUNT_TRAVERSAL) != 0;
+    p.split_brdf = (o->flags & MCPT_DEBUG_SPLIT_BRDF) != 0;
+    p.needs_prep = o->mode == MCPT_MODE_MIS || o->mode == MCPT_MODE_SHADE;
+    p.fused = !p.grid && o->mode == MCPT_MODE_BRDF && !p.split_brdf;
+    p.stale = o->mode == MCPT_MODE_MIS && !(o->flags & MCPT_RENDER_FRESH_PDF);
+    p.count_c1 = !(o->flags & MCPT_RENDER_NO_BACKFACE_STATS);
+    p.fp32 = (o->flags & MCPT_RENDER_PRECISION_FP32) != 0;
+    // exact pick: the opt-in fp32 precision makes no exactness claim, and the small-table prep (k_prep_lane) is exact
+    // by construction.  MCPT_EXACT_PICK=0 builds the pre-round-3 prep (VOS weights' own pick) for the cost A/B only
+    p.exact_pick = MCPT_EXACT_PICK && p.needs_prep && !p.fp32 && D.d.NL > kSmallNL;
+    p.no_cache = p.ray_roots || (o->flags & MCPT_DEBUG_NO_ROOT_CACHE) != 0;
+    // which traversal the MIS / shade ray sets take: the persistent refilling waves for trees beyond an XCD's
+    // 4 MiB L2 and for shade-area's rays (k_rays_persistent, or k_rays_cw8 on the 8-wide trees), else one ray
+    // per thread (k_mis_rays)
+    p.rays_pers = !p.grid && ((o->flags & MCPT_DEBUG_RAYS_PERSIST) || MCPT_RAYS_PERSISTENT > 0 ||
+                              (MCPT_RAYS_PERSISTENT < 0 && p.accel > (4ull << 20)) ||
+                              (MCPT_PERSIST_SHADE_AREA && o->mode == MCPT_MODE_SHADE_AREA));
+    // (round 6: k_rays_persistent handing the combine its hit points instead of (beta, gamma) was measured slower,
+    // C5 -2..-6%, shade-area -9%: profiles/round6_ab_hit_points.txt)
+    p.want_cw8 = MCPT_RAYS_CW8 || (o->flags & MCPT_DEBUG_RAYS_CW8);
+    return MCPT_OK;
+}
+
+// the per-pixel tables of a camera frame: every pixel's primary hit (k_primary) and its root's point, normal, weight
+// and kind (k_root_table).  A render and mcpt_render_aovs bind them, then launch them on D's stream.
+int bind_primary_tables(DeviceState& D, size_t npx) {
+    int rc;
+    if ((rc = ensure(D.hit_f, 4 * npx)) || (rc = ensure(D.hit_tbg, 24 * npx)) || (rc = ensure(D.root_pnw, 72 * npx)) ||
+        (rc = ensure(D.root_kind, 4 * npx)))
+        return rc;
+    return MCPT_OK;
+}
+int launch_primary_tables(DeviceState& D, const CamFrame& cf, int npx, bool grid) {
+    hipLaunchKernelGGL(grid ? k_primary<true> : k_primary<false>, dim3((npx + kTraceBlock - 1) / kTraceBlock),
+                       dim3(kTraceBlock), 0, D.stream, D.d, cf, (int*)D.hit_f.p, (double*)D.hit_tbg.p);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(k_root_table, dim3((npx + 255) / 256), dim3(256), 0, D.stream, D.d, cf, (const int*)D.hit_f.p,
+                       (const double*)D.hit_tbg.p, RootTab{(double*)D.root_pnw.p, (int*)D.root_kind.p});
+    HIP_OK(hipGetLastError());
+    return MCPT_OK;
+}
+
+// the views of D's buffers that the kernels of one call take (bind_buffers)
+struct Bound {
+    Queue qa{}, qb{};
+    Aux aux{};
+    Slots T{};  // the reduction's slot pool as allocated (a run grows its own copy)
+    uint64_t* masks = nullptr;  // candidate words of the split light prep (k_prep_cull -> k_prep_pk2<mask-in>): per node and chunk
     CullOrder corder{};
-    if (needs_prep && D.d.NL > kSmallNL) {
-        if ((rc = ensure(D.masks, (size_t)std::max(cap, npx) * mask_stride(nchunks) * 8))) return rc;
-        masks = (uint64_t*)D.masks.p;
-        if ((rc = cull_order_bufs(D, (size_t)std::max(cap, npx), &corder))) return rc;
-    }
-    // exact pick: nodes inside the ambiguity band go to k_prep_exact; the opt-in fp32
-    // precision makes no exactness claim, and the small-table prep (k_prep_lane) is exact by construction
-    // MCPT_EXACT_PICK=0 builds the pre-round-3 prep (VOS weights' own pick) for the cost A/B only
-    const bool exact_pick = MCPT_EXACT_PICK && needs_prep && !fp32 && D.d.NL > kSmallNL;
-    int *exact_list = nullptr, *maybe_list = nullptr;  // [0] count, entries from kExactHead
+    int *exact_list = nullptr, *maybe_list = nullptr;  // exact pick: [0] count, entries from kExactHead
     double *exact_scr = nullptr, *slack = nullptr;
-    if (exact_pick) {
-        if ((rc = ensure(D.exact, 8ull * ((size_t)cap + kExactHead))) ||
-            (rc = ensure(D.exact_scr, 8 * exact_scratch_doubles(D.d.NL))) || (rc = ensure(D.slack, 8ull * cap)))
-            return rc;
-        exact_list = (int*)D.exact.p;
-        maybe_list = exact_list + cap + kExactHead;
-#if MCPT_BAND_DIAG
-        HIP_OK(hipMemset((double*)D.exact_scr.p + (size_t)exact_waves(D.d.NL) * ((D.d.NL + 63) & ~63) * 3 / 2, 0,
-                         4ull * cam->width * cam->height));
-#endif
-        exact_scr = (double*)D.exact_scr.p;
-        slack = (double*)D.slack.p;
-    }
-    // root-point cache (see PrepCache): built here when the call has >= 2 samples per pixel and the
+    PrepCache pc{};       // root-point cache (pc.use: this call has one)
+    SmallCache scache{};  // the small-table prep's root-point cache
+    bool small_use = false;
+    RootLit rl{};  // roots' literal sums per pixel (k_prep_exact), up to 2 GiB of entries
+    RootTab rtab{};
+    bool rays_cw8 = false;  // the persistent traversal walks the 8-wide trees
+    int nblk = 0;           // adaptive: blocks of k_adaptive_mark / k_adaptive_compact
+};
+
+// the call's root caches, if it has any: they are filled later, inside the timed region (build_root_caches)
+int bind_root_caches(DeviceState& D, const RenderPlan& p, Bound& B) {
+    int rc;
+    // root-point cache (see PrepCache): built when the call has >= 2 samples per pixel and the
     // entries fit in the free HBM less a 16 GiB reserve (800x600 with N_L = 3012: 15 GB; 1600x1200:
     // 60 GB -- sized for the 288 GB of an MI355X)
-    PrepCache pc{};
-    const int lstride = 64 * nchunks;
+    const int npx = p.npx, nchunks = p.nchunks, lstride = p.lstride;
     const size_t cache_bytes = (size_t)npx * ((size_t)nchunks * 8 + (size_t)lstride * 10 + 16);
     size_t free_b = 0, total_b = 0;
     HIP_OK(hipMemGetInfo(&free_b, &total_b));
     const size_t held = D.cache_bt.bytes + D.cache_lst.bytes + D.cache_info.bytes + D.cache_w.bytes;
     const size_t budget = free_b + held > (16ull << 30) ? free_b + held - (16ull << 30) : 0;
-    const bool no_cache = ray_roots || (o->flags & MCPT_DEBUG_NO_ROOT_CACHE) != 0;  // the flag: A/B switch
-    if (needs_prep && s1 - s0 >= 2 && cache_bytes <= budget && !no_cache && D.d.NL > kSmallNL &&
-        prep_list_wave_bytes(nchunks) * 4 <= kPrepListMaxLds && D.d.NL <= 65535) {
+    const bool wanted = p.needs_prep && p.s1 - p.s0 >= 2 && !p.no_cache;
+    if (wanted && cache_bytes <= budget && D.d.NL > kSmallNL && prep_list_wave_bytes(nchunks) * 4 <= kPrepListMaxLds &&
+        D.d.NL <= 65535) {
         if ((rc = ensure(D.cache_bt, (size_t)npx * nchunks * 8)) || (rc = ensure(D.cache_lst, (size_t)npx * lstride * 2)) ||
             (rc = ensure(D.cache_info, (size_t)npx * 16)) || (rc = ensure(D.cache_w, (size_t)npx * lstride * 8)))
             return rc;
-        pc.w = (double*)D.cache_w.p;
-        pc.bt = (double*)D.cache_bt.p;
-        pc.lst = (unsigned short*)D.cache_lst.p;
-        pc.info = (int4*)D.cache_info.p;
-        pc.lstride = lstride;
-        pc.use = 1;  // built below, inside the timed region
+        B.pc.w = (double*)D.cache_w.p;
+        B.pc.bt = (double*)D.cache_bt.p;
+        B.pc.lst = (unsigned short*)D.cache_lst.p;
+        B.pc.info = (int4*)D.cache_info.p;
+        B.pc.lstride = lstride;
+        B.pc.use = 1;
     }
     // the small-table prep's root-point cache (SmallCache: N_L <= kSmallNL, e.g. the Cornell scene's
     // 2-triangle light): (N_L + 1.5) x 8 B per pixel
-    SmallCache scache{};
-    bool small_use = false;
-    if (needs_prep && s1 - s0 >= 2 && !no_cache && D.d.NL > 0 && D.d.NL <= kSmallNL &&
-        (size_t)npx * (8ull * D.d.NL + 12) <= budget) {
+    if (wanted && D.d.NL > 0 && D.d.NL <= kSmallNL && (size_t)npx * (8ull * D.d.NL + 12) <= budget) {
         if ((rc = ensure(D.sc_cum, 8ull * npx * D.d.NL)) || (rc = ensure(D.sc_wsum, 8ull * npx)) ||
             (rc = ensure(D.sc_last, 4ull * npx)))
             return rc;
-        scache.cum = (double*)D.sc_cum.p;
-        scache.wsum = (double*)D.sc_wsum.p;
-        scache.last = (int*)D.sc_last.p;
-        small_use = true;
+        B.scache.cum = (double*)D.sc_cum.p;
+        B.scache.wsum = (double*)D.sc_wsum.p;
+        B.scache.last = (int*)D.sc_last.p;
+        B.small_use = true;
     }
-    RootLit rl{};  // roots' literal sums per pixel (k_prep_exact), up to 2 GiB of entries
-    if (exact_pick && pc.use) {
-        rl.stride = (lstride + 8 + 7) & ~7;
-        rl.cap = (int)std::min<long long>({(long long)npx, (2ll << 30) / (8ll * rl.stride), 1ll << 20});
-        if ((rc = ensure(D.lit_slot, 4ull * (npx + 16))) || (rc = ensure(D.lit_pool, 8ull * rl.stride * rl.cap))) return rc;
-        rl.slot = (int*)D.lit_slot.p;
-        rl.pool = (double*)D.lit_pool.p;
+    if (p.exact_pick && B.pc.use) {
+        B.rl.stride = (lstride + 8 + 7) & ~7;
+        B.rl.cap = (int)std::min<long long>({(long long)npx, (2ll << 30) / (8ll * B.rl.stride), 1ll << 20});
+        if ((rc = ensure(D.lit_slot, 4ull * (npx + 16))) || (rc = ensure(D.lit_pool, 8ull * B.rl.stride * B.rl.cap))) return rc;
+        B.rl.slot = (int*)D.lit_slot.p;
+        B.rl.pool = (double*)D.lit_pool.p;
     }
-    if ((MCPT_RAYS_CW8 || (o->flags & MCPT_DEBUG_RAYS_CW8)) && (rc = ensure_bvh8(sc, &D))) return rc;
-    // which traversal the MIS / shade ray sets take: the persistent refilling waves for trees beyond an XCD's
-    // 4 MiB L2 and for shade-area's rays (k_rays_persistent, or k_rays_cw8 on the 8-wide trees), else one ray
-    // per thread (k_mis_rays)
-    const bool rays_pers = !grid && ((o->flags & MCPT_DEBUG_RAYS_PERSIST) || MCPT_RAYS_PERSISTENT > 0 ||
-                                     (MCPT_RAYS_PERSISTENT < 0 && accel > (4ull << 20)) ||
-                                     (MCPT_PERSIST_SHADE_AREA && o->mode == MCPT_MODE_SHADE_AREA));
-    // (round 6: k_rays_persistent handing the combine its hit points instead of (beta, gamma) was measured slower,
-    // C5 -2..-6%, shade-area -9%: profiles/round6_ab_hit_points.txt)
-    const bool rays_cw8 = rays_pers && (MCPT_RAYS_CW8 || (o->flags & MCPT_DEBUG_RAYS_CW8)) && D.d.bvh8 && D.d.lbvh8;
-    const int nblk = (npx + 255) / 256;  // adaptive: blocks of k_adaptive_mark / k_adaptive_compact
-    if (ad) {
+    return MCPT_OK;
+}
+
+// every allocation of a call, in a fixed order (the root caches' budget is the HBM left free after the queues), and
+// the views into them.  First-call hipMalloc is not device work: the timed region starts after this.
+int bind_buffers(mcpt_scene* sc, DeviceState& D, const RenderPlan& p, const mcpt_render_opts* o, bool adaptive, Bound* out) {
+    Bound& B = *out;
+    const int cap = p.cap, npx = p.npx;
+    int rc;
+    if (!p.ray_roots && (rc = bind_primary_tables(D, (size_t)npx))) return rc;
+    if ((rc = ensure(D.stats, kStatBytes)) || (rc = ensure(D.work, 256))) return rc;
+    if ((rc = alloc_queue(D.qa, cap, B.qa)) || (rc = alloc_queue(D.qb, cap, B.qb))) return rc;
+    if (!p.fused && (rc = alloc_aux(D.aux, cap, B.aux))) return rc;
+    if (p.stale && (rc = alloc_slots(D.sl, std::max(cap, 1 << 16) / kSlotShards + 1, B.T, D.stream, false, 0, nullptr))) return rc;
+    if (p.needs_prep && D.d.NL > kSmallNL) {
+        if ((rc = ensure(D.masks, (size_t)std::max(cap, npx) * mask_stride(p.nchunks) * 8))) return rc;
+        B.masks = (uint64_t*)D.masks.p;
+        if ((rc = cull_order_bufs(D, (size_t)std::max(cap, npx), &B.corder))) return rc;
+    }
+    if (p.exact_pick) {
+        if ((rc = ensure(D.exact, 8ull * ((size_t)cap + kExactHead))) ||
+            (rc = ensure(D.exact_scr, 8 * exact_scratch_doubles(D.d.NL))) || (rc = ensure(D.slack, 8ull * cap)))
+            return rc;
+        B.exact_list = (int*)D.exact.p;
+        B.maybe_list = B.exact_list + cap + kExactHead;
+#if MCPT_BAND_DIAG
+        HIP_OK(hipMemset((double*)D.exact_scr.p + (size_t)exact_waves(D.d.NL) * ((D.d.NL + 63) & ~63) * 3 / 2, 0, 4ull * npx));
+#endif
+        B.exact_scr = (double*)D.exact_scr.p;
+        B.slack = (double*)D.slack.p;
+    }
+    if ((rc = bind_root_caches(D, p, B))) return rc;
+    if (p.want_cw8 && (rc = ensure_bvh8(sc, &D))) return rc;
+    B.rays_cw8 = p.rays_pers && p.want_cw8 && D.d.bvh8 && D.d.lbvh8;
+    B.nblk = (npx + 255) / 256;
+    if (adaptive) {
         for (int k = 0; k < 2; k++)
             if ((rc = ensure(D.ad_acc[k], 24ull * npx)) || (rc = ensure(D.ad_list[k], 4ull * npx)) ||
                 (rc = ensure(D.ad_state[k], (size_t)npx)))
                 return rc;
-        if ((rc = ensure(D.ad_blk, 4ull * (nblk + 1))) || (rc = ensure(D.ad_count, 4ull * npx)) ||
+        if ((rc = ensure(D.ad_blk, 4ull * (B.nblk + 1))) || (rc = ensure(D.ad_count, 4ull * npx)) ||
             (rc = ensure(D.ad_noise, 8ull * npx)))
             return rc;
     }
-    // every buffer is allocated above (first-call hipMalloc of the cache is not device work); the
-    // timed region (seconds, HIP events) starts at the primary-hit kernel
-    HIP_OK(hipMemsetAsync(D.stats.p, 0, kStatBytes, st));
-    HIP_OK(hipEventRecord(D.ev0, st));
-    RootTab rtab{(double*)D.root_pnw.p, (int*)D.root_kind.p};
-    if (!ray_roots) {
-        hipLaunchKernelGGL(grid ? k_primary<true> : k_primary<false>, dim3((npx + kTraceBlock - 1) / kTraceBlock),
-                           dim3(kTraceBlock), 0, st, D.d, cf, (int*)D.hit_f.p, (double*)D.hit_tbg.p);
-        HIP_OK(hipGetLastError());
-        hipLaunchKernelGGL(k_root_table, dim3((npx + 255) / 256), dim3(256), 0, st, D.d, cf, (const int*)D.hit_f.p,
-                           (const double*)D.hit_tbg.p, rtab);
-        HIP_OK(hipGetLastError());
-        if (fused) P.root_pnw = rtab.pnw;  // BRDF-only: lite root entries (Params::root_pnw)
-    }
-    if (pc.use || small_use) {
-        HIP_OK(hipMemsetAsync(qb.count, 0, 4, st));
-        hipLaunchKernelGGL(k_root_points, dim3((npx + 255) / 256), dim3(256), 0, st, D.d, cf, (const int*)D.hit_f.p,
-                           (const double*)D.hit_tbg.p, qb);
-        HIP_OK(hipGetLastError());
-        HIP_OK(hipMemcpyAsync(D.pinned_count, qb.count, 4, hipMemcpyDeviceToHost, st));
-        HIP_OK(hipStreamSynchronize(st));
-        int nr = (int)std::min<unsigned>(D.pinned_count[0], (unsigned)cap);
-        if (D.pinned_count[0] > (unsigned)cap) {
-            // more root points than the queue holds (a frame of more pixels than the working set under memory
-            // pressure): k_root_points dropped some, and their pixels' cache rows would be stale -- no root cache
-            // in this call, every root runs the full prep (same image, slower)
-            pc.use = 0;
-            small_use = false;
-            rl = RootLit{};
-            nr = 0;
-        }
-        if (nr > 0 && small_use) {
-            HIP_OK(hipEventRecord(D.evp0, st));
-            HIP_OK(launch_prep_lane(D.d, o->seed, nr, qb.p, qb.n, qb.cap, qb.pixel, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                    nullptr, P.stats, st, scache, true));
-            HIP_OK(hipEventRecord(D.evp1, st));
-            HIP_OK(hipEventSynchronize(D.evp1));
-            float ms = 0;
-            HIP_OK(hipEventElapsedTime(&ms, D.evp0, D.evp1));
-            prep_ms += ms;
-            cache_ms = ms;
-            prep_launches++;
-            cache_points = (uint64_t)nr;
-        } else if (nr > 0) {
-            pc.build = 1;
-            HIP_OK(hipEventRecord(D.evp0, st));
-            HIP_OK(launch_prep(masks ? 17 : 8, D.d, o->seed, nr, qb.p, qb.n, qb.cap, qb.pixel, nullptr, nullptr, nullptr, nullptr,
-                               nullptr, nullptr, P.stats, (unsigned*)D.work.p, st, pc, masks, count_c1, fp32, corder));
-            HIP_OK(hipEventRecord(D.evp1, st));
-            HIP_OK(hipEventSynchronize(D.evp1));
-            float ms = 0;
-            HIP_OK(hipEventElapsedTime(&ms, D.evp0, D.evp1));
-            prep_ms += ms;
-            cache_ms = ms;
-            prep_launches++;
-            cache_points = (uint64_t)nr;
-        }
-        pc.build = 0;
-        if (rl.slot) {  // a fresh set of per-pixel literal sums for this call's cache
-            HIP_OK(hipMemsetAsync(rl.slot, 0, 64, st));
-            HIP_OK(hipMemsetAsync(rl.slot + 16, 0xff, 4ull * npx, st));
-        }
-    }
+    B.rtab = RootTab{(double*)D.root_pnw.p, (int*)D.root_kind.p};
+    return MCPT_OK;
+}
+
+// a call's running totals (fill_stats turns them into mcpt_stats)
+struct Counters {
+    double prep_ms = 0, trace_ms = 0, cache_ms = 0;
+    uint64_t gens = 0, prep_launches = 0, nodes_total = 0, cache_points = 0, trace_launches = 0, cached_roots = 0;
     uint64_t spilled = 0, roots_total = 0;
 #if MCPT_ADAPTIVE_DIAG
     int diag_runs = 0;
     double diag_drain_ms = 0, diag_kernel_ms = 0;
-    const auto diag_now = [] { return std::chrono::steady_clock::now(); };
-    const auto diag_ms = [](std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1) {
-        return std::chrono::duration<double, std::milli>(t1 - t0).count();
-    };
 #endif
-    // The wavefront loop: samples [a, b) of the pixels active[0, nact) (nullptr: the frame's nact = npx
-    // pixels) are traced to the end of their trees and added into P.fb with weight P.inv_spp.  The setup above
-    // holds for every run: the root table and the root-point cache are keyed by pixel.
-    auto wavefront = [&](int a, int b, const int* active, int nact) -> int {
-        const long long R = (long long)(b - a) * nact;
-        const int nminor = minor_of(b - a);
-        roots_total += (uint64_t)R;
-        Queue* cur = &qa;
-        Queue* nxt = &qb;
-        HIP_OK(hipMemsetAsync(cur->count, 0, 4, st));
-        long long rnext = 0;
-        // Slicing: an MIS node has up to 2 children (shade / BRDF: 1), so a generation of at most `slice`
-        // nodes always fits its children into nxt.  A larger generation (supercritical trees, e.g. occluded
-        // lights: 2 x RR 0.6 = 1.2 children per node) parks its excess on a spill stack in HBM (grown on
-        // demand) and takes it back, last in first out, before fresh roots -- so deep subtrees drain
-        // first and the stack stays bounded by ~depth x slice.  The image does not depend on the order.
-        const int branch = o->mode == MCPT_MODE_MIS ? 2 : 1;
-        const int slice = cap / branch;
-        const int fill = std::min(target, slice);  // refill / pop up to this many nodes per generation
-        Queue qs{};
-        long long spill_n = 0;
-        auto grow_spill = [&](long long need) -> int {
-            if (need <= D.spill_cap && qs.p) return MCPT_OK;
-            if (need > (1ll << 30)) {
-                set_error("spill stack beyond 2^30 nodes");
-                return MCPT_E_DEVICE;
-            }
-            const int ncap = (int)std::min<long long>(std::max<long long>(need, 2ll * D.spill_cap), 1ll << 30);
-            DevBuf nb[14];
-            Queue nq;
-            int r;
-            if ((r = alloc_queue(nb, ncap, nq))) return r;
-            if (spill_n > 0 && qs.p)
-                hipLaunchKernelGGL(k_queue_move, dim3((unsigned)((spill_n + 255) / 256)), dim3(256), 0, st, qs, 0, nq, 0, (int)spill_n);
-            HIP_OK(hipStreamSynchronize(st));
-            for (int k = 0; k < 14; k++) {
-                if (D.qs[k].p) HIP_OK(hipFree(D.qs[k].p));
-                D.qs[k] = nb[k];
-            }
-            D.spill_cap = ncap;
-            qs = nq;
-            return MCPT_OK;
-        };
-        if (D.spill_cap > 0) {  // the stack of an earlier call (empty)
-            int r;
-            if ((r = alloc_queue(D.qs, D.spill_cap, qs))) return r;
-        }
-        auto read_count = [&](unsigned* out) -> int {  // cur's node count; fails on a queue overflow
-            HIP_OK(hipMemcpyAsync(D.pinned_count, cur->count, 4, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipMemcpyAsync(D.pinned_count + 2, (char*)D.stats.p + 32, 8, hipMemcpyDeviceToHost, st));
-            if (stale) HIP_OK(hipMemcpyAsync(D.pinned_count + 16, T.ctrl, kCtrlBytes, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            if (*(unsigned long long*)(D.pinned_count + 2)) {
-                set_error("wavefront queue overflow (capacity %d); raise queue_factor", cap);
-                return MCPT_E_OVERFLOW;
-            }
-            *out = std::min<unsigned>(D.pinned_count[0], (unsigned)cap);
-            return MCPT_OK;
-        };
+};
 #if MCPT_ADAPTIVE_DIAG
-        bool diag_draining = false;
-        auto diag_t0 = diag_now();
+inline std::chrono::steady_clock::time_point diag_now() { return std::chrono::steady_clock::now(); }
+inline double diag_ms(std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1) {
+    return std::chrono::duration<double, std::milli>(t1 - t0).count();
+}
+#endif
+
+// prep_seconds times the full light-prep launches only: events evp0 / evp1 around the launch, read once the caller
+// has enqueued whatever it wants to overlap with the wait
+int prep_timer_start(DeviceState& D) {
+    HIP_OK(hipEventRecord(D.evp0, D.stream));
+    return MCPT_OK;
+}
+int prep_timer_stop(DeviceState& D) {
+    HIP_OK(hipEventRecord(D.evp1, D.stream));
+    return MCPT_OK;
+}
+int prep_timer_ms(DeviceState& D, float* ms) {
+    HIP_OK(hipEventSynchronize(D.evp1));
+    HIP_OK(hipEventElapsedTime(ms, D.evp0, D.evp1));
+    return MCPT_OK;
+}
+
+// fills the call's root caches from the frame's root points: one prep launch over them (the small-table lanes, or
+// the cull + k_prep_pk2 in its cache-building form)
+int build_root_caches(const RenderPlan& p, Bound& B, DeviceState& D, const mcpt_render_opts* o, Counters& C) {
+    if (!B.pc.use && !B.small_use) return MCPT_OK;
+    const hipStream_t st = D.stream;
+    const Queue& qb = B.qb;
+    unsigned long long* dstats = (unsigned long long*)D.stats.p;
+    HIP_OK(hipMemsetAsync(qb.count, 0, 4, st));
+    hipLaunchKernelGGL(k_root_points, dim3((p.npx + 255) / 256), dim3(256), 0, st, D.d, p.cf, (const int*)D.hit_f.p,
+                       (const double*)D.hit_tbg.p, qb);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(D.pinned_count, qb.count, 4, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    int nr = (int)std::min<unsigned>(D.pinned_count[0], (unsigned)p.cap);
+    if (D.pinned_count[0] > (unsigned)p.cap) {
+        // more root points than the queue holds (a frame of more pixels than the working set under memory
+        // pressure): k_root_points dropped some, and their pixels' cache rows would be stale -- no root cache
+        // in this call, every root runs the full prep (same image, slower)
+        B.pc.use = 0;
+        B.small_use = false;
+        B.rl = RootLit{};
+        nr = 0;
+    }
+    if (nr > 0) {
+        B.pc.build = B.small_use ? 0 : 1;
+        int rc;
+        if ((rc = prep_timer_start(D))) return rc;
+        if (B.small_use)
+            HIP_OK(launch_prep_lane(D.d, o->seed, nr, qb.p, qb.n, qb.cap, qb.pixel, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                    nullptr, dstats, st, B.scache, true));
+        else
+            HIP_OK(launch_prep(B.masks ? 17 : 8, D.d, o->seed, nr, qb.p, qb.n, qb.cap, qb.pixel, nullptr, nullptr, nullptr, nullptr,
+                               nullptr, nullptr, dstats, (unsigned*)D.work.p, st, B.pc, B.masks, p.count_c1, p.fp32, B.corder));
+        float ms = 0;
+        if ((rc = prep_timer_stop(D)) || (rc = prep_timer_ms(D, &ms))) return rc;
+        C.prep_ms += ms;
+        C.cache_ms = ms;
+        C.prep_launches++;
+        C.cache_points = (uint64_t)nr;
+    }
+    B.pc.build = 0;
+    if (B.rl.slot) {  // a fresh set of per-pixel literal sums for this call's cache
+        HIP_OK(hipMemsetAsync(B.rl.slot, 0, 64, st));
+        HIP_OK(hipMemsetAsync(B.rl.slot + 16, 0xff, 4ull * p.npx, st));
+    }
+    return MCPT_OK;
+}
+
+// The wavefront loop over a call's plan and bound buffers.  run() traces samples [a, b) of a set of pixels to the end
+// of their trees and adds them into the framebuffer with weight P.inv_spp; what the per-call setup made (root table,
+// root caches) is keyed by pixel and holds for every run.  A plain render runs once, an adaptive one twice per pass.
+struct WavefrontRun {
+    using RaysFn = void (*)(DScene, Queue, int, Aux, int, unsigned long long*, int, int);
+    using RaysPersistFn = void (*)(DScene, Queue, int, Aux, int, int, unsigned*, unsigned long long*, int);
+
+    const RenderPlan& pl;
+    const Bound& B;
+    Counters& C;
+    DeviceState& D;
+    const mcpt_render_opts* const o;
+    const hipStream_t st;
+    const unsigned* const hctrl;  // slot control words, read back with the queue count
+    Params P;
+    Slots T;     // the reduction's slot pool (grown on demand)
+    int rp = 0;  // ready list being filled
+    // Slicing: an MIS node has up to 2 children (shade / BRDF: 1), so a generation of at most `slice`
+    // nodes always fits its children into nxt.  A larger generation (supercritical trees, e.g. occluded
+    // lights: 2 x RR 0.6 = 1.2 children per node) parks its excess on a spill stack in HBM (grown on
+    // demand) and takes it back, last in first out, before fresh roots -- so deep subtrees drain
+    // first and the stack stays bounded by ~depth x slice.  The image does not depend on the order.
+    int slice, fill;  // fill: refill / pop up to this many nodes per generation
+    RaysFn k_rays;    // the ray sets' traversal: one ray per thread ...
+    RaysPersistFn k_rays_pers;  // ... or the persistent refilling waves (pl.rays_pers)
+    // the run in progress
+    const Queue *cur = nullptr, *nxt = nullptr;
+    Queue qs{};  // the spill stack (D.qs) and the nodes on it
+    long long spill_n = 0;
+    int a = 0, b = 0, nact = 0, nminor = 0;  // samples [a, b) of the pixels active[0, nact) (nullptr: the frame)
+    const int* active = nullptr;
+    long long R = 0, rnext = 0;  // the run's roots, and how many of them have been queued
+#if MCPT_ADAPTIVE_DIAG
+    bool diag_draining = false;
+    std::chrono::steady_clock::time_point diag_t0;
+#endif
+
+    WavefrontRun(const RenderPlan& pl_, const Bound& B_, Counters& C_, DeviceState& D_, const mcpt_render_opts* o_,
+                 double* fb, bool adaptive)
+        : pl(pl_), B(B_), C(C_), D(D_), o(o_), st(D_.stream), hctrl(D_.pinned_count + 16), T(B_.T) {
+        P.S = D.d;
+        P.seed = o->seed;
+        P.inv_spp = adaptive ? 1.0 : 1.0 / o->spp;  // adaptive: raw sums into the half set by accumulate_into
+        P.fb = fb;
+        P.stats = (unsigned long long*)D.stats.p;
+        P.mode = o->mode;
+        P.root_pnw = !pl.ray_roots && pl.fused ? B.rtab.pnw : nullptr;  // BRDF-only: lite root entries (Params::root_pnw)
+        slice = pl.cap / (o->mode == MCPT_MODE_MIS ? 2 : 1);
+        fill = std::min(pl.target, slice);
+        k_rays = pl.grid ? k_mis_rays<true> : pl.count_trav ? k_mis_rays<false, true> : k_mis_rays<false>;
+        k_rays_pers = B.rays_cw8 ? (pl.count_trav ? k_rays_cw8<true> : k_rays_cw8<false>)
+                                 : (pl.count_trav ? k_rays_persistent<true> : k_rays_persistent<false>);
+    }
+
+    // what an adaptive call changes between its runs
+    void accumulate_into(double* fb) { P.fb = fb; }
+    int reset_slot_pool() {  // an empty slot pool, as alloc_slots left it for the first run
+        HIP_OK(hipMemsetAsync(T.ctrl, 0, kCtrlBytes, st));
+        rp = 0;
+        return MCPT_OK;
+    }
+
+    // cur's node count; fails on a queue overflow.  pinned_count: the count at word 0, the overflow flag at 2, the
+    // slot control words from 16
+    int read_count(unsigned* out) {
+        HIP_OK(hipMemcpyAsync(D.pinned_count, cur->count, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(D.pinned_count + 2, (char*)D.stats.p + 32, 8, hipMemcpyDeviceToHost, st));
+        if (pl.stale) HIP_OK(hipMemcpyAsync(D.pinned_count + 16, T.ctrl, kCtrlBytes, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        if (*(unsigned long long*)(D.pinned_count + 2)) {
+            set_error("wavefront queue overflow (capacity %d); raise queue_factor", pl.cap);
+            return MCPT_E_OVERFLOW;
+        }
+        *out = std::min<unsigned>(D.pinned_count[0], (unsigned)pl.cap);
+        return MCPT_OK;
+    }
+
+    int grow_spill(long long need) {
+        if (need <= D.spill_cap && qs.p) return MCPT_OK;
+        if (need > (1ll << 30)) {
+            set_error("spill stack beyond 2^30 nodes");
+            return MCPT_E_DEVICE;
+        }
+        const int ncap = (int)std::min<long long>(std::max<long long>(need, 2ll * D.spill_cap), 1ll << 30);
+        DevBuf nb[14];
+        Queue nq;
+        int r;
+        if ((r = alloc_queue(nb, ncap, nq))) return r;
+        if (spill_n > 0 && qs.p)
+            hipLaunchKernelGGL(k_queue_move, dim3((unsigned)((spill_n + 255) / 256)), dim3(256), 0, st, qs, 0, nq, 0, (int)spill_n);
+        HIP_OK(hipStreamSynchronize(st));
+        for (int k = 0; k < 14; k++) {
+            if (D.qs[k].p) HIP_OK(hipFree(D.qs[k].p));
+            D.qs[k] = nb[k];
+        }
+        D.spill_cap = ncap;
+        qs = nq;
+        return MCPT_OK;
+    }
+
+    // cur holds *n nodes: pushes the children beyond `slice` onto the spill stack, or pops spilled children up to
+    // `fill` before new roots are taken
+    int balance_spill(unsigned* n) {
+        int rc;
+        if (*n > (unsigned)slice) {
+            const int m = (int)*n - slice;
+            if ((rc = grow_spill(spill_n + m))) return rc;
+            hipLaunchKernelGGL(k_queue_move, dim3((m + 255) / 256), dim3(256), 0, st, *cur, slice, qs, (int)spill_n, m);
+            HIP_OK(hipGetLastError());
+            spill_n += m;
+            C.spilled += (uint64_t)m;
+            *n = (unsigned)slice;
+            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)cur->count, (int)*n, 1, st));
+        } else if (spill_n > 0 && *n < (unsigned)fill) {
+            const int m = (int)std::min<long long>((long long)fill - *n, spill_n);
+            spill_n -= m;
+            hipLaunchKernelGGL(k_queue_move, dim3((m + 255) / 256), dim3(256), 0, st, qs, (int)spill_n, *cur, (int)*n, m);
+            HIP_OK(hipGetLastError());
+            *n += (unsigned)m;
+            HIP_OK(hipMemsetD32Async((hipDeviceptr_t)cur->count, (int)*n, 1, st));
+        }
+        return MCPT_OK;
+    }
+
+    // appends the run's next m roots to cur (through node_entry): from the caller's / the jittered rays, or from the
+    // per-pixel root table
+    int refill_roots(int m) {
+        if (pl.ray_roots)
+            hipLaunchKernelGGL(k_roots_rays, dim3((m + 256 * kRayRootsPT - 1) / (256 * kRayRootsPT)), dim3(256), 0, st, P,
+                               pl.cf, pl.rr, nact, a, rnext, m, *cur, std::max(1, nminor), b - a);
+        else
+            hipLaunchKernelGGL(active ? k_roots_t<true> : k_roots_t<false>, dim3((m + 256 * kRootsPT - 1) / (256 * kRootsPT)),
+                               dim3(256), 0, st, P, (const int*)D.hit_f.p, nact, a, rnext, m, *cur, std::max(1, nminor), b - a,
+                               B.rtab, P.root_pnw ? 1 : 0, active);
+        HIP_OK(hipGetLastError());
+        rnext += m;
+        return MCPT_OK;
+    }
+
+    // room in the slot pool for a generation of n nodes: a shard serves at most ceil(blocks / 32) workgroups of 256
+    // nodes per generation
+    int grow_slots(unsigned n) {
+        const unsigned per_shard = ((n + 255) / 256 + kSlotShards - 1) / kSlotShards * 256;
+        unsigned bump = 0;
+        for (int sh = 0; sh < kSlotShards; sh++) bump = std::max(bump, hctrl[16 * sh]);
+        if (bump + per_shard <= (unsigned)T.rcap) return MCPT_OK;
+        const long long nr = std::max<long long>(2ll * T.rcap, (long long)bump + per_shard + 4096);
+        if (nr * kSlotShards > (1ll << 30)) {
+            set_error("MIS reduction slot pool beyond 2^30 slots");
+            return MCPT_E_DEVICE;
+        }
+        return alloc_slots(D.sl, (int)nr, T, st, true, rp, hctrl);
+    }
+
+    // the timed full light prep of cur's nodes [0, n)
+    int full_prep(int n, const PrepCache& cx, uint64_t* masks) {
+        int rc;
+        if ((rc = prep_timer_start(D))) return rc;
+        HIP_OK(launch_prep(-1, D.d, o->seed, n, cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr, cur->wsum,
+                           cur->pick, nullptr, P.stats, (unsigned*)D.work.p, st, cx, masks, pl.count_c1, pl.fp32, B.corder));
+        return prep_timer_stop(D);
+    }
+
+    // cur's roots [nc, nc + nr) pick from their pixels' root-cache rows
+    int pick_cached_roots(int nc, int nr) {
+        if (B.small_use) {
+            hipLaunchKernelGGL(k_prep_lane_pick, dim3((nr + 255) / 256), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
+                               cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr, B.scache);
+        } else {
+            PrepCache pr = B.pc;
+            pr.exact = B.exact_list;
+            pr.exact_off = nc;
+            if (MCPT_PICK_GROUPS && pl.nchunks <= 64) {  // 16 lanes per root
+                const int blocks = std::max(1, std::min((nr + 16 * kPickSlots - 1) / (16 * kPickSlots), 8192));
+                hipLaunchKernelGGL(k_prep_pick_g, dim3(blocks), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
+                                   cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr, pl.nchunks, pr);
+            } else {
+                const int blocks = std::max(1, std::min((nr + 4 * kPickNodes - 1) / (4 * kPickNodes), 8192));
+                hipLaunchKernelGGL(k_prep_pick, dim3(blocks), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
+                                   cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr, pl.nchunks, pr);
+            }
+        }
+        HIP_OK(hipGetLastError());
+        return MCPT_OK;
+    }
+
+    // the band's nodes: the reference's literal prep and pick.  Nodes [0, nmask) have candidate words; nodes
+    // [root_off, ni) are roots with a cached candidate list
+    int exact_band(int nmask, int root_off) {
+        hipLaunchKernelGGL(k_prep_band, dim3(kBandBlocks), dim3(256), 0, st, D.d, B.maybe_list, B.slack, cur->p, cur->cap,
+                           B.masks, nmask, pl.nchunks, B.exact_list, P.stats);
+        // launch ids 2g and 2g + 1 (generation g): the follow-up launch reads what the first one stored
+        const int lid = (int)std::min<uint64_t>(2 * C.gens, 2046);
+        const RootLit& rl = B.rl;
+        const PrepCache& pc = B.pc;
+        int* defer = MCPT_EXACT_DEFER && rl.slot && !(o->flags & MCPT_DEBUG_NO_EXACT_DEFER) ? B.maybe_list
+                                                                                            : nullptr;  // k_prep_band has consumed it
+        if (defer) HIP_OK(hipMemsetAsync(defer, 0, 4, st));
+        hipLaunchKernelGGL(k_prep_exact, dim3(exact_blocks(D.d.NL)), dim3(kExactBlock), 0, st, D.d, o->seed, B.exact_list,
+                           cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr, cur->wsum, cur->pick,
+                           nullptr, P.stats, B.exact_scr, B.masks, nmask, pl.nchunks, pc.use ? pc.lst : nullptr,
+                           pc.use ? pc.info : nullptr, pc.lstride, root_off,
+                           RootLit{rl.slot, rl.pool, rl.cap, rl.stride, lid}, defer);
+        if (defer)  // the deferred roots (counted above already: no stats)
+            hipLaunchKernelGGL(k_prep_exact, dim3(exact_blocks(D.d.NL)), dim3(kExactBlock), 0, st, D.d, o->seed, defer,
+                               cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr, cur->wsum,
+                               cur->pick, nullptr, nullptr, B.exact_scr, B.masks, nmask, pl.nchunks, pc.use ? pc.lst : nullptr,
+                               pc.use ? pc.info : nullptr, pc.lstride, root_off,
+                               RootLit{rl.slot, rl.pool, rl.cap, rl.stride, lid + 1}, nullptr);
+        HIP_OK(hipGetLastError());
+        return MCPT_OK;
+    }
+
+    // the generation's light prep: cur's [0, nc) are children, [nc, ni) fresh roots.  Children (and, without a root
+    // cache, the roots) run the full prep -- *timed: its events are pending --, cached roots pick from their rows,
+    // and the exact pick redoes the ambiguity band
+    int light_prep(int ni, int nc, bool* timed) {
+        int rc;
+        PrepCache cx{};  // the children's full prep: no cache, the picks' slack
+        int nmask = 0;
+        int root_off = INT_MAX;
+        cx.slack = B.slack;
+        cx.maybe = B.maybe_list;
+        if (pl.exact_pick) {
+            HIP_OK(hipMemsetAsync(B.exact_list, 0, 4, st));
+            HIP_OK(hipMemsetAsync(B.maybe_list, 0, 4, st));
+        }
+        if (B.pc.use || B.small_use) {
+            const int nr = ni - nc;
+            if (nc > 0) {
+                // MCPT_DEBUG_FUSED_CULL (A/B): the cheap stages inside k_prep_pk2, wave per node (variant 8)
+                uint64_t* cmasks = (o->flags & MCPT_DEBUG_FUSED_CULL) ? nullptr : B.masks;
+                nmask = prep_writes_masks(D.d, cmasks) ? nc : 0;
+                if ((rc = full_prep(nc, cx, cmasks))) return rc;
+                *timed = true;
+            }
+            // the cached roots are counted here (nr is known): the pick kernels' per-wave atomics on
+            // one statistics word serialised at ~88 per us -- 2.3 of k_prep_lane_pick's 2.5 ms per C5 launch
+            if (nr > 0) {
+                C.cached_roots += (uint64_t)nr;
+                if (!B.small_use) root_off = nc;
+                if ((rc = pick_cached_roots(nc, nr))) return rc;
+            }
+        } else {
+            nmask = prep_writes_masks(D.d, B.masks) ? ni : 0;
+            if ((rc = full_prep(ni, cx, B.masks))) return rc;
+            *timed = true;
+        }
+        C.prep_launches += *timed;
+        return pl.exact_pick ? exact_band(nmask, root_off) : MCPT_OK;
+    }
+
+    // nsets ray sets of cur's ni nodes, from first_set
+    void launch_rays(int ni, int first_set, int nsets, int seeded) {
+        unsigned long long* tcnt = P.stats + 8;  // node visits, triangle tests (MCPT_DEBUG_COUNT_TRAVERSAL)
+        // shade() with uniform-area light points: its shadow and bounce rays run 4% faster on the refilling
+        // persistent waves even on the small stand-in (shade_area 2 104-2 126 -> 2 185-2 191 Msamples/s, same
+        // binary, profiles/round5_ab_persistent_veach.txt); MIS and shade() are slower there (-1%, -1%)
+        if (pl.rays_pers) {
+            unsigned* pool = (unsigned*)D.work.p + 8;
+            (void)hipMemsetAsync(pool, 0, sizeof(unsigned), st);
+            const long long items = (long long)nsets * ni;
+            const int blocks = (int)std::max<long long>(1, std::min<long long>((items + kRayBlock - 1) / kRayBlock, 2048));
+            hipLaunchKernelGGL(k_rays_pers, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, B.aux, first_set, nsets, pool,
+                               tcnt, MCPT_SEED_LIGHT ? seeded : 0);
+        } else {
+            hipLaunchKernelGGL(k_rays, dim3((ni + kRayBlock - 1) / kRayBlock, nsets), dim3(kRayBlock), 0, st, D.d, *cur, ni, B.aux,
+                               first_set, tcnt, MCPT_SEED_LIGHT ? seeded : 0, o->mode == MCPT_MODE_MIS ? 0 : 1);
+        }
+    }
+
+    // one level of the bottom-up reduction
+    void reduce_level() {
+        hipLaunchKernelGGL(k_mis_complete, dim3(32, kSlotShards), dim3(256), 0, st, P, T, rp);
+        hipLaunchKernelGGL(k_slot_fixup, dim3(1), dim3(kSlotShards), 0, st, T, rp);
+        rp ^= 1;
+    }
+
+    // the extension of cur's ni nodes into nxt: gen -> rays -> combine per mode (BRDF-only: one kernel).
+    // trace_seconds: events evr0 / evr1 around the traversal kernel
+    int extend(int ni) {
+        HIP_OK(hipMemsetAsync(nxt->count, 0, 4, st));
+        const dim3 g256((ni + 255) / 256), b256(256);
+        const Aux& aux = B.aux;
+        if (!pl.fused && o->mode == MCPT_MODE_MIS) {
+            hipLaunchKernelGGL(pl.stale ? k_mis_gen<true> : k_mis_gen<false>, g256, b256, 0, st, P, *cur, ni, aux);
+            HIP_OK(hipEventRecord(D.evr0, st));
+            launch_rays(ni, 0, 3, 1);
+            HIP_OK(hipEventRecord(D.evr1, st));
+            hipLaunchKernelGGL(pl.stale ? k_mis_combine<true> : k_mis_combine<false>, g256, b256, 0, st, P, *cur, ni, aux, *nxt,
+                               T, rp);
+            if (pl.stale) reduce_level();  // one level per generation
+        } else if (!pl.fused && (o->mode == MCPT_MODE_SHADE || o->mode == MCPT_MODE_SHADE_AREA)) {
+            hipLaunchKernelGGL(k_shade_gen, g256, b256, 0, st, P, *cur, ni, aux);
+            HIP_OK(hipEventRecord(D.evr0, st));
+            launch_rays(ni, 0, 2, 1);
+            HIP_OK(hipEventRecord(D.evr1, st));
+            hipLaunchKernelGGL(k_shade_combine, g256, b256, 0, st, P, *cur, ni, aux, *nxt);
+        } else if (!pl.fused) {
+            hipLaunchKernelGGL(k_brdf_gen, g256, b256, 0, st, P, *cur, ni, aux);
+            HIP_OK(hipEventRecord(D.evr0, st));
+            launch_rays(ni, 1, 1, 0);
+            HIP_OK(hipEventRecord(D.evr1, st));
+            hipLaunchKernelGGL(k_brdf_combine, g256, b256, 0, st, P, *cur, ni, aux, *nxt);
+        } else {
+            HIP_OK(hipEventRecord(D.evr0, st));
+            hipLaunchKernelGGL(pl.count_trav ? k_extend_brdf<true> : k_extend_brdf<false>, dim3((ni + kBrdfBlock - 1) / kBrdfBlock),
+                               dim3(kBrdfBlock), 0, st, P, *cur, ni, *nxt);
+            HIP_OK(hipEventRecord(D.evr1, st));
+        }
+        HIP_OK(hipGetLastError());
+        return MCPT_OK;
+    }
+
+    // drains the reduction: the trees' remaining levels up to their roots
+    int drain_reduction() {
+        while (pl.stale) {
+            HIP_OK(hipMemcpyAsync(D.pinned_count + 16, T.ctrl, kCtrlBytes, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            unsigned pending = 0;
+            for (int sh = 0; sh < kSlotShards; sh++) pending += hctrl[16 * sh + 4 + rp];
+            if (pending == 0) break;
+            reduce_level();
+        }
+        return MCPT_OK;
+    }
+
+    // samples [a_, b_) of the pixels active_[0, nact_) (nullptr: the frame's nact_ = npx pixels)
+    int run(int a_, int b_, const int* active_, int nact_) {
+        int rc;
+        a = a_, b = b_, active = active_, nact = nact_;
+        R = (long long)(b - a) * nact;
+        nminor = pl.minor_of(b - a);
+        rnext = 0;
+        C.roots_total += (uint64_t)R;
+        cur = &B.qa;
+        nxt = &B.qb;
+        HIP_OK(hipMemsetAsync(cur->count, 0, 4, st));
+        qs = Queue{};
+        spill_n = 0;
+        if (D.spill_cap > 0 && (rc = alloc_queue(D.qs, D.spill_cap, qs))) return rc;  // the stack of an earlier call (empty)
+#if MCPT_ADAPTIVE_DIAG
+        diag_draining = false;
+        diag_t0 = diag_now();
 #endif
         while (true) {
             unsigned n = 0;
@@ -5566,373 +5904,213 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
 #if MCPT_ADAPTIVE_DIAG
             if (rnext >= R && !diag_draining) diag_draining = true, diag_t0 = diag_now();  // the stream is idle here
 #endif
-            if (n > (unsigned)slice) {  // push the excess children onto the spill stack
-                const int m = (int)n - slice;
-                if ((rc = grow_spill(spill_n + m))) return rc;
-                hipLaunchKernelGGL(k_queue_move, dim3((m + 255) / 256), dim3(256), 0, st, *cur, slice, qs, (int)spill_n, m);
-                HIP_OK(hipGetLastError());
-                spill_n += m;
-                spilled += (uint64_t)m;
-                n = (unsigned)slice;
-                HIP_OK(hipMemsetD32Async((hipDeviceptr_t)cur->count, (int)n, 1, st));
-            } else if (spill_n > 0 && n < (unsigned)fill) {  // pop spilled children before new roots
-                const int m = (int)std::min<long long>((long long)fill - n, spill_n);
-                spill_n -= m;
-                hipLaunchKernelGGL(k_queue_move, dim3((m + 255) / 256), dim3(256), 0, st, qs, (int)spill_n, *cur, (int)n, m);
-                HIP_OK(hipGetLastError());
-                n += (unsigned)m;
-                HIP_OK(hipMemsetD32Async((hipDeviceptr_t)cur->count, (int)n, 1, st));
-            }
+            if ((rc = balance_spill(&n))) return rc;
             const unsigned n_children = n;  // [0, n_children) children, [n_children, n) fresh roots
-            if (rnext < R && n < (unsigned)fill) {  // refill with roots (appended through node_entry)
-                const int m = (int)std::min<long long>((long long)fill - n, R - rnext);
-                if (ray_roots)
-                    hipLaunchKernelGGL(k_roots_rays, dim3((m + 256 * kRayRootsPT - 1) / (256 * kRayRootsPT)), dim3(256), 0, st, P,
-                                       cf, rr, nact, a, rnext, m, *cur, std::max(1, nminor), b - a);
-                else
-                    hipLaunchKernelGGL(active ? k_roots_t<true> : k_roots_t<false>,
-                                       dim3((m + 256 * kRootsPT - 1) / (256 * kRootsPT)), dim3(256), 0, st, P,
-                                       (const int*)D.hit_f.p, nact, a, rnext, m, *cur, std::max(1, nminor), b - a, rtab,
-                                       P.root_pnw ? 1 : 0, active);
-                HIP_OK(hipGetLastError());
-                rnext += m;
-                if ((rc = read_count(&n))) return rc;
+            if (rnext < R && n < (unsigned)fill) {
+                if ((rc = refill_roots((int)std::min<long long>((long long)fill - n, R - rnext))) || (rc = read_count(&n))) return rc;
             }
             if (n == 0) {
                 if (rnext >= R && spill_n == 0) break;
                 continue;  // every root of the refill terminated at entry: refill again
             }
-            if (stale) {  // a shard serves at most ceil(blocks / 32) workgroups of 256 nodes per generation
-                const unsigned per_shard = ((n + 255) / 256 + kSlotShards - 1) / kSlotShards * 256;
-                unsigned bump = 0;
-                for (int sh = 0; sh < kSlotShards; sh++) bump = std::max(bump, hctrl[16 * sh]);
-                if (bump + per_shard > (unsigned)T.rcap) {
-                    const long long nr = std::max<long long>(2ll * T.rcap, (long long)bump + per_shard + 4096);
-                    if (nr * kSlotShards > (1ll << 30)) {
-                        set_error("MIS reduction slot pool beyond 2^30 slots");
-                        return MCPT_E_DEVICE;
-                    }
-                    if ((rc = alloc_slots(D.sl, (int)nr, T, st, true, rp, hctrl))) return rc;
-                }
-            }
-            gens++;
-            nodes_total += (uint64_t)n;
-            const int ni = (int)n;
-            // prep_seconds / prep_launches time the full light-prep kernel (k_prep_pk2) launches only
-            bool timed = false;
-            if (needs_prep) {
-                PrepCache cx{};  // the children's full prep: no cache, the picks' slack
-                int nmask = 0;   // nodes [0, nmask) have candidate words (k_prep_exact)
-                int root_off = INT_MAX;  // nodes [root_off, ni) are roots with a cached candidate list
-                cx.slack = slack;
-                cx.maybe = maybe_list;
-                if (exact_pick) {
-                    HIP_OK(hipMemsetAsync(exact_list, 0, 4, st));
-                    HIP_OK(hipMemsetAsync(maybe_list, 0, 4, st));
-                }
-                if (pc.use || small_use) {  // children: full prep; roots: pick from the root-point cache
-                    const int nc = (int)n_children, nr = ni - nc;
-                    if (nc > 0) {
-                        // MCPT_DEBUG_FUSED_CULL (A/B): the cheap stages inside k_prep_pk2, wave per node (variant 8)
-                        uint64_t* cmasks = (o->flags & MCPT_DEBUG_FUSED_CULL) ? nullptr : masks;
-                        nmask = prep_writes_masks(D.d, cmasks) ? nc : 0;
-                        HIP_OK(hipEventRecord(D.evp0, st));
-                        HIP_OK(launch_prep(-1, D.d, o->seed, nc, cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr,
-                                           cur->wsum, cur->pick, nullptr, P.stats, (unsigned*)D.work.p, st, cx, cmasks,
-                                           count_c1, fp32, corder));
-                        HIP_OK(hipEventRecord(D.evp1, st));
-                        timed = true;
-                    }
-                    // the cached roots are counted here (nr is known): the pick kernels' per-wave atomics on
-                    // one statistics word serialised at ~88 per us -- 2.3 of k_prep_lane_pick's 2.5 ms per C5 launch
-                    if (nr > 0) cached_roots += (uint64_t)nr;
-                    if (nr > 0 && small_use) {
-                        hipLaunchKernelGGL(k_prep_lane_pick, dim3((nr + 255) / 256), dim3(256), 0, st, D.d, o->seed, nr,
-                                           cur->pixel + nc, cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc,
-                                           nullptr, scache);
-                        HIP_OK(hipGetLastError());
-                    } else if (nr > 0) {
-                        root_off = nc;
-                        PrepCache pr = pc;
-                        pr.exact = exact_list;
-                        pr.exact_off = nc;
-                        if (MCPT_PICK_GROUPS && nchunks <= 64) {  // 16 lanes per root
-                            const int blocks = std::max(1, std::min((nr + 16 * kPickSlots - 1) / (16 * kPickSlots), 8192));
-                            hipLaunchKernelGGL(k_prep_pick_g, dim3(blocks), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
-                                               cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr,
-                                               nchunks, pr);
-                        } else {
-                            const int blocks = std::max(1, std::min((nr + 4 * kPickNodes - 1) / (4 * kPickNodes), 8192));
-                            hipLaunchKernelGGL(k_prep_pick, dim3(blocks), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
-                                               cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr,
-                                               nchunks, pr);
-                        }
-                        HIP_OK(hipGetLastError());
-                    }
-                } else {
-                    nmask = prep_writes_masks(D.d, masks) ? ni : 0;
-                    HIP_OK(hipEventRecord(D.evp0, st));
-                    HIP_OK(launch_prep(-1, D.d, o->seed, ni, cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr,
-                                       cur->wsum, cur->pick, nullptr, P.stats, (unsigned*)D.work.p, st, cx, masks,
-                                       count_c1, fp32, corder));
-                    HIP_OK(hipEventRecord(D.evp1, st));
-                    timed = true;
-                }
-                prep_launches += timed;
-                if (exact_pick) {  // the band's nodes: the reference's literal prep and pick
-                    hipLaunchKernelGGL(k_prep_band, dim3(kBandBlocks), dim3(256), 0, st, D.d, maybe_list, slack, cur->p, cur->cap,
-                                       masks, nmask, nchunks, exact_list, P.stats);
-                    // launch ids 2g and 2g + 1 (generation g): the follow-up launch reads what the first one stored
-                    const int lid = (int)std::min<uint64_t>(2 * gens, 2046);
-                    int* defer = MCPT_EXACT_DEFER && rl.slot && !(o->flags & MCPT_DEBUG_NO_EXACT_DEFER) ? maybe_list
-                                                                                                        : nullptr;  // k_prep_band has consumed it
-                    if (defer) HIP_OK(hipMemsetAsync(defer, 0, 4, st));
-                    hipLaunchKernelGGL(k_prep_exact, dim3(exact_blocks(D.d.NL)), dim3(kExactBlock), 0, st, D.d, o->seed, exact_list,
-                                       cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr, cur->wsum, cur->pick,
-                                       nullptr, P.stats, exact_scr, masks, nmask, nchunks, pc.use ? pc.lst : nullptr,
-                                       pc.use ? pc.info : nullptr, pc.lstride, root_off,
-                                       RootLit{rl.slot, rl.pool, rl.cap, rl.stride, lid}, defer);
-                    if (defer)  // the deferred roots (counted above already: no stats)
-                        hipLaunchKernelGGL(k_prep_exact, dim3(exact_blocks(D.d.NL)), dim3(kExactBlock), 0, st, D.d, o->seed, defer,
-                                           cur->p, cur->n, cur->cap, cur->pixel, cur->sample, cur->node, nullptr, cur->wsum,
-                                           cur->pick, nullptr, nullptr, exact_scr, masks, nmask, nchunks, pc.use ? pc.lst : nullptr,
-                                           pc.use ? pc.info : nullptr, pc.lstride, root_off,
-                                           RootLit{rl.slot, rl.pool, rl.cap, rl.stride, lid + 1}, nullptr);
-                    HIP_OK(hipGetLastError());
-                }
-            }
-            HIP_OK(hipMemsetAsync(nxt->count, 0, 4, st));
-            const dim3 g256((ni + 255) / 256), b256(256);
-            unsigned long long* tcnt = P.stats + 8;  // node visits, triangle tests (MCPT_DEBUG_COUNT_TRAVERSAL)
-        auto launch_rays = [&](int first_set, int nsets, int seeded) {
-            // shade() with uniform-area light points: its shadow and bounce rays run 4% faster on the refilling
-            // persistent waves even on the small stand-in (shade_area 2 104-2 126 -> 2 185-2 191 Msamples/s, same
-            // binary, profiles/round5_ab_persistent_veach.txt); MIS and shade() are slower there (-1%, -1%)
-            if (rays_pers) {
-                unsigned* pool = (unsigned*)D.work.p + 8;
-                (void)hipMemsetAsync(pool, 0, sizeof(unsigned), st);
-                const long long items = (long long)nsets * ni;
-                const int blocks = (int)std::max<long long>(1, std::min<long long>((items + kRayBlock - 1) / kRayBlock, 2048));
-                if (rays_cw8) {
-                    if (count_trav)
-                        hipLaunchKernelGGL(k_rays_cw8<true>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux, first_set, nsets,
-                                           pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
-                    else
-                        hipLaunchKernelGGL(k_rays_cw8<false>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux, first_set, nsets,
-                                           pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
-                } else if (count_trav)
-                    hipLaunchKernelGGL(k_rays_persistent<true>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux,
-                                       first_set, nsets, pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
-                else
-                    hipLaunchKernelGGL(k_rays_persistent<false>, dim3(blocks), dim3(kRayBlock), 0, st, D.d, *cur, ni, aux,
-                                       first_set, nsets, pool, tcnt, MCPT_SEED_LIGHT ? seeded : 0);
-            } else {
-                hipLaunchKernelGGL(K_MIS_RAYS, dim3((ni + kRayBlock - 1) / kRayBlock, nsets), dim3(kRayBlock), 0, st, D.d,
-                                   *cur, ni, aux, first_set, tcnt, MCPT_SEED_LIGHT ? seeded : 0,
-                                   o->mode == MCPT_MODE_MIS ? 0 : 1);
-            }
-        };
-            // trace_seconds: HIP events around the traversal kernel (k_mis_rays; BRDF-only: k_extend_brdf)
-            if (!fused && o->mode == MCPT_MODE_MIS) {
-                hipLaunchKernelGGL(stale ? k_mis_gen<true> : k_mis_gen<false>, g256, b256, 0, st, P, *cur, ni, aux);
-                HIP_OK(hipEventRecord(D.evr0, st));
-                launch_rays(0, 3, 1);
-                HIP_OK(hipEventRecord(D.evr1, st));
-                hipLaunchKernelGGL(stale ? k_mis_combine<true> : k_mis_combine<false>, g256, b256, 0, st, P, *cur, ni, aux,
-                                   *nxt, T, rp);
-                if (stale) {  // one level of the bottom-up reduction per generation
-                    hipLaunchKernelGGL(k_mis_complete, dim3(32, kSlotShards), dim3(256), 0, st, P, T, rp);
-                    hipLaunchKernelGGL(k_slot_fixup, dim3(1), dim3(kSlotShards), 0, st, T, rp);
-                    rp ^= 1;
-                }
-            } else if (!fused && (o->mode == MCPT_MODE_SHADE || o->mode == MCPT_MODE_SHADE_AREA)) {
-                hipLaunchKernelGGL(k_shade_gen, g256, b256, 0, st, P, *cur, ni, aux);
-                HIP_OK(hipEventRecord(D.evr0, st));
-                launch_rays(0, 2, 1);
-                HIP_OK(hipEventRecord(D.evr1, st));
-                hipLaunchKernelGGL(k_shade_combine, g256, b256, 0, st, P, *cur, ni, aux, *nxt);
-            } else if (!fused) {
-                hipLaunchKernelGGL(k_brdf_gen, g256, b256, 0, st, P, *cur, ni, aux);
-                HIP_OK(hipEventRecord(D.evr0, st));
-                launch_rays(1, 1, 0);
-                HIP_OK(hipEventRecord(D.evr1, st));
-                hipLaunchKernelGGL(k_brdf_combine, g256, b256, 0, st, P, *cur, ni, aux, *nxt);
-            } else {
-                HIP_OK(hipEventRecord(D.evr0, st));
-                hipLaunchKernelGGL(count_trav ? k_extend_brdf<true> : k_extend_brdf<false>, dim3((ni + kBrdfBlock - 1) / kBrdfBlock),
-                                   dim3(kBrdfBlock), 0, st, P, *cur, ni, *nxt);
-                HIP_OK(hipEventRecord(D.evr1, st));
-            }
-            HIP_OK(hipGetLastError());
-            trace_launches++;
+            if (pl.stale && (rc = grow_slots(n))) return rc;
+            C.gens++;
+            C.nodes_total += (uint64_t)n;
+            bool timed = false;  // the full prep's events are pending: collected once the extension is enqueued
+            if (pl.needs_prep && (rc = light_prep((int)n, (int)n_children, &timed))) return rc;
+            if ((rc = extend((int)n))) return rc;
+            C.trace_launches++;
+            float ms = 0;
             if (timed) {
-                float ms = 0;
-                HIP_OK(hipEventSynchronize(D.evp1));
-                HIP_OK(hipEventElapsedTime(&ms, D.evp0, D.evp1));
-                prep_ms += ms;
+                if ((rc = prep_timer_ms(D, &ms))) return rc;
+                C.prep_ms += ms;
             }
-            {
-                float ms = 0;
-                HIP_OK(hipEventSynchronize(D.evr1));
-                HIP_OK(hipEventElapsedTime(&ms, D.evr0, D.evr1));
-                trace_ms += ms;
-            }
+            HIP_OK(hipEventSynchronize(D.evr1));
+            HIP_OK(hipEventElapsedTime(&ms, D.evr0, D.evr1));
+            C.trace_ms += ms;
             std::swap(cur, nxt);
             // (an adaptive call reports the samples of all its runs so far against the cap's total)
-            if (o->progress && o->progress(o->progress_user, roots_total - (uint64_t)(R - rnext), (uint64_t)(s1 - s0) * npx)) {
+            if (o->progress &&
+                o->progress(o->progress_user, C.roots_total - (uint64_t)(R - rnext), (uint64_t)(pl.s1 - pl.s0) * pl.npx)) {
                 HIP_OK(hipStreamSynchronize(st));
                 set_error("render cancelled by the progress callback after %lld of %lld camera samples", rnext, R);
                 return MCPT_E_CANCELLED;
             }
         }
-        while (stale) {  // drain the reduction: the trees' remaining levels up to their roots
-            HIP_OK(hipMemcpyAsync(D.pinned_count + 16, T.ctrl, kCtrlBytes, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            unsigned pending = 0;
-            for (int sh = 0; sh < kSlotShards; sh++) pending += hctrl[16 * sh + 4 + rp];
-            if (pending == 0) break;
-            hipLaunchKernelGGL(k_mis_complete, dim3(32, kSlotShards), dim3(256), 0, st, P, T, rp);
-            hipLaunchKernelGGL(k_slot_fixup, dim3(1), dim3(kSlotShards), 0, st, T, rp);
-            rp ^= 1;
-        }
+        if ((rc = drain_reduction())) return rc;
 #if MCPT_ADAPTIVE_DIAG
         HIP_OK(hipStreamSynchronize(st));
-        diag_runs++;
-        if (diag_draining) diag_drain_ms += diag_ms(diag_t0, diag_now());
+        C.diag_runs++;
+        if (diag_draining) C.diag_drain_ms += diag_ms(diag_t0, diag_now());
 #endif
         return MCPT_OK;
-    };
-    if (!ad) {
-        if ((rc = wavefront(s0, s1, nullptr, npx))) return rc;
-    } else {
-        // Adaptive passes (include/mcpt.h, mcpt_adaptive_opts): pass 0 renders samples [0, min_spp) of every
-        // pixel, each later pass the next pass_spp (cut at the cap) of the active pixels; the first half of a
-        // pass adds into A, the second into B.  After a pass k_adaptive_error rates the active pixels and
-        // k_adaptive_mark / k_adaptive_compact build the next ascending list.
-        const mcpt_adaptive_opts& ao = ad->a;
-        double* acc[2] = {(double*)D.ad_acc[0].p, (double*)D.ad_acc[1].p};
-        int* count = ad->count ? ad->count : (int*)D.ad_count.p;
-        double* noise = ad->noise ? ad->noise : (double*)D.ad_noise.p;
-        unsigned* blk = (unsigned*)D.ad_blk.p;
-        HIP_OK(hipMemsetAsync(acc[0], 0, 24ull * npx, st));
-        HIP_OK(hipMemsetAsync(acc[1], 0, 24ull * npx, st));
-        const int* active = nullptr;  // pass 0: the whole frame
-        int nact = npx, n = 0, li = 0;
-        D.ad_last_list = -1, D.ad_last_n = 0;
-        for (int pass = 0; nact > 0 && n < ao.max_spp; pass++) {
-            const int pa = n, pb = std::min(n + (pass == 0 ? ao.min_spp : ao.pass_spp), ao.max_spp), ph = pa + (pb - pa) / 2;
-            const int cut[3] = {pa, ph, pb};
-            for (int half = 0; half < 2; half++) {
-                if (cut[half + 1] == cut[half]) continue;  // a one-sample last pass: all of it in B
-                if (stale && (pass > 0 || half > 0)) {  // an empty slot pool, as alloc_slots left it for the first run
-                    HIP_OK(hipMemsetAsync(T.ctrl, 0, kCtrlBytes, st));
-                    rp = 0;
-                }
-                P.fb = acc[half];
-                if ((rc = wavefront(cut[half], cut[half + 1], active, nact))) return rc;
-            }
-            n = pb;
-            unsigned char* state = (unsigned char*)D.ad_state[li].p;
-#if MCPT_ADAPTIVE_DIAG
-            const auto diag_k0 = diag_now();  // the stream is idle (the run's last read_count)
-#endif
-            hipLaunchKernelGGL(k_adaptive_error, dim3((nact + 255) / 256), dim3(256), 0, st, active, nact, acc[0], acc[1], n,
-                               ao.threshold, noise, count, state);
-            HIP_OK(hipGetLastError());
-#if MCPT_ADAPTIVE_DIAG
-            if (n >= ao.max_spp) {
-                HIP_OK(hipStreamSynchronize(st));
-                diag_kernel_ms += diag_ms(diag_k0, diag_now());
-            }
-#endif
-            if (n >= ao.max_spp) break;
-            unsigned char* state_next = (unsigned char*)D.ad_state[li ^ 1].p;
-            int* list = (int*)D.ad_list[li].p;  // not the list this pass read (ad_list[li ^ 1], or none)
-            hipLaunchKernelGGL(k_adaptive_mark, dim3(nblk), dim3(256), 0, st, state, state_next, W, H, ao.radius, blk);
-            hipLaunchKernelGGL(k_adaptive_compact, dim3(nblk), dim3(256), 0, st, state_next, npx, blk, list, blk + nblk);
-            HIP_OK(hipGetLastError());
-            HIP_OK(hipMemcpyAsync(D.pinned_count, blk + nblk, 4, hipMemcpyDeviceToHost, st));
-            HIP_OK(hipStreamSynchronize(st));
-            nact = (int)std::min<unsigned>(D.pinned_count[0], (unsigned)npx);
-#if MCPT_ADAPTIVE_DIAG
-            diag_kernel_ms += diag_ms(diag_k0, diag_now());
-#endif
-            active = list;
-            D.ad_last_list = li, D.ad_last_n = nact;
-            li ^= 1;
+    }
+};
+
+// Adaptive passes (include/mcpt.h, mcpt_adaptive_opts): pass 0 renders samples [0, min_spp) of every
+// pixel, each later pass the next pass_spp (cut at the cap) of the active pixels; the first half of a
+// pass adds into A, the second into B.  After a pass k_adaptive_error rates the active pixels and
+// k_adaptive_mark / k_adaptive_compact build the next ascending list.  The mean goes into dfb at the end.
+int run_adaptive(WavefrontRun& wf, const AdaptiveRun& ad, double* dfb) {
+    DeviceState& D = wf.D;
+    const hipStream_t st = wf.st;
+    const int W = wf.pl.W, H = wf.pl.H, npx = wf.pl.npx, nblk = wf.B.nblk;
+    const mcpt_adaptive_opts& ao = ad.a;
+    int rc;
+    double* acc[2] = {(double*)D.ad_acc[0].p, (double*)D.ad_acc[1].p};
+    int* count = ad.count ? ad.count : (int*)D.ad_count.p;
+    double* noise = ad.noise ? ad.noise : (double*)D.ad_noise.p;
+    unsigned* blk = (unsigned*)D.ad_blk.p;
+    HIP_OK(hipMemsetAsync(acc[0], 0, 24ull * npx, st));
+    HIP_OK(hipMemsetAsync(acc[1], 0, 24ull * npx, st));
+    const int* active = nullptr;  // pass 0: the whole frame
+    int nact = npx, n = 0, li = 0;
+    D.ad_last_list = -1, D.ad_last_n = 0;
+    for (int pass = 0; nact > 0 && n < ao.max_spp; pass++) {
+        const int pa = n, pb = std::min(n + (pass == 0 ? ao.min_spp : ao.pass_spp), ao.max_spp), ph = pa + (pb - pa) / 2;
+        const int cut[3] = {pa, ph, pb};
+        for (int half = 0; half < 2; half++) {
+            if (cut[half + 1] == cut[half]) continue;  // a one-sample last pass: all of it in B
+            if (wf.pl.stale && (pass > 0 || half > 0) && (rc = wf.reset_slot_pool())) return rc;
+            wf.accumulate_into(acc[half]);
+            if ((rc = wf.run(cut[half], cut[half + 1], active, nact))) return rc;
         }
+        n = pb;
+        unsigned char* state = (unsigned char*)D.ad_state[li].p;
 #if MCPT_ADAPTIVE_DIAG
-        const auto diag_f0 = diag_now();
+        const auto diag_k0 = diag_now();  // the stream is idle (the run's last read_count)
 #endif
-        hipLaunchKernelGGL(k_adaptive_finalize, dim3((3 * npx + 255) / 256), dim3(256), 0, st, dfb, acc[0], acc[1], count, npx);
+        hipLaunchKernelGGL(k_adaptive_error, dim3((nact + 255) / 256), dim3(256), 0, st, active, nact, acc[0], acc[1], n,
+                           ao.threshold, noise, count, state);
         HIP_OK(hipGetLastError());
 #if MCPT_ADAPTIVE_DIAG
-        HIP_OK(hipStreamSynchronize(st));
-        diag_kernel_ms += diag_ms(diag_f0, diag_now());
+        if (n >= ao.max_spp) {
+            HIP_OK(hipStreamSynchronize(st));
+            wf.C.diag_kernel_ms += diag_ms(diag_k0, diag_now());
+        }
 #endif
+        if (n >= ao.max_spp) break;
+        unsigned char* state_next = (unsigned char*)D.ad_state[li ^ 1].p;
+        int* list = (int*)D.ad_list[li].p;  // not the list this pass read (ad_list[li ^ 1], or none)
+        hipLaunchKernelGGL(k_adaptive_mark, dim3(nblk), dim3(256), 0, st, state, state_next, W, H, ao.radius, blk);
+        hipLaunchKernelGGL(k_adaptive_compact, dim3(nblk), dim3(256), 0, st, state_next, npx, blk, list, blk + nblk);
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipMemcpyAsync(D.pinned_count, blk + nblk, 4, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+        nact = (int)std::min<unsigned>(D.pinned_count[0], (unsigned)npx);
+#if MCPT_ADAPTIVE_DIAG
+        wf.C.diag_kernel_ms += diag_ms(diag_k0, diag_now());
+#endif
+        active = list;
+        D.ad_last_list = li, D.ad_last_n = nact;
+        li ^= 1;
     }
+#if MCPT_ADAPTIVE_DIAG
+    const auto diag_f0 = diag_now();
+#endif
+    hipLaunchKernelGGL(k_adaptive_finalize, dim3((3 * npx + 255) / 256), dim3(256), 0, st, dfb, acc[0], acc[1], count, npx);
+    HIP_OK(hipGetLastError());
+#if MCPT_ADAPTIVE_DIAG
+    HIP_OK(hipStreamSynchronize(st));
+    wf.C.diag_kernel_ms += diag_ms(diag_f0, diag_now());
+#endif
+    return MCPT_OK;
+}
+
+// a finished call's statistics: the device's counters and the driver's totals; ms: the call's timed region
+int fill_stats(const RenderPlan& p, const Bound& B, DeviceState& D, const Counters& C, float ms, mcpt_stats* stats) {
+    unsigned long long hs[kStatBytes / 8] = {0};
+    HIP_OK(hipMemcpy(hs, D.stats.p, kStatBytes, hipMemcpyDeviceToHost));
+    for (int k = 1; k <= kStatShards; k++) hs[2] += hs[16 * k], hs[3] += hs[16 * k + 1];  // ray_stats shards
+    stats->seconds = ms * 1e-3;
+    stats->device_seconds[0] = stats->seconds;
+    stats->camera_samples = C.roots_total;  // plain: (s1 - s0) * npx; adaptive: the sum of the count map
+    stats->light_evals_survived = hs[1];
+    stats->rays = hs[2];
+    stats->light_rays = hs[3];
+    stats->generations = C.gens;
+    stats->shading_nodes = C.nodes_total;
+
+    // k_prep_pk2 counts its full-prep nodes (hs[7]) and k_prep_pick the cached roots (hs[0]);
+    // k_prep / k_prep_lane (huge / tiny light sets) run every node in full
+    const uint64_t full = hs[7] ? hs[7] : (p.needs_prep ? C.nodes_total : 0);
+    stats->prep_full_nodes = full;
+    stats->prep_cached_nodes = hs[0] + C.cached_roots;
+    stats->prep_cache_points = C.cache_points;
+    stats->light_evals_total = full * (uint64_t)D.d.NL;
+    stats->light_evals_culled_backface = p.count_c1 ? hs[6] : 0;
+    stats->light_evals_candidates = hs[5];
+    stats->light_evals_culled_plane = stats->light_evals_total - hs[5] - stats->light_evals_culled_backface;
+    stats->spilled_nodes = C.spilled;
+    stats->trace_seconds = C.trace_ms * 1e-3;
+    stats->trace_launches = C.trace_launches;
+    stats->node_visits = hs[8];
+    stats->tri_tests = hs[9];
+    stats->reduce_seconds = 0;
+    stats->devices_used = 1;
+    stats->prep_seconds = C.prep_ms * 1e-3;
+    stats->prep_launches = C.prep_launches;
+    stats->prep_exact_nodes = hs[10];
+    stats->prep_band_nodes = hs[11];
+#if MCPT_TRACE_DIAG
+    if (hs[8])
+        fprintf(stderr, "trace diag: %llu visits over %llu wave node-iterations (lane use %.3f), %llu tests over %llu wave "
+                        "leaf-iterations (lane use %.3f)\n", hs[8], hs[14], hs[8] / (64.0 * std::max<unsigned long long>(hs[14], 1)),
+                hs[9], hs[15], hs[9] / (64.0 * std::max<unsigned long long>(hs[15], 1)));
+#endif
+#if MCPT_BAND_DIAG
+    fprintf(stderr, "exact diag (10 ns ticks summed over nodes): lists %llu literal %llu lists+literal+sum %llu pick %llu\n",
+            hs[12], hs[13], hs[14], hs[15]);
+    if (B.exact_scr) {
+        const int nlp = (D.d.NL + 63) & ~63;
+        std::vector<int> pc(p.npx);
+        HIP_OK(hipMemcpy(pc.data(), reinterpret_cast<int*>(B.exact_scr + (size_t)exact_waves(D.d.NL) * nlp * 3 / 2),
+                         4ull * p.npx, hipMemcpyDeviceToHost));
+        long long tot = 0, distinct = 0, mx = 0;
+        for (int v : pc) tot += v, distinct += v > 0, mx = std::max<long long>(mx, v);
+        fprintf(stderr, "exact diag: roots %lld over %lld pixels (max %lld per pixel)\n", tot, distinct, mx);
+    }
+#endif
+    stats->cache_build_seconds = C.cache_ms * 1e-3;
+    return MCPT_OK;
+}
+
+// The wavefront render into a device framebuffer already resident on D's device: plan the call, bind its buffers,
+// then, inside the timed region (seconds, HIP events), make the per-pixel tables and the root caches, run the
+// wavefront loop -- once over [s0, s1) for a plain render, twice per pass for an adaptive one (ad != nullptr: o->spp
+// is the cap, the statistics are summed over the passes) -- and report.  With roots from rays (make_plan) the
+// per-pixel setup (primary hits, root table, root caches, RootLit pool) is skipped.
+int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt_render_opts* o,
+                     double* dfb, mcpt_stats* stats, const AdaptiveRun* ad = nullptr, const RayRoots* rays = nullptr) {
+    RenderPlan pl;
+    Bound B;
+    Counters C;
+    int rc;
+    if ((rc = make_plan(sc, D, cam, o, ad != nullptr, rays, &pl)) || (rc = bind_buffers(sc, D, pl, o, ad != nullptr, &B)))
+        return rc;
+    const hipStream_t st = D.stream;
+    HIP_OK(hipMemsetAsync(D.stats.p, 0, kStatBytes, st));
+    HIP_OK(hipEventRecord(D.ev0, st));
+    if (!pl.ray_roots && (rc = launch_primary_tables(D, pl.cf, pl.npx, pl.grid))) return rc;
+    if ((rc = build_root_caches(pl, B, D, o, C))) return rc;
+    WavefrontRun wf(pl, B, C, D, o, dfb, ad != nullptr);
+    if ((rc = ad ? run_adaptive(wf, *ad, dfb) : wf.run(pl.s0, pl.s1, nullptr, pl.npx))) return rc;
     HIP_OK(hipEventRecord(D.ev1, st));
     HIP_OK(hipEventSynchronize(D.ev1));
     float ms = 0;
     HIP_OK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
 #if MCPT_ADAPTIVE_DIAG
-    fprintf(stderr, "adaptive diag: runs %d drain_ms %.3f adaptive_kernels_ms %.3f total_ms %.3f\n", diag_runs, diag_drain_ms,
-            diag_kernel_ms, (double)ms);
+    fprintf(stderr, "adaptive diag: runs %d drain_ms %.3f adaptive_kernels_ms %.3f total_ms %.3f\n", C.diag_runs, C.diag_drain_ms,
+            C.diag_kernel_ms, (double)ms);
 #endif
-    if (stats) {
-        unsigned long long hs[kStatBytes / 8] = {0};
-        HIP_OK(hipMemcpy(hs, D.stats.p, kStatBytes, hipMemcpyDeviceToHost));
-        for (int k = 1; k <= kStatShards; k++) hs[2] += hs[16 * k], hs[3] += hs[16 * k + 1];  // ray_stats shards
-        stats->seconds = ms * 1e-3;
-        stats->device_seconds[0] = stats->seconds;
-        stats->camera_samples = roots_total;  // plain: (s1 - s0) * npx; adaptive: the sum of the count map
-        stats->light_evals_survived = hs[1];
-        stats->rays = hs[2];
-        stats->light_rays = hs[3];
-        stats->generations = gens;
-        stats->shading_nodes = nodes_total;
+    return stats ? fill_stats(pl, B, D, C, ms, stats) : MCPT_OK;
+}
 
-        // k_prep_pk2 counts its full-prep nodes (hs[7]) and k_prep_pick the cached roots (hs[0]);
-        // k_prep / k_prep_lane (huge / tiny light sets) run every node in full
-        const uint64_t full = hs[7] ? hs[7] : (needs_prep ? nodes_total : 0);
-        stats->prep_full_nodes = full;
-        stats->prep_cached_nodes = hs[0] + cached_roots;
-        stats->prep_cache_points = cache_points;
-        stats->light_evals_total = full * (uint64_t)D.d.NL;
-        stats->light_evals_culled_backface = count_c1 ? hs[6] : 0;
-        stats->light_evals_candidates = hs[5];
-        stats->light_evals_culled_plane = stats->light_evals_total - hs[5] - stats->light_evals_culled_backface;
-        stats->spilled_nodes = spilled;
-        stats->trace_seconds = trace_ms * 1e-3;
-        stats->trace_launches = trace_launches;
-        stats->node_visits = hs[8];
-        stats->tri_tests = hs[9];
-        stats->reduce_seconds = 0;
-        stats->devices_used = 1;
-        stats->prep_seconds = prep_ms * 1e-3;
-        stats->prep_launches = prep_launches;
-        stats->prep_exact_nodes = hs[10];
-        stats->prep_band_nodes = hs[11];
-#if MCPT_TRACE_DIAG
-        if (hs[8])
-            fprintf(stderr, "trace diag: %llu visits over %llu wave node-iterations (lane use %.3f), %llu tests over %llu wave "
-                            "leaf-iterations (lane use %.3f)\n", hs[8], hs[14], hs[8] / (64.0 * std::max<unsigned long long>(hs[14], 1)),
-                    hs[9], hs[15], hs[9] / (64.0 * std::max<unsigned long long>(hs[15], 1)));
-#endif
-#if MCPT_BAND_DIAG
-        fprintf(stderr, "exact diag (10 ns ticks summed over nodes): lists %llu literal %llu lists+literal+sum %llu pick %llu\n",
-                hs[12], hs[13], hs[14], hs[15]);
-        if (exact_scr) {
-            const int nlp = (D.d.NL + 63) & ~63;
-            std::vector<int> pc(npx);
-            HIP_OK(hipMemcpy(pc.data(), reinterpret_cast<int*>(exact_scr + (size_t)exact_waves(D.d.NL) * nlp * 3 / 2),
-                             4ull * npx, hipMemcpyDeviceToHost));
-            long long tot = 0, distinct = 0, mx = 0;
-            for (int v : pc) tot += v, distinct += v > 0, mx = std::max<long long>(mx, v);
-            fprintf(stderr, "exact diag: roots %lld over %lld pixels (max %lld per pixel)\n", tot, distinct, mx);
-        }
-#endif
-        stats->cache_build_seconds = cache_ms * 1e-3;
+// the entry points that take one device only (`what` names the entry point in the message)
+int check_single_device(const mcpt_render_opts* o, const char* what) {
+    if (o->struct_size == sizeof(mcpt_render_opts) && (o->num_devices > 0 || o->comm)) {
+        set_error("%s is single-device: a device list or a communicator is not supported", what);
+        return MCPT_E_INVALID;
     }
     return MCPT_OK;
 }
@@ -5978,13 +6156,6 @@ int check_device_buffer(const void* p, int device, const char* name = "dev_out_r
         return MCPT_E_INVALID;
     }
     return MCPT_OK;
-}
-
-// [s0, s1) of the whole job (0,0 = [0, spp))
-void job_range(const mcpt_render_opts* o, int* s0, int* s1) {
-    const bool all = o->sample_begin == 0 && o->sample_end == 0;
-    *s0 = all ? 0 : o->sample_begin;
-    *s1 = all ? o->spp : o->sample_end;
 }
 
 // shard k of n of [s0, s1): contiguous and balanced (sizes differ by at most one sample)
@@ -6673,12 +6844,8 @@ static int check_render_rays(mcpt_scene* sc, const mcpt_render_opts* o, int32_t 
         set_error("mcpt_render_rays: null argument: %s", !sc ? "scene" : !o ? "opts" : !origin ? "origin" : !dir ? "dir" : "out_rgb");
         return MCPT_E_INVALID;
     }
-    if (o->struct_size == sizeof(mcpt_render_opts) && (o->num_devices > 0 || o->comm)) {
-        set_error("mcpt_render_rays is single-device: a device list or a communicator is not supported");
-        return MCPT_E_INVALID;
-    }
     int rc;
-    if ((rc = check_opts(o))) return rc;
+    if ((rc = check_single_device(o, "mcpt_render_rays")) || (rc = check_opts(o))) return rc;
     if (n < 1) {
         set_error("mcpt_render_rays: n = %d rays (must be >= 1)", n);
         return MCPT_E_INVALID;
@@ -6792,12 +6959,8 @@ static int check_adaptive(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_ren
         set_error("null argument");
         return MCPT_E_INVALID;
     }
-    if (base->struct_size == sizeof(mcpt_render_opts) && (base->num_devices > 0 || base->comm)) {
-        set_error("adaptive render is single-device: a device list or a communicator is not supported");
-        return MCPT_E_INVALID;
-    }
     int rc;
-    if ((rc = check_opts(base)) || (rc = validate_camera(cam))) return rc;
+    if ((rc = check_single_device(base, "adaptive render")) || (rc = check_opts(base)) || (rc = validate_camera(cam))) return rc;
     if (base->flags & MCPT_RENDER_PIXEL_JITTER) {
         set_error("adaptive render: MCPT_RENDER_PIXEL_JITTER is not supported (the passes' roots come from the per-pixel tables)");
         return MCPT_E_INVALID;
@@ -6870,7 +7033,7 @@ int mcpt_render_adaptive(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_rend
     return MCPT_OK;
 }
 
-// mcpt_render_aovs / _device: the per-call setup of a render (k_primary, k_root_table) and k_aovs.  host: the
+// mcpt_render_aovs / _device: a render's per-pixel tables (bind / launch_primary_tables) and k_aovs.  host: the
 // maps go through D.aov and are copied out; else `out` holds device pointers and k_aovs writes them directly.
 static int render_aovs_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o, const mcpt_aov_buffers* out,
                             bool host) {
@@ -6878,12 +7041,8 @@ static int render_aovs_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_r
         set_error("null argument");
         return MCPT_E_INVALID;
     }
-    if (o->struct_size == sizeof(mcpt_render_opts) && (o->num_devices > 0 || o->comm)) {
-        set_error("mcpt_render_aovs is single-device: a device list or a communicator is not supported");
-        return MCPT_E_INVALID;
-    }
     int rc;
-    if ((rc = check_opts(o)) || (rc = validate_camera(cam))) return rc;
+    if ((rc = check_single_device(o, "mcpt_render_aovs")) || (rc = check_opts(o)) || (rc = validate_camera(cam))) return rc;
     if (o->accel != MCPT_ACCEL_BVH && o->accel != MCPT_ACCEL_GRID) {
         set_error("invalid accel %d", o->accel);
         return MCPT_E_INVALID;
@@ -6898,9 +7057,7 @@ static int render_aovs_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_r
         const double eye[3] = {cf.eye.x, cf.eye.y, cf.eye.z};
         if ((rc = use_grid(sc, *D, eye, 100000))) return rc;
     }
-    if ((rc = ensure(D->hit_f, 4 * npx)) || (rc = ensure(D->hit_tbg, 24 * npx)) || (rc = ensure(D->root_pnw, 72 * npx)) ||
-        (rc = ensure(D->root_kind, 4 * npx)))
-        return rc;
+    if ((rc = bind_primary_tables(*D, npx))) return rc;
     mcpt_aov_buffers dev = *out;
     if (host) {
         if ((rc = ensure(D->aov, 80 * npx))) return rc;
@@ -6918,12 +7075,7 @@ static int render_aovs_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_r
     }
     const hipStream_t st = D->stream;
     const int n = (int)npx;
-    hipLaunchKernelGGL(grid ? k_primary<true> : k_primary<false>, dim3((n + kTraceBlock - 1) / kTraceBlock), dim3(kTraceBlock),
-                       0, st, D->d, cf, (int*)D->hit_f.p, (double*)D->hit_tbg.p);
-    HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(k_root_table, dim3((n + 255) / 256), dim3(256), 0, st, D->d, cf, (const int*)D->hit_f.p,
-                       (const double*)D->hit_tbg.p, RootTab{(double*)D->root_pnw.p, (int*)D->root_kind.p});
-    HIP_OK(hipGetLastError());
+    if ((rc = launch_primary_tables(*D, cf, n, grid))) return rc;
     hipLaunchKernelGGL(k_aovs, dim3((n + 255) / 256), dim3(256), 0, st, D->d, cf, (const int*)D->hit_f.p,
                        (const double*)D->root_pnw.p, dev);
     HIP_OK(hipGetLastError());
