@@ -35,7 +35,9 @@ extern "C" {
                                * mcpt_sequence_info, the mcpt_sequence_* functions, mcpt_tone_map_device and
                                * mcpt_frame_stats_device); radiance along caller-supplied rays and pixel jitter
                                * (mcpt_render_rays and its _device form, mcpt_camera_rays, the flag
-                               * MCPT_RENDER_PIXEL_JITTER);
+                               * MCPT_RENDER_PIXEL_JITTER); guided upsampling (mcpt_upsample_opts, mcpt_upsample and its
+                               * _device form, mcpt_camera_scaled, mcpt_sequence_create_upsampled,
+                               * mcpt_sequence_upsample_info, the selector MCPT_SEQ_UPSAMPLED);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -546,6 +548,56 @@ int mcpt_temporal_accumulate_clamped_device(const mcpt_temporal_opts* opts, cons
                                             double* dev_out_color, double* dev_out_moments, double* dev_out_fast,
                                             double* dev_out_variance, double* dev_out_shift, double* device_seconds);
 
+/* Guided upsampling (joint bilateral upsampling, Kopf et al. 2007; no counterpart in the reference): trace at 1 / f of
+ * the shown size and reconstruct the full-size frame from the low-size radiance and full-size guides.  A camera's
+ * extent does not depend on its pixel count (pixellen = tan(fovy/360) |w| / (height / 2) and a row's offset is
+ * pixellen (i - (H - 1) / 2)), so the camera with f times the rows and columns (mcpt_camera_scaled) covers the same
+ * image plane: low-size pixel I spans the full-size rows f I .. f I + f - 1, its centre at full-size row
+ * f I + (f - 1) / 2.  Inputs: the low-size colour C (h*w*3), the low-size guides g (normal N, position X, albedo rho,
+ * depth) at h x w, the full-size guides G at (f h) x (f w), the integer factor f.  All arithmetic is fp64, with no
+ * contraction.  For each full-size pixel p = (i, j):
+ *   source   y = (i - (f - 1) / 2.0) / f, x = (j - (f - 1) / 2.0) / f; i0 = floor(y), j0 = floor(x), fy = y - i0,
+ *            fx = x - j0
+ *   taps     q = (i0 + di, j0 + dj) for (di, dj) = (0, 0), (0, 1), (1, 0), (1, 1) in this order; taps outside the low
+ *            frame are skipped; b_q = (di ? fy : 1 - fy) * (dj ? fx : 1 - fx)
+ *   weight   w_q = b_q * geo(p, q), geo the denoiser's (mcpt_denoise above) with the centre taken from G at p (so the
+ *            plane term uses sigma_plane * depth_p of G) and the tap from g at q: w_n w_x w_a when both hit, 1 when
+ *            both miss, 0 when exactly one hits
+ *   result   Wsum = sum of w_q; if Wsum >= min_weight, out(p) = (sum of w_q C(q)) / Wsum; otherwise the fallback
+ *            out(p) = C(i / f, j / f) (integer division: the low pixel that contains p), and p counts as a fallback
+ *            pixel
+ * out ((f h)*(f w)*3) is overwritten, not added to.  The fallback count is an integer reduced with integer atomics:
+ * exact, and the same on every run.  The albedo is not demodulated, the variance is not upsampled, f is an integer and
+ * nothing is searched beyond the four taps.  Single device. */
+typedef struct {
+    uint32_t struct_size;  /* sizeof(mcpt_upsample_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
+    int32_t factor;        /* default 2, 2..4: the full frame is factor times the low one along each axis */
+    double sigma_normal;   /* default 128 */
+    double sigma_plane;    /* default 0.01    geo(p, q), as in mcpt_denoise_opts */
+    double sigma_albedo;   /* default 0.1 */
+    double min_weight;     /* default 1e-4, finite and in (0, 1]: below this sum of weights a pixel takes the fallback */
+    int32_t device;        /* HIP device ordinal (-1 = current) */
+} mcpt_upsample_opts;
+/* zero-fills *opts and sets struct_size and the defaults above (device = -1) */
+void mcpt_upsample_opts_init(mcpt_upsample_opts* opts);
+/* Host arrays in, host arrays out.  width and height are the LOW size; color and guides hold height*width pixels,
+ * full_guides and out (factor*height)*(factor*width).  All four arrays of both guide sets are required.
+ * fallback_count (the number of fallback pixels) and device_seconds (device time of the kernel, HIP events) may be
+ * NULL.  Refused with MCPT_E_INVALID before any device work: a struct_size mismatch, factor outside 2..4, a sigma that
+ * is not finite or not > 0, a min_weight that is not finite or outside (0, 1], width or height < 1 or a full frame of
+ * more than 2^28 pixels, a NULL colour or output array, a NULL array in either guide set, out aliasing an input. */
+int mcpt_upsample(const mcpt_upsample_opts* opts, int32_t width, int32_t height, const double* color,
+                  const mcpt_aov_buffers* guides, const mcpt_aov_buffers* full_guides, double* out,
+                  uint64_t* fallback_count, double* device_seconds);
+/* same with every array in DEVICE memory on opts->device (fallback_count and device_seconds stay host pointers) */
+int mcpt_upsample_device(const mcpt_upsample_opts* opts, int32_t width, int32_t height, const double* dev_color,
+                         const mcpt_aov_buffers* dev_guides, const mcpt_aov_buffers* dev_full_guides, double* dev_out,
+                         uint64_t* fallback_count, double* device_seconds);
+/* Host helper: *out = *in with width * factor and height * factor -- the one definition of "the full-size camera of a
+ * low-size camera".  MCPT_E_INVALID for a NULL pointer, factor < 1, a width or height < 1 or a product beyond 32 bits.
+ * in and out may be the same struct. */
+int mcpt_camera_scaled(const mcpt_camera* in, int32_t factor, mcpt_camera* out);
+
 /* Host helper: *out = *in with eye rotated by `degrees` about the axis through lookat along k = up / |up|
  * (Rodrigues, right-handed): with v = eye - lookat, t = degrees * pi / 180 and vp = v - k (k . v),
  * eye' = eye + (k x v) sin t - vp (1 - cos t); 0 degrees returns eye bit for bit.  MCPT_E_INVALID for a NULL
@@ -657,6 +709,9 @@ int mcpt_sequence_frame(mcpt_sequence* seq, const mcpt_camera* cam, uint64_t see
  * only) */
 enum { MCPT_SEQ_RAW = 0, MCPT_SEQ_ACCUMULATED = 1, MCPT_SEQ_MOMENTS = 2, MCPT_SEQ_VARIANCE = 3, MCPT_SEQ_FILTERED = 4,
        MCPT_SEQ_FAST = 5, MCPT_SEQ_SHIFT = 6, MCPT_SEQ_RGB8 = 7 };
+/* a sequence created by mcpt_sequence_create_upsampled only: UPSAMPLED the shown full-size frame ((f h)*(f w)*3
+ * doubles); its RGB8 is that frame's (f h)*(f w)*3 bytes.  Refused (an unknown selector) by any other sequence */
+enum { MCPT_SEQ_UPSAMPLED = 8 };
 /* copies one of them to the host.  MCPT_E_INVALID: a NULL argument, an unknown selector (RGB8 included), FAST or
  * SHIFT without clamp, FILTERED without denoise, no frame since create / reset / a failed frame */
 int mcpt_sequence_read(mcpt_sequence* seq, int32_t what, double* host_out);
@@ -666,6 +721,25 @@ int mcpt_sequence_device_buffer(mcpt_sequence* seq, int32_t what, const void** d
 /* the next frame starts every history (as the first frame did); the buffers stay allocated */
 int mcpt_sequence_reset(mcpt_sequence* seq);
 void mcpt_sequence_destroy(mcpt_sequence* seq);
+/* A sequence that renders at opts->width x opts->height and shows factor times that (mcpt_upsample's rule;
+ * mcpt_sequence_create and mcpt_sequence_opts are unchanged).  upsample is required (its device field is ignored);
+ * everything mcpt_sequence_create and mcpt_upsample refuse is refused here, the full frame's size included.  Every
+ * buffer is still allocated once, here: the full-size guides, the upsampled colour and the full-size 8-bit frame too.
+ * mcpt_sequence_frame still takes the render-size camera.  A frame runs render, AOVs, accumulation, statistics and
+ * filter at the render size exactly as a plain sequence does (those buffers hold the same bits), then the AOVs of
+ * mcpt_camera_scaled(cam, factor) into the full-size guides, mcpt_upsample's kernel on the shown low frame (the
+ * filtered colour if denoise, else the accumulated one), the tone map of the full-size frame and the copy: out_rgb8 is
+ * then (f h)*(f w)*3 bytes.  MCPT_RENDER_PIXEL_JITTER moves the samples, not the guides, as in a plain sequence. */
+int mcpt_sequence_create_upsampled(mcpt_scene* scene, const mcpt_render_opts* base, const mcpt_sequence_opts* opts,
+                                   const mcpt_temporal_opts* temporal, const mcpt_temporal_clamp_opts* clamp,
+                                   const mcpt_denoise_opts* denoise, const mcpt_upsample_opts* upsample,
+                                   mcpt_sequence** out);
+/* the last frame's new stages (HIP events): guide_seconds the window of the full-size mcpt_render_aovs_device,
+ * upsample_seconds the upsampling kernel; fallback_share = fallback pixels / full-size pixels.  Any output may be
+ * NULL.  MCPT_E_INVALID: a NULL handle, a sequence created without upsampling, no frame since create / reset / a
+ * failed frame.  (mcpt_sequence_info is not extended; its tonemap_seconds is the full-size tone map's.) */
+int mcpt_sequence_upsample_info(mcpt_sequence* seq, double* guide_seconds, double* upsample_seconds,
+                                double* fallback_share);
 
 /* Multi-process communicator (see mcpt_comm above): ncclGetUniqueId / ncclCommInitRank /
  * ncclCommDestroy.  device -1 = the current device. */

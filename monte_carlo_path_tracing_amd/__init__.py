@@ -21,6 +21,7 @@ __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_rays", 
            "TemporalOpts", "TemporalAccumulator", "temporal_accumulate", "temporal_accumulate_device", "camera_orbit",
            "TemporalClampOpts", "temporal_accumulate_clamped", "temporal_accumulate_clamped_device",
            "SequenceOpts", "SequenceInfo", "FrameSequence", "tone_map_device", "frame_stats_device",
+           "UpsampleOpts", "upsample", "upsample_device", "camera_scaled",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -109,6 +110,13 @@ class TemporalClampOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("alpha_fast", C.c_double), ("sigma", C.c_double)]
 
 
+class UpsampleOpts(C.Structure):
+    """mcpt_upsample_opts: the guided upsampling's parameters (include/mcpt.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("factor", C.c_int32), ("sigma_normal", C.c_double),
+                ("sigma_plane", C.c_double), ("sigma_albedo", C.c_double), ("min_weight", C.c_double),
+                ("device", C.c_int32)]
+
+
 class SequenceOpts(C.Structure):
     """mcpt_sequence_opts: what a device-resident frame sequence is created with (include/mcpt.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32),
@@ -128,7 +136,7 @@ class SequenceInfo(C.Structure):
 
 # mcpt_sequence_read / _device_buffer selectors: name -> (MCPT_SEQ_*, trailing shape)
 SEQ_BUFFERS = {"raw": (0, (3,)), "accumulated": (1, (3,)), "moments": (2, (4,)), "variance": (3, ()), "filtered": (4, (3,)),
-               "fast": (5, (3,)), "shift": (6, ()), "rgb8": (7, (3,))}
+               "fast": (5, (3,)), "shift": (6, ()), "rgb8": (7, (3,)), "upsampled": (8, (3,))}
 
 
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
@@ -171,7 +179,8 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_write_bmp", "mcpt_comm_unique_id", "mcpt_comm_init_rank", "mcpt_comm_destroy",
            "mcpt_tone_map_device", "mcpt_frame_stats_device", "mcpt_sequence_opts_init", "mcpt_sequence_create",
            "mcpt_sequence_frame", "mcpt_sequence_read", "mcpt_sequence_device_buffer", "mcpt_sequence_reset",
-           "mcpt_sequence_destroy"]
+           "mcpt_sequence_destroy", "mcpt_upsample_opts_init", "mcpt_upsample", "mcpt_upsample_device",
+           "mcpt_camera_scaled", "mcpt_sequence_create_upsampled", "mcpt_sequence_upsample_info"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active"]  # include/mcpt_debug.h
@@ -257,6 +266,17 @@ def lib():
             L.mcpt_sequence_reset.argtypes = [P]
             L.mcpt_sequence_destroy.argtypes = [P]
             L.mcpt_sequence_destroy.restype = None
+        if hasattr(L, "mcpt_upsample"):  # and the guided upsampling
+            L.mcpt_upsample_opts_init.argtypes = [C.POINTER(UpsampleOpts)]
+            L.mcpt_upsample_opts_init.restype = None
+            L.mcpt_upsample.argtypes = [C.POINTER(UpsampleOpts), I, I, P, C.POINTER(AovBuffers), C.POINTER(AovBuffers), P,
+                                        C.POINTER(C.c_uint64), C.POINTER(D)]
+            L.mcpt_upsample_device.argtypes = L.mcpt_upsample.argtypes
+            L.mcpt_camera_scaled.argtypes = [C.POINTER(Camera), I, C.POINTER(Camera)]
+            L.mcpt_sequence_create_upsampled.argtypes = [P, C.POINTER(RenderOpts), C.POINTER(SequenceOpts), C.POINTER(TemporalOpts),
+                                                         C.POINTER(TemporalClampOpts), C.POINTER(DenoiseOpts),
+                                                         C.POINTER(UpsampleOpts), C.POINTER(P)]
+            L.mcpt_sequence_upsample_info.argtypes = [P, C.POINTER(D), C.POINTER(D), C.POINTER(D)]
         if hasattr(L, "mcpt_render_rays"):  # and the radiance along caller-supplied rays
             L.mcpt_render_rays.argtypes = [P, C.POINTER(RenderOpts), I, P, P, P, C.POINTER(Stats)]
             L.mcpt_render_rays_device.argtypes = L.mcpt_render_rays.argtypes
@@ -645,6 +665,64 @@ def camera_orbit(camera, degrees):
     return out
 
 
+def camera_scaled(camera, factor):
+    """mcpt_camera_scaled: a copy of `camera` with factor times the width and height -- the full-size camera of a
+    low-size one (the same image plane: low pixel I spans the full-size rows factor I .. factor I + factor - 1)."""
+    out = Camera()
+    _check(lib().mcpt_camera_scaled(C.byref(camera), int(factor), C.byref(out)))
+    return out
+
+
+UPSAMPLE_OPTS = ("factor", "sigma_normal", "sigma_plane", "sigma_albedo", "min_weight")
+
+
+def _upsample_opts(factor, sigma_normal, sigma_plane, sigma_albedo, min_weight, device):
+    o = UpsampleOpts()
+    lib().mcpt_upsample_opts_init(C.byref(o))
+    if factor is not None:
+        o.factor = int(factor)
+    for k, v in (("sigma_normal", sigma_normal), ("sigma_plane", sigma_plane), ("sigma_albedo", sigma_albedo),
+                 ("min_weight", min_weight)):
+        if v is not None:
+            setattr(o, k, float(v))
+    o.device = -1 if device is None else int(device)
+    return o
+
+
+def upsample(color, aovs, full_aovs, factor=2, sigma_normal=None, sigma_plane=None, sigma_albedo=None, min_weight=None,
+             device=None):
+    """Guided upsampling (mcpt_upsample; include/mcpt.h states the rule): color h x w x 3 and aovs (the dict of
+    render_aovs) at the low size, full_aovs the guides of camera_scaled(camera, factor) at (factor h) x (factor w).
+    None parameters take the library defaults (sigmas 128 / 0.01 / 0.1, min_weight 1e-4).  Returns (the full-size
+    frame, the number of pixels that took the fallback)."""
+    color = _d(color)
+    h, w = color.shape[:2]
+    assert color.shape == (h, w, 3)
+    f = int(factor)
+    keys = ("albedo", "normal", "position", "depth")
+    g = {k: _d(aovs[k], (h, w) if k == "depth" else (h, w, 3)) for k in keys}
+    G = {k: _d(full_aovs[k], (f * h, f * w) if k == "depth" else (f * h, f * w, 3)) for k in keys}
+    b, B = AovBuffers(*[g[k].ctypes.data for k in keys]), AovBuffers(*[G[k].ctypes.data for k in keys])
+    out, n = np.zeros((f * h, f * w, 3)), C.c_uint64()
+    o = _upsample_opts(f, sigma_normal, sigma_plane, sigma_albedo, min_weight, device)
+    _check(lib().mcpt_upsample(C.byref(o), w, h, color.ctypes.data, C.byref(b), C.byref(B), out.ctypes.data, C.byref(n), None))
+    return out, n.value
+
+
+def upsample_device(width, height, color_ptr, aov_ptrs, full_aov_ptrs, out_ptr, factor=2, sigma_normal=None, sigma_plane=None,
+                    sigma_albedo=None, min_weight=None, device=None):
+    """upsample over device buffers (e.g. torch CUDA float64 tensors' data_ptr()): width and height are the low size,
+    aov_ptrs and full_aov_ptrs dicts of the four guides' pointers at the low and the full size.  Returns (the
+    fallback count, the device seconds)."""
+    keys = ("albedo", "normal", "position", "depth")
+    b, B = AovBuffers(*[int(aov_ptrs[k]) for k in keys]), AovBuffers(*[int(full_aov_ptrs[k]) for k in keys])
+    n, sec = C.c_uint64(), C.c_double()
+    o = _upsample_opts(factor, sigma_normal, sigma_plane, sigma_albedo, min_weight, device)
+    _check(lib().mcpt_upsample_device(C.byref(o), int(width), int(height), C.c_void_p(int(color_ptr)), C.byref(b), C.byref(B),
+                                      C.c_void_p(int(out_ptr)), C.byref(n), C.byref(sec)))
+    return n.value, sec.value
+
+
 TEMPORAL_OPTS = ("alpha", "max_history", "normal_min", "plane_max", "min_weight", "variance_min_history", "sigma_normal",
                  "sigma_plane", "sigma_albedo", "device")
 
@@ -824,10 +902,14 @@ class FrameSequence:
     clamp: None or False (plain accumulation), True or a dict of radius / alpha_fast / sigma (history clamping).
     denoise: False, True (the filter's defaults) or a dict of iterations / sigma_color / sigma_normal / sigma_plane /
     sigma_albedo.  temporal_opts: the fields of TemporalOpts, as for temporal_accumulate (device excepted).
+    upsample: None (the default), a factor F in 2..4 or a dict of factor / sigma_normal / sigma_plane / sigma_albedo /
+    min_weight: width x height stays the render's size, the shown frame (frame()'s return, read("upsampled"),
+    device_buffer("rgb8")) is F times that along each axis, reconstructed by upsample()'s rule from the shown low frame
+    and the guides of camera_scaled(camera, F); upsample_info() then gives the new stages' times.
     After a frame: `info` (SequenceInfo: stage device times, kept, mean_history, clamped) and `stats` (the render's)."""
 
     def __init__(self, scene, width, height, spp, mode="mis", denoise=True, clamp=None, device=None, accel="bvh", flags=0,
-                 tone_max=None, tone_gamma=None, **temporal_opts):
+                 tone_max=None, tone_gamma=None, upsample=None, **temporal_opts):
         self.h = None
         self._destroy = lib().mcpt_sequence_destroy
         if clamp is False:
@@ -851,16 +933,29 @@ class FrameSequence:
                 raise TypeError("unknown denoise option %r (one of %s)" % (sorted(unknown)[0], ", ".join(DENOISE_OPTS)))
             dn = _denoise_opts(*[d.get(k) for k in DENOISE_OPTS], device)
         h = C.c_void_p()
-        _check(lib().mcpt_sequence_create(scene.h, C.byref(base), C.byref(o), C.byref(tp), None if tc is None else C.byref(tc),
-                                          None if dn is None else C.byref(dn), C.byref(h)))
+        self.factor = 1
+        if upsample is None or upsample is False:
+            _check(lib().mcpt_sequence_create(scene.h, C.byref(base), C.byref(o), C.byref(tp), None if tc is None else C.byref(tc),
+                                              None if dn is None else C.byref(dn), C.byref(h)))
+        else:
+            u = dict(upsample) if isinstance(upsample, dict) else {"factor": upsample}
+            unknown = set(u) - set(UPSAMPLE_OPTS)
+            if unknown:
+                raise TypeError("unknown upsample option %r (one of %s)" % (sorted(unknown)[0], ", ".join(UPSAMPLE_OPTS)))
+            up = _upsample_opts(*[u.get(k) for k in UPSAMPLE_OPTS], device)
+            _check(lib().mcpt_sequence_create_upsampled(scene.h, C.byref(base), C.byref(o), C.byref(tp),
+                                                        None if tc is None else C.byref(tc), None if dn is None else C.byref(dn),
+                                                        C.byref(up), C.byref(h)))
+            self.factor = up.factor
         self.h, self.scene = h, scene  # the scene must outlive the handle
         self.width, self.height, self.spp, self.denoise, self.clamp = o.width, o.height, o.spp, bool(denoise), clamp
         self.info, self.stats = None, None
 
     def frame(self, camera, seed=DEFAULT_SEED, readback=True):
-        """One frame with `camera` (of the sequence's size) and `seed`; returns the tone-mapped H x W x 3 uint8 frame,
-        or None with readback=False (the frame then stays on the device: device_buffer("rgb8"))."""
-        out = np.zeros((self.height, self.width, 3), np.uint8) if readback else None
+        """One frame with `camera` (of the sequence's size) and `seed`; returns the tone-mapped H x W x 3 uint8 frame
+        (with upsample=F: F H x F W x 3), or None with readback=False (the frame then stays on the device:
+        device_buffer("rgb8"))."""
+        out = np.zeros((self.factor * self.height, self.factor * self.width, 3), np.uint8) if readback else None
         info, st = SequenceInfo(), Stats()
         _check(lib().mcpt_sequence_frame(self.h, C.byref(camera), int(seed), None if out is None else out.ctypes.data,
                                          C.byref(info), C.byref(st)))
@@ -869,9 +964,10 @@ class FrameSequence:
 
     def read(self, name):
         """The last frame's buffer `name` as a float64 array: raw, accumulated, filtered, fast (H x W x 3), moments
-        (H x W x 4), variance, shift (H x W)."""
+        (H x W x 4), variance, shift (H x W); with upsample=F also upsampled (F H x F W x 3)."""
         what, tail = SEQ_BUFFERS.get(name, (-1, ()))
-        out = np.zeros((self.height, self.width) + tail)
+        f = self.factor if name == "upsampled" else 1
+        out = np.zeros((f * self.height, f * self.width) + tail)
         _check(lib().mcpt_sequence_read(self.h, what, out.ctypes.data))
         return out
 
@@ -881,6 +977,13 @@ class FrameSequence:
         p = C.c_void_p()
         _check(lib().mcpt_sequence_device_buffer(self.h, SEQ_BUFFERS.get(name, (-1, ()))[0], C.byref(p)))
         return p.value
+
+    def upsample_info(self):
+        """mcpt_sequence_upsample_info of the last frame: dict of guide_seconds (the full-size AOVs), upsample_seconds
+        (the upsampling kernel) and fallback_share (fallback pixels / full-size pixels); upsample=F only."""
+        g, u, s = C.c_double(), C.c_double(), C.c_double()
+        _check(lib().mcpt_sequence_upsample_info(self.h, C.byref(g), C.byref(u), C.byref(s)))
+        return dict(guide_seconds=g.value, upsample_seconds=u.value, fallback_share=s.value)
 
     def reset(self):
         """The next frame starts every history."""

@@ -36,6 +36,12 @@
 //   included, works on device buffers allocated once, and per frame only the 8-bit image (and the HDR frame, when
 //   --hdr asks for it) comes back.  The files and the lines printed are those of the default path.  One device; not
 //   with --aov-out (the handle does not hand out the guides).
+//               [--upsample F]
+//   --upsample F (2..4) traces at 1 / F of the size asked for and reconstructs the full-size frame by guided upsampling
+//   (mcpt_upsample): --width and --height are the shown size and must be divisible by F; the render, the AOVs, the
+//   accumulation and the filter run at size / F, then the AOVs of the full-size camera (mcpt_camera_scaled) guide the
+//   upsampling, and --out and --hdr carry the full-size frame.  Works for a single frame, with --frames and with
+//   --frames --device-sequence (mcpt_sequence_create_upsampled); not with --adaptive, --grid or --aov-out.
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -142,9 +148,41 @@ struct SequenceArgs {
 };
 
 // --frames: render, accumulate (and filter) frame after frame; the history ping-pongs between two sets of buffers
+// the full-size guides of `cam` scaled by up.factor, then mcpt_upsample of the low frame `low` into `full`; prints the
+// stage's line
+int upsample_frame(mcpt_scene* scene, const mcpt_camera& cam, const mcpt_upsample_opts& up, const std::vector<double>& low,
+                   const mcpt_aov_buffers& aov, std::vector<double>& full) {
+    mcpt_camera fc;
+    if (mcpt_camera_scaled(&cam, up.factor, &fc) != MCPT_OK) {
+        std::fprintf(stderr, "%s\n", mcpt_last_error());
+        return 1;
+    }
+    const size_t NPX = (size_t)fc.width * fc.height;
+    std::vector<double> albedo(3 * NPX), normal(3 * NPX), position(3 * NPX), depth(NPX);
+    const mcpt_aov_buffers faov{albedo.data(), normal.data(), position.data(), depth.data()};
+    mcpt_render_opts ao;
+    mcpt_render_opts_init(&ao);
+    if (mcpt_render_aovs(scene, &fc, &ao, &faov) != MCPT_OK) {
+        std::fprintf(stderr, "AOV render failed: %s\n", mcpt_last_error());
+        return 1;
+    }
+    full.assign(3 * NPX, 0.0);
+    uint64_t fell = 0;
+    double usec = 0;
+    if (mcpt_upsample(&up, cam.width, cam.height, low.data(), &aov, &faov, full.data(), &fell, &usec) != MCPT_OK) {
+        std::fprintf(stderr, "upsampling failed: %s\n", mcpt_last_error());
+        return 1;
+    }
+    std::printf("  upsampled: factor %d to %dx%d, %.2f%% of the pixels took the fallback, %.3f ms device\n", up.factor, fc.width,
+                fc.height, 100.0 * (double)fell / (double)NPX, usec * 1e3);
+    return 0;
+}
+
 int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceArgs& a, const std::vector<int32_t>& devices,
-                    const mcpt_temporal_opts& tp, const mcpt_temporal_clamp_opts* clamp, const mcpt_denoise_opts& dn) {
+                    const mcpt_temporal_opts& tp, const mcpt_temporal_clamp_opts* clamp, const mcpt_denoise_opts& dn,
+                    const mcpt_upsample_opts* up) {
     const int W = cam0.width, H = cam0.height;
+    const int SW = up ? W * up->factor : W, SH = up ? H * up->factor : H;  // the shown size
     const size_t npx = (size_t)W * H;
     struct Frame {
         mcpt_camera cam;
@@ -155,7 +193,7 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
         f.color.resize(3 * npx), f.moments.resize(4 * npx);
         if (clamp) f.fast.resize(3 * npx);
     }
-    std::vector<double> hdr, variance(npx), filtered(3 * npx), shift(clamp ? npx : 0);
+    std::vector<double> hdr, variance(npx), filtered(3 * npx), shift(clamp ? npx : 0), upsampled;
     for (int k = 0; k < a.frames; k++) {
         Frame &cur = fr[k & 1], &prev = fr[(k & 1) ^ 1];
         if (mcpt_camera_orbit(&cam0, k * a.orbit, &cur.cam) != MCPT_OK) {
@@ -220,13 +258,17 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
                 return 1;
             }
         }
+        if (up) {
+            if (upsample_frame(scene, cur.cam, *up, *shown, aov, upsampled)) return 1;
+            shown = &upsampled;
+        }
         std::vector<uint8_t> rgb8(shown->size());
-        mcpt_tone_map(shown->data(), W, H, 380.0, 0.25, rgb8.data());  // main.cpp:583
-        if (mcpt_write_bmp(frame_path(a.out, k).c_str(), rgb8.data(), W, H) != MCPT_OK) {
+        mcpt_tone_map(shown->data(), SW, SH, 380.0, 0.25, rgb8.data());  // main.cpp:583
+        if (mcpt_write_bmp(frame_path(a.out, k).c_str(), rgb8.data(), SW, SH) != MCPT_OK) {
             std::fprintf(stderr, "%s\n", mcpt_last_error());
             return 1;
         }
-        if (!a.hdr_out.empty() && !write_pfm(frame_path(a.hdr_out, k).c_str(), *shown, W, H)) {
+        if (!a.hdr_out.empty() && !write_pfm(frame_path(a.hdr_out, k).c_str(), *shown, SW, SH)) {
             std::fprintf(stderr, "cannot write %s\n", frame_path(a.hdr_out, k).c_str());
             return 1;
         }
@@ -236,8 +278,8 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
 
 // --frames --device-sequence: the same sequence through mcpt_sequence; the lines and files of render_sequence
 int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceArgs& a, const mcpt_temporal_opts& tp,
-                           const mcpt_temporal_clamp_opts* clamp, const mcpt_denoise_opts& dn) {
-    const int W = cam0.width, H = cam0.height;
+                           const mcpt_temporal_clamp_opts* clamp, const mcpt_denoise_opts& dn, const mcpt_upsample_opts* up) {
+    const int W = up ? cam0.width * up->factor : cam0.width, H = up ? cam0.height * up->factor : cam0.height;  // the shown size
     const size_t npx = (size_t)W * H;
     mcpt_render_opts base;
     mcpt_render_opts_init(&base);
@@ -251,10 +293,11 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
     }
     mcpt_sequence_opts so;
     mcpt_sequence_opts_init(&so);
-    so.width = W, so.height = H, so.spp = a.spp;
+    so.width = cam0.width, so.height = cam0.height, so.spp = a.spp;
     so.denoise = a.denoise, so.clamp = clamp != nullptr;
     mcpt_sequence* seq = nullptr;
-    if (mcpt_sequence_create(scene, &base, &so, &tp, clamp, a.denoise ? &dn : nullptr, &seq) != MCPT_OK) {
+    if ((up ? mcpt_sequence_create_upsampled(scene, &base, &so, &tp, clamp, a.denoise ? &dn : nullptr, up, &seq)
+            : mcpt_sequence_create(scene, &base, &so, &tp, clamp, a.denoise ? &dn : nullptr, &seq)) != MCPT_OK) {
         std::fprintf(stderr, "sequence setup failed: %s\n", mcpt_last_error());
         return 1;
     }
@@ -279,13 +322,24 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
         if (a.denoise)
             std::printf("  denoised: %d iterations, sigma_color %g, variance from the temporal moments, %.3f ms device\n",
                         dn.iterations, dn.sigma_color, fi.denoise_seconds * 1e3);
+        if (up) {
+            double usec = 0, share = 0;
+            if (mcpt_sequence_upsample_info(seq, nullptr, &usec, &share) != MCPT_OK) {
+                std::fprintf(stderr, "%s\n", mcpt_last_error());
+                rc = 1;
+                break;
+            }
+            std::printf("  upsampled: factor %d to %dx%d, %.2f%% of the pixels took the fallback, %.3f ms device\n", up->factor, W, H,
+                        100.0 * share, usec * 1e3);
+        }
         if (mcpt_write_bmp(frame_path(a.out, k).c_str(), rgb8.data(), W, H) != MCPT_OK) {
             std::fprintf(stderr, "%s\n", mcpt_last_error());
             rc = 1;
         }
         if (!rc && !a.hdr_out.empty()) {
             shown.resize(3 * npx);
-            if (mcpt_sequence_read(seq, a.denoise ? MCPT_SEQ_FILTERED : MCPT_SEQ_ACCUMULATED, shown.data()) != MCPT_OK) {
+            if (mcpt_sequence_read(seq, up ? MCPT_SEQ_UPSAMPLED : a.denoise ? MCPT_SEQ_FILTERED : MCPT_SEQ_ACCUMULATED,
+                                   shown.data()) != MCPT_OK) {
                 std::fprintf(stderr, "%s\n", mcpt_last_error());
                 rc = 1;
             } else if (!write_pfm(frame_path(a.hdr_out, k).c_str(), shown, W, H)) {
@@ -324,6 +378,9 @@ int main(int argc, char** argv) {
     bool device_sequence = false;
     mcpt_temporal_clamp_opts tc;
     mcpt_temporal_clamp_opts_init(&tc);
+    bool upsample = false;
+    mcpt_upsample_opts up;
+    mcpt_upsample_opts_init(&up);
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -388,6 +445,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--clamp-radius")) tc.radius = std::atoi(next()), clamp_flag = sequence_flag = true;
         else if (!std::strcmp(argv[a], "--clamp-alpha-fast")) tc.alpha_fast = std::atof(next()), clamp_flag = sequence_flag = true;
         else if (!std::strcmp(argv[a], "--device-sequence")) device_sequence = true;
+        else if (!std::strcmp(argv[a], "--upsample")) up.factor = std::atoi(next()), upsample = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -411,6 +469,29 @@ int main(int argc, char** argv) {
         }
         if (grid) {
             std::fprintf(stderr, "--jitter traces its camera rays over the BVH; drop --grid\n");
+            return 2;
+        }
+    }
+    if (upsample) {  // refused before anything is loaded
+        if (up.factor < 2 || up.factor > 4) {
+            std::fprintf(stderr, "--upsample needs a factor in 2..4, not %d\n", up.factor);
+            return 2;
+        }
+        if (adaptive) {
+            std::fprintf(stderr, "--upsample reconstructs plain renders; drop --adaptive\n");
+            return 2;
+        }
+        if (grid) {
+            std::fprintf(stderr, "--upsample takes its guides over the BVH; drop --grid\n");
+            return 2;
+        }
+        if (!aov_out.empty()) {
+            std::fprintf(stderr, "--upsample has guides at two sizes; drop --aov-out\n");
+            return 2;
+        }
+        if (W < 1 || H < 1 || W % up.factor || H % up.factor) {
+            std::fprintf(stderr, "--upsample %d: --width %d and --height %d are the shown size and must be divisible by %d\n",
+                         up.factor, W, H, up.factor);
             return 2;
         }
     }
@@ -449,6 +530,8 @@ int main(int argc, char** argv) {
         cam.fovy = 20.1143;
     }
     cam.dist_scale = dist_scale;
+    const int SW = W, SH = H;  // the shown size; W x H from here on is the render's
+    if (upsample) W /= up.factor, H /= up.factor;
     cam.width = W;
     cam.height = H;
     std::vector<double> hdr;
@@ -477,8 +560,9 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
             return 2;
         }
-        const int rc = device_sequence ? render_sequence_device(scene, cam, sa, tp, history_clamp ? &tc : nullptr, dn)
-                                       : render_sequence(scene, cam, sa, devices, tp, history_clamp ? &tc : nullptr, dn);
+        const mcpt_upsample_opts* upp = upsample ? &up : nullptr;
+        const int rc = device_sequence ? render_sequence_device(scene, cam, sa, tp, history_clamp ? &tc : nullptr, dn, upp)
+                                       : render_sequence(scene, cam, sa, devices, tp, history_clamp ? &tc : nullptr, dn, upp);
         mcpt_scene_destroy(scene);
         return rc;
     }
@@ -516,7 +600,7 @@ int main(int argc, char** argv) {
             }
         }
     }
-    if (denoise || !aov_out.empty()) {
+    if (denoise || !aov_out.empty() || upsample) {
         const size_t npx = (size_t)W * H;
         std::vector<double> albedo(3 * npx), normal(3 * npx), position(3 * npx), depth(npx);
         const mcpt_aov_buffers aov{albedo.data(), normal.data(), position.data(), depth.data()};
@@ -550,14 +634,19 @@ int main(int argc, char** argv) {
             std::printf("  denoised: %d iterations, sigma_color %g, variance from %s, %.3f ms device\n", dn.iterations,
                         dn.sigma_color, adaptive ? "the adaptive noise map" : "the spatial estimate", dsec * 1e3);
         }
+        if (upsample) {
+            std::vector<double> full;
+            if (upsample_frame(scene, cam, up, hdr, aov, full)) return 1;
+            hdr.swap(full);
+        }
     }
     std::vector<uint8_t> rgb8(hdr.size());
-    mcpt_tone_map(hdr.data(), W, H, 380.0, 0.25, rgb8.data());  // main.cpp:583
-    if (mcpt_write_bmp(out.c_str(), rgb8.data(), W, H) != MCPT_OK) {
+    mcpt_tone_map(hdr.data(), SW, SH, 380.0, 0.25, rgb8.data());  // main.cpp:583
+    if (mcpt_write_bmp(out.c_str(), rgb8.data(), SW, SH) != MCPT_OK) {
         std::fprintf(stderr, "%s\n", mcpt_last_error());
         return 1;
     }
-    if (!hdr_out.empty() && !write_pfm(hdr_out.c_str(), hdr, W, H)) {
+    if (!hdr_out.empty() && !write_pfm(hdr_out.c_str(), hdr, SW, SH)) {
         std::fprintf(stderr, "cannot write %s\n", hdr_out.c_str());
         return 1;
     }

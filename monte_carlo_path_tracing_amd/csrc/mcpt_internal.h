@@ -149,4 +149,10 @@ int denoise_check_opts(const mcpt_denoise_opts* o);
 int denoise_enqueue(const mcpt_denoise_opts* o, int32_t W, int32_t H, const double* dC, const double* dV,
                     const mcpt_aov_buffers* g, double* dOut, double* dOutV, double* tmp);
 
+// upsample.hip -- the guided upsampling in the same form: every check of mcpt_upsample_device that needs no device,
+// then the count's memset and the kernel on the null stream.  dCount: one 64-bit word of device memory.
+int upsample_check_opts(const mcpt_upsample_opts* o);
+int upsample_enqueue(const mcpt_upsample_opts* o, int32_t w, int32_t h, const double* dC, const mcpt_aov_buffers* g,
+                     const mcpt_aov_buffers* G, double* dOut, unsigned long long* dCount);
+
 }  // namespace mcpt

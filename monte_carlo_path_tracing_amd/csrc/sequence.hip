@@ -12,7 +12,10 @@
 // run on the scene's stream and wait for it), then temporal_enqueue, the statistics, denoise_enqueue
 // (mcpt_internal.h) and the tone map on the null stream, separated by the handle's events, and one synchronisation.
 // Everything a frame touches is allocated in mcpt_sequence_create: one device allocation, cut into the buffers
-// below, and 32 pinned bytes for the statistics.
+// below, and 40 pinned bytes for the statistics and the upsampling's fallback count.  A sequence created by
+// mcpt_sequence_create_upsampled adds three stages between the filter and the tone map: the AOVs of the scaled camera
+// (mcpt_render_aovs_device again, into the full-size guides), upsample_enqueue (mcpt_internal.h) and the tone map of the
+// full-size frame; everything before them is the plain sequence's code on the plain sequence's buffers.
 //
 // The tone map's loads are plain: lane k reads values 4 k .. 4 k + 3 (32 consecutive bytes, a wave 2 KB), stores
 // are one dword per lane.  pow is the device library's; -ffp-contract=off as everywhere.  The statistics read the
@@ -160,7 +163,7 @@ int enqueue_tone_map(const double* dRgb, size_t n, double maxr, double gamma, ui
     return MCPT_OK;
 }
 
-bool frame_size_ok(int W, int H) { return W >= 1 && H >= 1 && (long long)W * H <= (1ll << 28); }
+bool frame_size_ok(long long W, long long H) { return W >= 1 && H >= 1 && W * H <= (1ll << 28); }
 
 }  // namespace
 
@@ -171,6 +174,9 @@ struct mcpt_sequence {
     mcpt_temporal_opts tp{};
     mcpt_temporal_clamp_opts tc{};
     mcpt_denoise_opts dn{};
+    mcpt_upsample_opts up{};
+    int factor = 0;   // 0: no upsampling; else the shown frame is factor times the render's along each axis
+    size_t NPX = 0;   // the shown frame's pixels (npx without upsampling)
     int device = -1;  // the ordinal, resolved in create
     size_t npx = 0;
     // one device allocation: raw, two sets, variance, shift, filtered, the filter's scratch, the statistics' words, rgb8
@@ -183,9 +189,13 @@ struct mcpt_sequence {
     } set[2];
     double *variance = nullptr, *shift = nullptr, *filtered = nullptr, *tmp = nullptr;
     void* stats_words = nullptr;
+    mcpt_aov_buffers full{};      // upsampling: the guides of the scaled camera
+    double* upsampled = nullptr;  // and the shown full-size colour
+    unsigned long long* fallbacks = nullptr;
     uint8_t* rgb8 = nullptr;
-    StatsOut* host_stats = nullptr;  // pinned
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    StatsOut* host_stats = nullptr;  // pinned; one more word behind it: the fallback count
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    double guide_seconds = 0, upsample_seconds = 0, fallback_share = 0;  // the last frame's (mcpt_sequence_upsample_info)
     int cur = 0;            // the set the next frame writes
     bool has_prev = false;  // set[cur ^ 1] holds a history
     bool has_last = false;  // set[cur ^ 1] and the shared buffers hold the last frame
@@ -241,13 +251,22 @@ int locate(mcpt_sequence* s, int32_t what, bool allow_rgb8, const void** dev, si
             break;
         case MCPT_SEQ_RGB8:
             if (allow_rgb8) {
-                p = s->rgb8, b = 3 * n;
+                p = s->rgb8, b = 3 * s->NPX;
+                break;
+            }
+            [[fallthrough]];
+        case MCPT_SEQ_UPSAMPLED:
+            if (what == MCPT_SEQ_UPSAMPLED && s->factor) {
+                p = s->upsampled, b = 3 * s->NPX * d;
                 break;
             }
             [[fallthrough]];
         default:
-            set_error("unknown buffer selector %d%s", what, what == MCPT_SEQ_RGB8 ? " (MCPT_SEQ_RGB8 is not an array of doubles: "
-                      "use mcpt_sequence_device_buffer, or the frame's out_rgb8)" : "");
+            set_error("unknown buffer selector %d%s", what,
+                      what == MCPT_SEQ_RGB8 ? " (MCPT_SEQ_RGB8 is not an array of doubles: use mcpt_sequence_device_buffer, or "
+                                              "the frame's out_rgb8)"
+                      : what == MCPT_SEQ_UPSAMPLED ? " for this sequence (MCPT_SEQ_UPSAMPLED: the sequence was created "
+                                                     "without upsampling; use mcpt_sequence_create_upsampled)" : "");
             return MCPT_E_INVALID;
     }
     if (!s->has_last) {
@@ -323,9 +342,10 @@ void mcpt_sequence_opts_init(mcpt_sequence_opts* o) {
     o->tone_gamma = 0.25;
 }
 
-int mcpt_sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, const mcpt_sequence_opts* o,
-                         const mcpt_temporal_opts* tp, const mcpt_temporal_clamp_opts* tc, const mcpt_denoise_opts* dn,
-                         mcpt_sequence** out) {
+// both constructors; up == nullptr: mcpt_sequence_create
+static int sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, const mcpt_sequence_opts* o,
+                           const mcpt_temporal_opts* tp, const mcpt_temporal_clamp_opts* tc, const mcpt_denoise_opts* dn,
+                           const mcpt_upsample_opts* up, mcpt_sequence** out) {
     if (!scene || !base || !o || !out) {
         set_error("mcpt_sequence_create: null argument: %s", !scene ? "scene" : !base ? "base" : !o ? "opts" : "out");
         return MCPT_E_INVALID;
@@ -378,6 +398,14 @@ int mcpt_sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, const 
     if ((rc = check_tone(o->tone_max, o->tone_gamma, "tone_max", "tone_gamma"))) return rc;
     if ((rc = mcpt::temporal_check_opts(tp, tc, o->clamp != 0))) return rc;
     if (o->denoise && (rc = mcpt::denoise_check_opts(dn))) return rc;
+    if (up) {
+        if ((rc = mcpt::upsample_check_opts(up))) return rc;
+        if (!frame_size_ok(o->width * (long long)up->factor, o->height * (long long)up->factor)) {
+            set_error("invalid frame size: width %d, height %d at upsample factor %d (the full frame may hold 2^28 pixels)",
+                      o->width, o->height, up->factor);
+            return MCPT_E_INVALID;
+        }
+    }
 
     mcpt_sequence* s = new (std::nothrow) mcpt_sequence;
     if (!s) {
@@ -395,14 +423,16 @@ int mcpt_sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, const 
     s->tp = *tp;
     if (o->clamp) s->tc = *tc;
     if (o->denoise) s->dn = *dn;
+    if (up) s->up = *up, s->factor = up->factor;
     const size_t npx = s->npx = (size_t)o->width * o->height;
+    const size_t NPX = s->NPX = up ? npx * up->factor * up->factor : npx;
     Scratch S;  // restores the caller's device
     if ((rc = select_device(base->device, S, &s->device))) return rc;
     s->base.device = s->tp.device = s->dn.device = s->device;
     const size_t per_set = 10 + 3 + 4 + (o->clamp ? 3 : 0);
     const size_t doubles = 3 + 2 * per_set + 1 + (o->clamp ? 1 : 0) + (o->denoise ? 3 + 8 : 0);
-    const size_t words = doubles * npx + stats_words(npx);
-    DN_HIP_OK(hipMalloc(&s->mem, words * 8 + 3 * npx));
+    const size_t words = doubles * npx + stats_words(npx) + (up ? 13 * NPX + 1 : 0);
+    DN_HIP_OK(hipMalloc(&s->mem, words * 8 + 3 * NPX));
     double* q = s->mem;
     auto take = [&](size_t k) {
         double* r = q;
@@ -419,11 +449,53 @@ int mcpt_sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, const 
     if (o->clamp) s->shift = take(1);
     if (o->denoise) s->filtered = take(3), s->tmp = take(8);
     s->stats_words = q;
+    if (up) {
+        q += stats_words(npx);
+        s->fallbacks = (unsigned long long*)q++;
+        s->full.albedo = q, s->full.normal = q + 3 * NPX, s->full.position = q + 6 * NPX, s->full.depth = q + 9 * NPX;
+        s->upsampled = q + 10 * NPX;
+    }
     s->rgb8 = (uint8_t*)(s->mem + words);  // after whole 8-byte words: 8-byte aligned
-    DN_HIP_OK(hipHostMalloc((void**)&s->host_stats, sizeof(StatsOut)));
+    DN_HIP_OK(hipHostMalloc((void**)&s->host_stats, sizeof(StatsOut) + sizeof(unsigned long long)));
     for (auto& e : s->ev) DN_HIP_OK(hipEventCreate(&e));
     guard.s = nullptr;
     *out = s;
+    return MCPT_OK;
+}
+
+int mcpt_sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, const mcpt_sequence_opts* o,
+                         const mcpt_temporal_opts* tp, const mcpt_temporal_clamp_opts* tc, const mcpt_denoise_opts* dn,
+                         mcpt_sequence** out) {
+    return sequence_create(scene, base, o, tp, tc, dn, nullptr, out);
+}
+
+int mcpt_sequence_create_upsampled(mcpt_scene* scene, const mcpt_render_opts* base, const mcpt_sequence_opts* o,
+                                   const mcpt_temporal_opts* tp, const mcpt_temporal_clamp_opts* tc,
+                                   const mcpt_denoise_opts* dn, const mcpt_upsample_opts* up, mcpt_sequence** out) {
+    if (!up) {
+        if (out) *out = nullptr;
+        set_error("mcpt_sequence_create_upsampled: null argument: upsample");
+        return MCPT_E_INVALID;
+    }
+    return sequence_create(scene, base, o, tp, tc, dn, up, out);
+}
+
+int mcpt_sequence_upsample_info(mcpt_sequence* s, double* guide_seconds, double* upsample_seconds, double* fallback_share) {
+    if (!s) {
+        set_error("null mcpt_sequence");
+        return MCPT_E_INVALID;
+    }
+    if (!s->factor) {
+        set_error("mcpt_sequence_upsample_info: the sequence was created without upsampling");
+        return MCPT_E_INVALID;
+    }
+    if (!s->has_last) {
+        set_error("the sequence holds no frame (none since create, reset or a failed frame)");
+        return MCPT_E_INVALID;
+    }
+    if (guide_seconds) *guide_seconds = s->guide_seconds;
+    if (upsample_seconds) *upsample_seconds = s->upsample_seconds;
+    if (fallback_share) *fallback_share = s->fallback_share;
     return MCPT_OK;
 }
 
@@ -475,13 +547,33 @@ int mcpt_sequence_frame(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed,
         shown = s->filtered;
     }
     DN_HIP_OK(hipEventRecord(s->ev[3], nullptr));
-    if ((rc = enqueue_tone_map(shown, 3 * npx, s->opts.tone_max, s->opts.tone_gamma, s->rgb8))) return rc;
+    unsigned long long* hfall = (unsigned long long*)(s->host_stats + 1);
+    if (s->factor) {  // the full-size guides, then the shown low frame onto them: ev[3] .. ev[5] .. ev[6], the tone map ends at ev[4]
+        mcpt_camera fullcam;
+        if ((rc = mcpt_camera_scaled(cam, s->factor, &fullcam))) return rc;
+        if ((rc = mcpt_render_aovs_device(s->scene, &fullcam, &ro, &s->full))) return rc;
+        DN_HIP_OK(hipSetDevice(device));
+        DN_HIP_OK(hipEventRecord(s->ev[5], nullptr));
+        if ((rc = mcpt::upsample_enqueue(&s->up, W, H, shown, &C.g, &s->full, s->upsampled, s->fallbacks))) return rc;
+        shown = s->upsampled;
+        DN_HIP_OK(hipEventRecord(s->ev[6], nullptr));
+    }
+    if ((rc = enqueue_tone_map(shown, 3 * s->NPX, s->opts.tone_max, s->opts.tone_gamma, s->rgb8))) return rc;
     DN_HIP_OK(hipEventRecord(s->ev[4], nullptr));
     DN_HIP_OK(hipMemcpyAsync(s->host_stats, dres, sizeof(StatsOut), hipMemcpyDeviceToHost, nullptr));
-    if (out_rgb8) DN_HIP_OK(hipMemcpyAsync(out_rgb8, s->rgb8, 3 * npx, hipMemcpyDeviceToHost, nullptr));
+    if (s->factor) DN_HIP_OK(hipMemcpyAsync(hfall, s->fallbacks, sizeof *hfall, hipMemcpyDeviceToHost, nullptr));
+    if (out_rgb8) DN_HIP_OK(hipMemcpyAsync(out_rgb8, s->rgb8, 3 * s->NPX, hipMemcpyDeviceToHost, nullptr));
     DN_HIP_OK(hipStreamSynchronize(nullptr));
     float ms[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 4; k++) DN_HIP_OK(hipEventElapsedTime(&ms[k], s->ev[k], s->ev[k + 1]));
+    for (int k = 0; k < 3; k++) DN_HIP_OK(hipEventElapsedTime(&ms[k], s->ev[k], s->ev[k + 1]));
+    DN_HIP_OK(hipEventElapsedTime(&ms[3], s->ev[s->factor ? 6 : 3], s->ev[4]));
+    if (s->factor) {
+        float g = 0, u = 0;
+        DN_HIP_OK(hipEventElapsedTime(&g, s->ev[3], s->ev[5]));
+        DN_HIP_OK(hipEventElapsedTime(&u, s->ev[5], s->ev[6]));
+        s->guide_seconds = g * 1e-3, s->upsample_seconds = u * 1e-3;
+        s->fallback_share = (double)*hfall / (double)s->NPX;
+    }
     mcpt_sequence_info fi{};
     fi.render_seconds = st.seconds;
     fi.aov_seconds = ms[0] * 1e-3, fi.temporal_seconds = ms[1] * 1e-3;
