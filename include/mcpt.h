@@ -598,6 +598,84 @@ int mcpt_upsample_device(const mcpt_upsample_opts* opts, int32_t width, int32_t 
  * in and out may be the same struct. */
 int mcpt_camera_scaled(const mcpt_camera* in, int32_t factor, mcpt_camera* out);
 
+/* Temporal upsampling (no counterpart in the reference): instead of tracing a low-size camera and guessing the pixels
+ * in between (mcpt_upsample), every frame traces a different 1 / f^2 subset of the FULL-size camera's pixels -- those
+ * with row mod f == a and column mod f == b, the frame's phase (a, b) -- and accumulates them in a full-size history,
+ * so that a static or slowly moving camera converges to a full-resolution image at the tracing cost of a low one.
+ * Inputs: the factor f (mcpt_upsample_opts.factor, 2..4), the phase (a, b) with 0 <= a, b < f, the low size w x h (the
+ * full size is W = f w, H = f h), the low colour C (h*w*3) where C(I, J) is the radiance of FULL-size pixel
+ * (f I + a, f J + b) through that pixel's centre (mcpt_camera_phase_rays gives those rays), this frame's full-size
+ * guides G and, optionally, the previous state AT FULL SIZE: its full-size camera, its guides G', its colour Hc'
+ * (H*W*3) and its moments Hm' (H*W*4, interleaved (m1, m2, n, g)).  All arithmetic is fp64, with no contraction.  For
+ * each full-size pixel p = (i, j):
+ *   traced   p is traced when i mod f == a and j mod f == b; then c = C(i / f, j / f) (integer division) and
+ *            l = (c.r + c.g + c.b) / 3
+ *   history  mcpt_temporal_accumulate's `source`, `taps` and `history` steps word for word, at W x H with G, G' and the
+ *            previous camera (a tap with n'_q == 0 is invalid, as there): "p has history" and, if so,
+ *            (Hc, m1', m2', n', g')
+ *   traced, with history     mcpt_temporal_accumulate's `blend` with C = c
+ *   traced, without history  out = c, moments (l, l^2, 1, 1)
+ *   untraced, with history   out = Hc, moments (m1', m2', n', g'): nothing is blended and n is not incremented
+ *   untraced, without history (the fill)
+ *            source   y = (i - a) / f, x = (j - b) / f (as doubles); i0 = floor(y), j0 = floor(x), fy = y - i0,
+ *                     fx = x - j0
+ *            taps     the low pixels q = (i0 + di, j0 + dj) for (di, dj) = (0, 0), (0, 1), (1, 0), (1, 1) in this order;
+ *                     taps outside the low frame are skipped; b_q = (di ? fy : 1 - fy) * (dj ? fx : 1 - fx)
+ *            weight   w_q = b_q * geo(p, q'), geo the denoiser's with mcpt_upsample_opts' sigmas, the centre G at p, the
+ *                     tap G at q' = (f q_i + a, f q_j + b), the full-size pixel q was traced through (no low-size
+ *                     guides exist in this mode)
+ *            result   Wsum = sum of w_q; if Wsum >= mcpt_upsample_opts.min_weight, out = (sum of w_q C(q)) / Wsum;
+ *                     otherwise the fallback out = C(I*, J*) with I* = clamp(floor(y + 0.5), 0, h - 1) and J* likewise
+ *                     from x and w (the nearest traced pixel), and p counts as a fallback pixel
+ *            moments  (l_out, l_out^2, 0, 1): n = 0 marks a value that is nobody's sample.  It is shown, but it never
+ *                     serves as history (its tap is invalid in the next frame)
+ *   variance as in mcpt_temporal_accumulate, from out and the moments: the temporal formula where
+ *            n > variance_min_history - 0.5 and g < 1, otherwise the spatial estimate V_0 of out with G and
+ *            mcpt_temporal_opts' sigmas
+ *   counts   filled = the pixels in the fill case, fallback = those of them that took the fallback; integers reduced
+ *            with integer atomics, exact and the same on every run
+ * The phase of frame k (mcpt_upsample_phase): k' = k mod f^2, a = k' mod f, b = (a + k' div f) mod f -- a bijection onto
+ * the f^2 phases, for f = 2: (0,0), (1,1), (0,1), (1,0).  A pixel is traced every f^2-th frame, so its history forgets
+ * over f^2 / alpha frames, not 1 / alpha.  The history is not clamped, samples and guides are not jittered, f is an
+ * integer.  Single device. */
+/* Host helper: the phase of frame `frame_index` at `factor` (2..4).  MCPT_E_INVALID for a NULL pointer or a factor
+ * outside 2..4. */
+int mcpt_upsample_phase(int32_t factor, uint64_t frame_index, int32_t* a, int32_t* b);
+/* The (height / factor) * (width / factor) rays of full_cam's pixels (factor I + a, factor J + b), row-major in (I, J):
+ * origin and dir n*3 each (host arrays), computed on `device` (-1 = current) by the function the render's root kernel
+ * calls, so they are mcpt_camera_rays(full_cam)'s rays at those pixels bit for bit.  MCPT_E_INVALID before any device
+ * work: a NULL pointer, an invalid camera, a factor outside 2..4, a width or height that factor does not divide, a
+ * phase outside [0, factor). */
+int mcpt_camera_phase_rays(const mcpt_camera* full_cam, int32_t factor, int32_t a, int32_t b, int32_t device,
+                           double* origin, double* dir);
+/* same with origin and dir in DEVICE memory on `device` */
+int mcpt_camera_phase_rays_device(const mcpt_camera* full_cam, int32_t factor, int32_t a, int32_t b, int32_t device,
+                                  double* dev_origin, double* dev_dir);
+/* Host arrays in, host arrays out.  width and height are the LOW size: color holds height*width pixels, every other
+ * array (factor*height)*(factor*width).  full_guides: all four arrays are required.  The previous state --
+ * prev_full_cam, prev_full_guides (normal, position and depth required), prev_color, prev_moments -- is given whole or
+ * not at all; prev_full_cam must be (factor*width) x (factor*height).  out_color, out_moments and out_variance
+ * (optional) are overwritten.  filled_count, fallback_count and device_seconds (device time of the kernels, HIP events)
+ * may be NULL.  temporal->device selects the device (upsample->device is ignored).  Refused with MCPT_E_INVALID before
+ * any device work: everything mcpt_temporal_accumulate and mcpt_upsample refuse (a struct_size mismatch or an option out
+ * of range in either struct, a NULL required array, a partial previous state, a previous camera of another size, an
+ * output aliasing an input or another output, width or height < 1 or a full frame of more than 2^28 pixels) and a
+ * phase outside [0, factor). */
+int mcpt_temporal_upsample(const mcpt_temporal_opts* temporal, const mcpt_upsample_opts* upsample, int32_t a, int32_t b,
+                           const mcpt_camera* prev_full_cam, int32_t width, int32_t height, const double* color,
+                           const mcpt_aov_buffers* full_guides, const mcpt_aov_buffers* prev_full_guides,
+                           const double* prev_color, const double* prev_moments, double* out_color, double* out_moments,
+                           double* out_variance, uint64_t* filled_count, uint64_t* fallback_count, double* device_seconds);
+/* same with every array in DEVICE memory on temporal->device (the options, prev_full_cam, the counts and device_seconds
+ * stay host pointers) */
+int mcpt_temporal_upsample_device(const mcpt_temporal_opts* temporal, const mcpt_upsample_opts* upsample, int32_t a,
+                                  int32_t b, const mcpt_camera* prev_full_cam, int32_t width, int32_t height,
+                                  const double* dev_color, const mcpt_aov_buffers* dev_full_guides,
+                                  const mcpt_aov_buffers* dev_prev_full_guides, const double* dev_prev_color,
+                                  const double* dev_prev_moments, double* dev_out_color, double* dev_out_moments,
+                                  double* dev_out_variance, uint64_t* filled_count, uint64_t* fallback_count,
+                                  double* device_seconds);
+
 /* Host helper: *out = *in with eye rotated by `degrees` about the axis through lookat along k = up / |up|
  * (Rodrigues, right-handed): with v = eye - lookat, t = degrees * pi / 180 and vp = v - k (k . v),
  * eye' = eye + (k x v) sin t - vp (1 - cos t); 0 degrees returns eye bit for bit.  MCPT_E_INVALID for a NULL
@@ -740,6 +818,28 @@ int mcpt_sequence_create_upsampled(mcpt_scene* scene, const mcpt_render_opts* ba
  * failed frame.  (mcpt_sequence_info is not extended; its tonemap_seconds is the full-size tone map's.) */
 int mcpt_sequence_upsample_info(mcpt_sequence* seq, double* guide_seconds, double* upsample_seconds,
                                 double* fallback_share);
+/* A sequence that traces opts->width x opts->height rays a frame and accumulates them at factor times that size
+ * (mcpt_temporal_upsample's rule; the other constructors are unchanged).  mcpt_sequence_frame still takes the
+ * render-size camera.  A frame takes its phase from frame_index (mcpt_upsample_phase), writes the phase rays of
+ * mcpt_camera_scaled(cam, factor), zeroes the low raw buffer, traces the rays (mcpt_render_rays_device: n = w h, the
+ * frame's seed, ray r draws the random numbers of pixel r), renders the full-size AOVs, runs mcpt_temporal_upsample's
+ * kernels onto the previous full-size state, reduces the statistics over the full-size moments, filters at full size (if
+ * denoise), tone-maps the full-size frame and copies its (f h)*(f w)*3 bytes out; then the history buffers swap.  Every
+ * buffer is allocated here.  Selectors: RAW is h*w*3 (the traced samples, row-major in (I, J)); ACCUMULATED, MOMENTS,
+ * VARIANCE, FILTERED and RGB8 are full size; FAST, SHIFT and UPSAMPLED are refused.  mcpt_sequence_info's kept and
+ * mean_history are over the full-size pixels, its render_seconds the traced rays', its aov_seconds the full-size
+ * guides'.  Refused with MCPT_E_INVALID: everything mcpt_sequence_create_upsampled refuses, opts->clamp (the history
+ * clamp is not defined for this rule), MCPT_RENDER_PIXEL_JITTER and MCPT_ACCEL_GRID in base (mcpt_render_rays refuses
+ * them).  The traced rays share no root-point cache (see mcpt_render_rays): the mode is for few-spp sequences. */
+int mcpt_sequence_create_temporal_upsampled(mcpt_scene* scene, const mcpt_render_opts* base, const mcpt_sequence_opts* opts,
+                                            const mcpt_temporal_opts* temporal, const mcpt_denoise_opts* denoise,
+                                            const mcpt_upsample_opts* upsample, mcpt_sequence** out);
+/* the last frame's phase (a, b), rays_seconds the phase-ray kernel's device time (HIP events), filled_share = fill pixels
+ * / full-size pixels and fallback_share = fallback pixels / full-size pixels.  Any output may be NULL.
+ * MCPT_E_INVALID: a NULL handle, a sequence not created by mcpt_sequence_create_temporal_upsampled, no frame since create
+ * / reset / a failed frame. */
+int mcpt_sequence_temporal_upsample_info(mcpt_sequence* seq, int32_t* a, int32_t* b, double* rays_seconds,
+                                         double* filled_share, double* fallback_share);
 
 /* Multi-process communicator (see mcpt_comm above): ncclGetUniqueId / ncclCommInitRank /
  * ncclCommDestroy.  device -1 = the current device. */

@@ -22,6 +22,7 @@ __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_rays", 
            "TemporalClampOpts", "temporal_accumulate_clamped", "temporal_accumulate_clamped_device",
            "SequenceOpts", "SequenceInfo", "FrameSequence", "tone_map_device", "frame_stats_device",
            "UpsampleOpts", "upsample", "upsample_device", "camera_scaled",
+           "upsample_phase", "camera_phase_rays", "temporal_upsample", "temporal_upsample_device",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -180,7 +181,9 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_tone_map_device", "mcpt_frame_stats_device", "mcpt_sequence_opts_init", "mcpt_sequence_create",
            "mcpt_sequence_frame", "mcpt_sequence_read", "mcpt_sequence_device_buffer", "mcpt_sequence_reset",
            "mcpt_sequence_destroy", "mcpt_upsample_opts_init", "mcpt_upsample", "mcpt_upsample_device",
-           "mcpt_camera_scaled", "mcpt_sequence_create_upsampled", "mcpt_sequence_upsample_info"]
+           "mcpt_camera_scaled", "mcpt_sequence_create_upsampled", "mcpt_sequence_upsample_info",
+           "mcpt_upsample_phase", "mcpt_camera_phase_rays", "mcpt_camera_phase_rays_device", "mcpt_temporal_upsample",
+           "mcpt_temporal_upsample_device", "mcpt_sequence_create_temporal_upsampled", "mcpt_sequence_temporal_upsample_info"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active"]  # include/mcpt_debug.h
@@ -277,6 +280,19 @@ def lib():
                                                          C.POINTER(TemporalClampOpts), C.POINTER(DenoiseOpts),
                                                          C.POINTER(UpsampleOpts), C.POINTER(P)]
             L.mcpt_sequence_upsample_info.argtypes = [P, C.POINTER(D), C.POINTER(D), C.POINTER(D)]
+        if hasattr(L, "mcpt_temporal_upsample"):  # and the temporal upsampling
+            L.mcpt_upsample_phase.argtypes = [I, C.c_uint64, C.POINTER(I), C.POINTER(I)]
+            L.mcpt_camera_phase_rays.argtypes = [C.POINTER(Camera), I, I, I, I, P, P]
+            L.mcpt_camera_phase_rays_device.argtypes = L.mcpt_camera_phase_rays.argtypes
+            L.mcpt_temporal_upsample.argtypes = [C.POINTER(TemporalOpts), C.POINTER(UpsampleOpts), I, I, C.POINTER(Camera), I, I, P,
+                                                 C.POINTER(AovBuffers), C.POINTER(AovBuffers), P, P, P, P, P,
+                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(D)]
+            L.mcpt_temporal_upsample_device.argtypes = L.mcpt_temporal_upsample.argtypes
+            L.mcpt_sequence_create_temporal_upsampled.argtypes = [P, C.POINTER(RenderOpts), C.POINTER(SequenceOpts),
+                                                                  C.POINTER(TemporalOpts), C.POINTER(DenoiseOpts),
+                                                                  C.POINTER(UpsampleOpts), C.POINTER(P)]
+            L.mcpt_sequence_temporal_upsample_info.argtypes = [P, C.POINTER(I), C.POINTER(I), C.POINTER(D), C.POINTER(D),
+                                                               C.POINTER(D)]
         if hasattr(L, "mcpt_render_rays"):  # and the radiance along caller-supplied rays
             L.mcpt_render_rays.argtypes = [P, C.POINTER(RenderOpts), I, P, P, P, C.POINTER(Stats)]
             L.mcpt_render_rays_device.argtypes = L.mcpt_render_rays.argtypes
@@ -723,6 +739,88 @@ def upsample_device(width, height, color_ptr, aov_ptrs, full_aov_ptrs, out_ptr, 
     return n.value, sec.value
 
 
+def upsample_phase(factor, frame_index):
+    """mcpt_upsample_phase: the phase (a, b) of frame `frame_index` of a temporally upsampled sequence at `factor`:
+    k = frame_index mod factor^2, a = k mod factor, b = (a + k div factor) mod factor."""
+    a, b = C.c_int32(), C.c_int32()
+    _check(lib().mcpt_upsample_phase(int(factor), int(frame_index), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def camera_phase_rays(full_camera, factor, a, b, device=None):
+    """mcpt_camera_phase_rays: the rays of full_camera's pixels (factor I + a, factor J + b) as (origin, dir),
+    (H / factor) * (W / factor) x 3 each, row-major in (I, J): camera_rays(full_camera)'s rays at those pixels bit for
+    bit -- what a temporally upsampled frame of phase (a, b) traces."""
+    n = (full_camera.width // int(factor)) * (full_camera.height // int(factor)) if int(factor) > 0 else 0
+    origin, dir = np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3))
+    _check(lib().mcpt_camera_phase_rays(C.byref(full_camera), int(factor), int(a), int(b), -1 if device is None else int(device),
+                                        origin.ctypes.data, dir.ctypes.data))
+    return origin[:n], dir[:n]
+
+
+def _fill_opts(factor, fill):
+    """the UpsampleOpts of a temporal upsampling: the factor and the fill's dict"""
+    u = dict(fill or {}, factor=factor)
+    unknown = set(u) - set(UPSAMPLE_OPTS)
+    if unknown:
+        raise TypeError("unknown fill option %r (one of %s)" % (sorted(unknown)[0], ", ".join(UPSAMPLE_OPTS[1:])))
+    return _upsample_opts(*[u.get(k) for k in UPSAMPLE_OPTS], None)
+
+
+def temporal_upsample(color, full_aovs, a, b, prev=None, factor=2, fill=None, **opts):
+    """Temporal upsampling (mcpt_temporal_upsample; include/mcpt.h states the rule).  color h x w x 3 holds the radiance
+    of the full-size pixels (factor I + a, factor J + b) (render_rays over camera_phase_rays), full_aovs the guides of the
+    full-size camera at (factor h) x (factor w); prev is None or the previous FULL-SIZE state (camera, aovs, colour,
+    moments): the full-size Camera and guides of the previous frame and the colour and moments this function returned for
+    it.  fill: None or a dict of the fill's sigma_normal, sigma_plane, sigma_albedo and min_weight (UpsampleOpts; they
+    share their names with the accumulation's); opts: the fields of TemporalOpts, as for temporal_accumulate.  Returns (colour, moments (m1, m2, n, g), variance -- all full size --, the
+    number of filled pixels, the number of them that took the fallback, the device seconds)."""
+    color = _d(color)
+    h, w = color.shape[:2]
+    assert color.shape == (h, w, 3)
+    f = int(factor)
+    H, W = f * h, f * w
+    keys = ("albedo", "normal", "position", "depth")
+    g = {k: _d(full_aovs[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys}
+    B = AovBuffers(*[g[k].ctypes.data for k in keys])
+    pc = pb = pcol = pmom = None
+    if prev is not None:
+        pcam, paov, pcol, pmom = prev
+        pg = {k: _d(paov[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys[1:]}
+        pb = AovBuffers(None, *[pg[k].ctypes.data for k in keys[1:]])
+        pcol, pmom = _d(pcol, (H, W, 3)), _d(pmom, (H, W, 4))
+        pc = C.byref(pcam)
+    out, mom, var = np.zeros((H, W, 3)), np.zeros((H, W, 4)), np.zeros((H, W))
+    filled, fell, sec = C.c_uint64(), C.c_uint64(), C.c_double()
+    o, u = _temporal_opts(opts), _fill_opts(f, fill)
+    _check(lib().mcpt_temporal_upsample(
+        C.byref(o), C.byref(u), int(a), int(b), pc, w, h, color.ctypes.data, C.byref(B), None if pb is None else C.byref(pb),
+        None if pcol is None else pcol.ctypes.data, None if pmom is None else pmom.ctypes.data, out.ctypes.data,
+        mom.ctypes.data, var.ctypes.data, C.byref(filled), C.byref(fell), C.byref(sec)))
+    return out, mom, var, filled.value, fell.value, sec.value
+
+
+def temporal_upsample_device(width, height, color_ptr, full_aov_ptrs, a, b, out_color_ptr, out_moments_ptr,
+                             out_variance_ptr=None, prev=None, factor=2, fill=None, **opts):
+    """temporal_upsample over device buffers (e.g. torch CUDA float64 tensors' data_ptr()): width and height are the low
+    size, full_aov_ptrs a dict of the four full-size guides' pointers; prev is None or (full-size camera, dict of the
+    previous normal / position / depth pointers, previous colour pointer, previous moments pointer); out_variance_ptr
+    may be None.  Returns (filled count, fallback count, device seconds)."""
+    B = AovBuffers(*[int(full_aov_ptrs[k]) for k in ("albedo", "normal", "position", "depth")])
+    pc = pb = pcol = pmom = None
+    if prev is not None:
+        pcam, paov, pcol, pmom = prev
+        pb = AovBuffers(None, *[int(paov[k]) for k in ("normal", "position", "depth")])
+        pc, pcol, pmom = C.byref(pcam), C.c_void_p(int(pcol)), C.c_void_p(int(pmom))
+    filled, fell, sec = C.c_uint64(), C.c_uint64(), C.c_double()
+    o, u = _temporal_opts(opts), _fill_opts(factor, fill)
+    _check(lib().mcpt_temporal_upsample_device(
+        C.byref(o), C.byref(u), int(a), int(b), pc, int(width), int(height), C.c_void_p(int(color_ptr)), C.byref(B),
+        None if pb is None else C.byref(pb), pcol, pmom, C.c_void_p(int(out_color_ptr)), C.c_void_p(int(out_moments_ptr)),
+        None if out_variance_ptr is None else C.c_void_p(int(out_variance_ptr)), C.byref(filled), C.byref(fell), C.byref(sec)))
+    return filled.value, fell.value, sec.value
+
+
 TEMPORAL_OPTS = ("alpha", "max_history", "normal_min", "plane_max", "min_weight", "variance_min_history", "sigma_normal",
                  "sigma_plane", "sigma_albedo", "device")
 
@@ -906,10 +1004,14 @@ class FrameSequence:
     min_weight: width x height stays the render's size, the shown frame (frame()'s return, read("upsampled"),
     device_buffer("rgb8")) is F times that along each axis, reconstructed by upsample()'s rule from the shown low frame
     and the guides of camera_scaled(camera, F); upsample_info() then gives the new stages' times.
+    temporal_upsample=True (with upsample=F; no clamp, jitter or grid): every frame traces width x height rays through a
+    different 1 / F^2 subset of the full-size pixels (upsample_phase) and accumulates them in a full-size history
+    (temporal_upsample()'s rule): read("raw") is H x W x 3, accumulated / moments / variance / filtered are full size,
+    "upsampled", "fast" and "shift" are refused, and temporal_upsample_info() gives the phase and the fill's shares.
     After a frame: `info` (SequenceInfo: stage device times, kept, mean_history, clamped) and `stats` (the render's)."""
 
     def __init__(self, scene, width, height, spp, mode="mis", denoise=True, clamp=None, device=None, accel="bvh", flags=0,
-                 tone_max=None, tone_gamma=None, upsample=None, **temporal_opts):
+                 tone_max=None, tone_gamma=None, upsample=None, temporal_upsample=False, **temporal_opts):
         self.h = None
         self._destroy = lib().mcpt_sequence_destroy
         if clamp is False:
@@ -933,7 +1035,9 @@ class FrameSequence:
                 raise TypeError("unknown denoise option %r (one of %s)" % (sorted(unknown)[0], ", ".join(DENOISE_OPTS)))
             dn = _denoise_opts(*[d.get(k) for k in DENOISE_OPTS], device)
         h = C.c_void_p()
-        self.factor = 1
+        self.factor, self.temporal_upsample = 1, bool(temporal_upsample)
+        if temporal_upsample and (upsample is None or upsample is False):
+            raise ValueError("temporal_upsample=True needs upsample=F (the factor)")
         if upsample is None or upsample is False:
             _check(lib().mcpt_sequence_create(scene.h, C.byref(base), C.byref(o), C.byref(tp), None if tc is None else C.byref(tc),
                                               None if dn is None else C.byref(dn), C.byref(h)))
@@ -943,9 +1047,13 @@ class FrameSequence:
             if unknown:
                 raise TypeError("unknown upsample option %r (one of %s)" % (sorted(unknown)[0], ", ".join(UPSAMPLE_OPTS)))
             up = _upsample_opts(*[u.get(k) for k in UPSAMPLE_OPTS], device)
-            _check(lib().mcpt_sequence_create_upsampled(scene.h, C.byref(base), C.byref(o), C.byref(tp),
-                                                        None if tc is None else C.byref(tc), None if dn is None else C.byref(dn),
-                                                        C.byref(up), C.byref(h)))
+            if temporal_upsample:
+                _check(lib().mcpt_sequence_create_temporal_upsampled(scene.h, C.byref(base), C.byref(o), C.byref(tp),
+                                                                     None if dn is None else C.byref(dn), C.byref(up), C.byref(h)))
+            else:
+                _check(lib().mcpt_sequence_create_upsampled(scene.h, C.byref(base), C.byref(o), C.byref(tp),
+                                                            None if tc is None else C.byref(tc),
+                                                            None if dn is None else C.byref(dn), C.byref(up), C.byref(h)))
             self.factor = up.factor
         self.h, self.scene = h, scene  # the scene must outlive the handle
         self.width, self.height, self.spp, self.denoise, self.clamp = o.width, o.height, o.spp, bool(denoise), clamp
@@ -966,7 +1074,7 @@ class FrameSequence:
         """The last frame's buffer `name` as a float64 array: raw, accumulated, filtered, fast (H x W x 3), moments
         (H x W x 4), variance, shift (H x W); with upsample=F also upsampled (F H x F W x 3)."""
         what, tail = SEQ_BUFFERS.get(name, (-1, ()))
-        f = self.factor if name == "upsampled" else 1
+        f = self.factor if name == "upsampled" or (self.temporal_upsample and name != "raw") else 1
         out = np.zeros((f * self.height, f * self.width) + tail)
         _check(lib().mcpt_sequence_read(self.h, what, out.ctypes.data))
         return out
@@ -984,6 +1092,14 @@ class FrameSequence:
         g, u, s = C.c_double(), C.c_double(), C.c_double()
         _check(lib().mcpt_sequence_upsample_info(self.h, C.byref(g), C.byref(u), C.byref(s)))
         return dict(guide_seconds=g.value, upsample_seconds=u.value, fallback_share=s.value)
+
+    def temporal_upsample_info(self):
+        """mcpt_sequence_temporal_upsample_info of the last frame: dict of phase (a, b), rays_seconds (the phase-ray
+        kernel), filled_share and fallback_share (fill and fallback pixels / full-size pixels); temporal_upsample=True
+        only."""
+        a, b, r, s, t = C.c_int32(), C.c_int32(), C.c_double(), C.c_double(), C.c_double()
+        _check(lib().mcpt_sequence_temporal_upsample_info(self.h, C.byref(a), C.byref(b), C.byref(r), C.byref(s), C.byref(t)))
+        return dict(phase=(a.value, b.value), rays_seconds=r.value, filled_share=s.value, fallback_share=t.value)
 
     def reset(self):
         """The next frame starts every history."""

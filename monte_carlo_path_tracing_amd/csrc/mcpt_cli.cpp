@@ -42,6 +42,11 @@
 //   accumulation and the filter run at size / F, then the AOVs of the full-size camera (mcpt_camera_scaled) guide the
 //   upsampling, and --out and --hdr carry the full-size frame.  Works for a single frame, with --frames and with
 //   --frames --device-sequence (mcpt_sequence_create_upsampled); not with --adaptive, --grid or --aov-out.
+//               [--temporal-upsample]
+//   --temporal-upsample (with --frames N --device-sequence --upsample F) traces, every frame, a different 1 / F^2 subset
+//   of the full-size pixels and accumulates them in a full-size history (mcpt_sequence_create_temporal_upsampled): the
+//   same files and lines as the --upsample arm, the "upsampled" line carrying the frame's phase and the share of the
+//   pixels that were filled in.  Not with --history-clamp, --jitter, --grid or --adaptive.
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -278,7 +283,8 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
 
 // --frames --device-sequence: the same sequence through mcpt_sequence; the lines and files of render_sequence
 int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceArgs& a, const mcpt_temporal_opts& tp,
-                           const mcpt_temporal_clamp_opts* clamp, const mcpt_denoise_opts& dn, const mcpt_upsample_opts* up) {
+                           const mcpt_temporal_clamp_opts* clamp, const mcpt_denoise_opts& dn, const mcpt_upsample_opts* up,
+                           bool temporal_upsample) {
     const int W = up ? cam0.width * up->factor : cam0.width, H = up ? cam0.height * up->factor : cam0.height;  // the shown size
     const size_t npx = (size_t)W * H;
     mcpt_render_opts base;
@@ -296,8 +302,9 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
     so.width = cam0.width, so.height = cam0.height, so.spp = a.spp;
     so.denoise = a.denoise, so.clamp = clamp != nullptr;
     mcpt_sequence* seq = nullptr;
-    if ((up ? mcpt_sequence_create_upsampled(scene, &base, &so, &tp, clamp, a.denoise ? &dn : nullptr, up, &seq)
-            : mcpt_sequence_create(scene, &base, &so, &tp, clamp, a.denoise ? &dn : nullptr, &seq)) != MCPT_OK) {
+    if ((temporal_upsample ? mcpt_sequence_create_temporal_upsampled(scene, &base, &so, &tp, a.denoise ? &dn : nullptr, up, &seq)
+         : up              ? mcpt_sequence_create_upsampled(scene, &base, &so, &tp, clamp, a.denoise ? &dn : nullptr, up, &seq)
+                           : mcpt_sequence_create(scene, &base, &so, &tp, clamp, a.denoise ? &dn : nullptr, &seq)) != MCPT_OK) {
         std::fprintf(stderr, "sequence setup failed: %s\n", mcpt_last_error());
         return 1;
     }
@@ -322,7 +329,17 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
         if (a.denoise)
             std::printf("  denoised: %d iterations, sigma_color %g, variance from the temporal moments, %.3f ms device\n",
                         dn.iterations, dn.sigma_color, fi.denoise_seconds * 1e3);
-        if (up) {
+        if (temporal_upsample) {
+            int32_t pa = 0, pb = 0;
+            double rsec = 0, filled = 0, share = 0;
+            if (mcpt_sequence_temporal_upsample_info(seq, &pa, &pb, &rsec, &filled, &share) != MCPT_OK) {
+                std::fprintf(stderr, "%s\n", mcpt_last_error());
+                rc = 1;
+                break;
+            }
+            std::printf("  upsampled: factor %d to %dx%d, %.2f%% of the pixels took the fallback, %.3f ms phase rays; phase (%d, %d), "
+                        "%.2f%% of the pixels filled\n", up->factor, W, H, 100.0 * share, rsec * 1e3, pa, pb, 100.0 * filled);
+        } else if (up) {
             double usec = 0, share = 0;
             if (mcpt_sequence_upsample_info(seq, nullptr, &usec, &share) != MCPT_OK) {
                 std::fprintf(stderr, "%s\n", mcpt_last_error());
@@ -338,7 +355,7 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
         }
         if (!rc && !a.hdr_out.empty()) {
             shown.resize(3 * npx);
-            if (mcpt_sequence_read(seq, up ? MCPT_SEQ_UPSAMPLED : a.denoise ? MCPT_SEQ_FILTERED : MCPT_SEQ_ACCUMULATED,
+            if (mcpt_sequence_read(seq, up && !temporal_upsample ? MCPT_SEQ_UPSAMPLED : a.denoise ? MCPT_SEQ_FILTERED : MCPT_SEQ_ACCUMULATED,
                                    shown.data()) != MCPT_OK) {
                 std::fprintf(stderr, "%s\n", mcpt_last_error());
                 rc = 1;
@@ -378,7 +395,7 @@ int main(int argc, char** argv) {
     bool device_sequence = false;
     mcpt_temporal_clamp_opts tc;
     mcpt_temporal_clamp_opts_init(&tc);
-    bool upsample = false;
+    bool upsample = false, temporal_upsample = false;
     mcpt_upsample_opts up;
     mcpt_upsample_opts_init(&up);
     for (int a = 1; a < argc; a++) {
@@ -446,6 +463,7 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--clamp-alpha-fast")) tc.alpha_fast = std::atof(next()), clamp_flag = sequence_flag = true;
         else if (!std::strcmp(argv[a], "--device-sequence")) device_sequence = true;
         else if (!std::strcmp(argv[a], "--upsample")) up.factor = std::atoi(next()), upsample = true;
+        else if (!std::strcmp(argv[a], "--temporal-upsample")) temporal_upsample = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -469,6 +487,19 @@ int main(int argc, char** argv) {
         }
         if (grid) {
             std::fprintf(stderr, "--jitter traces its camera rays over the BVH; drop --grid\n");
+            return 2;
+        }
+    }
+    if (temporal_upsample) {  // refused before anything is loaded
+        const char* why = !upsample          ? "accumulates at --upsample F times the traced size; add --upsample F"
+                          : !device_sequence ? "runs in the device-resident sequence; add --frames N --device-sequence"
+                          : history_clamp    ? "has no history clamp; drop --history-clamp"
+                          : (flags & MCPT_RENDER_PIXEL_JITTER) ? "traces through the full-size pixels' centres; drop --jitter"
+                          : grid             ? "traces its rays over the BVH; drop --grid"
+                          : adaptive         ? "accumulates plain samples; drop --adaptive"
+                                             : nullptr;
+        if (why) {
+            std::fprintf(stderr, "--temporal-upsample %s\n", why);
             return 2;
         }
     }
@@ -561,7 +592,7 @@ int main(int argc, char** argv) {
             return 2;
         }
         const mcpt_upsample_opts* upp = upsample ? &up : nullptr;
-        const int rc = device_sequence ? render_sequence_device(scene, cam, sa, tp, history_clamp ? &tc : nullptr, dn, upp)
+        const int rc = device_sequence ? render_sequence_device(scene, cam, sa, tp, history_clamp ? &tc : nullptr, dn, upp, temporal_upsample)
                                        : render_sequence(scene, cam, sa, devices, tp, history_clamp ? &tc : nullptr, dn, upp);
         mcpt_scene_destroy(scene);
         return rc;

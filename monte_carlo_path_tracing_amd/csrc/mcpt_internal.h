@@ -155,4 +155,21 @@ int upsample_check_opts(const mcpt_upsample_opts* o);
 int upsample_enqueue(const mcpt_upsample_opts* o, int32_t w, int32_t h, const double* dC, const mcpt_aov_buffers* g,
                      const mcpt_aov_buffers* G, double* dOut, unsigned long long* dCount);
 
+// temporal.hip -- k_temporal_spatial alone, for temporal_upsample.hip: V_0 of dOutC with the guides g and o's sigmas
+// into dOutV wherever the moments dOutM fail the temporal variance's condition; no check, the null stream
+int temporal_spatial_enqueue(const mcpt_temporal_opts* o, int32_t W, int32_t H, const mcpt_aov_buffers* g, const double* dOutC,
+                             const double* dOutM, double* dOutV);
+
+// temporal_upsample.hip -- the temporal upsampling in the same form: every check of mcpt_temporal_upsample_device that
+// needs no device, then the counts' memset and the kernels on the null stream.  dCounts: two 64-bit words of device
+// memory (filled, fallback).
+int temporal_upsample_enqueue(const mcpt_temporal_opts* tp, const mcpt_upsample_opts* up, int32_t a, int32_t b,
+                              const mcpt_camera* prev_full_cam, int32_t w, int32_t h, const double* dC, const mcpt_aov_buffers* G,
+                              const mcpt_aov_buffers* pG, const double* dpC, const double* dpM, double* dOut, double* dOutM,
+                              double* dOutV, unsigned long long* dCounts);
+
+// render.hip -- mcpt_camera_phase_rays_device's checks that need no device, then its kernel on the null stream of the
+// current device
+int camera_phase_rays_enqueue(const mcpt_camera* full_cam, int32_t factor, int32_t a, int32_t b, double* dOrigin, double* dDir);
+
 }  // namespace mcpt

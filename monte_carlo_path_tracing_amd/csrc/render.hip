@@ -1288,6 +1288,18 @@ __global__ __launch_bounds__(256) void k_camera_rays(CamFrame cam, uint64_t seed
     dir[3 * (size_t)p] = rd.x, dir[3 * (size_t)p + 1] = rd.y, dir[3 * (size_t)p + 2] = rd.z;
 }
 
+// mcpt_camera_phase_rays: ray r = I * w + J of the w x h low frame is the pixel-centre ray of the full-size camera's
+// pixel (f I + a, f J + b), by the same function
+__global__ __launch_bounds__(256) void k_camera_phase_rays(CamFrame cam, int f, int a, int b, int w, int h, double* origin,
+                                                           double* dir) {
+    const int r = blockIdx.x * 256 + (int)threadIdx.x;
+    if (r >= w * h) return;
+    const int p = (f * (r / w) + a) * cam.W + f * (r % w) + b;
+    const d3 rd = pixel_ray_dir(cam, 0, p, 0, false);
+    origin[3 * (size_t)r] = cam.eye.x, origin[3 * (size_t)r + 1] = cam.eye.y, origin[3 * (size_t)r + 2] = cam.eye.z;
+    dir[3 * (size_t)r] = rd.x, dir[3 * (size_t)r + 1] = rd.y, dir[3 * (size_t)r + 2] = rd.z;
+}
+
 // moves nodes [sb, sb + m) of src to [db, db + m) of dst (every field a generation carries into the
 // next: point, normal, wo, throughput, facet, pixel, sample, node id) -- the spill stack's push and
 // pop when a generation is larger than its children buffer can take (WavefrontRun::balance_spill)
@@ -6580,6 +6592,50 @@ int light_prep_query(mcpt_scene* sc, int32_t n, const double* x1, const double* 
 
 }  // namespace
 
+// mcpt_internal.h: the phase rays for a caller that owns the buffers (sequence.hip)
+namespace mcpt {
+
+// every check of mcpt_camera_phase_rays[_device] that needs no device
+static int camera_phase_rays_check(const mcpt_camera* cam, int32_t f, int32_t a, int32_t b, const double* dOrigin, const double* dDir) {
+    if (!cam || !dOrigin || !dDir) {
+        set_error("mcpt_camera_phase_rays: null argument: %s", !cam ? "full_cam" : !dOrigin ? "origin" : "dir");
+        return MCPT_E_INVALID;
+    }
+    int rc;
+    if ((rc = validate_camera(cam))) return rc;
+    if (f < 2 || f > 4) {
+        set_error("mcpt_camera_phase_rays: factor %d is outside 2..4", f);
+        return MCPT_E_INVALID;
+    }
+    if (cam->width % f || cam->height % f) {
+        set_error("mcpt_camera_phase_rays: the full-size camera's width %d and height %d must be divisible by the factor %d",
+                  cam->width, cam->height, f);
+        return MCPT_E_INVALID;
+    }
+    if ((long long)cam->width * cam->height > (1ll << 28)) {
+        set_error("mcpt_camera_phase_rays: invalid frame size: width %d, height %d (the full frame may hold 2^28 pixels)",
+                  cam->width, cam->height);
+        return MCPT_E_INVALID;
+    }
+    if (a < 0 || a >= f || b < 0 || b >= f) {
+        set_error("mcpt_camera_phase_rays: invalid phase (%d, %d): both must lie in [0, factor = %d)", a, b, f);
+        return MCPT_E_INVALID;
+    }
+    return MCPT_OK;
+}
+
+int camera_phase_rays_enqueue(const mcpt_camera* cam, int32_t f, int32_t a, int32_t b, double* dOrigin, double* dDir) {
+    int rc;
+    if ((rc = camera_phase_rays_check(cam, f, a, b, dOrigin, dDir))) return rc;
+    const CamFrame cf = cam_setup(*cam);
+    const int w = cam->width / f, h = cam->height / f;
+    hipLaunchKernelGGL(k_camera_phase_rays, dim3((w * h + 255) / 256), dim3(256), 0, 0, cf, f, a, b, w, h, dOrigin, dDir);
+    HIP_OK(hipGetLastError());
+    return MCPT_OK;
+}
+
+}  // namespace mcpt
+
 // ============================================================================================
 // C ABI
 // ============================================================================================
@@ -6939,6 +6995,56 @@ int mcpt_camera_rays(const mcpt_camera* cam, uint64_t seed, int32_t sample, int3
     HIP_OK(hipMemcpy(origin, d, bytes, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(dir, d + 3 * (size_t)npx, bytes, hipMemcpyDeviceToHost));
     return MCPT_OK;
+}
+
+// both forms of mcpt_camera_phase_rays; host: origin and dir are host arrays
+static int camera_phase_rays(const mcpt_camera* cam, int32_t f, int32_t a, int32_t b, int32_t device, double* origin, double* dir,
+                             bool host) {
+    int rc;
+    if ((rc = camera_phase_rays_check(cam, f, a, b, origin, dir))) return rc;
+    struct Restore {  // the caller's current device
+        int prev = -1;
+        ~Restore() {
+            if (prev >= 0) (void)hipSetDevice(prev);
+        }
+    } restore;
+    if (device >= 0) {
+        HIP_OK(hipGetDevice(&restore.prev));
+        HIP_OK(hipSetDevice(device));
+    }
+    if (!host) {
+        int cur = 0;
+        HIP_OK(hipGetDevice(&cur));
+        if ((rc = check_device_buffer(origin, cur, "dev_origin")) || (rc = check_device_buffer(dir, cur, "dev_dir"))) return rc;
+        // the caller's arrays may still be in use by work on other streams (e.g. torch's)
+        HIP_OK(hipDeviceSynchronize());
+        if ((rc = camera_phase_rays_enqueue(cam, f, a, b, origin, dir))) return rc;
+        HIP_OK(hipStreamSynchronize(nullptr));
+        return MCPT_OK;
+    }
+    const size_t n = (size_t)(cam->width / f) * (cam->height / f), bytes = 3 * n * sizeof(double);
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() {
+            if (p) (void)hipFree(p);
+        }
+    } buf;
+    HIP_OK(hipMalloc(&buf.p, 2 * bytes));
+    double* d = (double*)buf.p;
+    if ((rc = camera_phase_rays_enqueue(cam, f, a, b, d, d + 3 * n))) return rc;
+    HIP_OK(hipMemcpy(origin, d, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dir, d + 3 * n, bytes, hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+int mcpt_camera_phase_rays(const mcpt_camera* full_cam, int32_t factor, int32_t a, int32_t b, int32_t device, double* origin,
+                           double* dir) {
+    return camera_phase_rays(full_cam, factor, a, b, device, origin, dir, true);
+}
+
+int mcpt_camera_phase_rays_device(const mcpt_camera* full_cam, int32_t factor, int32_t a, int32_t b, int32_t device,
+                                  double* dev_origin, double* dev_dir) {
+    return camera_phase_rays(full_cam, factor, a, b, device, dev_origin, dev_dir, false);
 }
 
 void mcpt_adaptive_opts_init(mcpt_adaptive_opts* a) {

@@ -15,7 +15,10 @@
 // below, and 40 pinned bytes for the statistics and the upsampling's fallback count.  A sequence created by
 // mcpt_sequence_create_upsampled adds three stages between the filter and the tone map: the AOVs of the scaled camera
 // (mcpt_render_aovs_device again, into the full-size guides), upsample_enqueue (mcpt_internal.h) and the tone map of the
-// full-size frame; everything before them is the plain sequence's code on the plain sequence's buffers.
+// full-size frame; everything before them is the plain sequence's code on the plain sequence's buffers.  A sequence
+// created by mcpt_sequence_create_temporal_upsampled has a frame function of its own (frame_temporal_upsampled): the
+// phase rays (camera_phase_rays_enqueue), mcpt_render_rays_device into the low raw frame, the full-size AOVs,
+// temporal_upsample_enqueue and from there the plain frame's stages on full-size buffers.
 //
 // The tone map's loads are plain: lane k reads values 4 k .. 4 k + 3 (32 consecutive bytes, a wave 2 KB), stores
 // are one dword per lane.  pow is the device library's; -ffp-contract=off as everywhere.  The statistics read the
@@ -192,8 +195,15 @@ struct mcpt_sequence {
     mcpt_aov_buffers full{};      // upsampling: the guides of the scaled camera
     double* upsampled = nullptr;  // and the shown full-size colour
     unsigned long long* fallbacks = nullptr;
+    // temporal upsampling (mcpt_sequence_create_temporal_upsampled): raw is the low frame, the two sets, variance,
+    // filtered, the scratch and the statistics are full size, `full` and `upsampled` are unused
+    bool tu = false;
+    double *ray_o = nullptr, *ray_d = nullptr;  // the phase rays, npx * 3 each
+    unsigned long long* tu_counts = nullptr;    // filled, fallback
+    int phase_a = 0, phase_b = 0;               // the last frame's (mcpt_sequence_temporal_upsample_info)
+    double rays_seconds = 0, filled_share = 0;
     uint8_t* rgb8 = nullptr;
-    StatsOut* host_stats = nullptr;  // pinned; one more word behind it: the fallback count
+    StatsOut* host_stats = nullptr;  // pinned; one more word behind it: the fallback count (tu: two more, its filled and fallback)
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     double guide_seconds = 0, upsample_seconds = 0, fallback_share = 0;  // the last frame's (mcpt_sequence_upsample_info)
     int cur = 0;            // the set the next frame writes
@@ -225,11 +235,17 @@ int locate(mcpt_sequence* s, int32_t what, bool allow_rgb8, const void** dev, si
         return MCPT_E_INVALID;
     }
     const mcpt_sequence::Set& L = s->set[s->cur ^ 1];
-    const size_t d = sizeof(double), n = s->npx;
+    const size_t d = sizeof(double), n = s->tu ? s->NPX : s->npx;  // temporal upsampling: all but RAW are full size
     const void* p = nullptr;
     size_t b = 0;
+    if (s->tu && (what == MCPT_SEQ_FAST || what == MCPT_SEQ_SHIFT || what == MCPT_SEQ_UPSAMPLED)) {
+        set_error("%s: a temporally upsampled sequence has no such buffer (its full-size frame is MCPT_SEQ_ACCUMULATED or "
+                  "MCPT_SEQ_FILTERED; the history clamp is not available)",
+                  what == MCPT_SEQ_FAST ? "MCPT_SEQ_FAST" : what == MCPT_SEQ_SHIFT ? "MCPT_SEQ_SHIFT" : "MCPT_SEQ_UPSAMPLED");
+        return MCPT_E_INVALID;
+    }
     switch (what) {
-        case MCPT_SEQ_RAW: p = s->raw, b = 3 * n * d; break;
+        case MCPT_SEQ_RAW: p = s->raw, b = 3 * s->npx * d; break;
         case MCPT_SEQ_ACCUMULATED: p = L.color, b = 3 * n * d; break;
         case MCPT_SEQ_MOMENTS: p = L.moments, b = 4 * n * d; break;
         case MCPT_SEQ_VARIANCE: p = s->variance, b = n * d; break;
@@ -342,10 +358,10 @@ void mcpt_sequence_opts_init(mcpt_sequence_opts* o) {
     o->tone_gamma = 0.25;
 }
 
-// both constructors; up == nullptr: mcpt_sequence_create
+// the three constructors; up == nullptr: mcpt_sequence_create; tu: mcpt_sequence_create_temporal_upsampled
 static int sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, const mcpt_sequence_opts* o,
                            const mcpt_temporal_opts* tp, const mcpt_temporal_clamp_opts* tc, const mcpt_denoise_opts* dn,
-                           const mcpt_upsample_opts* up, mcpt_sequence** out) {
+                           const mcpt_upsample_opts* up, mcpt_sequence** out, bool tu = false) {
     if (!scene || !base || !o || !out) {
         set_error("mcpt_sequence_create: null argument: %s", !scene ? "scene" : !base ? "base" : !o ? "opts" : "out");
         return MCPT_E_INVALID;
@@ -380,6 +396,19 @@ static int sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, cons
     }
     if ((base->flags & MCPT_RENDER_PIXEL_JITTER) && base->accel == MCPT_ACCEL_GRID) {
         set_error("MCPT_RENDER_PIXEL_JITTER is not supported with MCPT_ACCEL_GRID (the jittered roots are traced over the BVH)");
+        return MCPT_E_INVALID;
+    }
+    if (tu && base->accel == MCPT_ACCEL_GRID) {
+        set_error("temporal upsampling: MCPT_ACCEL_GRID is not supported (the phase rays are traced by mcpt_render_rays, over the BVH)");
+        return MCPT_E_INVALID;
+    }
+    if (tu && (base->flags & MCPT_RENDER_PIXEL_JITTER)) {
+        set_error("temporal upsampling: MCPT_RENDER_PIXEL_JITTER is not supported (the phase rays go through the full-size "
+                  "pixels' centres; mcpt_render_rays refuses the flag)");
+        return MCPT_E_INVALID;
+    }
+    if (tu && o->clamp != 0) {
+        set_error("temporal upsampling: mcpt_sequence_opts.clamp must be 0 (the history clamp is not defined for this rule)");
         return MCPT_E_INVALID;
     }
     if (o->spp < 1) {
@@ -429,6 +458,34 @@ static int sequence_create(mcpt_scene* scene, const mcpt_render_opts* base, cons
     Scratch S;  // restores the caller's device
     if ((rc = select_device(base->device, S, &s->device))) return rc;
     s->base.device = s->tp.device = s->dn.device = s->device;
+    if (tu) {  // the low raw frame and its rays; everything else at the full size
+        s->tu = true;
+        const size_t words = 9 * npx + (2 * 17 + 1 + (o->denoise ? 3 + 8 : 0)) * NPX + stats_words(NPX) + 2;
+        DN_HIP_OK(hipMalloc(&s->mem, words * 8 + 3 * NPX));
+        double* q = s->mem;
+        s->raw = q, s->ray_o = q + 3 * npx, s->ray_d = q + 6 * npx;
+        q += 9 * npx;
+        auto take = [&](size_t k) {
+            double* r = q;
+            q += k * NPX;
+            return r;
+        };
+        for (auto& t : s->set) {
+            t.g.albedo = take(3), t.g.normal = take(3), t.g.position = take(3), t.g.depth = take(1);
+            t.color = take(3), t.moments = take(4);
+        }
+        s->variance = take(1);
+        if (o->denoise) s->filtered = take(3), s->tmp = take(8);
+        s->stats_words = q;
+        q += stats_words(NPX);
+        s->tu_counts = (unsigned long long*)q;
+        s->rgb8 = (uint8_t*)(s->mem + words);  // after whole 8-byte words: 8-byte aligned
+        DN_HIP_OK(hipHostMalloc((void**)&s->host_stats, sizeof(StatsOut) + 3 * sizeof(unsigned long long)));
+        for (auto& e : s->ev) DN_HIP_OK(hipEventCreate(&e));
+        guard.s = nullptr;
+        *out = s;
+        return MCPT_OK;
+    }
     const size_t per_set = 10 + 3 + 4 + (o->clamp ? 3 : 0);
     const size_t doubles = 3 + 2 * per_set + 1 + (o->clamp ? 1 : 0) + (o->denoise ? 3 + 8 : 0);
     const size_t words = doubles * npx + stats_words(npx) + (up ? 13 * NPX + 1 : 0);
@@ -485,8 +542,9 @@ int mcpt_sequence_upsample_info(mcpt_sequence* s, double* guide_seconds, double*
         set_error("null mcpt_sequence");
         return MCPT_E_INVALID;
     }
-    if (!s->factor) {
-        set_error("mcpt_sequence_upsample_info: the sequence was created without upsampling");
+    if (!s->factor || s->tu) {
+        set_error("mcpt_sequence_upsample_info: the sequence %s", s->tu ? "upsamples temporally (use "
+                  "mcpt_sequence_temporal_upsample_info)" : "was created without upsampling");
         return MCPT_E_INVALID;
     }
     if (!s->has_last) {
@@ -496,6 +554,112 @@ int mcpt_sequence_upsample_info(mcpt_sequence* s, double* guide_seconds, double*
     if (guide_seconds) *guide_seconds = s->guide_seconds;
     if (upsample_seconds) *upsample_seconds = s->upsample_seconds;
     if (fallback_share) *fallback_share = s->fallback_share;
+    return MCPT_OK;
+}
+
+int mcpt_sequence_create_temporal_upsampled(mcpt_scene* scene, const mcpt_render_opts* base, const mcpt_sequence_opts* o,
+                                            const mcpt_temporal_opts* tp, const mcpt_denoise_opts* dn,
+                                            const mcpt_upsample_opts* up, mcpt_sequence** out) {
+    if (!up) {
+        if (out) *out = nullptr;
+        set_error("mcpt_sequence_create_temporal_upsampled: null argument: upsample");
+        return MCPT_E_INVALID;
+    }
+    return sequence_create(scene, base, o, tp, nullptr, dn, up, out, true);
+}
+
+int mcpt_sequence_temporal_upsample_info(mcpt_sequence* s, int32_t* a, int32_t* b, double* rays_seconds, double* filled_share,
+                                         double* fallback_share) {
+    if (!s) {
+        set_error("null mcpt_sequence");
+        return MCPT_E_INVALID;
+    }
+    if (!s->tu) {
+        set_error("mcpt_sequence_temporal_upsample_info: the sequence was created without temporal upsampling");
+        return MCPT_E_INVALID;
+    }
+    if (!s->has_last) {
+        set_error("the sequence holds no frame (none since create, reset or a failed frame)");
+        return MCPT_E_INVALID;
+    }
+    if (a) *a = s->phase_a;
+    if (b) *b = s->phase_b;
+    if (rays_seconds) *rays_seconds = s->rays_seconds;
+    if (filled_share) *filled_share = s->filled_share;
+    if (fallback_share) *fallback_share = s->fallback_share;
+    return MCPT_OK;
+}
+
+// a frame of a temporally upsampled sequence (the arguments are checked): ev[5] .. ev[6] the phase rays, then the traced
+// rays, ev[0] .. ev[4] as in a plain frame with every stage at the full size
+static int frame_temporal_upsampled(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed, uint8_t* out_rgb8,
+                                    mcpt_sequence_info* info, mcpt_stats* stats) {
+    const int w = s->opts.width, h = s->opts.height, f = s->factor, W = w * f, H = h * f;
+    const size_t npx = s->npx, NPX = s->NPX;
+    mcpt_sequence::Set &C = s->set[s->cur], &P = s->set[s->cur ^ 1];
+    int rc, device;
+    Scratch S;  // restores the caller's device
+    if ((rc = select_device(s->device, S, &device))) return rc;
+    int32_t pa = 0, pb = 0;
+    mcpt_camera fullcam;
+    if ((rc = mcpt_upsample_phase(f, s->frame_index, &pa, &pb)) || (rc = mcpt_camera_scaled(cam, f, &fullcam))) return rc;
+    s->has_last = false;  // the shared buffers are about to be overwritten
+    DN_HIP_OK(hipEventRecord(s->ev[5], nullptr));
+    if ((rc = mcpt::camera_phase_rays_enqueue(&fullcam, f, pa, pb, s->ray_o, s->ray_d))) return rc;
+    DN_HIP_OK(hipEventRecord(s->ev[6], nullptr));
+    DN_HIP_OK(hipMemsetAsync(s->raw, 0, 3 * npx * sizeof(double), nullptr));
+    mcpt_render_opts ro = s->base;
+    ro.seed = seed;
+    mcpt_stats st{};
+    mcpt_render_opts rs = ro;  // the library's own stats struct, whatever the caller's size
+    rs.stats_size = sizeof st;
+    if ((rc = mcpt_render_rays_device(s->scene, &rs, (int32_t)npx, s->ray_o, s->ray_d, s->raw, &st))) return rc;
+    DN_HIP_OK(hipSetDevice(device));
+    DN_HIP_OK(hipEventRecord(s->ev[0], nullptr));
+    if ((rc = mcpt_render_aovs_device(s->scene, &fullcam, &ro, &C.g))) return rc;
+    DN_HIP_OK(hipSetDevice(device));
+    DN_HIP_OK(hipEventRecord(s->ev[1], nullptr));
+    const bool hp = s->has_prev;
+    if ((rc = mcpt::temporal_upsample_enqueue(&s->tp, &s->up, pa, pb, hp ? &P.cam : nullptr, w, h, s->raw, &C.g, hp ? &P.g : nullptr,
+                                              hp ? P.color : nullptr, hp ? P.moments : nullptr, C.color, C.moments, s->variance,
+                                              s->tu_counts)))
+        return rc;
+    StatsOut* dres = nullptr;
+    if ((rc = enqueue_stats(C.moments, nullptr, NPX, s->stats_words, &dres))) return rc;
+    DN_HIP_OK(hipEventRecord(s->ev[2], nullptr));
+    const double* shown = C.color;
+    if (s->opts.denoise) {
+        if ((rc = mcpt::denoise_enqueue(&s->dn, W, H, C.color, s->variance, &C.g, s->filtered, nullptr, s->tmp))) return rc;
+        shown = s->filtered;
+    }
+    DN_HIP_OK(hipEventRecord(s->ev[3], nullptr));
+    if ((rc = enqueue_tone_map(shown, 3 * NPX, s->opts.tone_max, s->opts.tone_gamma, s->rgb8))) return rc;
+    DN_HIP_OK(hipEventRecord(s->ev[4], nullptr));
+    unsigned long long* hcounts = (unsigned long long*)(s->host_stats + 1) + 1;
+    DN_HIP_OK(hipMemcpyAsync(s->host_stats, dres, sizeof(StatsOut), hipMemcpyDeviceToHost, nullptr));
+    DN_HIP_OK(hipMemcpyAsync(hcounts, s->tu_counts, 2 * sizeof *hcounts, hipMemcpyDeviceToHost, nullptr));
+    if (out_rgb8) DN_HIP_OK(hipMemcpyAsync(out_rgb8, s->rgb8, 3 * NPX, hipMemcpyDeviceToHost, nullptr));
+    DN_HIP_OK(hipStreamSynchronize(nullptr));
+    float ms[5] = {0, 0, 0, 0, 0};
+    for (int k = 0; k < 4; k++) DN_HIP_OK(hipEventElapsedTime(&ms[k], s->ev[k], s->ev[k + 1]));
+    DN_HIP_OK(hipEventElapsedTime(&ms[4], s->ev[5], s->ev[6]));
+    s->phase_a = pa, s->phase_b = pb;
+    s->rays_seconds = ms[4] * 1e-3;
+    s->filled_share = (double)hcounts[0] / (double)NPX;
+    s->fallback_share = (double)hcounts[1] / (double)NPX;
+    mcpt_sequence_info fi{};
+    fi.render_seconds = st.seconds;
+    fi.aov_seconds = ms[0] * 1e-3, fi.temporal_seconds = ms[1] * 1e-3;
+    fi.denoise_seconds = s->opts.denoise ? ms[2] * 1e-3 : 0.0, fi.tonemap_seconds = ms[3] * 1e-3;
+    fi.kept = (double)s->host_stats->kept / (double)NPX;
+    fi.mean_history = s->host_stats->nsum / (double)NPX;
+    fi.frame_index = s->frame_index;
+    if (info) std::memcpy((void*)info, &fi, s->opts.info_size < sizeof fi ? s->opts.info_size : sizeof fi);
+    if (stats) std::memcpy((void*)stats, &st, s->base.stats_size < sizeof st ? s->base.stats_size : sizeof st);
+    C.cam = fullcam;
+    s->cur ^= 1;
+    s->has_prev = s->has_last = true;
+    s->frame_index++;
     return MCPT_OK;
 }
 
@@ -514,6 +678,7 @@ int mcpt_sequence_frame(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed,
         set_error("invalid camera");
         return MCPT_E_INVALID;
     }
+    if (s->tu) return frame_temporal_upsampled(s, cam, seed, out_rgb8, info, stats);
     const int W = s->opts.width, H = s->opts.height;
     const size_t npx = s->npx;
     mcpt_sequence::Set &C = s->set[s->cur], &P = s->set[s->cur ^ 1];

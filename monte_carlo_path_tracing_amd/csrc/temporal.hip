@@ -449,6 +449,19 @@ int temporal_enqueue(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t
     return enqueue_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, io ? &ca : nullptr);
 }
 
+int temporal_spatial_enqueue(const mcpt_temporal_opts* o, int32_t W, int32_t H, const mcpt_aov_buffers* g, const double* dOutC,
+                             const double* dOutM, double* dOutV) {
+    TpParams P{};  // what k_temporal_spatial reads of it
+    P.W = W, P.H = H;
+    P.var_n = o->variance_min_history - 0.5;
+    P.outC = const_cast<double*>(dOutC), P.outM = const_cast<double*>(dOutM), P.outV = dOutV;
+    const DnParams D{W, H, 0.0, o->sigma_normal, o->sigma_plane, o->sigma_albedo, g->albedo, g->normal, g->position, g->depth};
+    const dim3 grid((W + kBx - 1) / kBx, (H + kBy - 1) / kBy), block(kBx, kBy);
+    hipLaunchKernelGGL(k_temporal_spatial, grid, block, 0, nullptr, P, D);
+    DN_HIP_OK(hipGetLastError());
+    return MCPT_OK;
+}
+
 }  // namespace mcpt
 
 extern "C" {
