@@ -37,7 +37,9 @@ extern "C" {
                                * (mcpt_render_rays and its _device form, mcpt_camera_rays, the flag
                                * MCPT_RENDER_PIXEL_JITTER); guided upsampling (mcpt_upsample_opts, mcpt_upsample and its
                                * _device form, mcpt_camera_scaled, mcpt_sequence_create_upsampled,
-                               * mcpt_sequence_upsample_info, the selector MCPT_SEQ_UPSAMPLED);
+                               * mcpt_sequence_upsample_info, the selector MCPT_SEQ_UPSAMPLED); in-place geometry
+                               * updates with a device-side BVH refit (mcpt_update_stats, mcpt_scene_update and its
+                               * _device form);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -266,6 +268,52 @@ int mcpt_scene_arrays(const mcpt_scene* scene, float* positions, float* normals,
 /* the XML's <camera> block (README.md:339-343; ignored by the reference main.cpp:507-510) */
 int mcpt_scene_camera(const mcpt_scene* scene, mcpt_camera* cam);
 
+/* In-place geometry update: facets [first, first + count) get new vertex positions (and, unless `normals` is
+ * NULL, new vertex normals); no reference interface corresponds (the reference loads one static scene).
+ *
+ * The rule: after a successful call the scene behaves as one made by mcpt_scene_create from the new arrays would,
+ * for every entry point that takes the handle -- mcpt_closest_hit and mcpt_primary_hits return the same facet and
+ * (t, beta, gamma) bit for bit (closest hits are a total order on (t, facet), so they do not depend on how tight the
+ * refit boxes are), renders are equal up to the order of the framebuffer's fp64 atomics, and mcpt_scene_arrays returns
+ * the new positions and normals with the unique normals of the updated facets recomputed as at load time.  The topology
+ * of the BVH stays: on the host the binary tree's boxes are refit, and on every device the scene already lives on the
+ * facet and leaf arrays are rewritten and the 4-wide tree's boxes (fp32 and 64-byte quantised nodes) are refit by
+ * kernels, level by level; no rebuild, no light-table upload, no new buffers.  The call takes the scene's lock (one
+ * render or update at a time per handle); with a communicator every rank must make the same update call.
+ *
+ * The arena: the scene keeps the bounding box and the box margin (1e-5 of the largest axis extent `ext` + 1e-6) of its
+ * build; positions must stay inside that box grown by `ext` on every side, which keeps the traversals' fp32 plane
+ * arithmetic inside the margin.
+ *
+ * Refused with MCPT_E_INVALID and a message, before anything on the host or on any device is modified: a NULL scene
+ * or NULL positions; count < 1, first < 0 or first + count > nfacets; a stats struct_size mismatch; a facet of the
+ * range that is a light triangle (lights cannot move: the first such facet is named); a non-finite position or normal;
+ * a position outside the arena; in the device form a pointer that is not device memory on `device`.
+ *
+ * An update invalidates the host grid (the next MCPT_ACCEL_GRID render or mcpt_scene_meshing call rebuilds it from the
+ * new positions; MCPT_HIT_GRID queries need a new mcpt_scene_meshing call) and the opt-in 8-wide debug trees (refused
+ * for the handle from its first update on, include/mcpt_debug.h).  Not covered: light triangles, topology or facet
+ * count changes, a rebuild when the refit tree's quality degrades, motion vectors for the temporal accumulation (a moved
+ * surface fails its taps' plane / normal test and restarts its history). */
+typedef struct {
+    uint32_t struct_size;       /* sizeof(mcpt_update_stats) of the caller's header (mcpt_update_stats_init sets it) */
+    int32_t facets;             /* count of the call */
+    int64_t leaf_slots;         /* leaf slots rewritten (a facet with spatial-split references has several) */
+    int64_t nodes_refit;        /* 4-wide nodes with at least one slot box recomputed, per device state; the first one's */
+    int32_t levels;             /* tree levels launched */
+    int32_t device_states;      /* device states brought up to date (0: none existed yet) */
+    double device_seconds;      /* HIP events around the kernels of the first device state (0 if none) */
+} mcpt_update_stats;
+void mcpt_update_stats_init(mcpt_update_stats* stats);
+/* host arrays: positions count*9 (v0 v1 v2 per facet), normals count*9 or NULL (keep); stats may be NULL */
+int mcpt_scene_update(mcpt_scene* scene, int32_t first, int32_t count, const float* positions, const float* normals,
+                      mcpt_update_stats* stats);
+/* the same from device memory on `device` (-1 = current): the value checks run in a kernel that counts offending
+ * values, and the host reads that count back before any modifying kernel is enqueued; the host copy of the scene is
+ * brought up to date by a device-to-host copy of the range */
+int mcpt_scene_update_device(mcpt_scene* scene, int32_t device, int32_t first, int32_t count, const float* dev_positions,
+                             const float* dev_normals, mcpt_update_stats* stats);
+
 /* main.cpp:547-588: render samples [sample_begin, sample_end) of an spp-sample frame and ADD
  * sum_k L_k * (1/spp) into out_rgb (caller-owned host buffer, height*width*3 doubles, row 0 =
  * top image row).  Devices: opts->device, or opts->devices / opts->comm (see mcpt_render_opts). */
@@ -459,7 +507,9 @@ int mcpt_variance_from_noise(int32_t width, int32_t height, const double* rgb, c
  * out_color (h*w*3), out_moments (h*w*4) and out_variance (h*w, optional) are overwritten.  The history is the
  * caller's: feed out_color / out_moments of one call as prev_color / prev_moments of the next (two sets of buffers,
  * swapped; an output may not alias an input).  The filtered colour is NOT fed back, miss pixels keep no history,
- * the geometry must not move.  Single device. */
+ * and the reprojection follows the camera only: there are no motion vectors, so a surface moved by mcpt_scene_update
+ * fails its taps' plane or normal test and restarts its history (changed shading on static surfaces, a moving
+ * shadow, is what the clamped form is for).  Single device. */
 typedef struct {
     uint32_t struct_size;  /* sizeof(mcpt_temporal_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
     int32_t max_history;   /* default 64, >= 1: the cap of the history length n */

@@ -94,6 +94,18 @@ int mcpt_debug_bvh8_check(mcpt_scene* scene, int32_t light_only, int64_t out[6])
 // the host: out = {nodes, facets reached, facets in the binary tree, facets reached twice, errors (a vertex
 // outside an ancestor slot's box, a quantized slot box not containing its fp32 box, a bad index), depth}.
 int mcpt_debug_bvh4_check(mcpt_scene* scene, int32_t light_only, int64_t out[6]);
+// The same walk over what `device` (-1 = current) holds of the scene's main tree: its 4-wide nodes (leaf codes
+// unpacked), quantized nodes and leaf slots are downloaded and walked against the host positions; vertices of a leaf
+// slot or of the device's facet array that differ from the host positions count as errors too.  The check of the
+// device-side refit (mcpt_scene_update, include/mcpt.h).
+int mcpt_debug_bvh4_check_device(mcpt_scene* scene, int32_t device, int64_t out[6]);
+// Downloads that tree: counts = {nodes, leaf slots}; nodes (128 B each), qnodes (64 B each) and leaf_facets (the
+// facet of every slot) may each be NULL, else they hold at least cap_nodes / cap_slots entries (a smaller capacity
+// than the tree has is MCPT_E_INVALID).  Lets a test compare the nodes before and after an update.
+int mcpt_debug_bvh4_download(mcpt_scene* scene, int32_t device, int64_t counts[2], void* nodes, void* qnodes,
+                             int32_t* leaf_facets, int64_t cap_nodes, int64_t cap_slots);
+/* After a scene's first mcpt_scene_update the 8-wide trees are stale: MCPT_DEBUG_RAYS_CW8, MCPT_DEBUG_HIT_CW8 and
+ * mcpt_debug_bvh8_check are refused for that handle (MCPT_E_INVALID). */
 
 /* diagnostics: the last active-pixel list the scene's most recent adaptive render built on `device` (-1 = current)
  * -- the pixels sampled by its last pass, or the list built after pass 0 when max_spp = min_spp + pass_spp.

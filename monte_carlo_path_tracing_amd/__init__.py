@@ -168,6 +168,27 @@ class Stats(C.Structure):
 _lib = None
 
 # every symbol include/mcpt.h declares (tests check the .so exports them all)
+class SceneDesc(C.Structure):
+    """mcpt_scene_desc (include/mcpt.h)"""
+    _fields_ = [("nfacets", C.c_int32), ("nmaterials", C.c_int32), ("nlights", C.c_int32), ("positions", C.c_void_p),
+                ("normals", C.c_void_p), ("material_id", C.c_void_p), ("materials", C.c_void_p), ("light_facet", C.c_void_p),
+                ("light_radiance", C.c_void_p), ("light_group", C.c_void_p)]
+
+
+class UpdateStats(C.Structure):
+    """mcpt_update_stats (include/mcpt.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("facets", C.c_int32), ("leaf_slots", C.c_int64), ("nodes_refit", C.c_int64),
+                ("levels", C.c_int32), ("device_states", C.c_int32), ("device_seconds", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
+# mcpt_debug_bvh4_download's node layouts (BvhNode4 / BvhNode4Q of the library; leaf children as ~first slot, count)
+BVH4_NODE = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("child", np.int32, 4), ("count", np.int32, 4)])
+BVH4_QNODE = np.dtype([("org", np.float32, 3), ("ex", np.uint32), ("q", np.uint32, 6), ("pad", np.uint32, 2), ("child", np.int32, 4)])
+BVH4_EMPTY = 0x7fffffff
+
 EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_create", "mcpt_scene_destroy",
            "mcpt_scene_counts", "mcpt_scene_accel_bytes", "mcpt_scene_arrays", "mcpt_scene_camera", "mcpt_scene_meshing", "mcpt_scene_grid_info",
            "mcpt_render_opts_init", "mcpt_render", "mcpt_render_device",
@@ -183,10 +204,11 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_sequence_destroy", "mcpt_upsample_opts_init", "mcpt_upsample", "mcpt_upsample_device",
            "mcpt_camera_scaled", "mcpt_sequence_create_upsampled", "mcpt_sequence_upsample_info",
            "mcpt_upsample_phase", "mcpt_camera_phase_rays", "mcpt_camera_phase_rays_device", "mcpt_temporal_upsample",
-           "mcpt_temporal_upsample_device", "mcpt_sequence_create_temporal_upsampled", "mcpt_sequence_temporal_upsample_info"]
+           "mcpt_temporal_upsample_device", "mcpt_sequence_create_temporal_upsampled", "mcpt_sequence_temporal_upsample_info",
+           "mcpt_update_stats_init", "mcpt_scene_update", "mcpt_scene_update_device"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
-                 "mcpt_debug_adaptive_active"]  # include/mcpt_debug.h
+                 "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download"]  # include/mcpt_debug.h
 
 
 def lib():
@@ -297,6 +319,11 @@ def lib():
             L.mcpt_render_rays.argtypes = [P, C.POINTER(RenderOpts), I, P, P, P, C.POINTER(Stats)]
             L.mcpt_render_rays_device.argtypes = L.mcpt_render_rays.argtypes
             L.mcpt_camera_rays.argtypes = [C.POINTER(Camera), C.c_uint64, I, I, I, P, P]
+        if hasattr(L, "mcpt_scene_update"):  # and the in-place geometry updates
+            L.mcpt_update_stats_init.argtypes = [C.POINTER(UpdateStats)]
+            L.mcpt_update_stats_init.restype = None
+            L.mcpt_scene_update.argtypes = [P, I, I, P, P, C.POINTER(UpdateStats)]
+            L.mcpt_scene_update_device.argtypes = [P, I, I, I, P, P, C.POINTER(UpdateStats)]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -309,7 +336,9 @@ def lib():
                "mcpt_debug_set_collective_lib": [C.c_char_p],
                "mcpt_debug_bvh8_check": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
                "mcpt_debug_bvh4_check": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
-               "mcpt_debug_adaptive_active": [P, I, ip, I, C.POINTER(I)]}
+               "mcpt_debug_adaptive_active": [P, I, ip, I, C.POINTER(I)],
+               "mcpt_debug_bvh4_check_device": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
+               "mcpt_debug_bvh4_download": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C"), P, P, P, C.c_int64, C.c_int64]}
         for name, argt in dbg.items():
             if hasattr(L, name):
                 getattr(L, name).argtypes = argt
@@ -350,6 +379,26 @@ class Scene:
         _check(lib().mcpt_scene_load(os.fsencode(obj_path), os.fsencode(xml_path), C.byref(h)))
         return cls(h)
 
+    @classmethod
+    def create(cls, positions, normals, material_id, materials, light_facet, light_radiance, light_group=None):
+        """mcpt_scene_create: the flattened-array form (the arrays of Scene.arrays(); the library copies them).
+        light_group: optional ascending index of each light triangle's <light>."""
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 9)
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 9)
+        mat = np.ascontiguousarray(material_id, np.int32).reshape(-1)
+        mtl = np.ascontiguousarray(materials, np.float32).reshape(-1, 7)
+        lf = np.ascontiguousarray(light_facet, np.int32).reshape(-1)
+        lr = np.ascontiguousarray(light_radiance, np.float64).reshape(-1, 3)
+        lg = None if light_group is None else np.ascontiguousarray(light_group, np.int32).reshape(-1)
+        if nrm.shape != pos.shape or mat.shape[0] != pos.shape[0] or lr.shape[0] != lf.shape[0] or \
+                (lg is not None and lg.shape[0] != lf.shape[0]):
+            raise MCPTError("Scene.create: array shapes do not match")
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+        d = SceneDesc(pos.shape[0], mtl.shape[0], lf.shape[0], ptr(pos), ptr(nrm), ptr(mat), ptr(mtl), ptr(lf), ptr(lr), ptr(lg))
+        h = C.c_void_p()
+        _check(lib().mcpt_scene_create(C.byref(d), C.byref(h)))
+        return cls(h)
+
     def close(self):
         if getattr(self, "h", None):
             self._destroy(self.h)
@@ -357,6 +406,29 @@ class Scene:
 
     def __del__(self):
         self.close()
+
+    def update(self, first, positions, normals=None):
+        """mcpt_scene_update: facets [first, first + len(positions)) get new vertex positions (n x 9 floats) and,
+        unless normals is None, new vertex normals; the BVH is refit in place on the host and on every device the
+        scene lives on.  Light triangles cannot move.  Returns the call's mcpt_update_stats as a dict."""
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 9)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 9)
+        if nrm is not None and nrm.shape != pos.shape:
+            raise MCPTError("Scene.update: normals must match positions")
+        st = UpdateStats()
+        lib().mcpt_update_stats_init(C.byref(st))
+        _check(lib().mcpt_scene_update(self.h, int(first), pos.shape[0], pos.ctypes.data_as(C.c_void_p),
+                                       None if nrm is None else nrm.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return st.as_dict()
+
+    def update_device(self, first, count, positions_ptr, normals_ptr=None, device=None):
+        """mcpt_scene_update_device: the same from device memory (count x 9 floats each) on `device`."""
+        st = UpdateStats()
+        lib().mcpt_update_stats_init(C.byref(st))
+        _check(lib().mcpt_scene_update_device(self.h, -1 if device is None else int(device), int(first), int(count),
+                                              C.c_void_p(positions_ptr), C.c_void_p(normals_ptr) if normals_ptr else None,
+                                              C.byref(st)))
+        return st.as_dict()
 
     def arrays(self):
         F, M, NL = self.nfacets, self.nmaterials, self.nlights
@@ -1196,6 +1268,27 @@ def debug_bvh4_check(scene, light_only=False):
     out = np.zeros(6, np.int64)
     _check(lib().mcpt_debug_bvh4_check(scene.h, 1 if light_only else 0, out))
     return dict(zip(("nodes", "tris", "facets", "duplicates", "errors", "depth"), (int(v) for v in out)))
+
+
+def debug_bvh4_check_device(scene, device=-1):
+    """Diagnostics: debug_bvh4_check's walk over what `device` holds of the main tree (nodes, quantized nodes, leaf
+    slots), plus the device's vertices against the host positions (include/mcpt_debug.h).  Same dict."""
+    out = np.zeros(6, np.int64)
+    _check(lib().mcpt_debug_bvh4_check_device(scene.h, int(device), out))
+    return dict(zip(("nodes", "tris", "facets", "duplicates", "errors", "depth"), (int(v) for v in out)))
+
+
+def debug_bvh4_download(scene, device=-1):
+    """Diagnostics: the device's main 4-wide tree as (nodes [BVH4_NODE], quantized nodes [BVH4_QNODE], facet of every
+    leaf slot); leaf children read ~first slot with their count in "count" (include/mcpt_debug.h)."""
+    counts = np.zeros(2, np.int64)
+    _check(lib().mcpt_debug_bvh4_download(scene.h, int(device), counts, None, None, None, 0, 0))
+    nodes, qn = np.zeros(int(counts[0]), BVH4_NODE), np.zeros(int(counts[0]), BVH4_QNODE)
+    lf = np.zeros(max(int(counts[1]), 1), np.int32)
+    _check(lib().mcpt_debug_bvh4_download(scene.h, int(device), counts, nodes.ctypes.data_as(C.c_void_p),
+                                          qn.ctypes.data_as(C.c_void_p), lf.ctypes.data_as(C.c_void_p), nodes.shape[0],
+                                          lf.shape[0]))
+    return nodes, qn, lf[:int(counts[1])]
 
 
 def debug_tri_filter(tri, ro, rd, tlim=None):

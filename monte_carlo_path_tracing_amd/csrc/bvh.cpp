@@ -646,6 +646,99 @@ std::vector<BvhNode4Q> quantize_bvh4(const std::vector<BvhNode4>& in) {
     return out;
 }
 
+// ---- refit after mcpt_scene_update ----
+BvhRefitIndex make_bvh_refit_index(const Bvh& b) {
+    BvhRefitIndex ix;
+    ix.parent.assign(b.nodes.size(), -1);
+    ix.slot_owner.assign(b.leaf_facets.size(), -1);
+    for (size_t n = 0; n < b.nodes.size(); n++)
+        for (int k = 0; k < 2; k++) {
+            const int32_t c = b.nodes[n].child[k];
+            if (c >= 0) {
+                ix.parent[c] = static_cast<int32_t>(2 * n + k);
+            } else {
+                for (int32_t j = ~c; j < ~c + b.nodes[n].count[k]; j++) ix.slot_owner[j] = static_cast<int32_t>(2 * n + k);
+            }
+        }
+    return ix;
+}
+
+void box_with_margin(const double lo[3], const double hi[3], double margin, float* flo, float* fhi) {
+    for (int c = 0; c < 3; c++) {
+        flo[c] = std::nextafter(static_cast<float>(lo[c] - margin), -FLT_MAX);
+        fhi[c] = std::nextafter(static_cast<float>(hi[c] + margin), FLT_MAX);
+    }
+}
+
+void refit_bvh(Bvh& b, const BvhRefitIndex& ix, const HostScene& s, const std::vector<int32_t>& slots, double margin) {
+    // the leaves that hold a moved triangle: full bounds of every triangle of the leaf (a static triangle's full
+    // bounds contain its clipped reference, and they do not grow from update to update)
+    // the builders push a node before its children, so a child's index is larger than its parent's: taking the
+    // dirty nodes in descending order finishes every child before its parent reads it
+    // (a sorted list and a heap for a few slots; for many, marks and one descending sweep over the nodes are cheaper)
+    const bool sweep = slots.size() > b.nodes.size() / 64;
+    std::vector<uint8_t> mark(sweep ? b.nodes.size() : 0, 0);
+    std::vector<int32_t> leaves;
+    leaves.reserve(slots.size());
+    if (sweep) {
+        std::vector<uint8_t> seen(2 * b.nodes.size(), 0);
+        for (int32_t q : slots)
+            if (!seen[ix.slot_owner[q]]) seen[ix.slot_owner[q]] = 1, leaves.push_back(ix.slot_owner[q]);
+    } else {
+        for (int32_t q : slots) leaves.push_back(ix.slot_owner[q]);
+        std::sort(leaves.begin(), leaves.end());
+        leaves.erase(std::unique(leaves.begin(), leaves.end()), leaves.end());
+    }
+    std::vector<int32_t> heap;
+    auto push = [&](int32_t n) {
+        if (sweep) {
+            mark[n] = 1;
+            return;
+        }
+        heap.push_back(n);
+        std::push_heap(heap.begin(), heap.end());
+    };
+    auto lift = [&](int32_t n) {  // the slot of n's parent that holds n: the union of n's two slot boxes
+        const int32_t up = ix.parent[n];
+        if (up < 0) return;
+        const BvhNode& nd = b.nodes[n];
+        BvhNode& pn = b.nodes[up >> 1];
+        const int k = up & 1;
+        for (int c = 0; c < 3; c++) {
+            pn.lo[k][c] = std::min(nd.lo[0][c], nd.lo[1][c]);
+            pn.hi[k][c] = std::max(nd.hi[0][c], nd.hi[1][c]);
+        }
+        push(up >> 1);
+    };
+    for (int32_t code : leaves) {
+        BvhNode& nd = b.nodes[code >> 1];
+        const int k = code & 1;
+        Box bx;
+        for (int32_t j = ~nd.child[k]; j < ~nd.child[k] + nd.count[k]; j++)
+            for (int v = 0; v < 3; v++) {
+                const float* p = &s.pos[9 * static_cast<size_t>(b.leaf_facets[j]) + 3 * v];
+                const double d[3] = {p[0], p[1], p[2]};
+                bx.grow(d);
+            }
+        box_with_margin(bx.lo, bx.hi, margin, nd.lo[k], nd.hi[k]);
+        push(code >> 1);
+    }
+    if (sweep) {
+        for (int32_t n = static_cast<int32_t>(b.nodes.size()) - 1; n > 0; n--)
+            if (mark[n]) lift(n);
+        return;
+    }
+    int32_t last = -1;
+    while (!heap.empty()) {
+        std::pop_heap(heap.begin(), heap.end());
+        const int32_t n = heap.back();
+        heap.pop_back();
+        if (n == last) continue;  // pushed by both of its children
+        last = n;
+        lift(n);
+    }
+}
+
 // ---- 8-wide compressed tree (BvhNode8Q) ----
 namespace {
 struct BN {  // binary node with its own box: inner (l, r >= 0) or leaf (first, count <= 2 after splitting)

@@ -47,6 +47,11 @@
 //   of the full-size pixels and accumulates them in a full-size history (mcpt_sequence_create_temporal_upsampled): the
 //   same files and lines as the --upsample arm, the "upsampled" line carrying the frame's phase and the share of the
 //   pixels that were filled in.  Not with --history-clamp, --jitter, --grid or --adaptive.
+//               [--move FIRST:COUNT:DX,DY,DZ]
+//   --move (with --frames N, with or without --device-sequence) animates facets [FIRST, FIRST + COUNT): before frame
+//   k >= 1 they are set to float(double(original) + k * (DX, DY, DZ)) by mcpt_scene_update (the BVH is refit in place, no
+//   rebuild), and the frame prints a "moved" line with the update's statistics.  A range with a light triangle, or a
+//   step that leaves the scene's arena, ends the run with the library's message.
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -56,6 +61,7 @@
 //   --progress prints the share of camera samples dispatched (the reference prints per-row progress
 //   and updates its EasyX window, main.cpp:539-592) through mcpt_render_opts.progress.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -144,12 +150,54 @@ std::string frame_path(const std::string& path, int k) {
     return path.substr(0, dot) + tag + path.substr(dot);
 }
 
+// --move FIRST:COUNT:DX,DY,DZ: before frame k >= 1 facets [first, first + count) are set to
+// float(double(original) + k * d) through mcpt_scene_update, from the original arrays so that nothing drifts
+struct Mover {
+    int32_t first = 0, count = 0;
+    double d[3] = {0, 0, 0};
+    std::vector<float> original, moved;
+    bool parse(const char* arg) {
+        char tail = 0;
+        return std::sscanf(arg, "%d:%d:%lf,%lf,%lf%c", &first, &count, &d[0], &d[1], &d[2], &tail) == 5 && first >= 0 && count >= 1 &&
+               std::isfinite(d[0]) && std::isfinite(d[1]) && std::isfinite(d[2]);
+    }
+    // the range against the scene (a light facet in it is the library's refusal, at the first update)
+    int bind(mcpt_scene* scene) {
+        int32_t nf = 0;
+        mcpt_scene_counts(scene, &nf, nullptr, nullptr);
+        if ((int64_t)first + count > nf) {
+            std::fprintf(stderr, "--move: facets [%d, %lld) are not in the scene's %d\n", first, (long long)first + count, nf);
+            return 2;
+        }
+        std::vector<float> all(9 * (size_t)nf);
+        mcpt_scene_arrays(scene, all.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+        original.assign(all.begin() + 9 * (size_t)first, all.begin() + 9 * ((size_t)first + count));
+        moved.resize(original.size());
+        return 0;
+    }
+    int apply(mcpt_scene* scene, int k) {
+        if (k < 1) return 0;
+        for (size_t i = 0; i < original.size(); i++) moved[i] = (float)((double)original[i] + k * d[i % 3]);
+        mcpt_update_stats us;
+        mcpt_update_stats_init(&us);
+        if (mcpt_scene_update(scene, first, count, moved.data(), nullptr, &us) != MCPT_OK) {
+            std::fprintf(stderr, "--move failed: %s\n", mcpt_last_error());
+            return 1;
+        }
+        std::printf("  moved facets [%d, %d) by %d x (%g, %g, %g): %lld leaf slots, %lld nodes refit on %d levels, %.3f ms device\n",
+                    first, first + count, k, d[0], d[1], d[2], (long long)us.leaf_slots, (long long)us.nodes_refit, us.levels,
+                    us.device_seconds * 1e3);
+        return 0;
+    }
+};
+
 struct SequenceArgs {
     int frames, spp, mode, flags;
     double orbit;
     uint64_t seed;
     bool progress, grid, denoise;
     std::string out, hdr_out, aov_out;
+    Mover* move;  // --move, or null
 };
 
 // --frames: render, accumulate (and filter) frame after frame; the history ping-pongs between two sets of buffers
@@ -201,6 +249,7 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
     std::vector<double> hdr, variance(npx), filtered(3 * npx), shift(clamp ? npx : 0), upsampled;
     for (int k = 0; k < a.frames; k++) {
         Frame &cur = fr[k & 1], &prev = fr[(k & 1) ^ 1];
+        if (a.move && a.move->apply(scene, k)) return 1;
         if (mcpt_camera_orbit(&cam0, k * a.orbit, &cur.cam) != MCPT_OK) {
             std::fprintf(stderr, "%s\n", mcpt_last_error());
             return 1;
@@ -315,6 +364,10 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
         mcpt_camera cam;
         mcpt_sequence_info fi{};
         last = -10;
+        if (a.move && a.move->apply(scene, k)) {
+            rc = 1;
+            break;
+        }
         if (mcpt_camera_orbit(&cam0, k * a.orbit, &cam) != MCPT_OK ||
             mcpt_sequence_frame(seq, &cam, a.seed + k, rgb8.data(), &fi, nullptr) != MCPT_OK) {
             std::fprintf(stderr, "frame %d failed: %s\n", k, mcpt_last_error());
@@ -398,6 +451,8 @@ int main(int argc, char** argv) {
     bool upsample = false, temporal_upsample = false;
     mcpt_upsample_opts up;
     mcpt_upsample_opts_init(&up);
+    bool move_flag = false;
+    Mover mover;
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -464,6 +519,13 @@ int main(int argc, char** argv) {
         else if (!std::strcmp(argv[a], "--device-sequence")) device_sequence = true;
         else if (!std::strcmp(argv[a], "--upsample")) up.factor = std::atoi(next()), upsample = true;
         else if (!std::strcmp(argv[a], "--temporal-upsample")) temporal_upsample = true;
+        else if (!std::strcmp(argv[a], "--move")) {
+            if (!mover.parse(next())) {
+                std::fprintf(stderr, "--move needs FIRST:COUNT:DX,DY,DZ (a facet range and a finite step per frame), not %s\n", argv[a]);
+                return 2;
+            }
+            move_flag = true;
+        }
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -489,6 +551,10 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--jitter traces its camera rays over the BVH; drop --grid\n");
             return 2;
         }
+    }
+    if (move_flag && frames == 0) {  // refused before anything is loaded
+        std::fprintf(stderr, "--move moves facets between the frames of a sequence; add --frames N\n");
+        return 2;
     }
     if (temporal_upsample) {  // refused before anything is loaded
         const char* why = !upsample          ? "accumulates at --upsample F times the traced size; add --upsample F"
@@ -586,7 +652,11 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--frames accumulates plain renders; drop --adaptive\n");
             return 2;
         }
-        const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out};
+        if (move_flag) {
+            if (const int rc = mover.bind(scene)) return rc;
+        }
+        const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out,
+                              move_flag ? &mover : nullptr};
         if (clamp_flag && !history_clamp) {
             std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
             return 2;

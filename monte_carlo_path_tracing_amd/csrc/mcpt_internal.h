@@ -113,6 +113,50 @@ struct Bvh8 {
 // child box contains the fp32 box the binary tree holds for it, or its triangles' for a split leaf)
 Bvh8 build_bvh8(const HostScene& s, const Bvh& b);
 
+// leaf children of the device's 4-wide nodes are packed as ~((first leaf slot << kBvh4LeafBits) | count)
+constexpr int kBvh4LeafBits = 5;
+
+// bvh.cpp -- refit of a binary BVH after mcpt_scene_update moved facets: topology and leaf slots stay, only boxes
+// change.  The index is built once per tree (at its first update).
+struct BvhRefitIndex {
+    std::vector<int32_t> parent;      // node -> 2 * parent node + slot (-1: the root)
+    std::vector<int32_t> slot_owner;  // leaf slot -> 2 * node + slot of the leaf that holds it
+};
+BvhRefitIndex make_bvh_refit_index(const Bvh& b);
+// Builder::to_float_box's arithmetic: the margin applied in double, rounded to float, then one ulp outward
+void box_with_margin(const double lo[3], const double hi[3], double margin, float* flo, float* fhi);
+// every leaf holding one of `slots` gets the union of the FULL bounds of all its triangles (from s.pos), enlarged by
+// `margin`; every ancestor slot the union of its child node's two slot boxes.  Boxes off those paths are untouched.
+void refit_bvh(Bvh& b, const BvhRefitIndex& ix, const HostScene& s, const std::vector<int32_t>& slots, double margin);
+
+// scene_io.cpp -- Myobj::get_unique_normal_of_facet (Myobj.cpp:680-709) of facet f into s.unique_n
+void unique_normal_of_facet(HostScene& s, int f);
+
+// refit.hip -- the device side of mcpt_scene_update: the device pointers of one device state's main tree (owned by
+// render.hip's DeviceState) and the kernels that rewrite them.  Both functions only enqueue on `stream` (a
+// hipStream_t) of the current device.
+struct RefitDev {
+    float* tri_v;               // F * 3 float4
+    float* tri_n;               // F * 9
+    float* leaf_v;              // nslots * 3 float4 (w of the first = facet id bits)
+    BvhNode4* bvh4;             // breadth-first, leaf codes packed
+    BvhNode4Q* bvh4q;
+    const int32_t* slot_start;  // F + 1: CSR facet -> leaf slots
+    const int32_t* slot_list;
+    uint8_t* slot_dirty;        // nslots
+    uint8_t* node_dirty;        // nnodes
+    unsigned* counters;         // [0] offending values (refit_validate_enqueue), [1] nodes refit
+    int32_t F, nslots, nnodes;
+};
+// counts into r.counters[0] the non-finite values of dpos / dnrm (count * 9 floats each, dnrm may be null) and the
+// positions outside [lo, hi]
+int refit_validate_enqueue(const RefitDev& r, int32_t count, const float* dpos, const float* dnrm, const double lo[3],
+                           const double hi[3], void* stream);
+// scatter of facets [first, first + count), one refit launch per level (level l = nodes [level_first[l],
+// level_first[l + 1]), deepest first), then the dirty bytes cleared
+int refit_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, int32_t first, int32_t count, const float* dpos,
+                  const float* dnrm, double margin, void* stream);
+
 // grid.cpp -- the reference's uniform grid (Myobj.cpp:78-162) for the MCPT_ACCEL_GRID mode
 struct Grid {
     bool ok = false;

@@ -135,7 +135,7 @@ __device__ inline d3 cam_dir_at(const CamFrame& f, double y, double x) {
 // triangle test on every candidate.  Stack in LDS, [depth][thread] layout (conflict-free).
 // ============================================================================================
 constexpr int kStack = 48;
-constexpr int kLeafBits = 5;  // leaf code ~((first slot << kLeafBits) | count)
+constexpr int kLeafBits = kBvh4LeafBits;  // (5) leaf code ~((first slot << kLeafBits) | count)
 constexpr int kRayBlock = 256;
 constexpr int kRayLds = 16;  // LDS stack entries per lane of trace4_ww (16 KB per 256 lanes)
 // k_mis_rays: the first kRayTop nodes of the traversed BVH4 (breadth-first numbering: its top
@@ -4525,6 +4525,13 @@ struct DeviceState {
     bool bvh8_tried = false;  // ensure_bvh8 ran on this device
     DevBuf g_start, g_tri;  // the scene's uniform grid (MCPT_ACCEL_GRID), version grid_version
     int grid_version = 0;
+    // mcpt_scene_update on this device: what refit.hip's kernels need beside the scene's own arrays (built at the
+    // device state's first update: the facet -> leaf-slot map, the dirty bytes, the counters and the first node of
+    // every level of the breadth-first 4-wide tree) and the staging copies of a host call's arrays
+    bool refit_ready = false;
+    RefitDev refit{};
+    std::vector<int32_t> level_first;
+    DevBuf up_pos, up_nrm;
     unsigned* pinned_count = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evp0 = nullptr, evp1 = nullptr, evr0 = nullptr, evr1 = nullptr;
 };
@@ -4544,6 +4551,13 @@ struct mcpt_scene {
     std::vector<int> comm_devices;  // distinct devices of the cached ncclCommInitAll communicators
     std::vector<void*> comms;
     std::mutex mu;
+    // mcpt_scene_update: the build's bounding box, largest axis extent and box margin (Builder::margin) stay the
+    // scene's for good; `updated` once a call succeeded (the 8-wide trees are then stale and refused); the refit
+    // index of `bvh` and the facet -> leaf-slot map, both built at the first update
+    double build_lo[3] = {0, 0, 0}, build_hi[3] = {0, 0, 0}, build_ext = 0, margin = 0;
+    bool updated = false;
+    BvhRefitIndex refit_ix;
+    std::vector<int32_t> slot_start, slot_list;
 };
 
 namespace {
@@ -5160,7 +5174,14 @@ void ensure_bvh8_host(mcpt_scene* sc) {
     sc->lbvh8 = build_bvh8(sc->host, sc->lbvh);
     sc->bvh8_built = true;
 }
+int bvh8_refused(const mcpt_scene* sc) {
+    if (!sc->updated) return MCPT_OK;
+    set_error("the 8-wide trees are not refit by mcpt_scene_update: MCPT_DEBUG_RAYS_CW8, MCPT_DEBUG_HIT_CW8 and "
+              "mcpt_debug_bvh8_check are refused for a scene handle after its first update");
+    return MCPT_E_INVALID;
+}
 int ensure_bvh8(mcpt_scene* sc, DeviceState* D) {
+    if (int rc = bvh8_refused(sc)) return rc;
     ensure_bvh8_host(sc);
     if (D->bvh8_tried) return MCPT_OK;
     DScene& d = D->d;
@@ -6658,6 +6679,14 @@ static int finish_scene(HostScene&& hs, mcpt_scene** out) {
     constexpr int kMaxLeaf = MCPT_BVH_MAX_LEAF;
     sc->bvh = build_bvh(sc->host, all, kMaxLeaf);
     sc->lbvh = build_bvh(sc->host, lights, kMaxLeaf);
+    // build_bvh's scene box and margin over `all` (the arena of mcpt_scene_update)
+    for (int c = 0; c < 3; c++) sc->build_lo[c] = DBL_MAX, sc->build_hi[c] = -DBL_MAX;
+    for (size_t i = 0; i < sc->host.pos.size(); i++) {
+        sc->build_lo[i % 3] = std::min(sc->build_lo[i % 3], (double)sc->host.pos[i]);
+        sc->build_hi[i % 3] = std::max(sc->build_hi[i % 3], (double)sc->host.pos[i]);
+    }
+    for (int c = 0; c < 3; c++) sc->build_ext = std::max(sc->build_ext, sc->build_hi[c] - sc->build_lo[c]);
+    sc->margin = 1e-5 * sc->build_ext + 1e-6;
     *out = sc;
     return MCPT_OK;
 }
@@ -6744,7 +6773,7 @@ void mcpt_scene_destroy(mcpt_scene* sc) {
                                      &D->root_kind, &D->exact, &D->exact_scr, &D->slack, &D->lit_slot, &D->lit_pool,
                                      &D->sc_cum, &D->sc_wsum, &D->sc_last, &D->cull_keys, &D->cull_order, &D->cull_count,
                                      &D->ad_acc[0], &D->ad_acc[1], &D->ad_list[0], &D->ad_list[1], &D->ad_state[0],
-                                     &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise, &D->aov};
+                                     &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise, &D->aov, &D->up_pos, &D->up_nrm};
         for (int k = 0; k < 14; k++) bufs.insert(bufs.end(), {&D->qa[k], &D->qb[k], &D->qs[k]});
         for (int k = 0; k < 9; k++) bufs.push_back(&D->aux[k]);
         for (int k = 0; k < 13; k++) bufs.push_back(&D->sl[k]);
@@ -6788,6 +6817,233 @@ int mcpt_scene_arrays(const mcpt_scene* sc, float* pos, float* nrm, int32_t* mat
     if (lrad) std::copy(h.light_rad.begin(), h.light_rad.end(), lrad);
     if (un) std::copy(h.unique_n.begin(), h.unique_n.end(), un);
     return MCPT_OK;
+}
+
+// ---- mcpt_scene_update (include/mcpt.h; the kernels are refit.hip's) ----
+void mcpt_update_stats_init(mcpt_update_stats* st) {
+    if (!st) return;
+    std::memset((void*)st, 0, sizeof *st);
+    st->struct_size = sizeof *st;
+}
+
+// every refusal that needs neither the values nor a device
+static int update_check_args(const mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const mcpt_update_stats* stats) {
+    if (!sc || !pos) {
+        set_error("mcpt_scene_update: NULL %s", !sc ? "scene" : "positions");
+        return MCPT_E_INVALID;
+    }
+    if (count < 1 || first < 0 || (int64_t)first + count > sc->host.F) {
+        set_error("mcpt_scene_update: facets [%d, %lld) are not a non-empty range of the scene's %d facets", first,
+                  (long long)first + count, sc->host.F);
+        return MCPT_E_INVALID;
+    }
+    if (stats && stats->struct_size != sizeof(mcpt_update_stats)) {
+        set_error("mcpt_update_stats.struct_size %u does not match this library's %zu (header / library version mismatch)",
+                  stats->struct_size, sizeof(mcpt_update_stats));
+        return MCPT_E_INVALID;
+    }
+    return MCPT_OK;
+}
+static int update_check_lights(const mcpt_scene* sc, int32_t first, int32_t count) {
+    for (int f = first; f < first + count; f++)
+        if (sc->host.light_of[f] >= 0) {
+            set_error("mcpt_scene_update: facet %d is a light triangle (light %d); lights cannot move", f, sc->host.light_of[f]);
+            return MCPT_E_INVALID;
+        }
+    return MCPT_OK;
+}
+// the arena: the build's box grown by its largest axis extent on every side
+static void update_arena(const mcpt_scene* sc, double lo[3], double hi[3]) {
+    for (int a = 0; a < 3; a++) lo[a] = sc->build_lo[a] - sc->build_ext, hi[a] = sc->build_hi[a] + sc->build_ext;
+}
+static int update_check_values(const mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm) {
+    double lo[3], hi[3];
+    update_arena(sc, lo, hi);
+    for (size_t i = 0; i < 9 * (size_t)count; i++) {
+        const int f = first + (int)(i / 9), a = (int)(i % 3);
+        if (!std::isfinite(pos[i]) || (nrm && !std::isfinite(nrm[i]))) {
+            set_error("mcpt_scene_update: facet %d has a non-finite %s", f, std::isfinite(pos[i]) ? "normal" : "position");
+            return MCPT_E_INVALID;
+        }
+        if (pos[i] < lo[a] || pos[i] > hi[a]) {
+            set_error("mcpt_scene_update: facet %d has a position outside the arena (axis %d: %g not in [%g, %g], the "
+                      "build's box grown by its largest extent)", f, a, (double)pos[i], lo[a], hi[a]);
+            return MCPT_E_INVALID;
+        }
+    }
+    return MCPT_OK;
+}
+
+// what a device state's first update builds: the CSR facet -> leaf-slot map, the dirty bytes, the counters and the
+// first node of every level; the tree's indices are checked here once, so the kernels need no bounds tests
+static int ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
+    if (D.refit_ready) return MCPT_OK;
+    const DScene& d = D.d;
+    const size_t nslots = sc->bvh.leaf_facets.size();
+    std::vector<BvhNode4> b4(d.nbvh4);
+    HIP_OK(hipMemcpy(b4.data(), d.bvh4, b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
+    std::vector<int32_t> lf{0, 1};
+    bool ok = !b4.empty();
+    while (ok) {
+        const int32_t n0 = lf[lf.size() - 2], n1 = lf.back();
+        int64_t next = n1;  // breadth-first order: the inner children of a level are the next level, in order
+        for (int32_t n = n0; n < n1 && ok; n++)
+            for (int k = 0; k < 4; k++) {
+                const int32_t c = b4[n].child[k];
+                if (c == kBvh4Empty) continue;
+                if (c >= 0) {
+                    ok = ok && c == next++ && c < d.nbvh4;
+                } else {
+                    const int64_t s0 = ~c >> kLeafBits, cnt = ~c & ((1 << kLeafBits) - 1);
+                    ok = ok && s0 + cnt <= (int64_t)nslots;
+                }
+            }
+        if (next == n1) break;
+        ok = ok && next <= d.nbvh4;
+        lf.push_back((int32_t)next);
+    }
+    if (!ok || lf.back() != d.nbvh4) {
+        set_error("mcpt_scene_update: device %d's 4-wide tree is not in breadth-first order", D.device);
+        return MCPT_E_SCENE;
+    }
+    RefitDev& r = D.refit;
+    r.F = d.F;
+    r.nslots = (int32_t)nslots;
+    r.nnodes = d.nbvh4;
+    r.tri_v = const_cast<float*>(reinterpret_cast<const float*>(d.tri_v));
+    r.tri_n = const_cast<float*>(d.tri_n);
+    r.leaf_v = const_cast<float*>(reinterpret_cast<const float*>(d.leaf_v));
+    r.bvh4 = const_cast<BvhNode4*>(d.bvh4);
+    r.bvh4q = const_cast<BvhNode4Q*>(d.bvh4q);
+    int rc;
+    if ((rc = upload(D, sc->slot_start, &r.slot_start)) || (rc = upload(D, sc->slot_list, &r.slot_list))) return rc;
+    const std::vector<uint8_t> zs(std::max<size_t>(nslots, 1), 0), zn(std::max<size_t>(b4.size(), 1), 0);
+    const std::vector<unsigned> zc(16, 0);
+    const uint8_t *ds, *dn;
+    const unsigned* dc;
+    if ((rc = upload(D, zs, &ds)) || (rc = upload(D, zn, &dn)) || (rc = upload(D, zc, &dc))) return rc;
+    r.slot_dirty = const_cast<uint8_t*>(ds);
+    r.node_dirty = const_cast<uint8_t*>(dn);
+    r.counters = const_cast<unsigned*>(dc);
+    D.level_first = std::move(lf);
+    D.refit_ready = true;
+    return MCPT_OK;
+}
+
+// the call after its refusals: the host scene first (it stays the truth for device states made later, for the grid
+// and for the debug checks), then every device state the scene has.  src_device >= 0: dpos / dnrm are device memory
+// there and that device's state reads them directly; every other state gets a staging copy of the host arrays.
+static int update_apply(mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm, int src_device,
+                        const float* dpos, const float* dnrm, mcpt_update_stats* stats) {
+    HostScene& hs = sc->host;
+    if (sc->slot_start.empty()) {  // first update of the handle: the facet -> leaf-slot map and the binary tree's index
+        const std::vector<int32_t>& lfac = sc->bvh.leaf_facets;
+        sc->slot_start.assign((size_t)hs.F + 1, 0);
+        for (int32_t f : lfac) sc->slot_start[f + 1]++;
+        for (int f = 0; f < hs.F; f++) sc->slot_start[f + 1] += sc->slot_start[f];
+        sc->slot_list.resize(lfac.size());
+        std::vector<int32_t> at(sc->slot_start.begin(), sc->slot_start.end() - 1);
+        for (size_t q = 0; q < lfac.size(); q++) sc->slot_list[at[lfac[q]]++] = (int32_t)q;
+        sc->refit_ix = make_bvh_refit_index(sc->bvh);
+    }
+    std::copy(pos, pos + 9 * (size_t)count, hs.pos.begin() + 9 * (size_t)first);
+    if (nrm) std::copy(nrm, nrm + 9 * (size_t)count, hs.nrm.begin() + 9 * (size_t)first);
+    for (int f = first; f < first + count; f++) unique_normal_of_facet(hs, f);
+    const std::vector<int32_t> slots(sc->slot_list.begin() + sc->slot_start[first], sc->slot_list.begin() + sc->slot_start[first + count]);
+    refit_bvh(sc->bvh, sc->refit_ix, hs, slots, sc->margin);
+    sc->grid.ok = false;  // rebuilt from the new positions by the next grid-mode call
+    sc->updated = true;   // the 8-wide trees are stale from here on (bvh8_refused)
+    mcpt_update_stats st;
+    mcpt_update_stats_init(&st);
+    st.facets = count;
+    st.leaf_slots = (int64_t)slots.size();
+    std::vector<DeviceState*> devs;
+    {
+        std::lock_guard<std::mutex> lk(sc->devs_mu);
+        for (auto& D : sc->devs) devs.push_back(D.get());
+    }
+    int cur = 0;
+    if (!devs.empty()) HIP_OK(hipGetDevice(&cur));
+    for (DeviceState* D : devs) {
+        HIP_OK(hipSetDevice(D->device));
+        int rc;
+        if ((rc = ensure_refit_state(sc, *D))) return rc;
+        const float *sp = dpos, *sn = dnrm;
+        if (D->device != src_device) {
+            if ((rc = ensure(D->up_pos, 36ull * count)) || (nrm && (rc = ensure(D->up_nrm, 36ull * count)))) return rc;
+            HIP_OK(hipMemcpy(D->up_pos.p, pos, 36ull * count, hipMemcpyHostToDevice));
+            if (nrm) HIP_OK(hipMemcpy(D->up_nrm.p, nrm, 36ull * count, hipMemcpyHostToDevice));
+            sp = (const float*)D->up_pos.p;
+            sn = nrm ? (const float*)D->up_nrm.p : nullptr;
+        }
+        // work of other streams (the caller's, a frame sequence's) that still reads or writes these arrays
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipEventRecord(D->ev0, D->stream));
+        if ((rc = refit_enqueue(D->refit, D->level_first.data(), (int)D->level_first.size() - 1, first, count, sp, sn, sc->margin,
+                                D->stream)))
+            return rc;
+        HIP_OK(hipEventRecord(D->ev1, D->stream));
+        HIP_OK(hipStreamSynchronize(D->stream));
+        if (st.device_states++ == 0) {
+            float ms = 0;
+            unsigned n = 0;
+            HIP_OK(hipEventElapsedTime(&ms, D->ev0, D->ev1));
+            HIP_OK(hipMemcpy(&n, D->refit.counters + 1, sizeof n, hipMemcpyDeviceToHost));
+            st.device_seconds = 1e-3 * ms;
+            st.nodes_refit = n;
+            st.levels = (int32_t)D->level_first.size() - 1;
+        }
+    }
+    if (!devs.empty()) HIP_OK(hipSetDevice(cur));
+    if (stats) *stats = st;
+    return MCPT_OK;
+}
+
+int mcpt_scene_update(mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm, mcpt_update_stats* stats) {
+    int rc;
+    if ((rc = update_check_args(sc, first, count, pos, stats))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if ((rc = update_check_lights(sc, first, count)) || (rc = update_check_values(sc, first, count, pos, nrm))) return rc;
+    return update_apply(sc, first, count, pos, nrm, -1, nullptr, nullptr, stats);
+}
+
+int mcpt_scene_update_device(mcpt_scene* sc, int32_t device, int32_t first, int32_t count, const float* dpos, const float* dnrm,
+                             mcpt_update_stats* stats) {
+    int rc;
+    if ((rc = update_check_args(sc, first, count, dpos, stats))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if ((rc = update_check_lights(sc, first, count))) return rc;
+    int cur;
+    HIP_OK(hipGetDevice(&cur));
+    if (device < 0) device = cur;
+    if ((rc = check_device_buffer(dpos, device, "dev_positions")) || (dnrm && (rc = check_device_buffer(dnrm, device, "dev_normals"))))
+        return rc;
+    HIP_OK(hipSetDevice(device));
+    // the value checks: one word counted on the device and read back before anything is modified
+    HIP_OK(hipDeviceSynchronize());  // the caller's streams may still be writing the arrays
+    RefitDev v{};
+    void* word = nullptr;
+    HIP_OK(hipMalloc(&word, 64));
+    v.counters = (unsigned*)word;
+    double lo[3], hi[3];
+    update_arena(sc, lo, hi);
+    unsigned bad = 0;
+    rc = refit_validate_enqueue(v, count, dpos, dnrm, lo, hi, nullptr);
+    hipError_t e = rc ? hipSuccess : hipMemcpy(&bad, word, sizeof bad, hipMemcpyDeviceToHost);
+    (void)hipFree(word);
+    if (rc) return rc;
+    HIP_OK(e);
+    if (bad) {
+        set_error("mcpt_scene_update_device: %u values of the range are non-finite or positions outside the arena (the "
+                  "build's box grown by its largest extent)", bad);
+        (void)hipSetDevice(cur);
+        return MCPT_E_INVALID;
+    }
+    std::vector<float> hp(9 * (size_t)count), hn(dnrm ? 9 * (size_t)count : 0);
+    HIP_OK(hipMemcpy(hp.data(), dpos, 36ull * count, hipMemcpyDeviceToHost));
+    if (dnrm) HIP_OK(hipMemcpy(hn.data(), dnrm, 36ull * count, hipMemcpyDeviceToHost));
+    HIP_OK(hipSetDevice(cur));
+    return update_apply(sc, first, count, hp.data(), dnrm ? hn.data() : nullptr, device, dpos, dnrm, stats);
 }
 
 int mcpt_scene_camera(const mcpt_scene* sc, mcpt_camera* cam) {
@@ -7264,6 +7520,7 @@ int mcpt_closest_hit(mcpt_scene* sc, int32_t n, const double* ro, const double* 
     std::lock_guard<std::mutex> lk(sc->mu);
     DeviceState* D;
     int rc;
+    if ((flags & MCPT_DEBUG_HIT_CW8) && (rc = bvh8_refused(sc))) return rc;
     if ((rc = get_device_state(sc, -1, &D))) return rc;
     const bool grid = (flags & MCPT_HIT_GRID) != 0;
     if (grid) {
@@ -7356,7 +7613,7 @@ struct RefRegion {
     int32_t f;
     float lo[3], hi[3];
 };
-static int64_t check_coverage(const HostScene& hs, std::vector<RefRegion>& refs) {
+static int64_t check_coverage(const std::vector<float>& pos, std::vector<RefRegion>& refs) {
     std::sort(refs.begin(), refs.end(), [](const RefRegion& x, const RefRegion& y) { return x.f < y.f; });
     int64_t bad = 0;
     static const double kW[][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {.5, .5, 0}, {0, .5, .5}, {.5, 0, .5}, {1. / 3, 1. / 3, 1. / 3},
@@ -7365,7 +7622,7 @@ static int64_t check_coverage(const HostScene& hs, std::vector<RefRegion>& refs)
     for (size_t i = 0; i < refs.size();) {
         size_t j = i;
         while (j < refs.size() && refs[j].f == refs[i].f) j++;
-        const float* v = &hs.pos[9 * (size_t)refs[i].f];
+        const float* v = &pos[9 * (size_t)refs[i].f];
         const int npts = j - i == 1 ? 3 : (int)(sizeof(kW) / sizeof(kW[0]));
         for (int w = 0; w < npts; w++) {
             float x[3];
@@ -7385,18 +7642,13 @@ static int64_t check_coverage(const HostScene& hs, std::vector<RefRegion>& refs)
 // (quantize_bvh4), walked on the host: every facet of the binary tree reached, each reference's triangle
 // covered by the slot boxes on its path (check_coverage), and every quantized slot box containing its fp32
 // box (the conservative rounding the persistent traversal relies on)
-int mcpt_debug_bvh4_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
-    if (!sc || !out) {
-        set_error("invalid argument");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    const Bvh& bb = light_only ? sc->lbvh : sc->bvh;
-    const std::vector<BvhNode4> b4 = collapse_bvh4(bb);
-    const std::vector<BvhNode4Q> q4 = quantize_bvh4(b4);
-    const HostScene& hs = sc->host;
+// the walk itself, over any copy of a tree: nodes with unpacked leaf children (~first slot, count), their quantized
+// forms, the facet of every leaf slot and the positions (9 floats per facet) the triangles are checked with
+static void bvh4_walk(const std::vector<BvhNode4>& b4, const std::vector<BvhNode4Q>& q4, const std::vector<int32_t>& leaf_facets,
+                      const std::vector<float>& pos, int64_t* out) {
+    const int F = (int)(pos.size() / 9);
     int64_t nodes = 0, tris = 0, dup = 0, bad = 0, maxd = 0;
-    std::vector<int> seen(hs.F, 0);
+    std::vector<int> seen(F, 0);
     std::vector<RefRegion> refs;
     RefRegion cur{0, {-FLT_MAX, -FLT_MAX, -FLT_MAX}, {FLT_MAX, FLT_MAX, FLT_MAX}};
     std::function<void(int32_t, int)> walk = [&](int32_t ni, int depth) {
@@ -7425,11 +7677,11 @@ int mcpt_debug_bvh4_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
             } else {
                 const int32_t first = ~n.child[k];
                 for (int32_t j = first; j < first + n.count[k]; j++) {
-                    if (j < 0 || (size_t)j >= bb.leaf_facets.size() || bb.leaf_facets[j] < 0 || bb.leaf_facets[j] >= hs.F) {
+                    if (j < 0 || (size_t)j >= leaf_facets.size() || leaf_facets[j] < 0 || leaf_facets[j] >= F) {
                         bad++;
                         continue;
                     }
-                    const int f = bb.leaf_facets[j];
+                    const int f = leaf_facets[j];
                     tris++;
                     if (seen[f]++) dup++;
                     cur.f = f;
@@ -7440,13 +7692,102 @@ int mcpt_debug_bvh4_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
         }
     };
     if (!b4.empty()) walk(0, 1);
-    bad += check_coverage(hs, refs);
+    bad += check_coverage(pos, refs);
+    std::vector<int32_t> distinct(leaf_facets);
+    std::sort(distinct.begin(), distinct.end());
     out[0] = nodes;
     out[1] = tris - dup;  // distinct facets reached
-    out[2] = (int64_t)bb.leaf_facets.size() - dup_refs(bb);
+    out[2] = (int64_t)(std::unique(distinct.begin(), distinct.end()) - distinct.begin());
     out[3] = dup;
     out[4] = bad;
     out[5] = maxd;
+}
+int mcpt_debug_bvh4_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
+    if (!sc || !out) {
+        set_error("invalid argument");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    const Bvh& bb = light_only ? sc->lbvh : sc->bvh;
+    const std::vector<BvhNode4> b4 = collapse_bvh4(bb);
+    bvh4_walk(b4, quantize_bvh4(b4), bb.leaf_facets, sc->host.pos, out);
+    return MCPT_OK;
+}
+
+// what `device` holds of the main tree: nodes with their leaf codes unpacked, quantized nodes, the facet and the
+// vertices of every leaf slot, the facet array's vertices
+struct DeviceTree {
+    std::vector<BvhNode4> b4;
+    std::vector<BvhNode4Q> q4;
+    std::vector<float4> leaf_v, tri_v;
+    std::vector<int32_t> leaf_facets;
+};
+static int download_tree(mcpt_scene* sc, int32_t device, bool vertices, DeviceTree* t) {
+    DeviceState* D;
+    int rc;
+    if ((rc = get_device_state(sc, device, &D))) return rc;
+    HIP_OK(hipDeviceSynchronize());
+    const DScene& d = D->d;
+    const size_t nslots = sc->bvh.leaf_facets.size();
+    t->b4.resize(d.nbvh4);
+    t->q4.resize(d.nbvh4);
+    t->leaf_v.resize(3 * nslots);
+    HIP_OK(hipMemcpy(t->b4.data(), d.bvh4, t->b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(t->q4.data(), d.bvh4q, t->q4.size() * sizeof(BvhNode4Q), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(t->leaf_v.data(), d.leaf_v, t->leaf_v.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    if (vertices) {
+        t->tri_v.resize(3 * (size_t)d.F);
+        HIP_OK(hipMemcpy(t->tri_v.data(), d.tri_v, t->tri_v.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    }
+    for (BvhNode4& n : t->b4)
+        for (int k = 0; k < 4; k++)
+            if (n.child[k] < 0) n.child[k] = ~(~n.child[k] >> kLeafBits);  // pack_leaf_codes kept count[k]
+    t->leaf_facets.resize(nslots);
+    for (size_t q = 0; q < nslots; q++) std::memcpy(&t->leaf_facets[q], &t->leaf_v[3 * q].w, 4);
+    return MCPT_OK;
+}
+int mcpt_debug_bvh4_check_device(mcpt_scene* sc, int32_t device, int64_t* out) {
+    if (!sc || !out) {
+        set_error("invalid argument");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceTree t;
+    int rc;
+    if ((rc = download_tree(sc, device, true, &t))) return rc;
+    const std::vector<float>& pos = sc->host.pos;
+    bvh4_walk(t.b4, t.q4, t.leaf_facets, pos, out);
+    // the device's own copies of the vertices against the host's
+    auto differs = [&](const float4* v, int f) {
+        int64_t n = 0;
+        for (int k = 0; k < 3; k++) n += std::memcmp(&v[k].x, &pos[9 * (size_t)f + 3 * k], 12) != 0;
+        return n;
+    };
+    for (size_t q = 0; q < t.leaf_facets.size(); q++)
+        if (t.leaf_facets[q] >= 0 && t.leaf_facets[q] < sc->host.F) out[4] += differs(&t.leaf_v[3 * q], t.leaf_facets[q]);
+    for (int f = 0; f < sc->host.F; f++) out[4] += differs(&t.tri_v[3 * (size_t)f], f);
+    return MCPT_OK;
+}
+int mcpt_debug_bvh4_download(mcpt_scene* sc, int32_t device, int64_t* counts, void* nodes, void* qnodes, int32_t* leaf_facets,
+                             int64_t cap_nodes, int64_t cap_slots) {
+    if (!sc || !counts) {
+        set_error("invalid argument");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceTree t;
+    int rc;
+    if ((rc = download_tree(sc, device, false, &t))) return rc;
+    counts[0] = (int64_t)t.b4.size();
+    counts[1] = (int64_t)t.leaf_facets.size();
+    if (((nodes || qnodes) && cap_nodes < counts[0]) || (leaf_facets && cap_slots < counts[1])) {
+        set_error("mcpt_debug_bvh4_download: the tree has %lld nodes and %lld leaf slots, more than the buffers hold",
+                  (long long)counts[0], (long long)counts[1]);
+        return MCPT_E_INVALID;
+    }
+    if (nodes) std::memcpy(nodes, t.b4.data(), t.b4.size() * sizeof(BvhNode4));
+    if (qnodes) std::memcpy(qnodes, t.q4.data(), t.q4.size() * sizeof(BvhNode4Q));
+    if (leaf_facets) std::copy(t.leaf_facets.begin(), t.leaf_facets.end(), leaf_facets);
     return MCPT_OK;
 }
 
@@ -7456,6 +7797,7 @@ int mcpt_debug_bvh8_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
         return MCPT_E_INVALID;
     }
     std::lock_guard<std::mutex> lk(sc->mu);
+    if (int rc = bvh8_refused(sc)) return rc;
     ensure_bvh8_host(sc);
     const Bvh8& b = light_only ? sc->lbvh8 : sc->bvh8;
     const Bvh& bb = light_only ? sc->lbvh : sc->bvh;
@@ -7510,7 +7852,7 @@ int mcpt_debug_bvh8_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
         }
     };
     if (!b.nodes.empty()) walk(0, 1);
-    bad += check_coverage(hs, refs);
+    bad += check_coverage(hs.pos, refs);
     out[0] = nodes;
     out[1] = tris - dup;  // distinct facets reached
     out[2] = (int64_t)bb.leaf_facets.size() - dup_refs(bb);

@@ -374,20 +374,7 @@ double light_triangle_area(const HostScene& s, int f) {
     return 0.5 * d;
 }
 
-bool finalize_scene(HostScene& s, std::vector<LightDef> lights, std::string& err) {
-    for (int f = 0; f < s.F; f++)
-        if (s.mat[f] < 0 || s.mat[f] >= s.M) {
-            err = "facet " + std::to_string(f) + " has no material (the reference throws, main.cpp:425)";
-            return false;
-        }
-    auto sub = [](const double* a, const double* b, double* o) {
-        for (int c = 0; c < 3; c++) o[c] = a[c] - b[c];
-    };
-    auto cross = [](const double* a, const double* b, double* o) {
-        o[0] = a[1] * b[2] - a[2] * b[1];
-        o[1] = a[2] * b[0] - a[0] * b[2];
-        o[2] = a[0] * b[1] - a[1] * b[0];
-    };
+void unique_normal_of_facet(HostScene& s, int f) {
     auto dot = [](const double* a, const double* b) {
         double r = 0;
         r += a[0] * b[0];
@@ -396,9 +383,39 @@ bool finalize_scene(HostScene& s, std::vector<LightDef> lights, std::string& err
         return r;
     };
     auto norm = [](const double* a) { return std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); };
-    auto vert = [&](int f, int k, double* o) {
-        for (int c = 0; c < 3; c++) o[c] = s.pos[9 * f + 3 * k + c];
-    };
+    double a[3], b[3], c[3], ba[3], ca[3], n[3], nv[3][3];
+    for (int q = 0; q < 3; q++) {
+        a[q] = s.pos[9 * f + q];
+        b[q] = s.pos[9 * f + 3 + q];
+        c[q] = s.pos[9 * f + 6 + q];
+    }
+    for (int k = 0; k < 3; k++) {
+        double t[3] = {s.nrm[9 * f + 3 * k], s.nrm[9 * f + 3 * k + 1], s.nrm[9 * f + 3 * k + 2]};
+        double l = norm(t);
+        for (int q = 0; q < 3; q++) nv[k][q] = t[q] / l;
+    }
+    for (int q = 0; q < 3; q++) {
+        ba[q] = b[q] - a[q];
+        ca[q] = c[q] - a[q];
+    }
+    n[0] = ba[1] * ca[2] - ba[2] * ca[1];
+    n[1] = ba[2] * ca[0] - ba[0] * ca[2];
+    n[2] = ba[0] * ca[1] - ba[1] * ca[0];
+    double l = norm(n);
+    for (double& q : n) q = q / l;
+    double nr[3] = {n[0] * -1, n[1] * -1, n[2] * -1};
+    double w = dot(n, nv[0]) + dot(n, nv[1]) + dot(n, nv[2]);
+    double wr = dot(nr, nv[0]) + dot(nr, nv[1]) + dot(nr, nv[2]);
+    const double* u = w > wr ? n : nr;
+    for (int q = 0; q < 3; q++) s.unique_n[3 * static_cast<size_t>(f) + q] = u[q];
+}
+
+bool finalize_scene(HostScene& s, std::vector<LightDef> lights, std::string& err) {
+    for (int f = 0; f < s.F; f++)
+        if (s.mat[f] < 0 || s.mat[f] >= s.M) {
+            err = "facet " + std::to_string(f) + " has no material (the reference throws, main.cpp:425)";
+            return false;
+        }
     // gather_light_triangles (Mylight.cpp:32-100): table in light-name order, facets in order
     std::vector<int> lmat(s.F, -1);
     for (int f = 0; f < s.F; f++)
@@ -431,27 +448,7 @@ bool finalize_scene(HostScene& s, std::vector<LightDef> lights, std::string& err
     s.NL = static_cast<int>(s.light_facet.size());
     // unique normals (Myobj.cpp:680-709): geometric normal flipped toward the vertex normals
     s.unique_n.resize(3 * static_cast<size_t>(s.F));
-    for (int f = 0; f < s.F; f++) {
-        double a[3], b[3], c[3], ba[3], ca[3], n[3], nv[3][3];
-        vert(f, 0, a);
-        vert(f, 1, b);
-        vert(f, 2, c);
-        for (int k = 0; k < 3; k++) {
-            double t[3] = {s.nrm[9 * f + 3 * k], s.nrm[9 * f + 3 * k + 1], s.nrm[9 * f + 3 * k + 2]};
-            double l = norm(t);
-            for (int q = 0; q < 3; q++) nv[k][q] = t[q] / l;
-        }
-        sub(b, a, ba);
-        sub(c, a, ca);
-        cross(ba, ca, n);
-        double l = norm(n);
-        for (double& q : n) q = q / l;
-        double nr[3] = {n[0] * -1, n[1] * -1, n[2] * -1};
-        double w = dot(n, nv[0]) + dot(n, nv[1]) + dot(n, nv[2]);
-        double wr = dot(nr, nv[0]) + dot(nr, nv[1]) + dot(nr, nv[2]);
-        const double* u = w > wr ? n : nr;
-        for (int q = 0; q < 3; q++) s.unique_n[3 * f + q] = u[q];
-    }
+    for (int f = 0; f < s.F; f++) unique_normal_of_facet(s, f);
     (void)err;
     return true;
 }

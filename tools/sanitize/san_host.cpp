@@ -53,6 +53,28 @@ static int run_library(const char* obj, const char* xml, const std::string& out_
                 }
             if (used != bb->leaf_facets.size() || b8.nodes.empty()) return 6;
         }
+        // mcpt_scene_update's host half: move the slots of three facets (few slots: the sorted list and the heap),
+        // then every slot (marks and the sweep), refit the binary tree each time; it must still collapse and quantise
+        if (hs.F > 0) {
+            Bvh rb = b;
+            HostScene moved = hs;
+            const BvhRefitIndex ix = make_bvh_refit_index(rb);
+            for (int pass = 0; pass < 2; pass++) {
+                std::vector<int32_t> slots;
+                for (size_t q = 0; q < rb.leaf_facets.size(); q++) {
+                    const int f = rb.leaf_facets[q];
+                    if (pass == 1 || f == 0 || f == hs.F - 1 || f == hs.F / 2) slots.push_back((int32_t)q);
+                }
+                for (int32_t q : slots) {
+                    const int f = rb.leaf_facets[q];
+                    for (int c = 0; c < 9; c++) moved.pos[9 * (size_t)f + c] += 0.25f;
+                    unique_normal_of_facet(moved, f);
+                }
+                refit_bvh(rb, ix, moved, slots, 1e-5);
+                const std::vector<BvhNode4> r4 = collapse_bvh4(rb);
+                if (quantize_bvh4(r4).size() != r4.size()) return 7;
+            }
+        }
     }
     const double eye[3] = {hs.has_cam ? hs.cam.eye[0] : 0.0, hs.has_cam ? hs.cam.eye[1] : 0.0,
                            hs.has_cam ? hs.cam.eye[2] : 0.0};
