@@ -39,7 +39,11 @@ extern "C" {
                                * _device form, mcpt_camera_scaled, mcpt_sequence_create_upsampled,
                                * mcpt_sequence_upsample_info, the selector MCPT_SEQ_UPSAMPLED); in-place geometry
                                * updates with a device-side BVH refit (mcpt_update_stats, mcpt_scene_update and its
-                               * _device form);
+                               * _device form); object motion for the temporal accumulation (mcpt_scene_pose_save,
+                               * mcpt_motion_buffers, mcpt_render_motion_aovs and its _device form,
+                               * mcpt_temporal_accumulate_motion and its _device form, mcpt_sequence_set_motion,
+                               * mcpt_sequence_motion_info, the selectors MCPT_SEQ_PREV_POSITION and
+                               * MCPT_SEQ_PREV_NORMAL);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -293,8 +297,8 @@ int mcpt_scene_camera(const mcpt_scene* scene, mcpt_camera* cam);
  * An update invalidates the host grid (the next MCPT_ACCEL_GRID render or mcpt_scene_meshing call rebuilds it from the
  * new positions; MCPT_HIT_GRID queries need a new mcpt_scene_meshing call) and the opt-in 8-wide debug trees (refused
  * for the handle from its first update on, include/mcpt_debug.h).  Not covered: light triangles, topology or facet
- * count changes, a rebuild when the refit tree's quality degrades, motion vectors for the temporal accumulation (a moved
- * surface fails its taps' plane / normal test and restarts its history). */
+ * count changes, a rebuild when the refit tree's quality degrades.  The temporal accumulation follows moved geometry
+ * through the scene's previous pose (mcpt_scene_pose_save below, mcpt_temporal_accumulate_motion). */
 typedef struct {
     uint32_t struct_size;       /* sizeof(mcpt_update_stats) of the caller's header (mcpt_update_stats_init sets it) */
     int32_t facets;             /* count of the call */
@@ -313,6 +317,14 @@ int mcpt_scene_update(mcpt_scene* scene, int32_t first, int32_t count, const flo
  * brought up to date by a device-to-host copy of the range */
 int mcpt_scene_update_device(mcpt_scene* scene, int32_t device, int32_t first, int32_t count, const float* dev_positions,
                              const float* dev_normals, mcpt_update_stats* stats);
+/* The previous pose of a scene: the vertex positions and normals of every facet as they were at the last
+ * mcpt_scene_pose_save.  The call records the current ones -- on the host copy and, device to device on the state's
+ * stream (no host round trip), on every device state the scene has; a device state created later takes its previous
+ * pose from the host copy.  Storage is allocated at the first call; until then the previous pose IS the current pose
+ * (the same arrays, no copy).  mcpt_scene_update[_device] never touches the previous pose, so a frame loop is
+ * pose_save, updates, frame: mcpt_render_motion_aovs then tells where every visible surface point was a frame ago.
+ * Takes the scene's lock.  MCPT_E_INVALID for a NULL scene. */
+int mcpt_scene_pose_save(mcpt_scene* scene);
 
 /* main.cpp:547-588: render samples [sample_begin, sample_end) of an spp-sample frame and ADD
  * sum_k L_k * (1/spp) into out_rgb (caller-owned host buffer, height*width*3 doubles, row 0 =
@@ -415,6 +427,22 @@ int mcpt_render_aovs(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_rende
 /* same with the arrays in DEVICE memory (coarse-grained, on opts->device; see mcpt_render_device) */
 int mcpt_render_aovs_device(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* opts,
                             const mcpt_aov_buffers* dev_out);
+/* Motion AOVs: where the surface point a pixel shows was in the scene's PREVIOUS pose (mcpt_scene_pose_save).  For a
+ * pixel whose primary ray hits facet f at (beta, gamma) in the CURRENT pose, exactly as mcpt_primary_hits reports it:
+ *   prev_position  height*width*3: the interpolation of position above with the previous pose's vertices of f
+ *   prev_normal    height*width*3: the normalised interpolation of the previous pose's vertex normals of f
+ * -- the function that gives position and normal, on the other arrays; before any mcpt_scene_pose_save both maps equal
+ * mcpt_render_aovs' position and normal bit for bit.  A miss writes 0.  Either pointer may be NULL. */
+typedef struct {
+    double *prev_position, *prev_normal;
+} mcpt_motion_buffers;
+/* As mcpt_render_aovs: the same arguments, refusals and per-call setup (primary hits, root table), then one kernel
+ * that reads the primary hits and writes the two maps. */
+int mcpt_render_motion_aovs(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* opts,
+                            const mcpt_motion_buffers* out);
+/* same with the arrays in DEVICE memory (coarse-grained, on opts->device; see mcpt_render_device) */
+int mcpt_render_motion_aovs_device(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* opts,
+                                   const mcpt_motion_buffers* dev_out);
 
 /* Variance-guided edge-avoiding a-trous wavelet filter (Dammertz et al. 2010, "Edge-Avoiding A-Trous Wavelet
  * Transform for fast Global Illumination Filtering", with the luminance edge-stopping function scaled by the
@@ -507,9 +535,9 @@ int mcpt_variance_from_noise(int32_t width, int32_t height, const double* rgb, c
  * out_color (h*w*3), out_moments (h*w*4) and out_variance (h*w, optional) are overwritten.  The history is the
  * caller's: feed out_color / out_moments of one call as prev_color / prev_moments of the next (two sets of buffers,
  * swapped; an output may not alias an input).  The filtered colour is NOT fed back, miss pixels keep no history,
- * and the reprojection follows the camera only: there are no motion vectors, so a surface moved by mcpt_scene_update
- * fails its taps' plane or normal test and restarts its history (changed shading on static surfaces, a moving
- * shadow, is what the clamped form is for).  Single device. */
+ * and the reprojection follows the camera only: geometry moved by mcpt_scene_update is followed by
+ * mcpt_temporal_accumulate_motion below (changed shading on static surfaces, a moving shadow, is what the clamped
+ * form is for).  Single device. */
 typedef struct {
     uint32_t struct_size;  /* sizeof(mcpt_temporal_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
     int32_t max_history;   /* default 64, >= 1: the cap of the history length n */
@@ -597,6 +625,42 @@ int mcpt_temporal_accumulate_clamped_device(const mcpt_temporal_opts* opts, cons
                                             const double* dev_prev_moments, const double* dev_prev_fast,
                                             double* dev_out_color, double* dev_out_moments, double* dev_out_fast,
                                             double* dev_out_variance, double* dev_out_shift, double* device_seconds);
+
+/* Temporal accumulation with object motion (opt-in; the two forms above are unchanged).  Between the previous frame
+ * and this one geometry may have moved in place (mcpt_scene_update after mcpt_scene_pose_save): the surface point
+ * pixel p shows now lay elsewhere, and was oriented otherwise, when the previous frame's history was written.  The
+ * motion AOVs of this frame (mcpt_render_motion_aovs) say where: Xm = prev_position, Nm = prev_normal.  The rule is
+ * mcpt_temporal_accumulate's -- mcpt_temporal_accumulate_clamped's when clamp is not NULL -- word for word, with
+ * exactly three substitutions:
+ *   source   d = Xm_p - E (the previous position is what the previous camera saw)
+ *   taps     a tap needs Nm_p . N'_q >= normal_min
+ *            and |Nm_p . (X'_q - Xm_p)| <= plane_max * depth_p; depth_p stays the CURRENT depth
+ * Everything else reads the current guides: depth_p > 0 decides whether p has a source at all, `blend`, the moments,
+ * the fast history and the box of the clamp, and the spatial estimate of the variance.  With Xm = X and Nm = N (a
+ * scene that did not move) the outputs are those of the plain or clamped call bit for bit.  What it does not do: no
+ * screen-space motion vectors come out, lights do not move, and shading that changes on a static surface is still the
+ * clamp's job.
+ * Host arrays in, host arrays out; the arguments are those of the two forms above.  motion: both arrays are required.
+ * clamp == NULL selects the plain rule; prev_fast, out_fast and out_shift must then be NULL.  With clamp, prev_fast
+ * belongs to the previous state, out_fast is required and out_shift may be NULL.  Refused with MCPT_E_INVALID before
+ * any device work: everything the plain call (clamp == NULL) or the clamped call refuses, a NULL motion struct or
+ * array, an output aliasing a motion array, a fast-history or shift argument without clamp. */
+int mcpt_temporal_accumulate_motion(const mcpt_temporal_opts* opts, const mcpt_temporal_clamp_opts* clamp,
+                                    const mcpt_camera* prev_cam, int32_t width, int32_t height, const double* color,
+                                    const mcpt_aov_buffers* guides, const mcpt_motion_buffers* motion,
+                                    const mcpt_aov_buffers* prev_guides, const double* prev_color,
+                                    const double* prev_moments, const double* prev_fast, double* out_color,
+                                    double* out_moments, double* out_fast, double* out_shift, double* out_variance,
+                                    double* device_seconds);
+/* same with every array in DEVICE memory on opts->device (opts, clamp, prev_cam and device_seconds stay host pointers) */
+int mcpt_temporal_accumulate_motion_device(const mcpt_temporal_opts* opts, const mcpt_temporal_clamp_opts* clamp,
+                                           const mcpt_camera* prev_cam, int32_t width, int32_t height,
+                                           const double* dev_color, const mcpt_aov_buffers* dev_guides,
+                                           const mcpt_motion_buffers* dev_motion, const mcpt_aov_buffers* dev_prev_guides,
+                                           const double* dev_prev_color, const double* dev_prev_moments,
+                                           const double* dev_prev_fast, double* dev_out_color, double* dev_out_moments,
+                                           double* dev_out_fast, double* dev_out_shift, double* dev_out_variance,
+                                           double* device_seconds);
 
 /* Guided upsampling (joint bilateral upsampling, Kopf et al. 2007; no counterpart in the reference): trace at 1 / f of
  * the shown size and reconstruct the full-size frame from the low-size radiance and full-size guides.  A camera's
@@ -890,6 +954,21 @@ int mcpt_sequence_create_temporal_upsampled(mcpt_scene* scene, const mcpt_render
  * / reset / a failed frame. */
 int mcpt_sequence_temporal_upsample_info(mcpt_sequence* seq, int32_t* a, int32_t* b, double* rays_seconds,
                                          double* filled_share, double* fallback_share);
+/* Object motion in a sequence created by mcpt_sequence_create: on != 0 makes every frame from the next one on run the
+ * motion AOVs (mcpt_render_motion_aovs' kernel, on the primary-hit tables the frame's AOVs just built: no second
+ * primary trace) after the AOVs and accumulate by mcpt_temporal_accumulate_motion's rule, plain or clamped as the
+ * sequence was created; 0 returns to the rule it was created with.  The two maps are allocated at the first call
+ * with on != 0.  The caller saves the pose (mcpt_scene_pose_save, then the updates, then the frame); the sequence
+ * never does.  MCPT_E_INVALID: a NULL handle, a sequence created by mcpt_sequence_create_upsampled or
+ * mcpt_sequence_create_temporal_upsampled (motion there is not supported). */
+int mcpt_sequence_set_motion(mcpt_sequence* seq, int32_t on);
+/* the last frame's motion stage (HIP events around the motion AOVs; mcpt_sequence_info.aov_seconds does not include
+ * it).  MCPT_E_INVALID: a NULL handle, a last frame that ran without motion, no frame since create / reset / a failed
+ * frame.  motion_seconds may be NULL. */
+int mcpt_sequence_motion_info(mcpt_sequence* seq, double* motion_seconds);
+/* the last frame's motion AOVs (h*w*3 each), for mcpt_sequence_read and mcpt_sequence_device_buffer; refused while
+ * motion is off (and until a frame has run with it) */
+enum { MCPT_SEQ_PREV_POSITION = 9, MCPT_SEQ_PREV_NORMAL = 10 };
 
 /* Multi-process communicator (see mcpt_comm above): ncclGetUniqueId / ncclCommInitRank /
  * ncclCommDestroy.  device -1 = the current device. */

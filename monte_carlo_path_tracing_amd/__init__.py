@@ -23,6 +23,8 @@ __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_rays", 
            "SequenceOpts", "SequenceInfo", "FrameSequence", "tone_map_device", "frame_stats_device",
            "UpsampleOpts", "upsample", "upsample_device", "camera_scaled",
            "upsample_phase", "camera_phase_rays", "temporal_upsample", "temporal_upsample_device",
+           "MotionBuffers", "render_motion_aovs", "render_motion_aovs_device", "temporal_accumulate_motion",
+           "temporal_accumulate_motion_device",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -91,6 +93,11 @@ class AovBuffers(C.Structure):
     _fields_ = [("albedo", C.c_void_p), ("normal", C.c_void_p), ("position", C.c_void_p), ("depth", C.c_void_p)]
 
 
+class MotionBuffers(C.Structure):
+    """mcpt_motion_buffers: the two motion AOVs (include/mcpt.h)."""
+    _fields_ = [("prev_position", C.c_void_p), ("prev_normal", C.c_void_p)]
+
+
 class DenoiseOpts(C.Structure):
     """mcpt_denoise_opts: the a-trous filter's parameters (include/mcpt.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("sigma_color", C.c_double),
@@ -138,6 +145,8 @@ class SequenceInfo(C.Structure):
 # mcpt_sequence_read / _device_buffer selectors: name -> (MCPT_SEQ_*, trailing shape)
 SEQ_BUFFERS = {"raw": (0, (3,)), "accumulated": (1, (3,)), "moments": (2, (4,)), "variance": (3, ()), "filtered": (4, (3,)),
                "fast": (5, (3,)), "shift": (6, ()), "rgb8": (7, (3,)), "upsampled": (8, (3,))}
+# and of a sequence with motion: MCPT_SEQ_PREV_POSITION, MCPT_SEQ_PREV_NORMAL
+SEQ_MOTION_BUFFERS = {"prev_position": (9, (3,)), "prev_normal": (10, (3,))}
 
 
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
@@ -205,7 +214,10 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_camera_scaled", "mcpt_sequence_create_upsampled", "mcpt_sequence_upsample_info",
            "mcpt_upsample_phase", "mcpt_camera_phase_rays", "mcpt_camera_phase_rays_device", "mcpt_temporal_upsample",
            "mcpt_temporal_upsample_device", "mcpt_sequence_create_temporal_upsampled", "mcpt_sequence_temporal_upsample_info",
-           "mcpt_update_stats_init", "mcpt_scene_update", "mcpt_scene_update_device"]
+           "mcpt_update_stats_init", "mcpt_scene_update", "mcpt_scene_update_device",
+           "mcpt_scene_pose_save", "mcpt_render_motion_aovs", "mcpt_render_motion_aovs_device",
+           "mcpt_temporal_accumulate_motion", "mcpt_temporal_accumulate_motion_device", "mcpt_sequence_set_motion",
+           "mcpt_sequence_motion_info"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download"]  # include/mcpt_debug.h
@@ -324,6 +336,16 @@ def lib():
             L.mcpt_update_stats_init.restype = None
             L.mcpt_scene_update.argtypes = [P, I, I, P, P, C.POINTER(UpdateStats)]
             L.mcpt_scene_update_device.argtypes = [P, I, I, I, P, P, C.POINTER(UpdateStats)]
+        if hasattr(L, "mcpt_scene_pose_save"):  # and the object motion of the temporal accumulation
+            L.mcpt_scene_pose_save.argtypes = [P]
+            L.mcpt_render_motion_aovs.argtypes = [P, C.POINTER(Camera), C.POINTER(RenderOpts), C.POINTER(MotionBuffers)]
+            L.mcpt_render_motion_aovs_device.argtypes = L.mcpt_render_motion_aovs.argtypes
+            L.mcpt_temporal_accumulate_motion.argtypes = [C.POINTER(TemporalOpts), C.POINTER(TemporalClampOpts), C.POINTER(Camera), I, I,
+                                                          P, C.POINTER(AovBuffers), C.POINTER(MotionBuffers), C.POINTER(AovBuffers),
+                                                          P, P, P, P, P, P, P, P, C.POINTER(D)]
+            L.mcpt_temporal_accumulate_motion_device.argtypes = L.mcpt_temporal_accumulate_motion.argtypes
+            L.mcpt_sequence_set_motion.argtypes = [P, I]
+            L.mcpt_sequence_motion_info.argtypes = [P, C.POINTER(D)]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -429,6 +451,12 @@ class Scene:
                                               C.c_void_p(positions_ptr), C.c_void_p(normals_ptr) if normals_ptr else None,
                                               C.byref(st)))
         return st.as_dict()
+
+    def pose_save(self):
+        """mcpt_scene_pose_save: the current vertex positions and normals become the scene's previous pose, on the host
+        copy and (device to device) on every device the scene lives on; update() never touches it.  A frame loop is
+        pose_save, update, frame: render_motion_aovs then tells where each visible surface point was a frame ago."""
+        _check(lib().mcpt_scene_pose_save(self.h))
 
     def arrays(self):
         F, M, NL = self.nfacets, self.nmaterials, self.nlights
@@ -687,6 +715,26 @@ def render_aovs_device(scene, camera, albedo_ptr=None, normal_ptr=None, position
     b = AovBuffers(*[None if p is None else int(p) for p in (albedo_ptr, normal_ptr, position_ptr, depth_ptr)])
     o = _aov_opts(device, accel)
     _check(lib().mcpt_render_aovs_device(scene.h, C.byref(camera), C.byref(o), C.byref(b)))
+
+
+def render_motion_aovs(scene, camera, device=None, accel="bvh", flags=0):
+    """Motion AOVs (mcpt_render_motion_aovs, include/mcpt.h): dict of prev_position and prev_normal (H x W x 3 each) --
+    render_aovs' position and normal of every pixel's primary hit, evaluated over the scene's previous pose
+    (Scene.pose_save); equal to them until the first pose_save, 0 at a miss."""
+    H, W = camera.height, camera.width
+    a = dict(prev_position=np.zeros((H, W, 3)), prev_normal=np.zeros((H, W, 3)))
+    b = MotionBuffers(a["prev_position"].ctypes.data, a["prev_normal"].ctypes.data)
+    o = _aov_opts(device, accel, flags)
+    _check(lib().mcpt_render_motion_aovs(scene.h, C.byref(camera), C.byref(o), C.byref(b)))
+    return a
+
+
+def render_motion_aovs_device(scene, camera, prev_position_ptr=None, prev_normal_ptr=None, device=None, accel="bvh"):
+    """render_motion_aovs into device buffers (e.g. torch CUDA float64 tensors' data_ptr()): H*W*3 doubles each; either
+    may be None."""
+    b = MotionBuffers(*[None if p is None else int(p) for p in (prev_position_ptr, prev_normal_ptr)])
+    o = _aov_opts(device, accel)
+    _check(lib().mcpt_render_motion_aovs_device(scene.h, C.byref(camera), C.byref(o), C.byref(b)))
 
 
 def _denoise_opts(iterations, sigma_color, sigma_normal, sigma_plane, sigma_albedo, device):
@@ -1026,6 +1074,70 @@ def temporal_accumulate_clamped_device(width, height, color_ptr, aov_ptrs, out_c
     return sec.value
 
 
+def temporal_accumulate_motion(color, aovs, motion, prev=None, clamp=None, **opts):
+    """Temporal accumulation with object motion (mcpt_temporal_accumulate_motion; include/mcpt.h states the rule): as
+    temporal_accumulate (clamp=None) or temporal_accumulate_clamped (clamp=True or a dict), with the reprojected point and
+    the normal of the taps' tests taken from `motion`, the dict of render_motion_aovs (prev_position, prev_normal).
+    prev and the return value are those of the form chosen: (colour, moments, variance, seconds) without clamp,
+    (colour, moments, fast, variance, shift, seconds) with it."""
+    color = _d(color)
+    H, W = color.shape[:2]
+    assert color.shape == (H, W, 3)
+    keys = ("albedo", "normal", "position", "depth")
+    g = {k: _d(aovs[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys}
+    b = AovBuffers(*[g[k].ctypes.data for k in keys])
+    mo = {k: _d(motion[k], (H, W, 3)) for k in ("prev_position", "prev_normal")}
+    mb = MotionBuffers(mo["prev_position"].ctypes.data, mo["prev_normal"].ctypes.data)
+    pc = pb = pcol = pmom = pfast = None
+    if prev is not None:
+        pcam, paov, pcol, pmom = prev[:4]
+        pg = {k: _d(paov[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys[1:]}
+        pb = AovBuffers(None, *[pg[k].ctypes.data for k in keys[1:]])
+        pcol, pmom = _d(pcol, (H, W, 3)), _d(pmom, (H, W, 4))
+        if clamp is not None:
+            pfast = _d(prev[4], (H, W, 3))
+        pc = C.byref(pcam)
+    out, mom, var, sec = np.zeros((H, W, 3)), np.zeros((H, W, 4)), np.zeros((H, W)), C.c_double()
+    fast, shift = (np.zeros((H, W, 3)), np.zeros((H, W))) if clamp is not None else (None, None)
+    o = _temporal_opts(opts)
+    c = _clamp_opts(clamp) if clamp is not None else None
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _check(lib().mcpt_temporal_accumulate_motion(
+        C.byref(o), None if c is None else C.byref(c), pc, W, H, color.ctypes.data, C.byref(b), C.byref(mb),
+        None if pb is None else C.byref(pb), ptr(pcol), ptr(pmom), ptr(pfast), out.ctypes.data, mom.ctypes.data, ptr(fast),
+        ptr(shift), var.ctypes.data, C.byref(sec)))
+    if clamp is None:
+        return out, mom, var, sec.value
+    return out, mom, fast, var, shift, sec.value
+
+
+def temporal_accumulate_motion_device(width, height, color_ptr, aov_ptrs, motion_ptrs, out_color_ptr, out_moments_ptr,
+                                      out_fast_ptr=None, out_variance_ptr=None, out_shift_ptr=None, prev=None, clamp=None,
+                                      **opts):
+    """temporal_accumulate_motion over device buffers: motion_ptrs is a dict of the prev_position and prev_normal
+    pointers; prev is None or (camera, dict of the previous normal / position / depth pointers, previous colour and
+    moments pointers[, previous fast-history pointer with clamp]); out_fast_ptr is required with clamp and, like
+    out_shift_ptr, must be None without.  Returns the device seconds."""
+    b = AovBuffers(*[int(aov_ptrs[k]) for k in ("albedo", "normal", "position", "depth")])
+    mb = MotionBuffers(int(motion_ptrs["prev_position"]), int(motion_ptrs["prev_normal"]))
+    opt = lambda p: None if p is None else C.c_void_p(int(p))
+    pc = pb = pcol = pmom = pfast = None
+    if prev is not None:
+        pcam, paov, pcol, pmom = prev[:4]
+        pb = AovBuffers(None, *[int(paov[k]) for k in ("normal", "position", "depth")])
+        pc, pcol, pmom = C.byref(pcam), opt(pcol), opt(pmom)
+        if clamp is not None:
+            pfast = opt(prev[4])
+    sec = C.c_double()
+    o = _temporal_opts(opts)
+    c = _clamp_opts(clamp) if clamp is not None else None
+    _check(lib().mcpt_temporal_accumulate_motion_device(
+        C.byref(o), None if c is None else C.byref(c), pc, int(width), int(height), opt(color_ptr), C.byref(b), C.byref(mb),
+        None if pb is None else C.byref(pb), pcol, pmom, pfast, opt(out_color_ptr), opt(out_moments_ptr), opt(out_fast_ptr),
+        opt(out_shift_ptr), opt(out_variance_ptr), C.byref(sec)))
+    return sec.value
+
+
 class TemporalAccumulator:
     """The history of a frame sequence over a static scene: push(camera, color, aovs) accumulates one frame onto
     what the earlier pushes left and returns (accumulated colour, variance of its luminance); the unfiltered
@@ -1033,7 +1145,8 @@ class TemporalAccumulator:
     After a push: `moments` (H x W x 4), `seconds` (device time) and `kept` (share of pixels that kept a history).
     clamp: None (the default: plain accumulation), True or a dict of radius / alpha_fast / sigma for history clamping
     (temporal_accumulate_clamped); then a push also leaves `fast` (the fast history), `shift` and `clamped`, the share
-    of pixels with shift != 0."""
+    of pixels with shift != 0.  push(..., motion=render_motion_aovs(scene, camera)) follows geometry moved by
+    Scene.update since the last Scene.pose_save (temporal_accumulate_motion)."""
 
     def __init__(self, clamp=None, **opts):
         if clamp is False:
@@ -1045,15 +1158,22 @@ class TemporalAccumulator:
         self.state, self.moments, self.seconds, self.kept = None, None, 0.0, 0.0
         self.fast, self.shift, self.clamped = None, None, 0.0
 
-    def push(self, camera, color, aovs):
+    def push(self, camera, color, aovs, motion=None):
         cam = Camera.from_buffer_copy(camera)
         keep = {k: np.array(aovs[k], dtype=np.float64) for k in ("albedo", "normal", "position", "depth")}
         if self.clamp is None:
-            out, mom, var, self.seconds = temporal_accumulate(color, keep, self.state, **self.opts)
+            if motion is None:
+                out, mom, var, self.seconds = temporal_accumulate(color, keep, self.state, **self.opts)
+            else:
+                out, mom, var, self.seconds = temporal_accumulate_motion(color, keep, motion, self.state, **self.opts)
             self.state = (cam, keep, out, mom)
         else:
-            out, mom, self.fast, var, self.shift, self.seconds = temporal_accumulate_clamped(color, keep, self.state, self.clamp,
-                                                                                             **self.opts)
+            if motion is None:
+                out, mom, self.fast, var, self.shift, self.seconds = temporal_accumulate_clamped(color, keep, self.state, self.clamp,
+                                                                                                 **self.opts)
+            else:
+                out, mom, self.fast, var, self.shift, self.seconds = temporal_accumulate_motion(color, keep, motion, self.state,
+                                                                                                self.clamp, **self.opts)
             self.state = (cam, keep, out, mom, self.fast)
             self.clamped = float((self.shift != 0).mean())
         self.moments = mom
@@ -1080,10 +1200,14 @@ class FrameSequence:
     different 1 / F^2 subset of the full-size pixels (upsample_phase) and accumulates them in a full-size history
     (temporal_upsample()'s rule): read("raw") is H x W x 3, accumulated / moments / variance / filtered are full size,
     "upsampled", "fast" and "shift" are refused, and temporal_upsample_info() gives the phase and the fill's shares.
+    motion=True (not with upsample): every frame also runs the motion AOVs and accumulates by
+    temporal_accumulate_motion's rule, following geometry moved by Scene.update since the caller's last Scene.pose_save
+    (the sequence never saves the pose); read("prev_position") / read("prev_normal") and motion_info() then work, and
+    set_motion() switches it from the next frame on.
     After a frame: `info` (SequenceInfo: stage device times, kept, mean_history, clamped) and `stats` (the render's)."""
 
     def __init__(self, scene, width, height, spp, mode="mis", denoise=True, clamp=None, device=None, accel="bvh", flags=0,
-                 tone_max=None, tone_gamma=None, upsample=None, temporal_upsample=False, **temporal_opts):
+                 tone_max=None, tone_gamma=None, upsample=None, temporal_upsample=False, motion=False, **temporal_opts):
         self.h = None
         self._destroy = lib().mcpt_sequence_destroy
         if clamp is False:
@@ -1130,6 +1254,21 @@ class FrameSequence:
         self.h, self.scene = h, scene  # the scene must outlive the handle
         self.width, self.height, self.spp, self.denoise, self.clamp = o.width, o.height, o.spp, bool(denoise), clamp
         self.info, self.stats = None, None
+        self.motion = False
+        if motion:
+            self.set_motion(True)
+
+    def set_motion(self, on):
+        """mcpt_sequence_set_motion: from the next frame on, accumulate with (True) or without (False) object motion;
+        refused by an upsampled sequence."""
+        _check(lib().mcpt_sequence_set_motion(self.h, int(bool(on))))
+        self.motion = bool(on)
+
+    def motion_info(self):
+        """mcpt_sequence_motion_info of the last frame: the device seconds of the motion AOVs; motion=True only."""
+        s = C.c_double()
+        _check(lib().mcpt_sequence_motion_info(self.h, C.byref(s)))
+        return s.value
 
     def frame(self, camera, seed=DEFAULT_SEED, readback=True):
         """One frame with `camera` (of the sequence's size) and `seed`; returns the tone-mapped H x W x 3 uint8 frame
@@ -1144,8 +1283,9 @@ class FrameSequence:
 
     def read(self, name):
         """The last frame's buffer `name` as a float64 array: raw, accumulated, filtered, fast (H x W x 3), moments
-        (H x W x 4), variance, shift (H x W); with upsample=F also upsampled (F H x F W x 3)."""
-        what, tail = SEQ_BUFFERS.get(name, (-1, ()))
+        (H x W x 4), variance, shift (H x W); with upsample=F also upsampled (F H x F W x 3); with motion=True also
+        prev_position and prev_normal (H x W x 3)."""
+        what, tail = SEQ_BUFFERS.get(name, SEQ_MOTION_BUFFERS.get(name, (-1, ())))
         f = self.factor if name == "upsampled" or (self.temporal_upsample and name != "raw") else 1
         out = np.zeros((f * self.height, f * self.width) + tail)
         _check(lib().mcpt_sequence_read(self.h, what, out.ctypes.data))
@@ -1155,7 +1295,7 @@ class FrameSequence:
         """The device pointer (int) of the last frame's buffer `name` (read()'s names and rgb8), valid until the next
         frame, reset or close."""
         p = C.c_void_p()
-        _check(lib().mcpt_sequence_device_buffer(self.h, SEQ_BUFFERS.get(name, (-1, ()))[0], C.byref(p)))
+        _check(lib().mcpt_sequence_device_buffer(self.h, SEQ_BUFFERS.get(name, SEQ_MOTION_BUFFERS.get(name, (-1, ())))[0], C.byref(p)))
         return p.value
 
     def upsample_info(self):

@@ -52,6 +52,11 @@
 //   k >= 1 they are set to float(double(original) + k * (DX, DY, DZ)) by mcpt_scene_update (the BVH is refit in place, no
 //   rebuild), and the frame prints a "moved" line with the update's statistics.  A range with a light triangle, or a
 //   step that leaves the scene's arena, ends the run with the library's message.
+//               [--motion]
+//   --motion (with --frames N, with or without --device-sequence; meant for --move) lets the history follow the moved
+//   facets: before each frame's move the scene's pose is saved (mcpt_scene_pose_save), the frame renders the motion AOVs
+//   (mcpt_render_motion_aovs) and accumulates with mcpt_temporal_accumulate_motion (mcpt_sequence_set_motion in the device
+//   sequence), so a moved surface keeps its history instead of restarting it every frame.  Not with --upsample.
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -198,6 +203,7 @@ struct SequenceArgs {
     bool progress, grid, denoise;
     std::string out, hdr_out, aov_out;
     Mover* move;  // --move, or null
+    bool motion;  // --motion
 };
 
 // --frames: render, accumulate (and filter) frame after frame; the history ping-pongs between two sets of buffers
@@ -247,8 +253,13 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
         if (clamp) f.fast.resize(3 * npx);
     }
     std::vector<double> hdr, variance(npx), filtered(3 * npx), shift(clamp ? npx : 0), upsampled;
+    std::vector<double> prev_position(a.motion ? 3 * npx : 0), prev_normal(a.motion ? 3 * npx : 0);
     for (int k = 0; k < a.frames; k++) {
         Frame &cur = fr[k & 1], &prev = fr[(k & 1) ^ 1];
+        if (a.motion && mcpt_scene_pose_save(scene) != MCPT_OK) {
+            std::fprintf(stderr, "--motion failed: %s\n", mcpt_last_error());
+            return 1;
+        }
         if (a.move && a.move->apply(scene, k)) return 1;
         if (mcpt_camera_orbit(&cam0, k * a.orbit, &cur.cam) != MCPT_OK) {
             std::fprintf(stderr, "%s\n", mcpt_last_error());
@@ -268,8 +279,19 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
             std::fprintf(stderr, "AOV render failed: %s\n", mcpt_last_error());
             return 1;
         }
+        const mcpt_motion_buffers mo{prev_position.data(), prev_normal.data()};
+        if (a.motion && mcpt_render_motion_aovs(scene, &cur.cam, &ao, &mo) != MCPT_OK) {
+            std::fprintf(stderr, "motion AOV render failed: %s\n", mcpt_last_error());
+            return 1;
+        }
         double tsec = 0;
-        const int rc = clamp ? mcpt_temporal_accumulate_clamped(&tp, clamp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov,
+        const int rc = a.motion ? mcpt_temporal_accumulate_motion(&tp, clamp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov, &mo,
+                                                                  k ? &paov : nullptr, k ? prev.color.data() : nullptr,
+                                                                  k ? prev.moments.data() : nullptr,
+                                                                  clamp && k ? prev.fast.data() : nullptr, cur.color.data(),
+                                                                  cur.moments.data(), clamp ? cur.fast.data() : nullptr,
+                                                                  clamp ? shift.data() : nullptr, variance.data(), &tsec)
+                       : clamp ? mcpt_temporal_accumulate_clamped(&tp, clamp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov,
                                                                 k ? &paov : nullptr, k ? prev.color.data() : nullptr,
                                                                 k ? prev.moments.data() : nullptr, k ? prev.fast.data() : nullptr,
                                                                 cur.color.data(), cur.moments.data(), cur.fast.data(),
@@ -357,6 +379,11 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
         std::fprintf(stderr, "sequence setup failed: %s\n", mcpt_last_error());
         return 1;
     }
+    if (a.motion && mcpt_sequence_set_motion(seq, 1) != MCPT_OK) {
+        std::fprintf(stderr, "sequence setup failed: %s\n", mcpt_last_error());
+        mcpt_sequence_destroy(seq);
+        return 1;
+    }
     std::vector<uint8_t> rgb8(3 * npx);
     std::vector<double> shown;
     int rc = 0;
@@ -364,6 +391,11 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
         mcpt_camera cam;
         mcpt_sequence_info fi{};
         last = -10;
+        if (a.motion && mcpt_scene_pose_save(scene) != MCPT_OK) {
+            std::fprintf(stderr, "--motion failed: %s\n", mcpt_last_error());
+            rc = 1;
+            break;
+        }
         if (a.move && a.move->apply(scene, k)) {
             rc = 1;
             break;
@@ -451,7 +483,7 @@ int main(int argc, char** argv) {
     bool upsample = false, temporal_upsample = false;
     mcpt_upsample_opts up;
     mcpt_upsample_opts_init(&up);
-    bool move_flag = false;
+    bool move_flag = false, motion_flag = false;
     Mover mover;
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
@@ -526,6 +558,7 @@ int main(int argc, char** argv) {
             }
             move_flag = true;
         }
+        else if (!std::strcmp(argv[a], "--motion")) motion_flag = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -554,6 +587,11 @@ int main(int argc, char** argv) {
     }
     if (move_flag && frames == 0) {  // refused before anything is loaded
         std::fprintf(stderr, "--move moves facets between the frames of a sequence; add --frames N\n");
+        return 2;
+    }
+    if (motion_flag && (frames == 0 || upsample)) {  // refused before anything is loaded
+        std::fprintf(stderr, "--motion %s\n", frames == 0 ? "follows moved facets through the history of a sequence; add --frames N"
+                                                          : "is not supported with upsampling; drop --upsample");
         return 2;
     }
     if (temporal_upsample) {  // refused before anything is loaded
@@ -656,7 +694,7 @@ int main(int argc, char** argv) {
             if (const int rc = mover.bind(scene)) return rc;
         }
         const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out,
-                              move_flag ? &mover : nullptr};
+                              move_flag ? &mover : nullptr, motion_flag};
         if (clamp_flag && !history_clamp) {
             std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
             return 2;

@@ -184,10 +184,11 @@ struct TemporalClampIo {  // the clamped rule's extra arguments
     double* out_shift;  // required here: the kernels pass "has a history" through it (the public form's scratch)
 };
 int temporal_check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, bool clamped);
-// io == nullptr: mcpt_temporal_accumulate's rule, else mcpt_temporal_accumulate_clamped's
+// io == nullptr: mcpt_temporal_accumulate's rule, else mcpt_temporal_accumulate_clamped's; motion != nullptr: either
+// in mcpt_temporal_accumulate_motion's form (both arrays required)
 int temporal_enqueue(const mcpt_temporal_opts* o, const mcpt_camera* prev_cam, int32_t W, int32_t H, const double* dC,
                      const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut,
-                     double* dOutM, double* dOutV, const TemporalClampIo* io);
+                     double* dOutM, double* dOutV, const TemporalClampIo* io, const mcpt_motion_buffers* motion = nullptr);
 int denoise_check_opts(const mcpt_denoise_opts* o);
 // tmp: 8 * W * H doubles of scratch (two colour + variance buffers)
 int denoise_enqueue(const mcpt_denoise_opts* o, int32_t W, int32_t H, const double* dC, const double* dV,
@@ -215,5 +216,11 @@ int temporal_upsample_enqueue(const mcpt_temporal_opts* tp, const mcpt_upsample_
 // render.hip -- mcpt_camera_phase_rays_device's checks that need no device, then its kernel on the null stream of the
 // current device
 int camera_phase_rays_enqueue(const mcpt_camera* full_cam, int32_t factor, int32_t a, int32_t b, double* dOrigin, double* dDir);
+
+// render.hip -- k_motion_aovs alone, on the primary-hit tables the scene's state on `device` holds from its last
+// mcpt_render_aovs[_device] call, which must have been for a W x H camera (the frame sequence calls it right after the
+// frame's AOVs, so no second primary trace is made).  Takes the scene's lock, launches on the state's stream and waits
+// for it.  dev_out: device pointers on `device`, either may be null; no pointer query.
+int motion_aovs_enqueue(mcpt_scene* scene, int32_t device, int32_t W, int32_t H, const mcpt_motion_buffers* dev_out);
 
 }  // namespace mcpt

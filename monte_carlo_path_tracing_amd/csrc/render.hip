@@ -1038,6 +1038,22 @@ __global__ __launch_bounds__(256) void k_aovs(DScene S, CamFrame cam, const int*
     if (o.depth) o.depth[px] = depth;
 }
 
+// Motion AOVs (mcpt_render_motion_aovs): S is the scene with tri_v / tri_n pointing at the PREVIOUS pose, so node_point
+// -- the function k_root_table gave k_aovs' position and normal with -- evaluates the current hit's (facet, beta, gamma)
+// over the previous vertices.  Reads the primary hits, not the root table; a miss writes 0.  Either output may be null.
+// Lane per pixel: the loads of hit_f / hit_tbg and the stores are consecutive across a wave, the 18 floats of the facet
+// are a gather (neighbouring pixels mostly share the facet).
+__global__ __launch_bounds__(256) void k_motion_aovs(DScene S, int npx, const int* hit_f, const double* hit_tbg, mcpt_motion_buffers o) {
+    const int px = blockIdx.x * blockDim.x + threadIdx.x;
+    if (px >= npx) return;
+    const int f = hit_f[px];
+    d3 p = mk3(0, 0, 0), N = mk3(0, 0, 0);
+    if (f >= 0) node_point(S, f, hit_tbg[3 * (size_t)px + 1], hit_tbg[3 * (size_t)px + 2], &p, &N);
+    const size_t k = 3 * (size_t)px;
+    if (o.prev_position) o.prev_position[k] = p.x, o.prev_position[k + 1] = p.y, o.prev_position[k + 2] = p.z;
+    if (o.prev_normal) o.prev_normal[k] = N.x, o.prev_normal[k + 1] = N.y, o.prev_normal[k + 2] = N.z;
+}
+
 // pixel and sample of root rg (the call's root index; order above)
 __device__ inline void root_of(long long rg, int npx, int s0, int group, int nsamp, int* pixel, int* sample) {
     const long long full = (long long)(nsamp / group) * group * npx;  // roots in whole blocks
@@ -4532,6 +4548,9 @@ struct DeviceState {
     RefitDev refit{};
     std::vector<int32_t> level_first;
     DevBuf up_pos, up_nrm;
+    // mcpt_scene_pose_save: the previous pose's copies of d.tri_v / d.tri_n (null until the first save or, for a state
+    // created after it, from the host copy: the previous pose is then the current one)
+    DevBuf prev_v, prev_n;
     unsigned* pinned_count = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evp0 = nullptr, evp1 = nullptr, evr0 = nullptr, evr1 = nullptr;
 };
@@ -4558,6 +4577,9 @@ struct mcpt_scene {
     bool updated = false;
     BvhRefitIndex refit_ix;
     std::vector<int32_t> slot_start, slot_list;
+    // mcpt_scene_pose_save: host.pos / host.nrm as they were at the last save (empty until the first one)
+    bool pose_saved = false;
+    std::vector<float> prev_pos, prev_nrm;
 };
 
 namespace {
@@ -4880,6 +4902,16 @@ int get_device_state(mcpt_scene* sc, int device, DeviceState** out) {
     if ((rc = upload(*D, quantize_bvh4(b4), &d.bvh4q))) return rc;
     if ((rc = upload(*D, quantize_bvh4(lb4), &d.lbvh4q))) return rc;
     if ((rc = upload(*D, leaf_vertices(s, sc->lbvh), &d.lleaf_v))) return rc;
+    if (sc->pose_saved) {  // a state created after mcpt_scene_pose_save: its previous pose from the host copy
+        std::vector<float4> pv(tv.size());
+        for (int f = 0; f < s.F; f++)
+            for (int k = 0; k < 3; k++)
+                pv[3 * f + k] = make_float4(sc->prev_pos[9 * f + 3 * k], sc->prev_pos[9 * f + 3 * k + 1], sc->prev_pos[9 * f + 3 * k + 2], 0.f);
+        if ((rc = ensure(D->prev_v, pv.size() * sizeof(float4))) || (rc = ensure(D->prev_n, std::max<size_t>(s.nrm.size(), 1) * sizeof(float))))
+            return rc;
+        HIP_OK(hipMemcpy(D->prev_v.p, pv.data(), pv.size() * sizeof(float4), hipMemcpyHostToDevice));
+        if (!sc->prev_nrm.empty()) HIP_OK(hipMemcpy(D->prev_n.p, sc->prev_nrm.data(), sc->prev_nrm.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
     HIP_OK(hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking));
     HIP_OK(hipHostMalloc(&D->pinned_count, 64 + kCtrlBytes));
     HIP_OK(hipEventCreate(&D->ev0));
@@ -6773,7 +6805,8 @@ void mcpt_scene_destroy(mcpt_scene* sc) {
                                      &D->root_kind, &D->exact, &D->exact_scr, &D->slack, &D->lit_slot, &D->lit_pool,
                                      &D->sc_cum, &D->sc_wsum, &D->sc_last, &D->cull_keys, &D->cull_order, &D->cull_count,
                                      &D->ad_acc[0], &D->ad_acc[1], &D->ad_list[0], &D->ad_list[1], &D->ad_state[0],
-                                     &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise, &D->aov, &D->up_pos, &D->up_nrm};
+                                     &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise, &D->aov, &D->up_pos, &D->up_nrm,
+                                     &D->prev_v, &D->prev_n};
         for (int k = 0; k < 14; k++) bufs.insert(bufs.end(), {&D->qa[k], &D->qb[k], &D->qs[k]});
         for (int k = 0; k < 9; k++) bufs.push_back(&D->aux[k]);
         for (int k = 0; k < 13; k++) bufs.push_back(&D->sl[k]);
@@ -7044,6 +7077,39 @@ int mcpt_scene_update_device(mcpt_scene* sc, int32_t device, int32_t first, int3
     if (dnrm) HIP_OK(hipMemcpy(hn.data(), dnrm, 36ull * count, hipMemcpyDeviceToHost));
     HIP_OK(hipSetDevice(cur));
     return update_apply(sc, first, count, hp.data(), dnrm ? hn.data() : nullptr, device, dpos, dnrm, stats);
+}
+
+// ---- mcpt_scene_pose_save (include/mcpt.h) ----
+int mcpt_scene_pose_save(mcpt_scene* sc) {
+    if (!sc) {
+        set_error("mcpt_scene_pose_save: NULL scene");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    sc->prev_pos = sc->host.pos;
+    sc->prev_nrm = sc->host.nrm;
+    sc->pose_saved = true;
+    std::vector<DeviceState*> devs;
+    {
+        std::lock_guard<std::mutex> dl(sc->devs_mu);
+        for (auto& D : sc->devs) devs.push_back(D.get());
+    }
+    if (devs.empty()) return MCPT_OK;
+    int cur = 0;
+    HIP_OK(hipGetDevice(&cur));
+    for (DeviceState* D : devs) {
+        HIP_OK(hipSetDevice(D->device));
+        const size_t vb = 3 * (size_t)std::max(D->d.F, 1) * sizeof(float4), nb = 9 * (size_t)D->d.F * sizeof(float);
+        int rc;
+        if ((rc = ensure(D->prev_v, vb)) || (rc = ensure(D->prev_n, std::max<size_t>(nb, 4)))) return rc;
+        // device to device on the state's stream: ordered after the refits (mcpt_scene_update) and before the motion
+        // AOVs, which run there too
+        HIP_OK(hipMemcpyAsync(D->prev_v.p, D->d.tri_v, vb, hipMemcpyDeviceToDevice, D->stream));
+        if (nb) HIP_OK(hipMemcpyAsync(D->prev_n.p, D->d.tri_n, nb, hipMemcpyDeviceToDevice, D->stream));
+        HIP_OK(hipStreamSynchronize(D->stream));
+    }
+    HIP_OK(hipSetDevice(cur));
+    return MCPT_OK;
 }
 
 int mcpt_scene_camera(const mcpt_scene* sc, mcpt_camera* cam) {
@@ -7395,16 +7461,28 @@ int mcpt_render_adaptive(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_rend
     return MCPT_OK;
 }
 
-// mcpt_render_aovs / _device: a render's per-pixel tables (bind / launch_primary_tables) and k_aovs.  host: the
-// maps go through D.aov and are copied out; else `out` holds device pointers and k_aovs writes them directly.
+// k_motion_aovs on D's stream over D's primary-hit tables: the scene as the kernels see it, with the facet arrays of
+// the previous pose (the current ones until the first mcpt_scene_pose_save)
+static int launch_motion_aovs(DeviceState& D, int npx, const mcpt_motion_buffers& dev) {
+    DScene S = D.d;
+    if (D.prev_v.p) S.tri_v = (const float4*)D.prev_v.p, S.tri_n = (const float*)D.prev_n.p;
+    hipLaunchKernelGGL(k_motion_aovs, dim3((npx + 255) / 256), dim3(256), 0, D.stream, S, npx, (const int*)D.hit_f.p,
+                       (const double*)D.hit_tbg.p, dev);
+    HIP_OK(hipGetLastError());
+    return MCPT_OK;
+}
+
+// mcpt_render_aovs / _device (out) and mcpt_render_motion_aovs / _device (mout; the other one is null): a render's
+// per-pixel tables (bind / launch_primary_tables), then k_aovs or k_motion_aovs.  host: the maps go through D.aov and
+// are copied out; else the struct holds device pointers and the kernel writes them directly.
 static int render_aovs_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o, const mcpt_aov_buffers* out,
-                            bool host) {
-    if (!sc || !o || !out) {
+                            const mcpt_motion_buffers* mout, bool host, const char* what) {
+    if (!sc || !o || (!out && !mout)) {
         set_error("null argument");
         return MCPT_E_INVALID;
     }
     int rc;
-    if ((rc = check_single_device(o, "mcpt_render_aovs")) || (rc = check_opts(o)) || (rc = validate_camera(cam))) return rc;
+    if ((rc = check_single_device(o, what)) || (rc = check_opts(o)) || (rc = validate_camera(cam))) return rc;
     if (o->accel != MCPT_ACCEL_BVH && o->accel != MCPT_ACCEL_GRID) {
         set_error("invalid accel %d", o->accel);
         return MCPT_E_INVALID;
@@ -7420,44 +7498,67 @@ static int render_aovs_impl(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_r
         if ((rc = use_grid(sc, *D, eye, 100000))) return rc;
     }
     if ((rc = bind_primary_tables(*D, npx))) return rc;
-    mcpt_aov_buffers dev = *out;
+    struct Map {
+        double* user;  // the caller's pointer (null: not asked for)
+        size_t per_px;
+        const char* name;
+        double* dev;   // what the kernel writes
+    } maps[4];
+    int nmaps;
+    if (out) {
+        const Map m[4] = {{out->albedo, 3, "dev_out.albedo", nullptr}, {out->normal, 3, "dev_out.normal", nullptr},
+                          {out->position, 3, "dev_out.position", nullptr}, {out->depth, 1, "dev_out.depth", nullptr}};
+        std::copy(m, m + 4, maps), nmaps = 4;
+    } else {
+        const Map m[2] = {{mout->prev_position, 3, "dev_out.prev_position", nullptr},
+                          {mout->prev_normal, 3, "dev_out.prev_normal", nullptr}};
+        std::copy(m, m + 2, maps), nmaps = 2;
+    }
     if (host) {
         if ((rc = ensure(D->aov, 80 * npx))) return rc;
         double* b = (double*)D->aov.p;
-        dev = mcpt_aov_buffers{out->albedo ? b : nullptr, out->normal ? b + 3 * npx : nullptr,
-                               out->position ? b + 6 * npx : nullptr, out->depth ? b + 9 * npx : nullptr};
+        for (int k = 0; k < nmaps; b += maps[k].per_px * npx, k++) maps[k].dev = maps[k].user ? b : nullptr;
     } else {
-        if ((dev.albedo && (rc = check_device_buffer(dev.albedo, D->device, "dev_out.albedo"))) ||
-            (dev.normal && (rc = check_device_buffer(dev.normal, D->device, "dev_out.normal"))) ||
-            (dev.position && (rc = check_device_buffer(dev.position, D->device, "dev_out.position"))) ||
-            (dev.depth && (rc = check_device_buffer(dev.depth, D->device, "dev_out.depth"))))
-            return rc;
+        for (int k = 0; k < nmaps; k++) {
+            maps[k].dev = maps[k].user;
+            if (maps[k].dev && (rc = check_device_buffer(maps[k].dev, D->device, maps[k].name))) return rc;
+        }
         // the caller's buffers may still be written by work on other streams (e.g. torch's)
         HIP_OK(hipDeviceSynchronize());
     }
     const hipStream_t st = D->stream;
     const int n = (int)npx;
     if ((rc = launch_primary_tables(*D, cf, n, grid))) return rc;
-    hipLaunchKernelGGL(k_aovs, dim3((n + 255) / 256), dim3(256), 0, st, D->d, cf, (const int*)D->hit_f.p,
-                       (const double*)D->root_pnw.p, dev);
-    HIP_OK(hipGetLastError());
-    if (host) {
-        if (out->albedo) HIP_OK(hipMemcpyAsync(out->albedo, dev.albedo, 24 * npx, hipMemcpyDeviceToHost, st));
-        if (out->normal) HIP_OK(hipMemcpyAsync(out->normal, dev.normal, 24 * npx, hipMemcpyDeviceToHost, st));
-        if (out->position) HIP_OK(hipMemcpyAsync(out->position, dev.position, 24 * npx, hipMemcpyDeviceToHost, st));
-        if (out->depth) HIP_OK(hipMemcpyAsync(out->depth, dev.depth, 8 * npx, hipMemcpyDeviceToHost, st));
+    if (out) {
+        hipLaunchKernelGGL(k_aovs, dim3((n + 255) / 256), dim3(256), 0, st, D->d, cf, (const int*)D->hit_f.p,
+                           (const double*)D->root_pnw.p, mcpt_aov_buffers{maps[0].dev, maps[1].dev, maps[2].dev, maps[3].dev});
+        HIP_OK(hipGetLastError());
+    } else if ((rc = launch_motion_aovs(*D, n, mcpt_motion_buffers{maps[0].dev, maps[1].dev}))) {
+        return rc;
     }
+    if (host)
+        for (int k = 0; k < nmaps; k++)
+            if (maps[k].user) HIP_OK(hipMemcpyAsync(maps[k].user, maps[k].dev, 8 * maps[k].per_px * npx, hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
     return MCPT_OK;
 }
 
 int mcpt_render_aovs(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o, const mcpt_aov_buffers* out) {
-    return render_aovs_impl(sc, cam, o, out, true);
+    return render_aovs_impl(sc, cam, o, out, nullptr, true, "mcpt_render_aovs");
 }
 
 int mcpt_render_aovs_device(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o,
                             const mcpt_aov_buffers* dev_out) {
-    return render_aovs_impl(sc, cam, o, dev_out, false);
+    return render_aovs_impl(sc, cam, o, dev_out, nullptr, false, "mcpt_render_aovs");
+}
+
+int mcpt_render_motion_aovs(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o, const mcpt_motion_buffers* out) {
+    return render_aovs_impl(sc, cam, o, nullptr, out, true, "mcpt_render_motion_aovs");
+}
+
+int mcpt_render_motion_aovs_device(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o,
+                                   const mcpt_motion_buffers* dev_out) {
+    return render_aovs_impl(sc, cam, o, nullptr, dev_out, false, "mcpt_render_motion_aovs");
 }
 
 int mcpt_debug_adaptive_active(mcpt_scene* sc, int32_t device, int32_t* pixels, int32_t cap, int32_t* n) {
@@ -7949,3 +8050,27 @@ int mcpt_primary_hits(mcpt_scene* sc, const mcpt_camera* cam, int32_t* facet, do
 }
 
 }  // extern "C"
+
+// mcpt_internal.h: the motion AOVs on the tables of the state's last AOV call (sequence.hip)
+namespace mcpt {
+
+int motion_aovs_enqueue(mcpt_scene* sc, int32_t device, int32_t W, int32_t H, const mcpt_motion_buffers* dev_out) {
+    if (!sc || !dev_out || W < 1 || H < 1) {
+        set_error("motion_aovs_enqueue: invalid argument");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    int rc;
+    if ((rc = get_device_state(sc, device, &D))) return rc;
+    const size_t npx = (size_t)W * H;
+    if (!D->hit_f.p || D->hit_f.bytes < 4 * npx || !D->hit_tbg.p || D->hit_tbg.bytes < 24 * npx) {
+        set_error("motion_aovs_enqueue: device %d holds no primary-hit tables of %d x %d pixels", D->device, W, H);
+        return MCPT_E_INVALID;
+    }
+    if ((rc = launch_motion_aovs(*D, (int)npx, *dev_out))) return rc;
+    HIP_OK(hipStreamSynchronize(D->stream));
+    return MCPT_OK;
+}
+
+}  // namespace mcpt

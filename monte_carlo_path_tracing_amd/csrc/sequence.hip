@@ -20,6 +20,10 @@
 // phase rays (camera_phase_rays_enqueue), mcpt_render_rays_device into the low raw frame, the full-size AOVs,
 // temporal_upsample_enqueue and from there the plain frame's stages on full-size buffers.
 //
+// With mcpt_sequence_set_motion a plain sequence's frame adds one stage after the AOVs: motion_aovs_enqueue
+// (mcpt_internal.h: k_motion_aovs on the primary-hit tables the AOVs just built) into two maps allocated at the first
+// set_motion(on), and temporal_enqueue takes them (mcpt_temporal_accumulate_motion's rule).
+//
 // The tone map's loads are plain: lane k reads values 4 k .. 4 k + 3 (32 consecutive bytes, a wave 2 KB), stores
 // are one dword per lane.  pow is the device library's; -ffp-contract=off as everywhere.  The statistics read the
 // moments' n (every fourth double) and the shift once: thread t of a block takes the chunk's pixels t, t + 256, ...
@@ -210,16 +214,25 @@ struct mcpt_sequence {
     bool has_prev = false;  // set[cur ^ 1] holds a history
     bool has_last = false;  // set[cur ^ 1] and the shared buffers hold the last frame
     uint64_t frame_index = 0;
+    // object motion (mcpt_sequence_set_motion): the two motion AOVs, an allocation of their own made at the first
+    // set_motion(on); motion: the next frame runs with it; last_motion: the last frame did
+    bool motion = false, last_motion = false;
+    double* motion_mem = nullptr;
+    mcpt_motion_buffers mo{};
+    hipEvent_t ev_motion = nullptr;  // between the AOVs and the motion AOVs
+    double motion_seconds = 0;
 };
 
 namespace {
 
 void release(mcpt_sequence* s) {
     if (!s) return;
-    if (s->mem || s->host_stats || s->ev[0]) {
+    if (s->mem || s->host_stats || s->ev[0] || s->motion_mem || s->ev_motion) {
         int cur = 0;
         const bool sw = hipGetDevice(&cur) == hipSuccess && cur != s->device && hipSetDevice(s->device) == hipSuccess;
         if (s->mem) (void)hipFree(s->mem);
+        if (s->motion_mem) (void)hipFree(s->motion_mem);
+        if (s->ev_motion) (void)hipEventDestroy(s->ev_motion);
         if (s->host_stats) (void)hipHostFree(s->host_stats);
         for (hipEvent_t e : s->ev)
             if (e) (void)hipEventDestroy(e);
@@ -264,6 +277,16 @@ int locate(mcpt_sequence* s, int32_t what, bool allow_rgb8, const void** dev, si
             }
             if (what == MCPT_SEQ_FAST) p = L.fast, b = 3 * n * d;
             else p = s->shift, b = n * d;
+            break;
+        case MCPT_SEQ_PREV_POSITION:
+        case MCPT_SEQ_PREV_NORMAL:
+            if (!s->motion || (s->has_last && !s->last_motion)) {
+                set_error("%s: %s", what == MCPT_SEQ_PREV_POSITION ? "MCPT_SEQ_PREV_POSITION" : "MCPT_SEQ_PREV_NORMAL",
+                          !s->motion ? "motion is off for this sequence (mcpt_sequence_set_motion)"
+                                     : "the last frame ran before motion was switched on");
+                return MCPT_E_INVALID;
+            }
+            p = what == MCPT_SEQ_PREV_POSITION ? s->mo.prev_position : s->mo.prev_normal, b = 3 * n * d;
             break;
         case MCPT_SEQ_RGB8:
             if (allow_rgb8) {
@@ -697,11 +720,18 @@ int mcpt_sequence_frame(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed,
     DN_HIP_OK(hipEventRecord(s->ev[0], nullptr));
     if ((rc = mcpt_render_aovs_device(s->scene, cam, &ro, &C.g))) return rc;
     DN_HIP_OK(hipSetDevice(device));
+    const bool motion = s->motion;
+    if (motion) {  // ev[0] .. ev_motion the AOVs, ev_motion .. ev[1] the motion AOVs, on the tables the AOVs just built
+        DN_HIP_OK(hipEventRecord(s->ev_motion, nullptr));
+        if ((rc = mcpt::motion_aovs_enqueue(s->scene, device, W, H, &s->mo))) return rc;
+        DN_HIP_OK(hipSetDevice(device));
+    }
     DN_HIP_OK(hipEventRecord(s->ev[1], nullptr));
     const mcpt::TemporalClampIo io{&s->tc, s->has_prev ? P.fast : nullptr, C.fast, s->shift};
     const bool hp = s->has_prev;
     if ((rc = mcpt::temporal_enqueue(&s->tp, hp ? &P.cam : nullptr, W, H, s->raw, &C.g, hp ? &P.g : nullptr, hp ? P.color : nullptr,
-                                     hp ? P.moments : nullptr, C.color, C.moments, s->variance, s->opts.clamp ? &io : nullptr)))
+                                     hp ? P.moments : nullptr, C.color, C.moments, s->variance, s->opts.clamp ? &io : nullptr,
+                                     motion ? &s->mo : nullptr)))
         return rc;
     StatsOut* dres = nullptr;
     if ((rc = enqueue_stats(C.moments, s->shift, npx, s->stats_words, &dres))) return rc;
@@ -732,6 +762,13 @@ int mcpt_sequence_frame(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed,
     float ms[4] = {0, 0, 0, 0};
     for (int k = 0; k < 3; k++) DN_HIP_OK(hipEventElapsedTime(&ms[k], s->ev[k], s->ev[k + 1]));
     DN_HIP_OK(hipEventElapsedTime(&ms[3], s->ev[s->factor ? 6 : 3], s->ev[4]));
+    if (motion) {
+        float mm = 0;
+        DN_HIP_OK(hipEventElapsedTime(&ms[0], s->ev[0], s->ev_motion));
+        DN_HIP_OK(hipEventElapsedTime(&mm, s->ev_motion, s->ev[1]));
+        s->motion_seconds = mm * 1e-3;
+    }
+    s->last_motion = motion;
     if (s->factor) {
         float g = 0, u = 0;
         DN_HIP_OK(hipEventElapsedTime(&g, s->ev[3], s->ev[5]));
@@ -753,6 +790,46 @@ int mcpt_sequence_frame(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed,
     s->cur ^= 1;
     s->has_prev = s->has_last = true;
     s->frame_index++;
+    return MCPT_OK;
+}
+
+int mcpt_sequence_set_motion(mcpt_sequence* s, int32_t on) {
+    if (!s) {
+        set_error("null mcpt_sequence");
+        return MCPT_E_INVALID;
+    }
+    if (s->factor || s->tu) {
+        set_error("mcpt_sequence_set_motion: object motion is not supported in a sequence created by %s (use mcpt_sequence_create)",
+                  s->tu ? "mcpt_sequence_create_temporal_upsampled" : "mcpt_sequence_create_upsampled");
+        return MCPT_E_INVALID;
+    }
+    if (on && !s->motion_mem) {
+        int device;
+        Scratch S;  // restores the caller's device
+        int rc;
+        if ((rc = select_device(s->device, S, &device))) return rc;
+        if (!s->ev_motion) DN_HIP_OK(hipEventCreate(&s->ev_motion));
+        DN_HIP_OK(hipMalloc(&s->motion_mem, 6 * s->npx * sizeof(double)));
+        s->mo.prev_position = s->motion_mem, s->mo.prev_normal = s->motion_mem + 3 * s->npx;
+    }
+    s->motion = on != 0;
+    return MCPT_OK;
+}
+
+int mcpt_sequence_motion_info(mcpt_sequence* s, double* motion_seconds) {
+    if (!s) {
+        set_error("null mcpt_sequence");
+        return MCPT_E_INVALID;
+    }
+    if (!s->has_last) {
+        set_error("the sequence holds no frame (none since create, reset or a failed frame)");
+        return MCPT_E_INVALID;
+    }
+    if (!s->last_motion) {
+        set_error("mcpt_sequence_motion_info: the last frame ran without motion (mcpt_sequence_set_motion)");
+        return MCPT_E_INVALID;
+    }
+    if (motion_seconds) *motion_seconds = s->motion_seconds;
     return MCPT_OK;
 }
 

@@ -1,9 +1,10 @@
-// Temporal accumulation for gfx950 (mcpt_temporal_accumulate and mcpt_temporal_accumulate_clamped, include/mcpt.h
-// states both rules in full) and the host helper mcpt_camera_orbit.  No counterpart in the reference.
+// Temporal accumulation for gfx950 (mcpt_temporal_accumulate, mcpt_temporal_accumulate_clamped and
+// mcpt_temporal_accumulate_motion, include/mcpt.h states the rules in full) and the host helper mcpt_camera_orbit.  No
+// counterpart in the reference.
 //
 //   k_temporal_accumulate  lane per pixel : reproject, gather the four taps of the previous history, blend,
 //                                           and the temporal variance where the history is long enough; the
-//                                           <true> instantiation (the clamped call) gathers and blends the fast
+//                                           <true, *> instantiations (the clamped call) gather and blend the fast
 //                                           history with the same taps and leaves the variance to the clamp
 //   k_temporal_clamp       lane per pixel : (the clamped call) mean and standard deviation of the fast history over
 //                                           the hit taps of the clipped window (an LDS tile), two passes; clamps
@@ -11,6 +12,10 @@
 //                                           and the temporal variance; lanes without history leave early
 //   k_temporal_spatial     lane per pixel : V_0 of the a-trous filter on the blended colour, only in lanes whose
 //                                           history is short (the others leave at once)
+//
+// The <*, true> instantiations (mcpt_temporal_accumulate_motion) take the reprojected point and the normal of the tap tests
+// from the motion AOVs (the surface point's previous position and normal) instead of the current guides: three
+// substitutions, two more pointers in TpParams, 6 doubles more read per pixel; everything else is the same code.
 //
 // Everything is fp64 with -ffp-contract=off, so a numpy restatement of the rule reproduces the output to
 // rounding (tests/test_temporal.py).  A block is 64 x 4 pixels as in denoise.hip: the centre's loads and the
@@ -49,11 +54,13 @@ struct TpParams {
     double alpha_fast, sigma;
     const double* pF;
     double *outF, *outS;  // outS: k_temporal_accumulate<true> leaves "has a history" (1 or 0), k_temporal_clamp the shift
+    // the motion call only: the previous position and normal of every pixel's surface point
+    const double *mX, *mN;
 };
 
 __device__ inline bool temporal_variance_applies(const TpParams& P, double n, double g) { return n > P.var_n && g < 1.0; }
 
-template <bool FAST>
+template <bool FAST, bool MOTION>
 __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
     const int x = blockIdx.x * kBx + threadIdx.x, y = blockIdx.y * kBy + threadIdx.y;
     if (x >= P.W || y >= P.H) return;
@@ -65,8 +72,11 @@ __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
     double f0 = 0.0, f1 = 0.0, f2 = 0.0;  // FAST: the fast history's gather
     bool source = false;
     if (P.has_prev && depth > 0) {
-        const double N0 = P.N[3 * p], N1 = P.N[3 * p + 1], N2 = P.N[3 * p + 2];
-        const double X0 = P.X[3 * p], X1 = P.X[3 * p + 1], X2 = P.X[3 * p + 2];
+        // MOTION: the source and the taps' normal and plane tests take the point where it was a frame ago
+        const double* pn = MOTION ? P.mN : P.N;
+        const double* px = MOTION ? P.mX : P.X;
+        const double N0 = pn[3 * p], N1 = pn[3 * p + 1], N2 = pn[3 * p + 2];
+        const double X0 = px[3 * p], X1 = px[3 * p + 1], X2 = px[3 * p + 2];
         const double d0 = X0 - P.E[0], d1 = X1 - P.E[1], d2 = X2 - P.E[2];
         const double a = d0 * P.U[0] + d1 * P.U[1] + d2 * P.U[2];
         const double b = d0 * P.V[0] + d1 * P.V[1] + d2 * P.V[2];
@@ -292,7 +302,8 @@ int check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* c, b
 // every check a call makes before it touches a device; *has_prev: the previous state is given
 int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* color, const mcpt_aov_buffers* g,
                const mcpt_aov_buffers* pg, const double* pcol, const double* pmom, const double* out, const double* outm,
-               const double* outv, bool* has_prev, bool clamped = false, const ClampArgs& ca = ClampArgs{}) {
+               const double* outv, bool* has_prev, bool clamped = false, const ClampArgs& ca = ClampArgs{},
+               bool with_motion = false, const mcpt_motion_buffers* mo = nullptr) {
     int orc;
     if ((orc = check_opts(o, ca.clamp, clamped))) return orc;
     if (W < 1 || H < 1 || (long long)W * H > (1ll << 28)) {
@@ -310,6 +321,11 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
     if (!g || !g->albedo || !g->normal || !g->position || !g->depth) {
         set_error("null argument: guides (%s); all four guide arrays are required",
                   !g ? "the struct" : !g->albedo ? "albedo" : !g->normal ? "normal" : !g->position ? "position" : "depth");
+        return MCPT_E_INVALID;
+    }
+    if (with_motion && (!mo || !mo->prev_position || !mo->prev_normal)) {
+        set_error("null argument: motion (%s); both motion arrays are required",
+                  !mo ? "the struct" : !mo->prev_position ? "prev_position" : "prev_normal");
         return MCPT_E_INVALID;
     }
     const int given = (pc != nullptr) + (pg != nullptr) + (pcol != nullptr) + (pmom != nullptr);
@@ -350,7 +366,9 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
                          {"prev_guides.depth", *has_prev ? pg->depth : nullptr, npx},
                          {"prev_color", pcol, 3 * npx},
                          {"prev_moments", pmom, 4 * npx},
-                         {"prev_fast", ca.pfast, 3 * npx}},
+                         {"prev_fast", ca.pfast, 3 * npx},
+                         {"motion.prev_position", with_motion ? mo->prev_position : nullptr, 3 * npx},
+                         {"motion.prev_normal", with_motion ? mo->prev_normal : nullptr, 3 * npx}},
                 outs[] = {{"out_color", out, 3 * npx}, {"out_moments", outm, 4 * npx}, {"out_variance", outv, npx},
                           {"out_fast", ca.outf, 3 * npx}, {"out_shift", ca.outs, npx}};  // NULL: overlaps nothing
     for (const auto& w : outs)
@@ -369,10 +387,11 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
     return MCPT_OK;
 }
 
-// the kernels over device arrays, enqueued on the null stream; ca (the clamped call): its device arrays, outs never NULL
+// the kernels over device arrays, enqueued on the null stream; ca (the clamped call): its device arrays, outs never NULL;
+// mo (the motion call): its two device arrays
 int enqueue_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* dC, const mcpt_aov_buffers* g,
                        const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut, double* dOutM,
-                       double* dOutV, const ClampArgs* ca) {
+                       double* dOutV, const ClampArgs* ca, const mcpt_motion_buffers* mo = nullptr) {
     TpParams P{};
     P.W = W, P.H = H;
     P.has_prev = pc != nullptr;
@@ -394,12 +413,15 @@ int enqueue_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W
     }
     const DnParams D{W, H, 0.0, o->sigma_normal, o->sigma_plane, o->sigma_albedo, g->albedo, g->normal, g->position, g->depth};
     const dim3 grid((W + kBx - 1) / kBx, (H + kBy - 1) / kBy), block(kBx, kBy);
+    if (mo) P.mX = mo->prev_position, P.mN = mo->prev_normal;
     if (ca) {
-        hipLaunchKernelGGL(k_temporal_accumulate<true>, grid, block, 0, nullptr, P);
+        if (mo) hipLaunchKernelGGL((k_temporal_accumulate<true, true>), grid, block, 0, nullptr, P);
+        else hipLaunchKernelGGL((k_temporal_accumulate<true, false>), grid, block, 0, nullptr, P);
         DN_HIP_OK(hipGetLastError());
         if (P.has_prev) hipLaunchKernelGGL(k_temporal_clamp, grid, block, 0, nullptr, P);  // else no pixel has a history
     } else {
-        hipLaunchKernelGGL(k_temporal_accumulate<false>, grid, block, 0, nullptr, P);
+        if (mo) hipLaunchKernelGGL((k_temporal_accumulate<false, true>), grid, block, 0, nullptr, P);
+        else hipLaunchKernelGGL((k_temporal_accumulate<false, false>), grid, block, 0, nullptr, P);
     }
     DN_HIP_OK(hipGetLastError());
     if (dOutV) {
@@ -412,12 +434,12 @@ int enqueue_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W
 // the same, timed with two events and waited for
 int run_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* dC, const mcpt_aov_buffers* g,
                    const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut, double* dOutM,
-                   double* dOutV, Scratch& S, double* seconds, const ClampArgs* ca = nullptr) {
+                   double* dOutV, Scratch& S, double* seconds, const ClampArgs* ca = nullptr, const mcpt_motion_buffers* mo = nullptr) {
     int rc;
     DN_HIP_OK(hipEventCreate(&S.e0));
     DN_HIP_OK(hipEventCreate(&S.e1));
     DN_HIP_OK(hipEventRecord(S.e0, nullptr));
-    if ((rc = enqueue_accumulate(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, ca))) return rc;
+    if ((rc = enqueue_accumulate(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, ca, mo))) return rc;
     DN_HIP_OK(hipEventRecord(S.e1, nullptr));
     DN_HIP_OK(hipEventSynchronize(S.e1));
     float ms = 0;
@@ -437,16 +459,17 @@ int temporal_check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_o
 
 int temporal_enqueue(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* dC,
                      const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut,
-                     double* dOutM, double* dOutV, const TemporalClampIo* io) {
+                     double* dOutM, double* dOutV, const TemporalClampIo* io, const mcpt_motion_buffers* motion) {
     int rc;
     bool has_prev = false;
     const ClampArgs ca = io ? ClampArgs{io->clamp, io->prev_fast, io->out_fast, io->out_shift} : ClampArgs{};
-    if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev, io != nullptr, ca))) return rc;
+    if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev, io != nullptr, ca, motion != nullptr, motion)))
+        return rc;
     if (io && !io->out_shift) {  // the kernels pass "has a history" through it: the caller's scratch
         set_error("null argument: out_shift (required by the caller-owned form)");
         return MCPT_E_INVALID;
     }
-    return enqueue_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, io ? &ca : nullptr);
+    return enqueue_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, io ? &ca : nullptr, motion);
 }
 
 int temporal_spatial_enqueue(const mcpt_temporal_opts* o, int32_t W, int32_t H, const mcpt_aov_buffers* g, const double* dOutC,
@@ -482,13 +505,15 @@ void mcpt_temporal_opts_init(mcpt_temporal_opts* o) {
     o->sigma_albedo = 0.1;
 }
 
-// both device forms; ca: the clamped call's arguments, nullptr for the plain call
+// the device forms; ca: the clamped call's arguments, nullptr for the plain call; with_motion: the motion call, mo its arrays
 static int accumulate_device(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* dC,
                              const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM,
-                             double* dOut, double* dOutM, double* dOutV, double* seconds, const ClampArgs* ca) {
+                             double* dOut, double* dOutM, double* dOutV, double* seconds, const ClampArgs* ca,
+                             bool with_motion = false, const mcpt_motion_buffers* mo = nullptr) {
     int rc;
     bool has_prev = false;
-    if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev, ca != nullptr, ca ? *ca : ClampArgs{})))
+    if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev, ca != nullptr, ca ? *ca : ClampArgs{},
+                         with_motion, mo)))
         return rc;
     Scratch S;
     int device;
@@ -506,6 +531,9 @@ static int accumulate_device(const mcpt_temporal_opts* o, const mcpt_camera* pc,
                      (rc = check_device_array(dpC, device, "dev_prev_color")) ||
                      (rc = check_device_array(dpM, device, "dev_prev_moments"))))
         return rc;
+    if (with_motion && ((rc = check_device_array(mo->prev_position, device, "dev_motion.prev_position")) ||
+                        (rc = check_device_array(mo->prev_normal, device, "dev_motion.prev_normal"))))
+        return rc;
     ClampArgs dca{};
     if (ca) {
         if ((rc = check_device_array(ca->outf, device, "dev_out_fast")) ||
@@ -520,24 +548,27 @@ static int accumulate_device(const mcpt_temporal_opts* o, const mcpt_camera* pc,
     }
     // the caller's arrays may still be written by work on other streams (e.g. torch's)
     DN_HIP_OK(hipDeviceSynchronize());
-    return run_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, S, seconds, ca ? &dca : nullptr);
+    return run_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, S, seconds, ca ? &dca : nullptr,
+                          with_motion ? mo : nullptr);
 }
 
-// both host forms
+// the host forms
 static int accumulate_host(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* color,
                            const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* pcol, const double* pmom,
-                           double* out, double* outm, double* outv, double* seconds, const ClampArgs* ca) {
+                           double* out, double* outm, double* outv, double* seconds, const ClampArgs* ca,
+                           bool with_motion = false, const mcpt_motion_buffers* mo = nullptr) {
     int rc;
     bool has_prev = false;
-    if ((rc = check_call(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, &has_prev, ca != nullptr, ca ? *ca : ClampArgs{})))
+    if ((rc = check_call(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, &has_prev, ca != nullptr, ca ? *ca : ClampArgs{},
+                         with_motion, mo)))
         return rc;
     Scratch S;
     int device;
     if ((rc = select_device(o->device, S, &device))) return rc;
     const size_t npx = (size_t)W * H, B = sizeof(double);
     // colour 3, guides 3 + 3 + 3 + 1, out colour 3, moments 4, variance 1, then the previous state 3 + 3 + 1 + 3 + 4,
-    // then the clamped call's fast history 3, shift 1 and previous fast history 3
-    DN_HIP_OK(hipMalloc(&S.p, ((has_prev ? 35 : 21) + (ca ? 7 : 0)) * npx * B));
+    // then the clamped call's fast history 3, shift 1 and previous fast history 3, then the motion call's two maps 3 + 3
+    DN_HIP_OK(hipMalloc(&S.p, ((has_prev ? 35 : 21) + (ca ? 7 : 0) + (with_motion ? 6 : 0)) * npx * B));
     double* dC = S.p;
     const mcpt_aov_buffers dg{dC + 3 * npx, dC + 6 * npx, dC + 9 * npx, dC + 12 * npx};
     double* dOut = dC + 13 * npx;
@@ -569,8 +600,14 @@ static int accumulate_host(const mcpt_temporal_opts* o, const mcpt_camera* pc, i
             dca.pfast = dpF;
         }
     }
+    mcpt_motion_buffers dmo{};
+    if (with_motion) {
+        dmo.prev_position = S.p + ((has_prev ? 35 : 21) + (ca ? 7 : 0)) * npx, dmo.prev_normal = dmo.prev_position + 3 * npx;
+        DN_HIP_OK(hipMemcpy(dmo.prev_position, mo->prev_position, 3 * npx * B, hipMemcpyHostToDevice));
+        DN_HIP_OK(hipMemcpy(dmo.prev_normal, mo->prev_normal, 3 * npx * B, hipMemcpyHostToDevice));
+    }
     if ((rc = run_accumulate(o, has_prev ? pc : nullptr, W, H, dC, &dg, &dpg, dpC, dpM, dOut, dOutM, outv ? dOutV : nullptr, S,
-                             seconds, ca ? &dca : nullptr)))
+                             seconds, ca ? &dca : nullptr, with_motion ? &dmo : nullptr)))
         return rc;
     if (ca) {
         DN_HIP_OK(hipMemcpy(ca->outf, dca.outf, 3 * npx * B, hipMemcpyDeviceToHost));
@@ -618,6 +655,38 @@ int mcpt_temporal_accumulate_clamped(const mcpt_temporal_opts* o, const mcpt_tem
                                      double* out, double* outm, double* outf, double* outv, double* outs, double* seconds) {
     const ClampArgs ca{clamp, pfast, outf, outs};
     return accumulate_host(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, seconds, &ca);
+}
+
+// the motion call: clamp == NULL is the plain rule, whose fast-history and shift arguments must then be NULL
+static int motion_clamp_args(const mcpt_temporal_clamp_opts* clamp, const double* pfast, double* outf, double* outs) {
+    if (!clamp && (pfast || outf || outs)) {
+        set_error("%s is given without clamp: prev_fast, out_fast and out_shift belong to the clamped rule (pass clamp, or "
+                  "leave them NULL)", pfast ? "prev_fast" : outf ? "out_fast" : "out_shift");
+        return MCPT_E_INVALID;
+    }
+    return MCPT_OK;
+}
+
+int mcpt_temporal_accumulate_motion_device(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, const mcpt_camera* pc,
+                                           int32_t W, int32_t H, const double* dC, const mcpt_aov_buffers* g,
+                                           const mcpt_motion_buffers* mo, const mcpt_aov_buffers* pg, const double* dpC,
+                                           const double* dpM, const double* dpF, double* dOut, double* dOutM, double* dOutF,
+                                           double* dOutS, double* dOutV, double* seconds) {
+    int rc;
+    if ((rc = motion_clamp_args(clamp, dpF, dOutF, dOutS))) return rc;
+    const ClampArgs ca{clamp, dpF, dOutF, dOutS};
+    return accumulate_device(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, seconds, clamp ? &ca : nullptr, true, mo);
+}
+
+int mcpt_temporal_accumulate_motion(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, const mcpt_camera* pc,
+                                    int32_t W, int32_t H, const double* color, const mcpt_aov_buffers* g,
+                                    const mcpt_motion_buffers* mo, const mcpt_aov_buffers* pg, const double* pcol,
+                                    const double* pmom, const double* pfast, double* out, double* outm, double* outf,
+                                    double* outs, double* outv, double* seconds) {
+    int rc;
+    if ((rc = motion_clamp_args(clamp, pfast, outf, outs))) return rc;
+    const ClampArgs ca{clamp, pfast, outf, outs};
+    return accumulate_host(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, seconds, clamp ? &ca : nullptr, true, mo);
 }
 
 int mcpt_camera_orbit(const mcpt_camera* in, double degrees, mcpt_camera* out) {
