@@ -43,7 +43,9 @@ extern "C" {
                                * mcpt_motion_buffers, mcpt_render_motion_aovs and its _device form,
                                * mcpt_temporal_accumulate_motion and its _device form, mcpt_sequence_set_motion,
                                * mcpt_sequence_motion_info, the selectors MCPT_SEQ_PREV_POSITION and
-                               * MCPT_SEQ_PREV_NORMAL);
+                               * MCPT_SEQ_PREV_NORMAL); on-device transforms of facet ranges with a lazily synced
+                               * host copy (mcpt_scene_rest_save, mcpt_scene_transform, mcpt_scene_host_pending,
+                               * mcpt_scene_host_sync, mcpt_transform_rotation);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -325,6 +327,61 @@ int mcpt_scene_update_device(mcpt_scene* scene, int32_t device, int32_t first, i
  * pose_save, updates, frame: mcpt_render_motion_aovs then tells where every visible surface point was a frame ago.
  * Takes the scene's lock.  MCPT_E_INVALID for a NULL scene. */
 int mcpt_scene_pose_save(mcpt_scene* scene);
+
+/* On-device transforms of facet ranges: "this object is now rotated by M", evaluated where the vertices live
+ * (DESIGN.md §4.21).  No reference interface corresponds.
+ *
+ * mcpt_scene_rest_save records the current positions and normals of every facet as the scene's REST pose: on the host
+ * copy, and device to device on every device state (layout of tri_v / tri_n, as pose_save's prev_v / prev_n); a later
+ * device state takes it from the host copy.  Brings the host copy up to date first (see mcpt_scene_host_sync).
+ * MCPT_E_INVALID: NULL scene.
+ *
+ * mcpt_scene_transform: facets [first, first + count) := m applied to their REST pose.  m: 3x4 row-major doubles;
+ * normal_m: 3x3 row-major doubles for the vertex normals, NULL = the linear part of m.  stats as mcpt_scene_update's
+ * (may be NULL); device_seconds covers the transform kernel, the read-back of its count word and the refit.
+ *
+ * The rule, in fp64 with no contraction (the library is built with -ffp-contract=off on host and device), so that a
+ * caller can restate it bit for bit: for a rest vertex (x, y, z), floats widened to double, and row r of m,
+ *     out_r = (float)(((m[4r] * x + m[4r+1] * y) + m[4r+2] * z) + m[4r+3])      (round to nearest even)
+ * and for a rest vertex normal (nx, ny, nz) and row r of n = normal_m
+ *     out_r = (float)((n[3r] * nx + n[3r+1] * ny) + n[3r+2] * nz)
+ * which is not normalised (the AOVs normalise at interpolation).  The identity reproduces the rest pose value for value
+ * (a -0 becomes +0).  The source is always the rest pose, never the current one, so a frame loop does not drift.
+ *
+ * After a successful call mcpt_scene_update's rule holds word for word: the scene behaves as mcpt_scene_create of the
+ * arrays the rule produces -- hits bit for bit, renders up to the order of the fp64 atomics, mcpt_scene_arrays returns
+ * those arrays with the unique normals of the range recomputed as at load time.  The grid and the 8-wide debug trees
+ * are invalidated as by an update.
+ *
+ * Refused with MCPT_E_INVALID and a message, before anything on the host or on any device is modified: a NULL scene or
+ * m; count < 1, first < 0 or first + count > nfacets; a stats struct_size mismatch; a light triangle in the range (the
+ * first one is named); a non-finite entry of m or normal_m; no rest pose saved yet; a transformed position or normal
+ * that is non-finite after the conversion to float; a transformed position outside the arena (mcpt_scene_update's).
+ *
+ * The host copy is synced lazily.  While the scene has no device state the call computes the new arrays on the host by
+ * the rule and is an ordinary mcpt_scene_update of them.  Once a device state exists nothing is computed on the host:
+ * every device state evaluates the rule in a kernel from its own rest copy, counts the offending values (read back
+ * before any modifying kernel is enqueued), and refits as for an update; the host copy (positions, normals, unique
+ * normals, the binary tree) only gets the range recorded as BEHIND.  Everything that reads the host copy brings it up
+ * to date first -- mcpt_scene_arrays, a device state on a new device, the grid (mcpt_scene_meshing, MCPT_ACCEL_GRID
+ * renders), the mcpt_debug_bvh4_* walks, mcpt_scene_update[_device] (their host refit needs every triangle of a
+ * touched leaf) and mcpt_scene_rest_save -- by copying the ranges back from the first device state and running an
+ * update's host half over them, so a synced host copy equals an eagerly updated one.  mcpt_scene_pose_save does NOT
+ * sync: while ranges are behind it makes its device-to-device copies only, and the host's previous pose follows at the
+ * next sync (from the device copy, which changes only at a pose_save).  A frame loop pose_save, transform, frame
+ * therefore never waits for the host. */
+int mcpt_scene_rest_save(mcpt_scene* scene);
+int mcpt_scene_transform(mcpt_scene* scene, int32_t first, int32_t count, const double m[12], const double normal_m[9],
+                         mcpt_update_stats* stats);
+/* *facets = how many facets of the host copy are behind the devices (0: in sync) */
+int mcpt_scene_host_pending(const mcpt_scene* scene, int64_t* facets);
+/* brings the host copy up to date now (a no-op when nothing is pending) */
+int mcpt_scene_host_sync(mcpt_scene* scene);
+/* host helper, Rodrigues as mcpt_camera_orbit: rotation by `degrees` about the axis through `pivot` along axis/|axis|,
+ * then + translate (NULL = 0), as a 3x4 matrix.  0 degrees gives the identity's linear part exactly.
+ * MCPT_E_INVALID: NULL pointer, non-finite input, axis of length 0. */
+int mcpt_transform_rotation(const double axis[3], double degrees, const double pivot[3], const double translate[3],
+                            double m[12]);
 
 /* main.cpp:547-588: render samples [sample_begin, sample_end) of an spp-sample frame and ADD
  * sum_k L_k * (1/spp) into out_rgb (caller-owned host buffer, height*width*3 doubles, row 0 =

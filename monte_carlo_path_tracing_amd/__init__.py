@@ -24,7 +24,7 @@ __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_rays", 
            "UpsampleOpts", "upsample", "upsample_device", "camera_scaled",
            "upsample_phase", "camera_phase_rays", "temporal_upsample", "temporal_upsample_device",
            "MotionBuffers", "render_motion_aovs", "render_motion_aovs_device", "temporal_accumulate_motion",
-           "temporal_accumulate_motion_device",
+           "temporal_accumulate_motion_device", "transform_rotation",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -217,7 +217,9 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_update_stats_init", "mcpt_scene_update", "mcpt_scene_update_device",
            "mcpt_scene_pose_save", "mcpt_render_motion_aovs", "mcpt_render_motion_aovs_device",
            "mcpt_temporal_accumulate_motion", "mcpt_temporal_accumulate_motion_device", "mcpt_sequence_set_motion",
-           "mcpt_sequence_motion_info"]
+           "mcpt_sequence_motion_info",
+           "mcpt_scene_rest_save", "mcpt_scene_transform", "mcpt_scene_host_pending", "mcpt_scene_host_sync",
+           "mcpt_transform_rotation"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download"]  # include/mcpt_debug.h
@@ -346,6 +348,12 @@ def lib():
             L.mcpt_temporal_accumulate_motion_device.argtypes = L.mcpt_temporal_accumulate_motion.argtypes
             L.mcpt_sequence_set_motion.argtypes = [P, I]
             L.mcpt_sequence_motion_info.argtypes = [P, C.POINTER(D)]
+        if hasattr(L, "mcpt_scene_transform"):  # and the on-device transforms with the lazily synced host copy
+            L.mcpt_scene_rest_save.argtypes = [P]
+            L.mcpt_scene_transform.argtypes = [P, I, I, P, P, C.POINTER(UpdateStats)]
+            L.mcpt_scene_host_pending.argtypes = [P, C.POINTER(C.c_int64)]
+            L.mcpt_scene_host_sync.argtypes = [P]
+            L.mcpt_transform_rotation.argtypes = [P, D, P, P, P]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -457,6 +465,35 @@ class Scene:
         copy and (device to device) on every device the scene lives on; update() never touches it.  A frame loop is
         pose_save, update, frame: render_motion_aovs then tells where each visible surface point was a frame ago."""
         _check(lib().mcpt_scene_pose_save(self.h))
+
+    def rest_save(self):
+        """mcpt_scene_rest_save: the current vertex positions and normals become the scene's rest pose, the source of
+        every transform(); on the host copy and (device to device) on every device the scene lives on."""
+        _check(lib().mcpt_scene_rest_save(self.h))
+
+    def transform(self, first, count, m, normal_m=None):
+        """mcpt_scene_transform: facets [first, first + count) := m (anything that reshapes to 3 x 4) applied to their
+        rest pose, normal_m (3 x 3, None = the linear part of m) to their vertex normals, by the header's fp64 rule.
+        Once the scene lives on a device the arithmetic runs there and the host copy only follows on demand
+        (host_pending, host_sync; arrays() and every other reader sync by themselves).  Returns the stats dict of
+        update()."""
+        mm = _d(m).reshape(12)
+        nm = None if normal_m is None else _d(normal_m).reshape(9)
+        st = UpdateStats()
+        lib().mcpt_update_stats_init(C.byref(st))
+        _check(lib().mcpt_scene_transform(self.h, int(first), int(count), mm.ctypes.data_as(C.c_void_p),
+                                          None if nm is None else nm.ctypes.data_as(C.c_void_p), C.byref(st)))
+        return st.as_dict()
+
+    def host_pending(self):
+        """mcpt_scene_host_pending: how many facets of the host copy are behind the devices (0: in sync)"""
+        n = C.c_int64(0)
+        _check(lib().mcpt_scene_host_pending(self.h, C.byref(n)))
+        return int(n.value)
+
+    def host_sync(self):
+        """mcpt_scene_host_sync: brings the host copy up to date now (a no-op when nothing is pending)"""
+        _check(lib().mcpt_scene_host_sync(self.h))
 
     def arrays(self):
         F, M, NL = self.nfacets, self.nmaterials, self.nlights
@@ -799,6 +836,17 @@ def camera_orbit(camera, degrees):
     out = Camera()
     _check(lib().mcpt_camera_orbit(C.byref(camera), float(degrees), C.byref(out)))
     return out
+
+
+def transform_rotation(axis, degrees, pivot, translate=None):
+    """mcpt_transform_rotation: the (3, 4) float64 matrix of a rotation by `degrees` about the axis through `pivot`
+    along `axis`, then + translate; for Scene.transform."""
+    m = np.zeros((3, 4))
+    ax, pv = _d(axis, (3,)), _d(pivot, (3,))
+    tr = None if translate is None else _d(translate, (3,))
+    _check(lib().mcpt_transform_rotation(ax.ctypes.data_as(C.c_void_p), float(degrees), pv.ctypes.data_as(C.c_void_p),
+                                         None if tr is None else tr.ctypes.data_as(C.c_void_p), m.ctypes.data_as(C.c_void_p)))
+    return m
 
 
 def camera_scaled(camera, factor):

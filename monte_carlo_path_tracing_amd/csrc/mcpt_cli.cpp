@@ -52,8 +52,13 @@
 //   k >= 1 they are set to float(double(original) + k * (DX, DY, DZ)) by mcpt_scene_update (the BVH is refit in place, no
 //   rebuild), and the frame prints a "moved" line with the update's statistics.  A range with a light triangle, or a
 //   step that leaves the scene's arena, ends the run with the library's message.
+//               [--rotate FIRST:COUNT:AX,AY,AZ:DEG:PX,PY,PZ]
+//   --rotate (with --frames N, with or without --device-sequence; not with --move) turns facets [FIRST, FIRST + COUNT):
+//   the scene's rest pose is saved once before frame 0 (mcpt_scene_rest_save), and before frame k >= 1 the range is set
+//   to the rest pose rotated by k * DEG degrees about the axis (AX, AY, AZ) through (PX, PY, PZ) by mcpt_scene_transform
+//   (evaluated on the device; the host copy is not touched during the loop); the frame prints a "rotated" line.
 //               [--motion]
-//   --motion (with --frames N, with or without --device-sequence; meant for --move) lets the history follow the moved
+//   --motion (with --frames N, with or without --device-sequence; meant for --move and --rotate) lets the history follow the moved
 //   facets: before each frame's move the scene's pose is saved (mcpt_scene_pose_save), the frame renders the motion AOVs
 //   (mcpt_render_motion_aovs) and accumulates with mcpt_temporal_accumulate_motion (mcpt_sequence_set_motion in the device
 //   sequence), so a moved surface keeps its history instead of restarting it every frame.  Not with --upsample.
@@ -196,6 +201,49 @@ struct Mover {
     }
 };
 
+// --rotate FIRST:COUNT:AX,AY,AZ:DEG:PX,PY,PZ: the scene's rest pose is saved once before frame 0; before frame k >= 1
+// facets [first, first + count) are set to the rest pose rotated by k * DEG degrees about the axis through the pivot
+// (mcpt_transform_rotation, mcpt_scene_transform: evaluated on the device, always from the rest pose)
+struct Rotator {
+    int32_t first = 0, count = 0;
+    double axis[3] = {0, 0, 0}, deg = 0, pivot[3] = {0, 0, 0};
+    bool parse(const char* arg) {
+        char tail = 0;
+        if (std::sscanf(arg, "%d:%d:%lf,%lf,%lf:%lf:%lf,%lf,%lf%c", &first, &count, &axis[0], &axis[1], &axis[2], &deg, &pivot[0],
+                        &pivot[1], &pivot[2], &tail) != 9)
+            return false;
+        double m[12];
+        return first >= 0 && count >= 1 && mcpt_transform_rotation(axis, deg, pivot, nullptr, m) == MCPT_OK;
+    }
+    int bind(mcpt_scene* scene) {
+        int32_t nf = 0;
+        mcpt_scene_counts(scene, &nf, nullptr, nullptr);
+        if ((int64_t)first + count > nf) {
+            std::fprintf(stderr, "--rotate: facets [%d, %lld) are not in the scene's %d\n", first, (long long)first + count, nf);
+            return 2;
+        }
+        if (mcpt_scene_rest_save(scene) != MCPT_OK) {
+            std::fprintf(stderr, "--rotate failed: %s\n", mcpt_last_error());
+            return 1;
+        }
+        return 0;
+    }
+    int apply(mcpt_scene* scene, int k) {
+        if (k < 1) return 0;
+        double m[12];
+        mcpt_update_stats us;
+        mcpt_update_stats_init(&us);
+        if (mcpt_transform_rotation(axis, k * deg, pivot, nullptr, m) != MCPT_OK ||
+            mcpt_scene_transform(scene, first, count, m, nullptr, &us) != MCPT_OK) {
+            std::fprintf(stderr, "--rotate failed: %s\n", mcpt_last_error());
+            return 1;
+        }
+        std::printf("  rotated facets [%d, %d) by %g deg: %lld leaf slots, %lld nodes refit on %d levels, %.3f ms device\n", first,
+                    first + count, k * deg, (long long)us.leaf_slots, (long long)us.nodes_refit, us.levels, us.device_seconds * 1e3);
+        return 0;
+    }
+};
+
 struct SequenceArgs {
     int frames, spp, mode, flags;
     double orbit;
@@ -204,6 +252,7 @@ struct SequenceArgs {
     std::string out, hdr_out, aov_out;
     Mover* move;  // --move, or null
     bool motion;  // --motion
+    Rotator* rotate;  // --rotate, or null
 };
 
 // --frames: render, accumulate (and filter) frame after frame; the history ping-pongs between two sets of buffers
@@ -261,6 +310,7 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
             return 1;
         }
         if (a.move && a.move->apply(scene, k)) return 1;
+        if (a.rotate && a.rotate->apply(scene, k)) return 1;
         if (mcpt_camera_orbit(&cam0, k * a.orbit, &cur.cam) != MCPT_OK) {
             std::fprintf(stderr, "%s\n", mcpt_last_error());
             return 1;
@@ -396,7 +446,7 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
             rc = 1;
             break;
         }
-        if (a.move && a.move->apply(scene, k)) {
+        if ((a.move && a.move->apply(scene, k)) || (a.rotate && a.rotate->apply(scene, k))) {
             rc = 1;
             break;
         }
@@ -483,8 +533,9 @@ int main(int argc, char** argv) {
     bool upsample = false, temporal_upsample = false;
     mcpt_upsample_opts up;
     mcpt_upsample_opts_init(&up);
-    bool move_flag = false, motion_flag = false;
+    bool move_flag = false, motion_flag = false, rotate_flag = false;
     Mover mover;
+    Rotator rotator;
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -558,6 +609,14 @@ int main(int argc, char** argv) {
             }
             move_flag = true;
         }
+        else if (!std::strcmp(argv[a], "--rotate")) {
+            if (!rotator.parse(next())) {
+                std::fprintf(stderr, "--rotate needs FIRST:COUNT:AX,AY,AZ:DEG:PX,PY,PZ (a facet range, an axis of length > 0, finite "
+                                     "degrees per frame and a pivot), not %s\n", argv[a]);
+                return 2;
+            }
+            rotate_flag = true;
+        }
         else if (!std::strcmp(argv[a], "--motion")) motion_flag = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
@@ -587,6 +646,11 @@ int main(int argc, char** argv) {
     }
     if (move_flag && frames == 0) {  // refused before anything is loaded
         std::fprintf(stderr, "--move moves facets between the frames of a sequence; add --frames N\n");
+        return 2;
+    }
+    if (rotate_flag && (frames == 0 || move_flag)) {  // refused before anything is loaded
+        std::fprintf(stderr, "--rotate %s\n", frames == 0 ? "rotates facets between the frames of a sequence; add --frames N"
+                                                          : "and --move both rewrite their facets from an original pose; give one of them");
         return 2;
     }
     if (motion_flag && (frames == 0 || upsample)) {  // refused before anything is loaded
@@ -693,8 +757,11 @@ int main(int argc, char** argv) {
         if (move_flag) {
             if (const int rc = mover.bind(scene)) return rc;
         }
+        if (rotate_flag) {
+            if (const int rc = rotator.bind(scene)) return rc;
+        }
         const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out,
-                              move_flag ? &mover : nullptr, motion_flag};
+                              move_flag ? &mover : nullptr, motion_flag, rotate_flag ? &rotator : nullptr};
         if (clamp_flag && !history_clamp) {
             std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
             return 2;

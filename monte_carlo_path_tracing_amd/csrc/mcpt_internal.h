@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "mcpt.h"
@@ -132,6 +133,25 @@ void refit_bvh(Bvh& b, const BvhRefitIndex& ix, const HostScene& s, const std::v
 // scene_io.cpp -- Myobj::get_unique_normal_of_facet (Myobj.cpp:680-709) of facet f into s.unique_n
 void unique_normal_of_facet(HostScene& s, int f);
 
+// host_mirror.cpp -- the host side of mcpt_scene_transform (no HIP in it: the sanitizer driver runs it)
+// mcpt_scene_transform's rule (include/mcpt.h) for `count` facets: rest arrays -> pos / nrm (count * 9 floats each)
+void transform_facets(const float* rest_pos, const float* rest_nrm, size_t count, const double m[12], const double n[9],
+                      float* pos, float* nrm);
+// the facet ranges whose host copy is behind the devices: sorted, disjoint, non-touching [first, end) pairs; beyond
+// kPendingMax entries the list collapses to its hull
+constexpr size_t kPendingMax = 48;
+struct PendingRanges {
+    std::vector<std::pair<int32_t, int32_t>> r;
+    void add(int32_t first, int32_t count);
+    int64_t facets() const;
+};
+// the CSR facet -> leaf-slot map of a tree over facets [0, F)
+void make_facet_slot_map(const Bvh& b, int F, std::vector<int32_t>& slot_start, std::vector<int32_t>& slot_list);
+// the host half of an update once s.pos / s.nrm of the ranges are current: their unique normals, then one refit_bvh
+// over their slots; returns the number of slots
+int64_t host_refresh_ranges(HostScene& s, Bvh& b, const BvhRefitIndex& ix, const std::vector<int32_t>& slot_start,
+                            const std::vector<int32_t>& slot_list, const PendingRanges& ranges, double margin);
+
 // refit.hip -- the device side of mcpt_scene_update: the device pointers of one device state's main tree (owned by
 // render.hip's DeviceState) and the kernels that rewrite them.  Both functions only enqueue on `stream` (a
 // hipStream_t) of the current device.
@@ -156,6 +176,13 @@ int refit_validate_enqueue(const RefitDev& r, int32_t count, const float* dpos, 
 // level_first[l + 1]), deepest first), then the dirty bytes cleared
 int refit_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, int32_t first, int32_t count, const float* dpos,
                   const float* dnrm, double margin, void* stream);
+// mcpt_scene_transform on one device state: clears r.counters[0], then k_transform_range writes the rule's image of
+// facets [first, first + count) of the rest pose (rest_v: F * 3 float4, rest_n: F * 9) into out_pos / out_nrm
+// (count * 9 floats each) and counts the offending values (refit_validate_enqueue's terms) into r.counters[0];
+// nothing of the scene is modified
+int transform_enqueue(const RefitDev& r, const float* rest_v, const float* rest_n, int32_t first, int32_t count,
+                      const double m[12], const double n[9], const double lo[3], const double hi[3], float* out_pos,
+                      float* out_nrm, void* stream);
 
 // grid.cpp -- the reference's uniform grid (Myobj.cpp:78-162) for the MCPT_ACCEL_GRID mode
 struct Grid {

@@ -4,6 +4,8 @@
 //
 // Kernels, all on one stream:
 //   k_refit_validate  (device form only) counts non-finite values and positions outside the arena;
+//   k_transform_range (mcpt_scene_transform, §4.21) an affine map of a facet range of the rest pose into the staging
+//                     arrays, counting the same offenders; the host reads the count before the scatter is enqueued;
 //   k_refit_scatter   one thread per facet of the range: tri_v, tri_n, every leaf slot of the facet, its dirty byte;
 //   k_refit_level     one launch per tree level, deepest first, one thread per node: a leaf child with a dirty slot
 //                     gets the union of the full bounds of all its triangles, enlarged by the build's margin; an
@@ -100,6 +102,73 @@ __global__ __launch_bounds__(kRefitBlock) void k_refit_scatter(RefitDev r, int f
         lv[2] = v2;
         r.slot_dirty[s] = 1;
     }
+}
+
+// mcpt_scene_transform (include/mcpt.h): 168 bytes passed by value, so the matrices sit in SGPRs
+struct TransformArgs {
+    double m[12], n[9];
+};
+
+// One thread per facet of the range.  The rest vertices are three float4 per lane (consecutive lanes, consecutive
+// 48-byte records); the rest normals and both outputs (count * 9 floats each, the layout k_refit_scatter reads) go
+// through one LDS buffer at stride 9 (odd: no bank conflict) so that every global access has consecutive lanes on
+// consecutive dwords.  The 18 dot products are the header's rule: fp64, no contraction, the written order.  Offending
+// values (k_refit_validate's terms) are counted with one integer atomic per wave that has any; nothing else is shared
+// between blocks, and nothing of the scene is written.
+__global__ __launch_bounds__(kRefitBlock) void k_transform_range(const float* __restrict__ rest_v, const float* __restrict__ rest_n,
+                                                                 int first, int count, TransformArgs t, Arena ar,
+                                                                 float* __restrict__ out_pos, float* __restrict__ out_nrm,
+                                                                 unsigned* bad) {
+    __shared__ float sp[9 * kRefitBlock];
+    const int base = blockIdx.x * kRefitBlock;
+    const int nb = min(kRefitBlock, count - base);
+    const size_t off = 9 * (size_t)base;
+    const bool live = (int)threadIdx.x < nb;
+    float* mine = sp + 9 * threadIdx.x;
+    unsigned nbad = 0;
+    {
+        const float* in = rest_n + 9 * (size_t)(first + base);
+        for (int i = threadIdx.x; i < 9 * nb; i += kRefitBlock) sp[i] = in[i];
+    }
+    __syncthreads();
+    if (live) {
+        float o[9];
+#pragma unroll
+        for (int v = 0; v < 3; v++) {
+            const double x = mine[3 * v], y = mine[3 * v + 1], z = mine[3 * v + 2];
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                o[3 * v + r] = (float)((t.n[3 * r] * x + t.n[3 * r + 1] * y) + t.n[3 * r + 2] * z);
+                nbad += !isfinite(o[3 * v + r]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 9; i++) mine[i] = o[i];  // the thread's own nine words
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 9 * nb; i += kRefitBlock) out_nrm[off + i] = sp[i];
+    __syncthreads();
+    if (live) {
+        const float4* rv = reinterpret_cast<const float4*>(rest_v) + 3 * (size_t)(first + base + (int)threadIdx.x);
+#pragma unroll
+        for (int v = 0; v < 3; v++) {
+            const float4 p = rv[v];
+            const double x = p.x, y = p.y, z = p.z;
+#pragma unroll
+            for (int r = 0; r < 3; r++) {
+                const float q = (float)(((t.m[4 * r] * x + t.m[4 * r + 1] * y) + t.m[4 * r + 2] * z) + t.m[4 * r + 3]);
+                nbad += !isfinite(q) || (double)q < ar.lo[r] || (double)q > ar.hi[r];
+                mine[3 * v + r] = q;
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 9 * nb; i += kRefitBlock) out_pos[off + i] = sp[i];
+    // every lane of the block is still here: the ballot sees whole waves; only a refused call goes further
+    if (__ballot(nbad != 0) == 0) return;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) nbad += __shfl_xor(nbad, d);
+    if ((threadIdx.x & 63) == 0) atomicAdd(bad, nbad);
 }
 
 // quantize_bvh4's rule for one axis of one node: org = the used children's minimum, then the smallest power-of-two
@@ -244,6 +313,26 @@ int refit_validate_enqueue(const RefitDev& r, int32_t count, const float* dpos, 
     const int64_t n = 9 * (int64_t)count;
     hipLaunchKernelGGL(k_refit_validate, dim3((unsigned)((n + kRefitBlock - 1) / kRefitBlock)), dim3(kRefitBlock), 0, st, n, dpos,
                        dnrm, ar, r.counters);
+    REFIT_HIP_OK(hipGetLastError());
+    return MCPT_OK;
+}
+
+int transform_enqueue(const RefitDev& r, const float* rest_v, const float* rest_n, int32_t first, int32_t count,
+                      const double m[12], const double n[9], const double lo[3], const double hi[3], float* out_pos,
+                      float* out_nrm, void* stream) {
+    if (first < 0 || count < 1 || (int64_t)first + count > r.F || !rest_v || !rest_n || !out_pos || !out_nrm) {
+        set_error("transform: range or buffers do not match the device state");
+        return MCPT_E_INVALID;
+    }
+    TransformArgs t;
+    Arena ar;
+    for (int i = 0; i < 12; i++) t.m[i] = m[i];
+    for (int i = 0; i < 9; i++) t.n[i] = n[i];
+    for (int a = 0; a < 3; a++) ar.lo[a] = lo[a], ar.hi[a] = hi[a];
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    REFIT_HIP_OK(hipMemsetAsync(r.counters, 0, sizeof(unsigned), st));
+    hipLaunchKernelGGL(k_transform_range, dim3((count + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, rest_v, rest_n,
+                       first, count, t, ar, out_pos, out_nrm, r.counters);
     REFIT_HIP_OK(hipGetLastError());
     return MCPT_OK;
 }

@@ -4551,6 +4551,8 @@ struct DeviceState {
     // mcpt_scene_pose_save: the previous pose's copies of d.tri_v / d.tri_n (null until the first save or, for a state
     // created after it, from the host copy: the previous pose is then the current one)
     DevBuf prev_v, prev_n;
+    // mcpt_scene_rest_save: the rest pose's copies of d.tri_v / d.tri_n, the source of every mcpt_scene_transform
+    DevBuf rest_v, rest_n;
     unsigned* pinned_count = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evp0 = nullptr, evp1 = nullptr, evr0 = nullptr, evr1 = nullptr;
 };
@@ -4580,6 +4582,18 @@ struct mcpt_scene {
     // mcpt_scene_pose_save: host.pos / host.nrm as they were at the last save (empty until the first one)
     bool pose_saved = false;
     std::vector<float> prev_pos, prev_nrm;
+    // mcpt_scene_rest_save / mcpt_scene_transform: the rest pose (host.pos / host.nrm at the save);
+    // the facet ranges of host.pos / host.nrm / host.unique_n / bvh that are behind the devices, and whether prev_pos /
+    // prev_nrm are (a pose_save while ranges were pending); host_sync brings all of it up to date from the first
+    // device state.  host_mu guards pending and prev_stale and the sync itself: every read or write of the two takes it
+    // (transform, pose_save, host_pending, host_sync), so render_multi's workers, which create device states and so
+    // sync without holding `mu`, see a consistent list.  It does NOT order a render against a concurrent transform of
+    // the same handle: as for an update, one render or update at a time per handle is the caller's rule (`mu`)
+    bool rest_saved = false;
+    std::vector<float> rest_pos, rest_nrm;
+    PendingRanges pending;
+    bool prev_stale = false;
+    std::mutex host_mu;
 };
 
 namespace {
@@ -4706,6 +4720,82 @@ std::vector<float4> leaf_vertices(const HostScene& s, const Bvh& b) {
 
 int prep_chunks(int NL);
 
+// the facet -> leaf-slot map and the binary tree's refit index, built at the handle's first update or transform
+void ensure_slot_map(mcpt_scene* sc) {
+    if (!sc->slot_start.empty()) return;
+    make_facet_slot_map(sc->bvh, sc->host.F, sc->slot_start, sc->slot_list);
+    sc->refit_ix = make_bvh_refit_index(sc->bvh);
+}
+
+// puts the thread back on the device it was on when a function that visits device states returns, on every path
+struct DeviceRestore {
+    int device = -1;
+    ~DeviceRestore() {
+        if (device >= 0) (void)hipSetDevice(device);
+    }
+};
+
+// mcpt_scene_host_sync: the host copy brought up to date from the first device state (every state holds the same
+// arrays) -- the pending ranges of tri_v / tri_n into host.pos / host.nrm, then update_apply's host half over them,
+// and the previous pose as a whole if a pose_save left it stale.  Every reader of host.pos, host.nrm, host.unique_n,
+// the binary tree's boxes, prev_pos or prev_nrm calls this first; a no-op when nothing is pending.
+int host_sync(mcpt_scene* sc) {
+    std::lock_guard<std::mutex> lk(sc->host_mu);
+    if (sc->pending.r.empty() && !sc->prev_stale) return MCPT_OK;
+    DeviceState* D = nullptr;
+    {
+        std::lock_guard<std::mutex> dl(sc->devs_mu);
+        if (!sc->devs.empty()) D = sc->devs.front().get();
+    }
+    if (!D) {
+        set_error("the host copy is behind the devices but the scene has no device state");
+        return MCPT_E_DEVICE;
+    }
+    DeviceRestore back;
+    HIP_OK(hipGetDevice(&back.device));
+    HIP_OK(hipSetDevice(D->device));
+    HostScene& hs = sc->host;
+    // every copy lands in a buffer of its own first: a copy that fails leaves the host copy as it was, still pending
+    std::vector<std::vector<float4>> dv(sc->pending.r.size());
+    std::vector<std::vector<float>> dn(sc->pending.r.size());
+    for (size_t i = 0; i < sc->pending.r.size(); i++) {
+        const size_t f0 = (size_t)sc->pending.r[i].first, n = (size_t)sc->pending.r[i].second - f0;
+        dv[i].resize(3 * n);
+        dn[i].resize(9 * n);
+        HIP_OK(hipMemcpy(dv[i].data(), D->d.tri_v + 3 * f0, 3 * n * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(dn[i].data(), D->d.tri_n + 9 * f0, 9 * n * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    std::vector<float4> pv;
+    std::vector<float> pn;
+    if (sc->prev_stale && hs.F > 0) {  // the device copies change only at a pose_save: they are still that pose
+        pv.resize(3 * (size_t)hs.F);
+        pn.resize(hs.nrm.size());
+        HIP_OK(hipMemcpy(pv.data(), D->prev_v.p, pv.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(pn.data(), D->prev_n.p, pn.size() * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    auto unpack = [](const std::vector<float4>& v, float* out) {
+        for (size_t i = 0; i < v.size(); i++) out[3 * i] = v[i].x, out[3 * i + 1] = v[i].y, out[3 * i + 2] = v[i].z;
+    };
+    for (size_t i = 0; i < sc->pending.r.size(); i++) {
+        const size_t f0 = (size_t)sc->pending.r[i].first;
+        unpack(dv[i], hs.pos.data() + 9 * f0);
+        std::copy(dn[i].begin(), dn[i].end(), hs.nrm.begin() + 9 * f0);
+    }
+    if (!sc->pending.r.empty()) {
+        ensure_slot_map(sc);
+        host_refresh_ranges(hs, sc->bvh, sc->refit_ix, sc->slot_start, sc->slot_list, sc->pending, sc->margin);
+        sc->grid.ok = false;  // as update_apply: rebuilt from the new positions by the next grid-mode call
+    }
+    if (sc->prev_stale) {
+        sc->prev_pos.resize(hs.pos.size());
+        unpack(pv, sc->prev_pos.data());
+        sc->prev_nrm = std::move(pn);
+    }
+    sc->pending.r.clear();
+    sc->prev_stale = false;
+    return MCPT_OK;
+}
+
 // the device's scene state, created (scene, light tables and BVHs uploaded) on first use.  Thread-safe
 // for distinct devices: render_multi's workers create theirs concurrently (the lookup and the insertion
 // hold devs_mu, the uploads do not)
@@ -4720,6 +4810,7 @@ int get_device_state(mcpt_scene* sc, int device, DeviceState** out) {
                 return MCPT_OK;
             }
     }
+    if (int rs = host_sync(sc)) return rs;  // a new state is made from the host copy
     HIP_OK(hipSetDevice(device));
     auto D = std::make_unique<DeviceState>();
     D->device = device;
@@ -4911,6 +5002,14 @@ int get_device_state(mcpt_scene* sc, int device, DeviceState** out) {
             return rc;
         HIP_OK(hipMemcpy(D->prev_v.p, pv.data(), pv.size() * sizeof(float4), hipMemcpyHostToDevice));
         if (!sc->prev_nrm.empty()) HIP_OK(hipMemcpy(D->prev_n.p, sc->prev_nrm.data(), sc->prev_nrm.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (sc->rest_saved) {  // and one created after mcpt_scene_rest_save: its rest pose likewise
+        std::vector<float4> rv(tv.size());
+        for (size_t i = 0; i < 3 * (size_t)s.F; i++) rv[i] = make_float4(sc->rest_pos[3 * i], sc->rest_pos[3 * i + 1], sc->rest_pos[3 * i + 2], 0.f);
+        if ((rc = ensure(D->rest_v, rv.size() * sizeof(float4))) || (rc = ensure(D->rest_n, std::max<size_t>(s.nrm.size(), 1) * sizeof(float))))
+            return rc;
+        HIP_OK(hipMemcpy(D->rest_v.p, rv.data(), rv.size() * sizeof(float4), hipMemcpyHostToDevice));
+        if (!sc->rest_nrm.empty()) HIP_OK(hipMemcpy(D->rest_n.p, sc->rest_nrm.data(), sc->rest_nrm.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     HIP_OK(hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking));
     HIP_OK(hipHostMalloc(&D->pinned_count, 64 + kCtrlBytes));
@@ -5158,6 +5257,7 @@ hipError_t launch_prep(int variant, const DScene& d, uint64_t seed, int n, const
 // render_multi calls it on the calling thread before its device workers start, so the workers only
 // find an up-to-date grid and read it)
 int ensure_host_grid(mcpt_scene* sc, const double eye[3], int n0) {
+    if (int rs = host_sync(sc)) return rs;  // the grid is built from host.pos (and a sync drops a stale grid)
     Grid& g = sc->grid;
     if (!g.ok || g.n0 != n0 || g.eye[0] != eye[0] || g.eye[1] != eye[1] || g.eye[2] != eye[2]) {
         g = build_grid(sc->host, eye, n0);
@@ -6806,7 +6906,7 @@ void mcpt_scene_destroy(mcpt_scene* sc) {
                                      &D->sc_cum, &D->sc_wsum, &D->sc_last, &D->cull_keys, &D->cull_order, &D->cull_count,
                                      &D->ad_acc[0], &D->ad_acc[1], &D->ad_list[0], &D->ad_list[1], &D->ad_state[0],
                                      &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise, &D->aov, &D->up_pos, &D->up_nrm,
-                                     &D->prev_v, &D->prev_n};
+                                     &D->prev_v, &D->prev_n, &D->rest_v, &D->rest_n};
         for (int k = 0; k < 14; k++) bufs.insert(bufs.end(), {&D->qa[k], &D->qb[k], &D->qs[k]});
         for (int k = 0; k < 9; k++) bufs.push_back(&D->aux[k]);
         for (int k = 0; k < 13; k++) bufs.push_back(&D->sl[k]);
@@ -6841,6 +6941,11 @@ int mcpt_scene_counts(const mcpt_scene* sc, int32_t* nf, int32_t* nm, int32_t* n
 int mcpt_scene_arrays(const mcpt_scene* sc, float* pos, float* nrm, int32_t* mat, float* mtl, int32_t* lf,
                       double* lrad, double* un) {
     if (!sc) return MCPT_E_INVALID;
+    {  // a host copy behind the devices (mcpt_scene_transform) is brought up to date first
+        mcpt_scene* w = const_cast<mcpt_scene*>(sc);
+        std::lock_guard<std::mutex> lk(w->mu);
+        if (int rs = host_sync(w)) return rs;
+    }
     const HostScene& h = sc->host;
     if (pos) std::copy(h.pos.begin(), h.pos.end(), pos);
     if (nrm) std::copy(h.nrm.begin(), h.nrm.end(), nrm);
@@ -6860,13 +6965,15 @@ void mcpt_update_stats_init(mcpt_update_stats* st) {
 }
 
 // every refusal that needs neither the values nor a device
-static int update_check_args(const mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const mcpt_update_stats* stats) {
-    if (!sc || !pos) {
-        set_error("mcpt_scene_update: NULL %s", !sc ? "scene" : "positions");
+// `data`: the call's required pointer argument and its name in the message
+static int update_check_args(const mcpt_scene* sc, int32_t first, int32_t count, const void* data, const mcpt_update_stats* stats,
+                             const char* who = "mcpt_scene_update", const char* data_name = "positions") {
+    if (!sc || !data) {
+        set_error("%s: NULL %s", who, !sc ? "scene" : data_name);
         return MCPT_E_INVALID;
     }
     if (count < 1 || first < 0 || (int64_t)first + count > sc->host.F) {
-        set_error("mcpt_scene_update: facets [%d, %lld) are not a non-empty range of the scene's %d facets", first,
+        set_error("%s: facets [%d, %lld) are not a non-empty range of the scene's %d facets", who, first,
                   (long long)first + count, sc->host.F);
         return MCPT_E_INVALID;
     }
@@ -6877,10 +6984,10 @@ static int update_check_args(const mcpt_scene* sc, int32_t first, int32_t count,
     }
     return MCPT_OK;
 }
-static int update_check_lights(const mcpt_scene* sc, int32_t first, int32_t count) {
+static int update_check_lights(const mcpt_scene* sc, int32_t first, int32_t count, const char* who = "mcpt_scene_update") {
     for (int f = first; f < first + count; f++)
         if (sc->host.light_of[f] >= 0) {
-            set_error("mcpt_scene_update: facet %d is a light triangle (light %d); lights cannot move", f, sc->host.light_of[f]);
+            set_error("%s: facet %d is a light triangle (light %d); lights cannot move", who, f, sc->host.light_of[f]);
             return MCPT_E_INVALID;
         }
     return MCPT_OK;
@@ -6889,18 +6996,19 @@ static int update_check_lights(const mcpt_scene* sc, int32_t first, int32_t coun
 static void update_arena(const mcpt_scene* sc, double lo[3], double hi[3]) {
     for (int a = 0; a < 3; a++) lo[a] = sc->build_lo[a] - sc->build_ext, hi[a] = sc->build_hi[a] + sc->build_ext;
 }
-static int update_check_values(const mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm) {
+static int update_check_values(const mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm,
+                               const char* who = "mcpt_scene_update") {
     double lo[3], hi[3];
     update_arena(sc, lo, hi);
     for (size_t i = 0; i < 9 * (size_t)count; i++) {
         const int f = first + (int)(i / 9), a = (int)(i % 3);
         if (!std::isfinite(pos[i]) || (nrm && !std::isfinite(nrm[i]))) {
-            set_error("mcpt_scene_update: facet %d has a non-finite %s", f, std::isfinite(pos[i]) ? "normal" : "position");
+            set_error("%s: facet %d has a non-finite %s", who, f, std::isfinite(pos[i]) ? "normal" : "position");
             return MCPT_E_INVALID;
         }
         if (pos[i] < lo[a] || pos[i] > hi[a]) {
-            set_error("mcpt_scene_update: facet %d has a position outside the arena (axis %d: %g not in [%g, %g], the "
-                      "build's box grown by its largest extent)", f, a, (double)pos[i], lo[a], hi[a]);
+            set_error("%s: facet %d has a position outside the arena (axis %d: %g not in [%g, %g], the "
+                      "build's box grown by its largest extent)", who, f, a, (double)pos[i], lo[a], hi[a]);
             return MCPT_E_INVALID;
         }
     }
@@ -6969,16 +7077,7 @@ static int ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
 static int update_apply(mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm, int src_device,
                         const float* dpos, const float* dnrm, mcpt_update_stats* stats) {
     HostScene& hs = sc->host;
-    if (sc->slot_start.empty()) {  // first update of the handle: the facet -> leaf-slot map and the binary tree's index
-        const std::vector<int32_t>& lfac = sc->bvh.leaf_facets;
-        sc->slot_start.assign((size_t)hs.F + 1, 0);
-        for (int32_t f : lfac) sc->slot_start[f + 1]++;
-        for (int f = 0; f < hs.F; f++) sc->slot_start[f + 1] += sc->slot_start[f];
-        sc->slot_list.resize(lfac.size());
-        std::vector<int32_t> at(sc->slot_start.begin(), sc->slot_start.end() - 1);
-        for (size_t q = 0; q < lfac.size(); q++) sc->slot_list[at[lfac[q]]++] = (int32_t)q;
-        sc->refit_ix = make_bvh_refit_index(sc->bvh);
-    }
+    ensure_slot_map(sc);  // first update of the handle: the facet -> leaf-slot map and the binary tree's index
     std::copy(pos, pos + 9 * (size_t)count, hs.pos.begin() + 9 * (size_t)first);
     if (nrm) std::copy(nrm, nrm + 9 * (size_t)count, hs.nrm.begin() + 9 * (size_t)first);
     for (int f = first; f < first + count; f++) unique_normal_of_facet(hs, f);
@@ -7037,6 +7136,7 @@ int mcpt_scene_update(mcpt_scene* sc, int32_t first, int32_t count, const float*
     if ((rc = update_check_args(sc, first, count, pos, stats))) return rc;
     std::lock_guard<std::mutex> lk(sc->mu);
     if ((rc = update_check_lights(sc, first, count)) || (rc = update_check_values(sc, first, count, pos, nrm))) return rc;
+    if ((rc = host_sync(sc))) return rc;  // the host refit reads every triangle of a touched leaf
     return update_apply(sc, first, count, pos, nrm, -1, nullptr, nullptr, stats);
 }
 
@@ -7046,6 +7146,7 @@ int mcpt_scene_update_device(mcpt_scene* sc, int32_t device, int32_t first, int3
     if ((rc = update_check_args(sc, first, count, dpos, stats))) return rc;
     std::lock_guard<std::mutex> lk(sc->mu);
     if ((rc = update_check_lights(sc, first, count))) return rc;
+    if ((rc = host_sync(sc))) return rc;  // as mcpt_scene_update
     int cur;
     HIP_OK(hipGetDevice(&cur));
     if (device < 0) device = cur;
@@ -7086,8 +7187,15 @@ int mcpt_scene_pose_save(mcpt_scene* sc) {
         return MCPT_E_INVALID;
     }
     std::lock_guard<std::mutex> lk(sc->mu);
-    sc->prev_pos = sc->host.pos;
-    sc->prev_nrm = sc->host.nrm;
+    if (std::lock_guard<std::mutex> hl(sc->host_mu); sc->pending.r.empty()) {
+        sc->prev_pos = sc->host.pos;
+        sc->prev_nrm = sc->host.nrm;
+        sc->prev_stale = false;
+    } else {
+        // the host copy is behind the devices (mcpt_scene_transform) and a frame loop must not pay for a sync here:
+        // the device copies below are the pose, and host_sync refreshes prev_pos / prev_nrm from the first state's
+        sc->prev_stale = true;
+    }
     sc->pose_saved = true;
     std::vector<DeviceState*> devs;
     {
@@ -7110,6 +7218,170 @@ int mcpt_scene_pose_save(mcpt_scene* sc) {
     }
     HIP_OK(hipSetDevice(cur));
     return MCPT_OK;
+}
+
+// ---- mcpt_scene_rest_save, mcpt_scene_transform and the lazily synced host copy (include/mcpt.h, DESIGN.md §4.21;
+// the kernel is refit.hip's, the host arithmetic and the pending ranges host_mirror.cpp's) ----
+static std::vector<DeviceState*> device_states(mcpt_scene* sc) {
+    std::vector<DeviceState*> devs;
+    std::lock_guard<std::mutex> lk(sc->devs_mu);
+    for (auto& D : sc->devs) devs.push_back(D.get());
+    return devs;
+}
+
+int mcpt_scene_rest_save(mcpt_scene* sc) {
+    if (!sc) {
+        set_error("mcpt_scene_rest_save: NULL scene");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    int rc;
+    if ((rc = host_sync(sc))) return rc;
+    sc->rest_pos = sc->host.pos;
+    sc->rest_nrm = sc->host.nrm;
+    sc->rest_saved = true;
+    const std::vector<DeviceState*> devs = device_states(sc);
+    if (devs.empty()) return MCPT_OK;
+    DeviceRestore back;
+    HIP_OK(hipGetDevice(&back.device));
+    for (DeviceState* D : devs) {
+        HIP_OK(hipSetDevice(D->device));
+        const size_t vb = 3 * (size_t)std::max(D->d.F, 1) * sizeof(float4), nb = 9 * (size_t)D->d.F * sizeof(float);
+        if ((rc = ensure(D->rest_v, vb)) || (rc = ensure(D->rest_n, std::max<size_t>(nb, 4)))) return rc;
+        // device to device on the state's stream, as mcpt_scene_pose_save: ordered after the refits
+        HIP_OK(hipMemcpyAsync(D->rest_v.p, D->d.tri_v, vb, hipMemcpyDeviceToDevice, D->stream));
+        if (nb) HIP_OK(hipMemcpyAsync(D->rest_n.p, D->d.tri_n, nb, hipMemcpyDeviceToDevice, D->stream));
+        HIP_OK(hipStreamSynchronize(D->stream));
+    }
+    return MCPT_OK;
+}
+
+// the call after the refusals that need no values, on a scene with device states: every state transforms the range
+// from its own rest copy into its staging arrays and counts the offenders; the counts are read back before anything
+// is modified; then refit_enqueue as for an update.  The host copy only gets the range marked as behind.
+static int transform_on_devices(mcpt_scene* sc, const std::vector<DeviceState*>& devs, int32_t first, int32_t count,
+                                const double m[12], const double n[9], mcpt_update_stats* stats) {
+    ensure_slot_map(sc);
+    mcpt_update_stats st;
+    mcpt_update_stats_init(&st);
+    st.facets = count;
+    st.leaf_slots = (int64_t)sc->slot_start[first + count] - sc->slot_start[first];
+    double lo[3], hi[3];
+    update_arena(sc, lo, hi);
+    int rc;
+    DeviceRestore back;
+    HIP_OK(hipGetDevice(&back.device));
+    std::vector<unsigned> bad(devs.size(), 0);
+    for (size_t i = 0; i < devs.size(); i++) {
+        DeviceState* D = devs[i];
+        HIP_OK(hipSetDevice(D->device));
+        if ((rc = ensure_refit_state(sc, *D)) || (rc = ensure(D->up_pos, 36ull * count)) || (rc = ensure(D->up_nrm, 36ull * count)))
+            return rc;
+        if (!D->rest_v.p || !D->rest_n.p) {
+            set_error("mcpt_scene_transform: device %d holds no rest pose", D->device);
+            return MCPT_E_DEVICE;
+        }
+        // work of other streams (the caller's, a frame sequence's) that still reads or writes these arrays
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipEventRecord(D->ev0, D->stream));
+        if ((rc = transform_enqueue(D->refit, (const float*)D->rest_v.p, (const float*)D->rest_n.p, first, count, m, n, lo, hi,
+                                    (float*)D->up_pos.p, (float*)D->up_nrm.p, D->stream)))
+            return rc;
+        HIP_OK(hipMemcpyAsync(&bad[i], D->refit.counters, sizeof(unsigned), hipMemcpyDeviceToHost, D->stream));
+    }
+    unsigned nbad = 0;
+    for (size_t i = 0; i < devs.size(); i++) {
+        HIP_OK(hipSetDevice(devs[i]->device));
+        HIP_OK(hipStreamSynchronize(devs[i]->stream));
+        nbad = std::max(nbad, bad[i]);
+    }
+    if (nbad) {  // only the staging arrays were written
+        set_error("mcpt_scene_transform: %u transformed values of facets [%d, %d) are non-finite or positions outside the "
+                  "arena (the build's box grown by its largest extent)", nbad, first, first + count);
+        return MCPT_E_INVALID;
+    }
+    // the devices are modified from here on, so the marks come first: should a launch below fail, the host copy is
+    // still known to be behind (host.pos / host.nrm / host.unique_n and the binary tree follow at the next host_sync)
+    {
+        std::lock_guard<std::mutex> hl(sc->host_mu);
+        sc->pending.add(first, count);
+    }
+    sc->grid.ok = false;  // stale from here on, as after an update
+    sc->updated = true;   // the 8-wide trees are stale from here on (bvh8_refused)
+    for (DeviceState* D : devs) {
+        HIP_OK(hipSetDevice(D->device));
+        if ((rc = refit_enqueue(D->refit, D->level_first.data(), (int)D->level_first.size() - 1, first, count,
+                                (const float*)D->up_pos.p, (const float*)D->up_nrm.p, sc->margin, D->stream)))
+            return rc;
+        HIP_OK(hipEventRecord(D->ev1, D->stream));
+        HIP_OK(hipStreamSynchronize(D->stream));
+        if (st.device_states++ == 0) {
+            float ms = 0;
+            unsigned nn = 0;
+            HIP_OK(hipEventElapsedTime(&ms, D->ev0, D->ev1));
+            HIP_OK(hipMemcpy(&nn, D->refit.counters + 1, sizeof nn, hipMemcpyDeviceToHost));
+            st.device_seconds = 1e-3 * ms;
+            st.nodes_refit = nn;
+            st.levels = (int32_t)D->level_first.size() - 1;
+        }
+    }
+    if (stats) *stats = st;
+    return MCPT_OK;
+}
+
+int mcpt_scene_transform(mcpt_scene* sc, int32_t first, int32_t count, const double m[12], const double normal_m[9],
+                         mcpt_update_stats* stats) {
+    static const char* who = "mcpt_scene_transform";
+    int rc;
+    if ((rc = update_check_args(sc, first, count, m, stats, who, "m"))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if ((rc = update_check_lights(sc, first, count, who))) return rc;
+    double n[9];
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(m[i])) {
+            set_error("%s: m[%d] is not finite", who, i);
+            return MCPT_E_INVALID;
+        }
+    for (int i = 0; i < 9; i++) {
+        n[i] = normal_m ? normal_m[i] : m[4 * (i / 3) + i % 3];
+        if (!std::isfinite(n[i])) {
+            set_error("%s: normal_m[%d] is not finite", who, i);
+            return MCPT_E_INVALID;
+        }
+    }
+    if (!sc->rest_saved) {
+        set_error("%s: the scene has no rest pose yet (call mcpt_scene_rest_save first)", who);
+        return MCPT_E_INVALID;
+    }
+    const std::vector<DeviceState*> devs = device_states(sc);
+    if (!devs.empty()) return transform_on_devices(sc, devs, first, count, m, n, stats);
+    // no device state yet: the rule on the host, then an ordinary update (nothing is left pending)
+    std::vector<float> pos(9 * (size_t)count), nrm(9 * (size_t)count);
+    transform_facets(sc->rest_pos.data() + 9 * (size_t)first, sc->rest_nrm.data() + 9 * (size_t)first, (size_t)count, m, n, pos.data(),
+                     nrm.data());
+    if ((rc = update_check_values(sc, first, count, pos.data(), nrm.data(), who))) return rc;
+    return update_apply(sc, first, count, pos.data(), nrm.data(), -1, nullptr, nullptr, stats);
+}
+
+int mcpt_scene_host_pending(const mcpt_scene* sc, int64_t* facets) {
+    if (!sc || !facets) {
+        set_error("mcpt_scene_host_pending: NULL %s", !sc ? "scene" : "facets");
+        return MCPT_E_INVALID;
+    }
+    mcpt_scene* w = const_cast<mcpt_scene*>(sc);
+    std::lock_guard<std::mutex> lk(w->mu);
+    std::lock_guard<std::mutex> hl(w->host_mu);
+    *facets = sc->pending.facets();
+    return MCPT_OK;
+}
+
+int mcpt_scene_host_sync(mcpt_scene* sc) {
+    if (!sc) {
+        set_error("mcpt_scene_host_sync: NULL scene");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    return host_sync(sc);
 }
 
 int mcpt_scene_camera(const mcpt_scene* sc, mcpt_camera* cam) {
@@ -7582,6 +7854,7 @@ int mcpt_scene_meshing(mcpt_scene* sc, const double eye[3], int32_t n0) {
         return MCPT_E_INVALID;
     }
     std::lock_guard<std::mutex> lk(sc->mu);
+    if (int rs = host_sync(sc)) return rs;
     sc->grid = build_grid(sc->host, eye, n0);
     sc->grid_version++;
     if (!sc->grid.ok) {
@@ -7809,6 +8082,7 @@ int mcpt_debug_bvh4_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
         return MCPT_E_INVALID;
     }
     std::lock_guard<std::mutex> lk(sc->mu);
+    if (int rs = host_sync(sc)) return rs;
     const Bvh& bb = light_only ? sc->lbvh : sc->bvh;
     const std::vector<BvhNode4> b4 = collapse_bvh4(bb);
     bvh4_walk(b4, quantize_bvh4(b4), bb.leaf_facets, sc->host.pos, out);
@@ -7826,6 +8100,7 @@ struct DeviceTree {
 static int download_tree(mcpt_scene* sc, int32_t device, bool vertices, DeviceTree* t) {
     DeviceState* D;
     int rc;
+    if ((rc = host_sync(sc))) return rc;  // the device check compares against host.pos
     if ((rc = get_device_state(sc, device, &D))) return rc;
     HIP_OK(hipDeviceSynchronize());
     const DScene& d = D->d;

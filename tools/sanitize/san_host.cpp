@@ -1,6 +1,6 @@
 // Sanitizer driver (host code only, no GPU): built with -fsanitize=address,undefined by
 // `make -C monte_carlo_path_tracing_amd/csrc sanitize` together with the library's host sources
-// (scene_io.cpp, bvh.cpp, grid.cpp, image.cpp) and the oracle (oracle/mcpt_oracle.c).
+// (scene_io.cpp, bvh.cpp, grid.cpp, image.cpp, host_mirror.cpp) and the oracle (oracle/mcpt_oracle.c).
 //
 // For every (obj, xml) pair on the command line it runs what mcpt_scene_load does on the host --
 // Myobj::read / Mylight::read / gather_light_triangles (scene_io.cpp, the reference's Myobj.cpp:10-28,
@@ -10,6 +10,7 @@
 // malformed file must come back as an error, never as a sanitizer report.
 //
 //   san_host OUT_DIR obj1 xml1 [obj2 xml2 ...]
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -74,6 +75,46 @@ static int run_library(const char* obj, const char* xml, const std::string& out_
                 const std::vector<BvhNode4> r4 = collapse_bvh4(rb);
                 if (quantize_bvh4(r4).size() != r4.size()) return 7;
             }
+            // mcpt_scene_transform's host side (host_mirror.cpp): overlapping, touching and many scattered ranges
+            // merged into the pending list (past kPendingMax it collapses to the hull), every pending facet rotated
+            // from the rest pose by the rule, then the host half of the sync over the list
+            PendingRanges pend;
+            std::vector<uint8_t> marked(hs.F, 0);  // what was added, kept independently of the list
+            auto add = [&](int32_t a, int32_t c) {
+                pend.add(a, c);
+                for (int32_t g = a; g < a + c; g++) marked[g] = 1;
+            };
+            for (int32_t s : {0, hs.F / 2, hs.F - 1, 1, hs.F / 2 + 1, hs.F / 3}) add(s, std::min<int32_t>(2, hs.F - s));
+            for (int32_t f = 0; f < hs.F && f < 3 * (int32_t)kPendingMax; f += 3) add(f, 1);
+            int64_t covered = 0, want = 0;
+            const bool hull = pend.r.size() == 1;  // a collapsed list covers more than was added, never less
+            for (size_t i = 0; i < pend.r.size(); i++) {
+                if (pend.r[i].first < 0 || pend.r[i].second > hs.F || pend.r[i].first >= pend.r[i].second) return 8;
+                if (i && pend.r[i - 1].second >= pend.r[i].first) return 8;  // sorted, disjoint, not touching
+                covered += pend.r[i].second - pend.r[i].first;
+            }
+            for (int32_t g = 0; g < hs.F; g++) {
+                bool in = false;
+                for (const auto& p : pend.r) in = in || (g >= p.first && g < p.second);
+                if (marked[g] && !in) return 8;
+                if (!hull && in && !marked[g]) return 8;
+                want += marked[g];
+            }
+            if (pend.r.size() > kPendingMax || covered != pend.facets() || covered < want) return 8;
+            double m[12];
+            const double axis[3] = {0.3, 1.0, -0.2}, pivot[3] = {0.5, 0.25, -1.0}, shift[3] = {0.125, 0.0, -0.25};
+            if (mcpt_transform_rotation(axis, 33.0, pivot, shift, m) != MCPT_OK) return 8;
+            const double n[9] = {m[0], m[1], m[2], m[4], m[5], m[6], m[8], m[9], m[10]};
+            HostScene turned = hs;
+            for (const auto& p : pend.r)
+                transform_facets(hs.pos.data() + 9 * (size_t)p.first, hs.nrm.data() + 9 * (size_t)p.first, (size_t)(p.second - p.first),
+                                 m, n, turned.pos.data() + 9 * (size_t)p.first, turned.nrm.data() + 9 * (size_t)p.first);
+            Bvh tb = b;
+            std::vector<int32_t> slot_start, slot_list;
+            make_facet_slot_map(tb, hs.F, slot_start, slot_list);
+            if (host_refresh_ranges(turned, tb, ix, slot_start, slot_list, pend, 1e-5) < covered) return 8;
+            const std::vector<BvhNode4> t4 = collapse_bvh4(tb);
+            if (quantize_bvh4(t4).size() != t4.size()) return 8;
         }
     }
     const double eye[3] = {hs.has_cam ? hs.cam.eye[0] : 0.0, hs.has_cam ? hs.cam.eye[1] : 0.0,
@@ -135,10 +176,39 @@ static int run_oracle(const char* obj, const char* xml) {
     return 0;
 }
 
+// PendingRanges::add on lists that do not depend on any scene: merges of overlapping and touching ranges in any
+// order, and the collapse to the hull once more than kPendingMax disjoint ranges are held
+static bool check_pending_ranges() {
+    using R = std::vector<std::pair<int32_t, int32_t>>;
+    PendingRanges p;
+    p.add(5, 3);
+    p.add(8, 2);  // touches [5, 8)
+    if (p.r != R{{5, 10}}) return false;
+    p.add(0, 2);
+    p.add(20, 4);
+    p.add(12, 1);
+    if (p.r != R{{0, 2}, {5, 10}, {12, 13}, {20, 24}} || p.facets() != 12) return false;
+    p.add(7, 0);  // an empty range is ignored
+    p.add(1, 12);  // overlaps the first, swallows the second, touches the third
+    if (p.r != R{{0, 13}, {20, 24}} || p.facets() != 17) return false;
+    PendingRanges q;
+    const int32_t n = (int32_t)kPendingMax;
+    for (int32_t i = n - 1; i >= 0; i--) q.add(100 + 10 * i, 1);  // descending: every insertion is at the front
+    if (q.r.size() != kPendingMax || q.facets() != n || q.r.front() != std::make_pair(100, 101)) return false;
+    q.add(3, 2);  // one more disjoint range: the hull
+    if (q.r != R{{3, 100 + 10 * (n - 1) + 1}}) return false;
+    q.add(2000, 1);  // and the list grows again from there
+    return q.r == R{{3, 100 + 10 * (n - 1) + 1}, {2000, 2001}};
+}
+
 int main(int argc, char** argv) {
     if (argc < 4 || (argc - 2) % 2) {
         std::fprintf(stderr, "usage: %s OUT_DIR obj xml [obj xml ...]\n", argv[0]);
         return 2;
+    }
+    if (!check_pending_ranges()) {
+        std::fprintf(stderr, "san_host: PendingRanges::add gives a wrong list\n");
+        return 1;
     }
     const std::string out_dir = argv[1];
     int loaded = 0, rejected = 0, oloaded = 0, orejected = 0;
