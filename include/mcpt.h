@@ -46,6 +46,7 @@ extern "C" {
                                * MCPT_SEQ_PREV_NORMAL); on-device transforms of facet ranges with a lazily synced
                                * host copy (mcpt_scene_rest_save, mcpt_scene_transform, mcpt_scene_host_pending,
                                * mcpt_scene_host_sync, mcpt_transform_rotation);
+                               * mcpt_stats gains pick_table_roots (appended, guarded by stats_size: stats ABI 2.3);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
                                * time went; mcpt_render_opts gains stats_size (appended: a caller built against
@@ -250,6 +251,9 @@ typedef struct {
                                   * in order of first appearance; entries beyond 16 not recorded): wall time of
                                   * its shards, setup and reduce excluded -- max/min is the load imbalance.
                                   * Single device / mcpt_comm rank: [0] = this call's render time */
+    /* ABI 2.3 (appended; a caller with a smaller stats_size gets the prefix) */
+    uint64_t pick_table_roots;   /* cached roots (of prep_cached_nodes) whose pick came from the per-run root pick
+                                  * table instead of a search of the pixel's cached row */
 } mcpt_stats;
 /* With several devices, `seconds` is the wall time of the whole call (setup + shards + reduce; comm init
  * excluded), counts are summed over devices and prep_seconds is summed device time. */

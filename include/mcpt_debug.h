@@ -20,8 +20,12 @@ enum {
     MCPT_DEBUG_RAYS_PERSIST = 1 << 20,
     MCPT_DEBUG_RAYS_CW8 = 1 << 21,
     MCPT_DEBUG_FUSED_CULL = 1 << 22,
-    MCPT_DEBUG_NO_EXACT_DEFER = 1 << 23
+    MCPT_DEBUG_NO_EXACT_DEFER = 1 << 23,
+    MCPT_DEBUG_NO_PICK_TABLE = 1 << 24
 };
+/* MCPT_DEBUG_NO_PICK_TABLE: cached roots search their pixel's cached row in every generation (k_prep_pick_g)
+ * instead of looking their pick up in the run's root pick table (k_root_pick_table + k_pick_lookup; sums, picks,
+ * exact-list membership and frames are the same either way). */
 /* MCPT_DEBUG_NO_EXACT_DEFER: k_prep_exact recomputes a root's literal sums even when another wave of the same
  * launch is computing its pixel's, instead of deferring the root to the follow-up launch that only searches the
  * stored sums (the default since round 6; picks and sums are the same either way). */
@@ -111,6 +115,21 @@ int mcpt_debug_bvh4_download(mcpt_scene* scene, int32_t device, int64_t counts[2
  * -- the pixels sampled by its last pass, or the list built after pass 0 when max_spp = min_spp + pass_spp.
  * *n = its length (0: no list was built); up to `cap` pixel indices are copied to `pixels`. */
 int mcpt_debug_adaptive_active(mcpt_scene* scene, int32_t device, int32_t* pixels, int32_t cap, int32_t* n);
+
+/* The root pick table's rules, process-wide (0: the library's default): min_samples, the fewest samples per pixel
+ * of a run at which the table is built; window_samples, a cap on the samples one table covers (rounded down to whole
+ * root groups), so that a small run rolls over several windows.  For tests and the min_samples A/B. */
+int mcpt_debug_set_pick_table(int32_t min_samples, int32_t window_samples);
+
+/* diagnostics: the light pick of every root of a render call with these options (scene, camera, seed, mode, sample
+ * range, flags), without tracing anything: pick, weights_sum and ambiguous are [width * height][samples] arrays.  The
+ * picks come from the path the render's run would take -- the root pick table and its lookup, or with
+ * MCPT_DEBUG_NO_PICK_TABLE (or below min_samples) the pick kernel over the cached rows, driven by the run's root
+ * queue.  pick: the light index, -1 without one; ambiguous: 1 for a root the exact pick redoes.  A sample that
+ * terminates at entry (Russian roulette) and every sample of a pixel without a cached root carry the sentinel
+ * pick -2, weights_sum 0, ambiguous 0.  MCPT_E_INVALID when the call has no root-point cache. */
+int mcpt_debug_root_picks(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* opts, int32_t* pick,
+                          double* weights_sum, int32_t* ambiguous);
 
 #ifdef __cplusplus
 }

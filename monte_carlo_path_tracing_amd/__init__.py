@@ -79,6 +79,7 @@ DEBUG_RAYS_PERSIST = 1 << 20  # MIS / shade ray sets through the persistent refi
 DEBUG_RAYS_CW8 = 1 << 21  # the persistent traversal walks the 8-wide compressed trees (k_rays_cw8)
 DEBUG_FUSED_CULL = 1 << 22  # MIS children's prep: cheap stages inside k_prep_pk2 (variant 8) instead of k_prep_cull_lanes
 DEBUG_NO_EXACT_DEFER = 1 << 23  # k_prep_exact recomputes same-launch duplicate roots instead of deferring them
+DEBUG_NO_PICK_TABLE = 1 << 24  # cached roots search their pixel's cached row (k_prep_pick_g) instead of the root pick table
 DEBUG_HIT_CW8 = 1 << 8  # mcpt_closest_hit: trace through the 8-wide trees
 
 
@@ -163,7 +164,8 @@ class Stats(C.Structure):
                 ("trace_seconds", C.c_double), ("trace_launches", C.c_uint64), ("node_visits", C.c_uint64),
                 ("tri_tests", C.c_uint64), ("prep_exact_nodes", C.c_uint64), ("cache_build_seconds", C.c_double),
                 ("prep_band_nodes", C.c_uint64), ("comm_init_seconds", C.c_double),
-                ("device_setup_seconds", C.c_double), ("device_seconds", C.c_double * STATS_MAX_DEVICES)]
+                ("device_setup_seconds", C.c_double), ("device_seconds", C.c_double * STATS_MAX_DEVICES),
+                ("pick_table_roots", C.c_uint64)]
 
     def as_dict(self):
         """scalar fields (summable); device_seconds is in per_device_seconds()"""
@@ -222,7 +224,8 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_transform_rotation"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
-                 "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download"]  # include/mcpt_debug.h
+                 "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download",
+                 "mcpt_debug_set_pick_table", "mcpt_debug_root_picks"]  # include/mcpt_debug.h
 
 
 def lib():
@@ -368,6 +371,8 @@ def lib():
                "mcpt_debug_bvh4_check": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
                "mcpt_debug_adaptive_active": [P, I, ip, I, C.POINTER(I)],
                "mcpt_debug_bvh4_check_device": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
+               "mcpt_debug_set_pick_table": [I, I],
+               "mcpt_debug_root_picks": [P, C.POINTER(Camera), C.POINTER(RenderOpts), ip, dp, ip],
                "mcpt_debug_bvh4_download": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C"), P, P, P, C.c_int64, C.c_int64]}
         for name, argt in dbg.items():
             if hasattr(L, name):
@@ -1401,6 +1406,24 @@ def debug_adaptive_active(scene, device=-1):
     px = np.zeros(max(n.value, 1), np.int32)
     _check(lib().mcpt_debug_adaptive_active(scene.h, int(device), px, n.value, C.byref(n)))
     return px[:n.value]
+
+
+def debug_set_pick_table(min_samples=0, window_samples=0):
+    """mcpt_debug_set_pick_table (include/mcpt_debug.h): process-wide overrides of the root pick table's rules,
+    0 = the library's default."""
+    _check(lib().mcpt_debug_set_pick_table(int(min_samples), int(window_samples)))
+
+
+def debug_root_picks(scene, camera, spp, sample_range, mode="mis", seed=DEFAULT_SEED, flags=0, device=None):
+    """mcpt_debug_root_picks (include/mcpt_debug.h): (pick, weights_sum, ambiguous), each [pixels][samples of
+    sample_range], of the roots a render with these options would queue; pick -2 marks a sample that terminates at
+    entry or a pixel without a cached root."""
+    o = _opts(spp, mode, seed, sample_range, device, 0, 0, flags=flags)
+    n = (camera.width * camera.height, int(sample_range[1]) - int(sample_range[0]))
+    pick, wsum, amb = np.zeros(n, np.int32), np.zeros(n), np.zeros(n, np.int32)
+    _check(lib().mcpt_debug_root_picks(scene.h, C.byref(camera), C.byref(o), pick.reshape(-1), wsum.reshape(-1),
+                                       amb.reshape(-1)))
+    return pick, wsum, amb
 
 
 def closest_hit(scene, ro, rd, exclude=None, light_only=False, grid=False, wide=False):

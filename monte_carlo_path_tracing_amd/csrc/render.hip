@@ -16,7 +16,10 @@
 //                                       and the inverse-CDF pick; in build mode fills the cache
 //   k_prep_pick_g      16 LANES per root : the pick of a root from the root-point cache (k_prep_pick,
 //                      a wave per root, for tables of more than 64 chunks)
-//   k_prep / k_prep_lane              : the same prep for huge / tiny light sets
+//   k_root_pick_table  LANE per sample: the picks of all roots of a window of a run's samples, pixel-major
+//                                       with the pixel's cache row in LDS, once per window;
+//   k_pick_lookup      lane per root  : a generation's fresh roots take theirs from that table
+//   k_prep / k_prep_lane             : the same prep for huge / tiny light sets
 //   k_mis_gen / k_shade_gen / k_brdf_gen, k_mis_rays (BVH or the reference grid), k_*_combine:
 //                                       light + BRDF samples, their closest hits, MIS weights and the
 //                                       children's entry checks -> next generation's queue
@@ -2981,6 +2984,82 @@ __device__ inline int row_max_i32(int v) {
     v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x122, 0xf, 0xf, false));
     return max(v, __builtin_amdgcn_update_dpp(0, v, 0x121, 0xf, 0xf, false));
 }
+// A cached root's pick by its 16-lane group: the definitions k_prep_pick_g (a root from the queue, its row
+// from HBM) and k_root_pick_table (a pixel's samples, its row in LDS) share, so that the two give the same
+// sums, picks and ambiguity decisions by construction.  Lane gl of the group (first wave lane g0) holds
+// entries gl, gl + 16, gl + 32, gl + 48 of whatever row is searched; every lane of the group takes part.
+// The scalar definitions -- what is compared with what -- that every search of a cached row uses, whichever lanes
+// do the searching:
+// the batch of a target: the first one whose running total bv satisfies this
+__device__ inline bool pick_batch_hit(double bv, double target) { return bv >= target && bv > 0.0; }
+// the entry inside the batch (w: its signed in-batch prefix): the first non-culled one that satisfies this
+__device__ inline bool pick_entry_live(double w) { return !signbit(w); }
+__device__ inline bool pick_entry_hit(double base, double w, double target) { return base + fabs(w) >= target; }
+// pick_margin's terms for in-batch entry pl >= 0 (s1 = |w[pl]|, s0 = |w[max(pl - 1, 0)]|)
+__device__ inline double pick_entry_margin(double base, double s0, double s1, int pl, double target) {
+    const double c_hi = base + s1;
+    const double c_lo = pl > 0 ? base + s0 : base;
+    const double m_lo = c_lo == 0.0 ? INFINITY : target - c_lo;
+    return fmin(m_lo, c_hi - target);
+}
+// weights_sum of a row of nb batch totals (bv: its inclusive scan)
+__device__ inline double pickg_wsum(const double (&bv)[4], int nb, int g0) {
+    const int lw = max(nb - 1, 0);
+    const double W = bperm_f64(sel4(bv, lw >> 4), g0 + (lw & 15));
+    return nb > 0 ? W : 0.0;
+}
+// the batch of u: the first one with bv >= target && bv > 0 (-1: none), and the total below it
+__device__ inline void pickg_batch(const double (&bv)[4], int nb, double wsum, double u, int gl, int g0, double* target,
+                                   int* kb, double* base) {
+    const bool valid = !(fabs(wsum) < MCPT_EPS);
+    *target = u * wsum;
+    unsigned c = 64;
+#pragma unroll
+    for (int k = 3; k >= 0; k--) c = valid && 16 * k + gl < nb && pick_batch_hit(bv[k], *target) ? 16 * k + gl : c;
+    c = row_min_u32(c);
+    *kb = c < 64 ? (int)c : -1;
+    const int lb = max(*kb - 1, 0);
+    const double b = bperm_f64(sel4(bv, lb >> 4), g0 + (lb & 15));
+    *base = *kb > 0 ? b : 0.0;
+}
+// the pick inside the batch (wc: its signed in-batch prefixes, -0.0 beyond the list; lj: its list entries): the
+// first non-culled entry with base + |w| >= target, else the last non-culled one; its light and pick_margin's terms
+__device__ inline void pickg_entry(const double (&wc)[4], const int (&lj)[4], double base, double target, int gl, int g0,
+                                   int* pick, double* margin) {
+    int pl;
+    {
+        unsigned cf = 64;
+        int cl = -1;
+#pragma unroll
+        for (int k = 3; k >= 0; k--) {
+            const bool ok = pick_entry_live(wc[k]);
+            cf = ok && pick_entry_hit(base, wc[k], target) ? 16 * k + gl : cf;
+            cl = ok && cl < 0 ? 16 * k + gl : cl;  // the highest k wins
+        }
+        cf = row_min_u32(cf);
+        const int lastv = row_max_i32(cl);  // every lane of the row takes part in the DPP steps
+        pl = cf < 64 ? (int)cf : lastv;
+    }
+    *margin = INFINITY;
+    *pick = -1;
+    const int l1 = max(pl, 0), l0 = max(pl - 1, 0);
+    double sc[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) sc[k] = fabs(wc[k]);
+    const double s1 = bperm_f64(sel4(sc, l1 >> 4), g0 + (l1 & 15));
+    const double s0 = bperm_f64(sel4(sc, l0 >> 4), g0 + (l0 & 15));
+    const int pk = bperm_i32(sel4(lj, l1 >> 4), g0 + (l1 & 15));
+    if (pl >= 0) {
+        *margin = pick_entry_margin(base, s0, s1, pl, target);
+        *pick = pk;
+    }
+}
+// exact pick: inside the band stored by the cache build + this sum's rounding
+__device__ inline bool pickg_ambiguous(int4 inf, double margin, double wsum) {
+    const double band = (double)__int_as_float(inf.w) + band_round(inf.y, wsum);
+    return !(pick_slack(margin, wsum) > band);
+}
+
 __global__ __launch_bounds__(256, MCPT_LB_PICKG) void k_prep_pick_g(DScene S, uint64_t seed, int n, const int* __restrict__ qpixel,
                                                      const int* __restrict__ qsample, const uint64_t* __restrict__ qnode,
                                                      double* __restrict__ wsum_out, int* __restrict__ pick_out,
@@ -3026,23 +3105,8 @@ __global__ __launch_bounds__(256, MCPT_LB_PICKG) void k_prep_pick_g(DScene S, ui
         int kb[kPickSlots];
 #pragma unroll
         for (int s = 0; s < kPickSlots; s++) {
-            const int nb = inf[s].x;
-            const int lw = max(nb - 1, 0);
-            const double W = bperm_f64(sel4(bv[s], lw >> 4), g0 + (lw & 15));
-            wsum[s] = nb > 0 ? W : 0.0;
-            const bool valid = !(fabs(wsum[s]) < MCPT_EPS);
-            target[s] = bperm_f64(ul, 4 * s + g) * wsum[s];
-            {
-                unsigned c = 64;
-#pragma unroll
-                for (int k = 3; k >= 0; k--)
-                    c = valid && 16 * k + gl < nb && bv[s][k] >= target[s] && bv[s][k] > 0.0 ? 16 * k + gl : c;
-                c = row_min_u32(c);
-                kb[s] = c < 64 ? (int)c : -1;
-            }
-            const int lb = max(kb[s] - 1, 0);
-            const double b = bperm_f64(sel4(bv[s], lb >> 4), g0 + (lb & 15));
-            base[s] = kb[s] > 0 ? b : 0.0;
+            wsum[s] = pickg_wsum(bv[s], inf[s].x, g0);
+            pickg_batch(bv[s], inf[s].x, wsum[s], bperm_f64(ul, 4 * s + g), gl, g0, &target[s], &kb[s], &base[s]);
         }
         // the picked batch's signed in-batch prefixes and its 64 list entries
         double wc[kPickSlots][4];
@@ -3059,47 +3123,15 @@ __global__ __launch_bounds__(256, MCPT_LB_PICKG) void k_prep_pick_g(DScene S, ui
         }
 #pragma unroll
         for (int s = 0; s < kPickSlots; s++) {
-            int pl;
-            {
-                unsigned cf = 64;
-                int cl = -1;
-#pragma unroll
-                for (int k = 3; k >= 0; k--) {
-                    const bool ok = !signbit(wc[s][k]);
-                    cf = ok && (base[s] + fabs(wc[s][k]) >= target[s]) ? 16 * k + gl : cf;
-                    cl = ok && cl < 0 ? 16 * k + gl : cl;  // the highest k wins
-                }
-                cf = row_min_u32(cf);
-                const int lastv = row_max_i32(cl);  // every lane of the row takes part in the DPP steps
-                pl = cf < 64 ? (int)cf : lastv;
-            }
-            double margin = INFINITY;
-            int pick = -1;
-            {
-                const int l1 = max(pl, 0), l0 = max(pl - 1, 0);
-                double sc[4];
-#pragma unroll
-                for (int k = 0; k < 4; k++) sc[k] = fabs(wc[s][k]);
-                const double s1 = bperm_f64(sel4(sc, l1 >> 4), g0 + (l1 & 15));
-                const double s0 = bperm_f64(sel4(sc, l0 >> 4), g0 + (l0 & 15));
-                const int pk = bperm_i32(sel4(lj[s], l1 >> 4), g0 + (l1 & 15));
-                if (pl >= 0) {  // pick_margin's terms
-                    const double c_hi = base[s] + s1;
-                    const double c_lo = pl > 0 ? base[s] + s0 : base[s];
-                    const double m_lo = c_lo == 0.0 ? INFINITY : target[s] - c_lo;
-                    margin = fmin(m_lo, c_hi - target[s]);
-                    pick = pk;
-                }
-            }
+            double margin;
+            int pick;
+            pickg_entry(wc[s], lj[s], base[s], target[s], gl, g0, &pick, &margin);
             const int node = n0 + 4 * s + g;
             bool amb = false;
             if (gl == 0 && node < n) {
                 wsum_out[node] = wsum[s];
                 pick_out[node] = pick;
-                if (C.exact) {  // exact pick: the band stored by the cache build + this sum's rounding
-                    const double band = (double)__int_as_float(inf[s].w) + band_round(inf[s].y, wsum[s]);
-                    amb = !(pick_slack(margin, wsum[s]) > band);
-                }
+                if (C.exact) amb = pickg_ambiguous(inf[s], margin, wsum[s]);
             }
             if (C.exact) {  // one list atomic per wave (C.exact is launch-uniform)
                 const int q = wave_append(reinterpret_cast<unsigned*>(C.exact), amb);
@@ -3109,6 +3141,190 @@ __global__ __launch_bounds__(256, MCPT_LB_PICKG) void k_prep_pick_g(DScene S, ui
         cached += (unsigned long long)min(kR, n - n0);
     }
     if (lane == 0 && stats && cached) atomicAdd(stats + 0, cached);
+}
+
+// ---- The root pick table: a cached root's pick is a function of (seed, pixel, sample) alone, so one
+// pixel-major pass per window of a run's samples computes every root's pick with the pixel's row in LDS
+// (k_root_pick_table), and the generations look their fresh roots up (k_pick_lookup) instead of walking the rows in
+// HBM root by root (k_prep_pick_g).
+// The table is indexed by the run's root index (root_of's order) less the window's first root, so that the lookups of
+// a generation's roots -- queued in that order -- are consecutive 2-byte loads, and a tile of adjacent pixels fills
+// whole rows of tile x group entries.  An entry: the picked light in bits 0-14 (kPickNone: none), bit 15 the ambiguity
+// decision (the root goes on the exact list).
+constexpr unsigned kPickNone = 0x7FFF;
+// root_of's inverse: the root index of sample a + rel of pixel (index) p in a run of nsamp samples
+__device__ inline long long root_index(int p, int rel, int npx, int group, int nsamp) {
+    const int blk = rel / group, j = rel - blk * group;
+    const int gsz = blk < nsamp / group ? group : nsamp % group;
+    return (long long)blk * group * npx + (long long)p * gsz + j;
+}
+struct PickTable {
+    unsigned short* tab;  // [window roots]
+    double* wsum;         // [npx] a pixel's weights_sum
+    long long base;       // the window's first root index
+    int a, nsamp, group;  // the run: its first sample, its samples, root_of's group
+};
+#ifndef MCPT_PICK_TAB_ENTRIES
+#define MCPT_PICK_TAB_ENTRIES 4096  // A/B per 1024-spp C3 call: 8192 (3 blocks per CU) 25.2 ms, 4096 (4 blocks) 23.9 ms
+#endif
+constexpr int kPickTabEntries = MCPT_PICK_TAB_ENTRIES;  // LDS staging of the outputs: tile pixels x chunk samples
+constexpr int kPickTileMax = 32;       // pixels per block (group 1)
+constexpr int kPickStep = 8;           // totals / prefixes a lane's scan reads per trip (divides 64)
+// LDS index of row entry e: a batch's 64 prefixes take 65 doubles, so that lanes scanning different batches at the
+// same in-batch position do not all meet in one bank (512 B apart: the same bank for every batch)
+__device__ inline int pick_row_slot(int e) { return e + (e >> 6); }
+// Block (x, y): pixels [x tile, (x + 1) tile) and the run's samples (relative to a) [c_lo + y c_len, ... + c_len) cut
+// at c_hi.  tile > 1: c_lo and c_len are multiples of group (the block owns whole table rows of tile x group
+// entries); tile == 1: any range (a pixel's entries of a root block are consecutive).  Pixel by pixel: the row --
+// batch totals, the ncand in-batch prefixes and list entries -- is staged in LDS (the CU's other blocks search
+// meanwhile; fetching the next row into registers during the search spilled and was no faster); then LANE PER
+// SAMPLE: the RR and pick uniforms, a scan of the batch totals (every lane reads the same word: a broadcast) and a
+// scan of the picked batch, with the scalar definitions k_prep_pick_g's
+// 16-lane groups use (pick_batch_hit, pick_entry_live / _hit, pick_entry_margin, pickg_ambiguous) on the same
+// values, so "first" and "last" select the same entries.  With the row in LDS a lane's sequential scan issues fewer
+// wave instructions per root than the group search, whose wave instruction serves 4 roots (31.4 -> 23.9 ms per
+// 1024-spp C3 call).  rr: draw the root's RR (MIS, BRDF).
+// Dynamic LDS: lstride + nchunks + 64 doubles, lstride + tile c_len 16-bit words.
+__global__ __launch_bounds__(256, 4) void k_root_pick_table(uint64_t seed, int rr, int npx, const int* __restrict__ kind, int nchunks,
+                                                            PrepCache C, PickTable T, int tile, int c_lo, int c_len, int c_hi) {
+    extern __shared__ double pt_lds[];
+    __shared__ int4 s_inf[kPickTileMax];
+    __shared__ int s_cached[kPickTileMax];
+    double* sw = pt_lds;                          // [lstride + nchunks] in-batch prefixes (pick_row_slot)
+    double* sbt = pt_lds + C.lstride + nchunks;   // [64] batch totals
+    unsigned short* sl = reinterpret_cast<unsigned short*>(sbt + 64);
+    unsigned short* so = sl + C.lstride;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int p0 = blockIdx.x * tile, pn = min(tile, npx - p0);
+    const int c0 = c_lo + blockIdx.y * c_len, c1 = min(c0 + c_len, c_hi);
+    const int group = T.group, nfull = T.nsamp / group, gtail = T.nsamp % group;
+    // where (pixel pl of the tile, sample rel) goes in so
+    auto slot = [&](int pl, int rel) {
+        if (tile == 1) return rel - c0;
+        const int blk = rel / group, j = rel - blk * group;
+        return (blk - c0 / group) * (tile * group) + pl * (blk < nfull ? group : gtail) + j;
+    };
+    // the tile's pixels: whether each has a cached root, and its info
+    if ((int)threadIdx.x < pn) {
+        const bool c = kind[p0 + threadIdx.x] == -1;
+        s_inf[threadIdx.x] = c ? C.info[p0 + threadIdx.x] : make_int4(0, 0, 0, 0);
+        s_cached[threadIdx.x] = c ? 1 : 0;
+    }
+    __syncthreads();
+    for (int pl = 0; pl < pn; pl++) {
+        const int px = p0 + pl;
+        if (!s_cached[pl]) {  // no cached root: nothing looks these entries up
+            for (int rel = c0 + (int)threadIdx.x; rel < c1; rel += 256) so[slot(pl, rel)] = (unsigned short)kPickNone;
+            if (threadIdx.x == 0 && blockIdx.y == 0) T.wsum[px] = 0.0;
+            continue;
+        }
+        const int4 inf = s_inf[pl];
+        const int nb = min(inf.x, nchunks), ncand = inf.y;
+        __syncthreads();  // the previous pixel's searches are done with the row
+        {
+            const double* rw = C.w + (size_t)px * C.lstride;
+            const unsigned* rl = reinterpret_cast<const unsigned*>(C.lst + (size_t)px * C.lstride);  // lstride is even
+            for (int e = threadIdx.x; e < ncand; e += 256) sw[pick_row_slot(e)] = rw[e];
+            for (int e = threadIdx.x; 2 * e < ncand; e += 256) reinterpret_cast<unsigned*>(sl)[e] = rl[e];
+            if (threadIdx.x < 64) sbt[threadIdx.x] = (int)threadIdx.x < nb ? C.bt[(size_t)px * nchunks + threadIdx.x] : 0.0;
+        }
+        __syncthreads();
+        const double wsum = inf.x > 0 ? sbt[nb - 1] : 0.0;  // pickg_wsum's value
+        if (threadIdx.x == 0 && blockIdx.y == 0) T.wsum[px] = wsum;
+        const bool valid = !(fabs(wsum) < MCPT_EPS);
+#pragma unroll 1
+        for (int r0 = c0 + 64 * wid; r0 < c1; r0 += 256) {
+            const int rel = r0 + lane;
+            bool live = rel < c1;
+            double ul = 0.0;
+            if (live) {
+                const uint64_t key = counter_key(seed, (uint64_t)px, (uint64_t)(T.a + rel), 1);
+                ul = counter_u(key, 1);
+                if (rr && counter_u(key, 0) > MCPT_P_RR) {  // terminates at entry (k_roots_t's test)
+                    so[slot(pl, rel)] = (unsigned short)kPickNone;
+                    live = false;
+                }
+            }
+            const double target = ul * wsum;
+            // the batch: the first hit among the nb totals
+            // (kPickStep totals per trip: a trip's LDS reads are independent and cost one round trip, 33.5 -> 28.3 ms
+            // against one total per trip; totals from nb on are 0, never a hit)
+            int kb = -1;
+#pragma unroll 1
+            for (int k0 = 0; k0 < nb && __ballot(live && valid && kb < 0); k0 += kPickStep) {
+                double b[kPickStep];
+#pragma unroll
+                for (int t = 0; t < kPickStep; t++) b[t] = sbt[k0 + t];
+#pragma unroll
+                for (int t = 0; t < kPickStep; t++)
+                    if (live && valid && kb < 0 && pick_batch_hit(b[t], target)) kb = k0 + t;
+            }
+            const double base = kb > 0 ? sbt[kb - 1] : 0.0;
+            // inside it: the first live hit, else the last live entry
+            const int e0 = 64 * max(kb, 0), nin = kb >= 0 ? min(64, ncand - e0) : 0;
+            const double* wb = sw + pick_row_slot(e0);
+            int first = -1, last = -1;
+            bool open = live && nin > 0;
+#pragma unroll 1
+            for (int j0 = 0; __ballot(open); j0 += kPickStep) {
+                double w[kPickStep];
+#pragma unroll
+                for (int t = 0; t < kPickStep; t++) w[t] = open && j0 + t < nin ? wb[j0 + t] : -0.0;  // -0.0: not live
+#pragma unroll
+                for (int t = 0; t < kPickStep; t++)
+                    if (open && pick_entry_live(w[t])) {
+                        last = j0 + t;
+                        if (pick_entry_hit(base, w[t], target)) first = j0 + t, open = false;
+                    }
+                if (j0 + kPickStep >= nin) open = false;
+            }
+            if (live) {
+                const int pe = first >= 0 ? first : last;
+                double margin = INFINITY;
+                int pick = -1;
+                if (pe >= 0) {
+                    margin = pick_entry_margin(base, fabs(wb[max(pe - 1, 0)]), fabs(wb[pe]), pe, target);
+                    pick = (int)sl[e0 + pe];
+                }
+                const unsigned amb = C.exact && pickg_ambiguous(inf, margin, wsum) ? 0x8000u : 0u;
+                so[slot(pl, rel)] = (unsigned short)((pick < 0 ? kPickNone : (unsigned)pick) | amb);
+            }
+        }
+    }
+    __syncthreads();
+    // the staged entries to the table: consecutive threads, consecutive entries of a row
+    if (tile == 1) {
+        for (int e = threadIdx.x; e < c1 - c0; e += 256)
+            T.tab[root_index(p0, c0 + e, npx, group, T.nsamp) - T.base] = so[e];
+    } else {
+        const int rowlen = tile * group;
+        const int nrows = (c1 - c0 + group - 1) / group;
+        for (int e = threadIdx.x; e < nrows * rowlen; e += 256) {
+            const int bl = e / rowlen, r = e - bl * rowlen, blk = c0 / group + bl;
+            const int gsz = blk < nfull ? group : gtail;
+            if (r < pn * gsz) T.tab[(long long)blk * group * npx + (long long)p0 * gsz + r - T.base] = so[e];
+        }
+    }
+}
+
+// lane per root: cur's fresh roots take weights_sum and pick from the table, ambiguous ones go on the exact list
+// (k_prep_pick_g's outputs)
+__global__ __launch_bounds__(256) void k_pick_lookup(int n, int npx, const int* __restrict__ qpixel, const int* __restrict__ qsample,
+                                                     double* __restrict__ wsum_out, int* __restrict__ pick_out, PickTable T,
+                                                     int* exact, int exact_off) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool amb = false;
+    if (i < n) {
+        const int px = qpixel[i];
+        const unsigned t = T.tab[root_index(px, qsample[i] - T.a, npx, T.group, T.nsamp) - T.base];
+        wsum_out[i] = T.wsum[px];
+        pick_out[i] = (t & kPickNone) == kPickNone ? -1 : (int)(t & kPickNone);
+        amb = (t & 0x8000u) != 0;
+    }
+    if (exact) {  // launch-uniform
+        const int q = wave_append(reinterpret_cast<unsigned*>(exact), amb);
+        if (amb) exact[kExactHead + q] = exact_off + i;
+    }
 }
 
 // Exact pick, the band test's second half (lane per listed node): the per-chunk term
@@ -4531,6 +4747,7 @@ struct DeviceState {
     DevBuf exact, exact_scr, slack;  // exact pick: list, k_prep_exact's scratch, per-node slack
     DevBuf lit_slot, lit_pool;        // exact pick: roots' literal sums per pixel (RootLit)
     DevBuf sc_cum, sc_wsum, sc_last;  // small-table root-point cache (SmallCache)
+    DevBuf pick_tab, pick_wsum;       // the root pick table of a run's window (PickTable)
     // adaptive sampling: half sums A / B, active lists and state bytes (ping-pong), per-block survivor counts
     // (+ the total), the library's own count / noise maps
     DevBuf ad_acc[2], ad_list[2], ad_state[2], ad_blk, ad_count, ad_noise;
@@ -5380,7 +5597,7 @@ int validate_render(const mcpt_render_opts* o) {
     if (o->flags & ~(MCPT_RENDER_NO_BACKFACE_STATS | MCPT_RENDER_FRESH_PDF | MCPT_RENDER_PRECISION_FP32 |
                      MCPT_RENDER_PIXEL_JITTER | MCPT_DEBUG_SPLIT_BRDF | MCPT_DEBUG_NO_ROOT_CACHE | MCPT_DEBUG_COUNT_TRAVERSAL |
                      MCPT_DEBUG_SHARD_RANKS | MCPT_DEBUG_RAYS_PERSIST | MCPT_DEBUG_RAYS_CW8 | MCPT_DEBUG_FUSED_CULL |
-                     MCPT_DEBUG_NO_EXACT_DEFER)) {
+                     MCPT_DEBUG_NO_EXACT_DEFER | MCPT_DEBUG_NO_PICK_TABLE)) {
         set_error("unknown mcpt_render_opts.flags bits 0x%x", (unsigned)o->flags);
         return MCPT_E_INVALID;
     }
@@ -5394,6 +5611,18 @@ struct AdaptiveRun {
     int* count;
     double* noise;
 };
+
+// mcpt_debug_set_pick_table: process-wide overrides of the root pick table's rules (0: the default)
+std::atomic<int> g_pick_min_samples{0}, g_pick_window{0};
+// the fewest samples per pixel of a run (and of its windows) at which the table is built: a table pass stages a
+// pixel's whole row where k_prep_pick_g fetches ~457 B per root
+#ifndef MCPT_PICK_TABLE_MIN_SAMPLES
+#define MCPT_PICK_TABLE_MIN_SAMPLES 128
+#endif
+int pick_table_min_samples() {
+    const int v = g_pick_min_samples.load();
+    return v > 0 ? v : MCPT_PICK_TABLE_MIN_SAMPLES;
+}
 
 // ---- the render driver: plan -> bound buffers -> primary tables -> root caches -> run (plain or adaptive) ->
 // statistics (render_on_device, at the end of this section, reads in that order) ----
@@ -5415,6 +5644,7 @@ struct RenderPlan {
     bool rays_pers = false;   // the MIS / shade ray sets take the persistent refilling waves
     bool want_cw8 = false;    // ... over the 8-wide trees, where the device has them (Bound::rays_cw8)
     bool no_cache = false;    // no root-point cache: roots from rays, or the A/B switch MCPT_DEBUG_NO_ROOT_CACHE
+    uint32_t flags = 0;       // the call's mcpt_render_opts.flags
     int qf = 0, target = 0, cap = 0;  // queue factor, nodes per generation, queue capacity
     int nchunks = 0, lstride = 0;     // the light table's 64-triangle chunks; a cache row's candidate-list stride
     uint64_t accel = 0;               // bytes of the acceleration structures the rays walk
@@ -5497,6 +5727,7 @@ int make_plan(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt
     // by construction.  MCPT_EXACT_PICK=0 builds the pre-round-3 prep (VOS weights' own pick) for the cost A/B only
     p.exact_pick = MCPT_EXACT_PICK && p.needs_prep && !p.fp32 && D.d.NL > kSmallNL;
     p.no_cache = p.ray_roots || (o->flags & MCPT_DEBUG_NO_ROOT_CACHE) != 0;
+    p.flags = (uint32_t)o->flags;
     // which traversal the MIS / shade ray sets take: the persistent refilling waves for trees beyond an XCD's
     // 4 MiB L2 and for shade-area's rays (k_rays_persistent, or k_rays_cw8 on the 8-wide trees), else one ray
     // per thread (k_mis_rays)
@@ -5541,6 +5772,9 @@ struct Bound {
     SmallCache scache{};  // the small-table prep's root-point cache
     bool small_use = false;
     RootLit rl{};  // roots' literal sums per pixel (k_prep_exact), up to 2 GiB of entries
+    unsigned short* pick_tab = nullptr;  // the root pick table (null: the call has none) and the roots it holds
+    double* pick_wsum = nullptr;
+    long long pick_cap = 0;
     RootTab rtab{};
     bool rays_cw8 = false;  // the persistent traversal walks the 8-wide trees
     int nblk = 0;           // adaptive: blocks of k_adaptive_mark / k_adaptive_compact
@@ -5581,6 +5815,21 @@ int bind_root_caches(DeviceState& D, const RenderPlan& p, Bound& B) {
         B.scache.wsum = (double*)D.sc_wsum.p;
         B.scache.last = (int*)D.sc_last.p;
         B.small_use = true;
+    }
+    // the root pick table (PickTable): 2 B per root of a window, from the HBM left after the queues and the cache
+    // (the same 16 GiB kept free); a run decides whether and with which window it uses it (WavefrontRun::table_begin)
+    if (B.pc.use && MCPT_PICK_GROUPS && nchunks <= 64 && !(p.flags & MCPT_DEBUG_NO_PICK_TABLE) &&
+        p.s1 - p.s0 >= pick_table_min_samples()) {
+        HIP_OK(hipMemGetInfo(&free_b, &total_b));
+        const size_t theld = D.pick_tab.bytes + D.pick_wsum.bytes;
+        const size_t tbudget = free_b + theld > (16ull << 30) ? free_b + theld - (16ull << 30) : 0;
+        const long long roots = std::min<long long>((long long)(p.s1 - p.s0) * npx, (long long)(tbudget / 2));
+        if (roots >= 2ll * npx) {
+            if ((rc = ensure(D.pick_tab, 2ull * (size_t)roots)) || (rc = ensure(D.pick_wsum, 8ull * npx))) return rc;
+            B.pick_tab = (unsigned short*)D.pick_tab.p;
+            B.pick_wsum = (double*)D.pick_wsum.p;
+            B.pick_cap = roots;
+        }
     }
     if (p.exact_pick && B.pc.use) {
         B.rl.stride = (lstride + 8 + 7) & ~7;
@@ -5640,7 +5889,7 @@ int bind_buffers(mcpt_scene* sc, DeviceState& D, const RenderPlan& p, const mcpt
 // a call's running totals (fill_stats turns them into mcpt_stats)
 struct Counters {
     double prep_ms = 0, trace_ms = 0, cache_ms = 0;
-    uint64_t gens = 0, prep_launches = 0, nodes_total = 0, cache_points = 0, trace_launches = 0, cached_roots = 0;
+    uint64_t gens = 0, prep_launches = 0, nodes_total = 0, cache_points = 0, trace_launches = 0, cached_roots = 0, table_roots = 0;
     uint64_t spilled = 0, roots_total = 0;
 #if MCPT_ADAPTIVE_DIAG
     int diag_runs = 0;
@@ -5750,6 +5999,10 @@ struct WavefrontRun {
     int a = 0, b = 0, nact = 0, nminor = 0;  // samples [a, b) of the pixels active[0, nact) (nullptr: the frame)
     const int* active = nullptr;
     long long R = 0, rnext = 0;  // the run's roots, and how many of them have been queued
+    // the run's root pick table: the window (in samples) it is built by, and the roots [tab.base, tab_end) it holds
+    PickTable tab{};
+    int tab_window = 0;  // 0: this run's cached roots pick from their rows (k_prep_pick_g)
+    long long tab_end = 0;
 #if MCPT_ADAPTIVE_DIAG
     bool diag_draining = false;
     std::chrono::steady_clock::time_point diag_t0;
@@ -5857,6 +6110,54 @@ struct WavefrontRun {
         return MCPT_OK;
     }
 
+    // up to `room` of the run's remaining roots.  With a pick table a refill stays inside the table's window, and the
+    // next window's table is enqueued before the first refill that needs it (a generation's fresh roots are picked
+    // in that same generation, so stream order keeps the previous window's lookups ahead of the rebuild)
+    int refill_in_window(long long room) {
+        int rc;
+        long long m = std::min(room, R - rnext);
+        if (tab_window) {
+            if (rnext >= tab_end && (rc = table_build())) return rc;
+            m = std::min(m, tab_end - rnext);
+        }
+        return refill_roots((int)m);
+    }
+
+    // mcpt_debug_root_picks: the picks of the roots of samples [a_, b_) of the frame, by the path a render's run of
+    // those samples takes (the table and its lookup, or the pick kernel over the cached rows), scattered into
+    // [pixel][sample] arrays the caller has filled with the sentinel.  Needs the call's root-point cache.
+    int root_picks(int a_, int b_, int32_t* pick, double* wsum, int32_t* flag) {
+        int rc;
+        a = a_, b = b_, active = nullptr, nact = pl.npx;
+        R = (long long)(b - a) * nact;
+        nminor = pl.minor_of(b - a);
+        rnext = 0;
+        table_begin();
+        cur = &B.qa;
+        nxt = &B.qb;
+        std::vector<int> hp, hs, hk, hx;
+        std::vector<double> hw;
+        while (rnext < R) {
+            unsigned n = 0;
+            HIP_OK(hipMemsetAsync(cur->count, 0, 4, st));
+            if (B.exact_list) HIP_OK(hipMemsetAsync(B.exact_list, 0, 4, st));
+            if ((rc = refill_in_window(pl.cap)) || (rc = read_count(&n))) return rc;
+            if (n == 0) continue;
+            if ((rc = pick_cached_roots(0, (int)n))) return rc;
+            hp.resize(n), hs.resize(n), hk.resize(n), hw.resize(n), hx.assign((size_t)n + kExactHead, 0);
+            HIP_OK(hipMemcpyAsync(hp.data(), cur->pixel, 4ull * n, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(hs.data(), cur->sample, 4ull * n, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(hk.data(), cur->pick, 4ull * n, hipMemcpyDeviceToHost, st));
+            HIP_OK(hipMemcpyAsync(hw.data(), cur->wsum, 8ull * n, hipMemcpyDeviceToHost, st));
+            if (B.exact_list) HIP_OK(hipMemcpyAsync(hx.data(), B.exact_list, 4ull * (n + kExactHead), hipMemcpyDeviceToHost, st));
+            HIP_OK(hipStreamSynchronize(st));
+            auto at = [&](unsigned i) { return (size_t)hp[i] * (size_t)(b - a) + (size_t)(hs[i] - a); };
+            for (unsigned i = 0; i < n; i++) pick[at(i)] = hk[i], wsum[at(i)] = hw[i], flag[at(i)] = 0;
+            for (int j = 0; j < std::min<int>(hx[0], (int)n); j++) flag[at((unsigned)hx[kExactHead + j])] = 1;
+        }
+        return MCPT_OK;
+    }
+
     // room in the slot pool for a generation of n nodes: a shard serves at most ceil(blocks / 32) workgroups of 256
     // nodes per generation
     int grow_slots(unsigned n) {
@@ -5881,9 +6182,49 @@ struct WavefrontRun {
         return prep_timer_stop(D);
     }
 
-    // cur's roots [nc, nc + nr) pick from their pixels' root-cache rows
+    // Whether this run (a, b, active, nminor set) takes its cached roots' picks from the table, and by which window:
+    // a whole-frame run of table roots with at least pick_table_min_samples samples, in windows of as many whole
+    // root groups as the table holds (sample-minor order: the whole run or nothing).
+    void table_begin() {
+        tab = PickTable{};
+        tab_window = 0, tab_end = 0;
+        if (!B.pick_tab || !B.pc.use || B.small_use || pl.ray_roots || active || nminor < 1) return;
+        const int nsamp = b - a, floor_s = pick_table_min_samples(), wdbg = g_pick_window.load();
+        long long w = std::min<long long>(nsamp, B.pick_cap / pl.npx);
+        if (wdbg > 0) w = std::min<long long>(w, wdbg);
+        if (w < nsamp) w = w / nminor * nminor;
+        if (nsamp < floor_s || w < floor_s || w < 1) return;
+        tab_window = (int)w;
+        tab = PickTable{B.pick_tab, B.pick_wsum, 0, a, nsamp, nminor};
+    }
+    // the table of the window that starts at root rnext (a window's first root: a multiple of nminor samples)
+    int table_build() {
+        const int npx = pl.npx, w0 = (int)(rnext / npx), w1 = std::min(w0 + tab_window, b - a);
+        const int group = nminor;
+        const int tile = group >= 32 ? 1 : std::max(1, kPickTileMax / group);
+        int c_len = kPickTabEntries / tile;
+        if (tile > 1) c_len = std::max(group, c_len / group * group);
+        c_len = std::min(c_len, std::max(w1 - w0, 1));
+        if (tile > 1) c_len = (c_len + group - 1) / group * group;
+        tab.base = rnext;
+        tab_end = (long long)w1 * npx;
+        PrepCache pr = B.pc;
+        pr.exact = B.exact_list;
+        const size_t lds = 8ull * (pl.lstride + pl.nchunks + 64) + 2ull * pl.lstride + 2ull * tile * c_len;
+        const bool rr = !(o->mode == MCPT_MODE_SHADE || o->mode == MCPT_MODE_SHADE_AREA);
+        hipLaunchKernelGGL(k_root_pick_table, dim3((npx + tile - 1) / tile, (w1 - w0 + c_len - 1) / c_len), dim3(256), lds, st,
+                           o->seed, rr ? 1 : 0, npx, (const int*)B.rtab.kind, pl.nchunks, pr, tab, tile, w0, c_len, w1);
+        HIP_OK(hipGetLastError());
+        return MCPT_OK;
+    }
+
+    // cur's roots [nc, nc + nr) pick from the run's table, or from their pixels' root-cache rows
     int pick_cached_roots(int nc, int nr) {
-        if (B.small_use) {
+        if (tab_window) {
+            hipLaunchKernelGGL(k_pick_lookup, dim3((nr + 255) / 256), dim3(256), 0, st, nr, pl.npx, cur->pixel + nc,
+                               cur->sample + nc, cur->wsum + nc, cur->pick + nc, tab, B.exact_list, nc);
+            C.table_roots += (uint64_t)nr;
+        } else if (B.small_use) {
             hipLaunchKernelGGL(k_prep_lane_pick, dim3((nr + 255) / 256), dim3(256), 0, st, D.d, o->seed, nr, cur->pixel + nc,
                                cur->sample + nc, cur->node + nc, cur->wsum + nc, cur->pick + nc, nullptr, B.scache);
         } else {
@@ -6052,6 +6393,7 @@ struct WavefrontRun {
         R = (long long)(b - a) * nact;
         nminor = pl.minor_of(b - a);
         rnext = 0;
+        table_begin();
         C.roots_total += (uint64_t)R;
         cur = &B.qa;
         nxt = &B.qb;
@@ -6072,7 +6414,7 @@ struct WavefrontRun {
             if ((rc = balance_spill(&n))) return rc;
             const unsigned n_children = n;  // [0, n_children) children, [n_children, n) fresh roots
             if (rnext < R && n < (unsigned)fill) {
-                if ((rc = refill_roots((int)std::min<long long>((long long)fill - n, R - rnext))) || (rc = read_count(&n))) return rc;
+                if ((rc = refill_in_window((long long)fill - n)) || (rc = read_count(&n))) return rc;
             }
             if (n == 0) {
                 if (rnext >= R && spill_n == 0) break;
@@ -6217,6 +6559,7 @@ int fill_stats(const RenderPlan& p, const Bound& B, DeviceState& D, const Counte
     stats->prep_launches = C.prep_launches;
     stats->prep_exact_nodes = hs[10];
     stats->prep_band_nodes = hs[11];
+    stats->pick_table_roots = C.table_roots;
 #if MCPT_TRACE_DIAG
     if (hs[8])
         fprintf(stderr, "trace diag: %llu visits over %llu wave node-iterations (lane use %.3f), %llu tests over %llu wave "
@@ -6269,6 +6612,31 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
             C.diag_kernel_ms, (double)ms);
 #endif
     return stats ? fill_stats(pl, B, D, C, ms, stats) : MCPT_OK;
+}
+
+// mcpt_debug_root_picks: a render call's setup up to the root caches, then the roots' picks alone
+int root_picks_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt_render_opts* o, int32_t* pick,
+                         double* wsum, int32_t* flag) {
+    RenderPlan pl;
+    Bound B;
+    Counters C;
+    int rc;
+    if ((rc = make_plan(sc, D, cam, o, false, nullptr, &pl)) || (rc = bind_buffers(sc, D, pl, o, false, &B))) return rc;
+    if ((rc = ensure(D.fb, 24ull * pl.npx))) return rc;  // k_roots_t adds the emitter pixels' radiance somewhere
+    const hipStream_t st = D.stream;
+    HIP_OK(hipMemsetAsync(D.stats.p, 0, kStatBytes, st));
+    if (!pl.ray_roots && (rc = launch_primary_tables(D, pl.cf, pl.npx, pl.grid))) return rc;
+    if ((rc = build_root_caches(pl, B, D, o, C))) return rc;
+    if (!B.pc.use) {
+        set_error("mcpt_debug_root_picks: the call has no root-point cache (mode, light count, samples or memory)");
+        return MCPT_E_INVALID;
+    }
+    const size_t n = (size_t)pl.npx * (size_t)(pl.s1 - pl.s0);
+    std::fill(pick, pick + n, -2);
+    std::fill(wsum, wsum + n, 0.0);
+    std::fill(flag, flag + n, 0);
+    WavefrontRun wf(pl, B, C, D, o, (double*)D.fb.p, false);
+    return wf.root_picks(pl.s0, pl.s1, pick, wsum, flag);
 }
 
 // the entry points that take one device only (`what` names the entry point in the message)
@@ -6353,6 +6721,7 @@ void add_stats(mcpt_stats& t, const mcpt_stats& x) {
     t.tri_tests += x.tri_tests;
     t.prep_exact_nodes += x.prep_exact_nodes;
     t.prep_band_nodes += x.prep_band_nodes;
+    t.pick_table_roots += x.pick_table_roots;
     t.cache_build_seconds += x.cache_build_seconds;
 }
 
@@ -7846,6 +8215,30 @@ int mcpt_debug_adaptive_active(mcpt_scene* sc, int32_t device, int32_t* pixels, 
     const int m = std::min<int>(*n, cap);
     if (m > 0) HIP_OK(hipMemcpy(pixels, D->ad_list[D->ad_last_list].p, 4ull * m, hipMemcpyDeviceToHost));
     return MCPT_OK;
+}
+
+int mcpt_debug_set_pick_table(int32_t min_samples, int32_t window_samples) {
+    if (min_samples < 0 || window_samples < 0) {
+        set_error("mcpt_debug_set_pick_table: negative argument");
+        return MCPT_E_INVALID;
+    }
+    g_pick_min_samples.store(min_samples);
+    g_pick_window.store(window_samples);
+    return MCPT_OK;
+}
+
+int mcpt_debug_root_picks(mcpt_scene* sc, const mcpt_camera* cam, const mcpt_render_opts* o, int32_t* pick,
+                          double* weights_sum, int32_t* ambiguous) {
+    if (!sc || !o || !pick || !weights_sum || !ambiguous) {
+        set_error("null argument");
+        return MCPT_E_INVALID;
+    }
+    int rc;
+    if ((rc = check_opts(o)) || (rc = validate_camera(cam)) || (rc = check_single_device(o, "mcpt_debug_root_picks"))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    if ((rc = get_device_state(sc, o->device, &D))) return rc;
+    return root_picks_on_device(sc, *D, cam, o, pick, weights_sum, ambiguous);
 }
 
 int mcpt_scene_meshing(mcpt_scene* sc, const double eye[3], int32_t n0) {
