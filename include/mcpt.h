@@ -45,7 +45,8 @@ extern "C" {
                                * mcpt_sequence_motion_info, the selectors MCPT_SEQ_PREV_POSITION and
                                * MCPT_SEQ_PREV_NORMAL); on-device transforms of facet ranges with a lazily synced
                                * host copy (mcpt_scene_rest_save, mcpt_scene_transform, mcpt_scene_host_pending,
-                               * mcpt_scene_host_sync, mcpt_transform_rotation);
+                               * mcpt_scene_host_sync, mcpt_transform_rotation); an on-device rebuild of the main tree
+                               * (mcpt_rebuild_stats, mcpt_scene_rebuild, mcpt_scene_tree_cost);
                                * mcpt_stats gains pick_table_roots (appended, guarded by stats_size: stats ABI 2.3);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
@@ -303,8 +304,9 @@ int mcpt_scene_camera(const mcpt_scene* scene, mcpt_camera* cam);
  * An update invalidates the host grid (the next MCPT_ACCEL_GRID render or mcpt_scene_meshing call rebuilds it from the
  * new positions; MCPT_HIT_GRID queries need a new mcpt_scene_meshing call) and the opt-in 8-wide debug trees (refused
  * for the handle from its first update on, include/mcpt_debug.h).  Not covered: light triangles, topology or facet
- * count changes, a rebuild when the refit tree's quality degrades.  The temporal accumulation follows moved geometry
- * through the scene's previous pose (mcpt_scene_pose_save below, mcpt_temporal_accumulate_motion). */
+ * count changes.  A refit tree degrades as geometry moves far: mcpt_scene_tree_cost measures it and mcpt_scene_rebuild
+ * (below) replaces it.  The temporal accumulation follows moved geometry through the scene's previous pose
+ * (mcpt_scene_pose_save below, mcpt_temporal_accumulate_motion). */
 typedef struct {
     uint32_t struct_size;       /* sizeof(mcpt_update_stats) of the caller's header (mcpt_update_stats_init sets it) */
     int32_t facets;             /* count of the call */
@@ -386,6 +388,50 @@ int mcpt_scene_host_sync(mcpt_scene* scene);
  * MCPT_E_INVALID: NULL pointer, non-finite input, axis of length 0. */
 int mcpt_transform_rotation(const double axis[3], double degrees, const double pivot[3], const double translate[3],
                             double m[12]);
+
+/* On-device rebuild of the main tree.  Updates and transforms keep the topology of the tree the scene
+ * was created with, so the tree gets worse the further geometry moves.  No reference interface corresponds.
+ *
+ * mcpt_scene_rebuild: on every device state the scene has, the main 4-wide tree -- fp32 nodes, quantised nodes, leaf
+ * triangles and the refit's state -- is replaced by one built on that device from its current facet array: Morton order
+ * of the facet centroids (63-bit codes, a stable radix sort), a top-down build with one launch per level, numbered
+ * breadth-first by scans, one leaf slot per facet, at most 15 node levels for EVERY input (so at most 45 traversal
+ * stack entries, fewer than the kernels hold: many coincident triangles give a balanced tree), boxes and quantised
+ * nodes by the refit's own kernel.  The tree is a pure function of the positions: the same arrays give the same tree
+ * bit for bit.  After a successful call mcpt_scene_update's rule holds word for word: the scene behaves as
+ * mcpt_scene_create of the current arrays would -- hits bit for bit, renders up to the order of the fp64 atomics.
+ *
+ * Untouched: the light-only tree and every light table; the facet arrays, the previous pose and the rest pose; the
+ * host copy, including the host's binary tree, which keeps its topology (it is still a valid refit tree, and a device
+ * state created later is made from it).  The call does not sync the host: mcpt_scene_host_pending is the same before
+ * and after, so a loop of transform, rebuild, frame never waits for the host copy.  It takes the scene's lock and marks
+ * the handle as updated: the 8-wide debug trees are refused afterwards.  With a communicator every rank must make the
+ * same call.  Later updates and transforms refit the new tree.
+ *
+ * With no device state the call returns MCPT_OK with device_states = 0 and changes nothing.  MCPT_E_INVALID, before any
+ * work: a NULL scene, a stats struct_size mismatch.  The new tree is built beside the one in use and checked (its
+ * indices, its traversal-stack need, its leaf codes) before the state's pointers change: should a check fail, that
+ * state keeps its old tree and the call returns MCPT_E_SCENE.  Buffers for the build are allocated at a state's first
+ * rebuild (two sets of tree arrays for nfacets nodes and slots, used in turn) and reused by every later one.
+ *
+ * mcpt_scene_tree_cost: the surface-area cost of the fp32 4-wide tree `device` (-1 = current) holds, a quality number a
+ * caller can base a rebuild policy on.  With A(box) = 2 (dx dy + dy dz + dz dx) of the float planes widened to double
+ * and A0 = A(union of the root's used slots), cost = sum over nodes and used slots k of A(slot k) / A0 * (the slot's
+ * triangle count if it is a leaf, else 1); 0 when A0 == 0.  A used slot is one whose child is not the empty marker.
+ * Reduced on the device in a fixed order (per-block partials, then index order; no floating-point atomics), so two
+ * calls return the same bits.  Creates the device state if needed.  MCPT_E_INVALID: NULL scene or cost. */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(mcpt_rebuild_stats) of the caller's header (mcpt_rebuild_stats_init sets it) */
+    int32_t facets;          /* the scene's facets */
+    int32_t nodes, levels;   /* of the new 4-wide tree (the first device state's) */
+    int32_t stack_need;      /* the most traversal stack entries the new tree can need */
+    int32_t device_states;   /* states rebuilt (0: none existed) */
+    double cost_before, cost_after; /* mcpt_scene_tree_cost of the first state */
+    double device_seconds;   /* HIP events around the first state's build */
+} mcpt_rebuild_stats;
+void mcpt_rebuild_stats_init(mcpt_rebuild_stats* stats);
+int mcpt_scene_rebuild(mcpt_scene* scene, mcpt_rebuild_stats* stats);
+int mcpt_scene_tree_cost(mcpt_scene* scene, int32_t device, double* cost);
 
 /* main.cpp:547-588: render samples [sample_begin, sample_end) of an spp-sample frame and ADD
  * sum_k L_k * (1/spp) into out_rgb (caller-owned host buffer, height*width*3 doubles, row 0 =

@@ -121,6 +121,10 @@ int mcpt_debug_adaptive_active(mcpt_scene* scene, int32_t device, int32_t* pixel
  * root groups), so that a small run rolls over several windows.  For tests and the min_samples A/B. */
 int mcpt_debug_set_pick_table(int32_t min_samples, int32_t window_samples);
 
+/* mcpt_scene_rebuild's leaf size, process-wide: the most facets of a leaf child, 1..4 (0: the library's default, 2).
+ * For the leaf-size measurement of tools/rebuild_bench.py; every value gives a valid tree.  MCPT_E_INVALID otherwise. */
+int mcpt_debug_set_rebuild_leaf_max(int32_t leaf_max);
+
 /* diagnostics: the light pick of every root of a render call with these options (scene, camera, seed, mode, sample
  * range, flags), without tracing anything: pick, weights_sum and ambiguous are [width * height][samples] arrays.  The
  * picks come from the path the render's run would take -- the root pick table and its lookup, or with

@@ -195,6 +195,16 @@ class UpdateStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
+class RebuildStats(C.Structure):
+    """mcpt_rebuild_stats (include/mcpt.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("facets", C.c_int32), ("nodes", C.c_int32), ("levels", C.c_int32),
+                ("stack_need", C.c_int32), ("device_states", C.c_int32), ("cost_before", C.c_double),
+                ("cost_after", C.c_double), ("device_seconds", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
 # mcpt_debug_bvh4_download's node layouts (BvhNode4 / BvhNode4Q of the library; leaf children as ~first slot, count)
 BVH4_NODE = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("child", np.int32, 4), ("count", np.int32, 4)])
 BVH4_QNODE = np.dtype([("org", np.float32, 3), ("ex", np.uint32), ("q", np.uint32, 6), ("pad", np.uint32, 2), ("child", np.int32, 4)])
@@ -221,11 +231,12 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_temporal_accumulate_motion", "mcpt_temporal_accumulate_motion_device", "mcpt_sequence_set_motion",
            "mcpt_sequence_motion_info",
            "mcpt_scene_rest_save", "mcpt_scene_transform", "mcpt_scene_host_pending", "mcpt_scene_host_sync",
-           "mcpt_transform_rotation"]
+           "mcpt_transform_rotation",
+           "mcpt_rebuild_stats_init", "mcpt_scene_rebuild", "mcpt_scene_tree_cost"]
 DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download",
-                 "mcpt_debug_set_pick_table", "mcpt_debug_root_picks"]  # include/mcpt_debug.h
+                 "mcpt_debug_set_pick_table", "mcpt_debug_root_picks", "mcpt_debug_set_rebuild_leaf_max"]  # include/mcpt_debug.h
 
 
 def lib():
@@ -357,6 +368,11 @@ def lib():
             L.mcpt_scene_host_pending.argtypes = [P, C.POINTER(C.c_int64)]
             L.mcpt_scene_host_sync.argtypes = [P]
             L.mcpt_transform_rotation.argtypes = [P, D, P, P, P]
+        if hasattr(L, "mcpt_scene_rebuild"):  # and the on-device rebuild of the main tree
+            L.mcpt_rebuild_stats_init.argtypes = [C.POINTER(RebuildStats)]
+            L.mcpt_rebuild_stats_init.restype = None
+            L.mcpt_scene_rebuild.argtypes = [P, C.POINTER(RebuildStats)]
+            L.mcpt_scene_tree_cost.argtypes = [P, I, C.POINTER(D)]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -372,6 +388,7 @@ def lib():
                "mcpt_debug_adaptive_active": [P, I, ip, I, C.POINTER(I)],
                "mcpt_debug_bvh4_check_device": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
                "mcpt_debug_set_pick_table": [I, I],
+               "mcpt_debug_set_rebuild_leaf_max": [I],
                "mcpt_debug_root_picks": [P, C.POINTER(Camera), C.POINTER(RenderOpts), ip, dp, ip],
                "mcpt_debug_bvh4_download": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C"), P, P, P, C.c_int64, C.c_int64]}
         for name, argt in dbg.items():
@@ -499,6 +516,23 @@ class Scene:
     def host_sync(self):
         """mcpt_scene_host_sync: brings the host copy up to date now (a no-op when nothing is pending)"""
         _check(lib().mcpt_scene_host_sync(self.h))
+
+    def rebuild(self):
+        """mcpt_scene_rebuild: on every device the scene lives on, the main 4-wide tree is replaced by one built there
+        from the current positions (the refit of update() and transform() keeps the topology, so the tree degrades as
+        geometry moves far).  The host copy is neither read nor synced.  Returns the call's mcpt_rebuild_stats as a
+        dict; device_states is 0, and nothing changed, while the scene lives on no device."""
+        st = RebuildStats()
+        lib().mcpt_rebuild_stats_init(C.byref(st))
+        _check(lib().mcpt_scene_rebuild(self.h, C.byref(st)))
+        return st.as_dict()
+
+    def tree_cost(self, device=None):
+        """mcpt_scene_tree_cost: the surface-area cost of the 4-wide tree `device` holds (the header's formula), the
+        number a rebuild policy can watch: it grows as the refit tree degrades and drops at a rebuild."""
+        c = C.c_double(0.0)
+        _check(lib().mcpt_scene_tree_cost(self.h, -1 if device is None else int(device), C.byref(c)))
+        return float(c.value)
 
     def arrays(self):
         F, M, NL = self.nfacets, self.nmaterials, self.nlights
@@ -1412,6 +1446,12 @@ def debug_set_pick_table(min_samples=0, window_samples=0):
     """mcpt_debug_set_pick_table (include/mcpt_debug.h): process-wide overrides of the root pick table's rules,
     0 = the library's default."""
     _check(lib().mcpt_debug_set_pick_table(int(min_samples), int(window_samples)))
+
+
+def debug_set_rebuild_leaf_max(leaf_max=0):
+    """mcpt_debug_set_rebuild_leaf_max (include/mcpt_debug.h): the most facets of a leaf child of Scene.rebuild's trees,
+    1..4, process-wide; 0 = the library's default."""
+    _check(lib().mcpt_debug_set_rebuild_leaf_max(int(leaf_max)))
 
 
 def debug_root_picks(scene, camera, spp, sample_range, mode="mis", seed=DEFAULT_SEED, flags=0, device=None):

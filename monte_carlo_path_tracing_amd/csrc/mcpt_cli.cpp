@@ -57,6 +57,10 @@
 //   the scene's rest pose is saved once before frame 0 (mcpt_scene_rest_save), and before frame k >= 1 the range is set
 //   to the rest pose rotated by k * DEG degrees about the axis (AX, AY, AZ) through (PX, PY, PZ) by mcpt_scene_transform
 //   (evaluated on the device; the host copy is not touched during the loop); the frame prints a "rotated" line.
+//               [--rebuild RATIO]
+//   --rebuild (with --frames N and --move or --rotate) watches the tree the moves degrade: after each frame's move the
+//   tree's cost is read (mcpt_scene_tree_cost), and once it exceeds RATIO (finite, > 1) times the cost at the last build
+//   or rebuild the main tree is rebuilt on the device (mcpt_scene_rebuild) and the frame prints a "rebuilt" line.
 //               [--motion]
 //   --motion (with --frames N, with or without --device-sequence; meant for --move and --rotate) lets the history follow the moved
 //   facets: before each frame's move the scene's pose is saved (mcpt_scene_pose_save), the frame renders the motion AOVs
@@ -244,6 +248,42 @@ struct Rotator {
     }
 };
 
+// --rebuild RATIO (with --frames N and --move or --rotate): after each frame's move the main tree's cost is read
+// (mcpt_scene_tree_cost); once it exceeds RATIO x the cost at the last build or rebuild, the tree is rebuilt on the
+// device (mcpt_scene_rebuild) and one line says so
+struct Rebuilder {
+    double ratio = 0, base = 0;
+    bool have_base = false;
+    bool parse(const char* arg) {
+        char* e = nullptr;
+        ratio = std::strtod(arg, &e);
+        return e != arg && *e == 0 && std::isfinite(ratio) && ratio > 1.0;
+    }
+    int apply(mcpt_scene* scene, int k) {
+        double cost = 0;
+        if (mcpt_scene_tree_cost(scene, -1, &cost) != MCPT_OK) {
+            std::fprintf(stderr, "--rebuild failed: %s\n", mcpt_last_error());
+            return 1;
+        }
+        if (!have_base) {
+            base = cost, have_base = true;
+            return 0;
+        }
+        if (!(cost > ratio * base)) return 0;
+        mcpt_rebuild_stats rs;
+        mcpt_rebuild_stats_init(&rs);
+        if (mcpt_scene_rebuild(scene, &rs) != MCPT_OK) {
+            std::fprintf(stderr, "--rebuild failed: %s\n", mcpt_last_error());
+            return 1;
+        }
+        std::printf("  rebuilt the tree before frame %d: cost %.4g > %g x %.4g, now %.4g; %d nodes on %d levels, stack need %d, %.3f ms "
+                    "device\n", k, rs.cost_before, ratio, base, rs.cost_after, rs.nodes, rs.levels, rs.stack_need,
+                    rs.device_seconds * 1e3);
+        base = rs.cost_after;
+        return 0;
+    }
+};
+
 struct SequenceArgs {
     int frames, spp, mode, flags;
     double orbit;
@@ -253,6 +293,7 @@ struct SequenceArgs {
     Mover* move;  // --move, or null
     bool motion;  // --motion
     Rotator* rotate;  // --rotate, or null
+    Rebuilder* rebuild;  // --rebuild, or null
 };
 
 // --frames: render, accumulate (and filter) frame after frame; the history ping-pongs between two sets of buffers
@@ -311,6 +352,7 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
         }
         if (a.move && a.move->apply(scene, k)) return 1;
         if (a.rotate && a.rotate->apply(scene, k)) return 1;
+        if (a.rebuild && a.rebuild->apply(scene, k)) return 1;
         if (mcpt_camera_orbit(&cam0, k * a.orbit, &cur.cam) != MCPT_OK) {
             std::fprintf(stderr, "%s\n", mcpt_last_error());
             return 1;
@@ -446,7 +488,8 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
             rc = 1;
             break;
         }
-        if ((a.move && a.move->apply(scene, k)) || (a.rotate && a.rotate->apply(scene, k))) {
+        if ((a.move && a.move->apply(scene, k)) || (a.rotate && a.rotate->apply(scene, k)) ||
+            (a.rebuild && a.rebuild->apply(scene, k))) {
             rc = 1;
             break;
         }
@@ -536,6 +579,8 @@ int main(int argc, char** argv) {
     bool move_flag = false, motion_flag = false, rotate_flag = false;
     Mover mover;
     Rotator rotator;
+    bool rebuild_flag = false;
+    Rebuilder rebuilder;
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -617,6 +662,14 @@ int main(int argc, char** argv) {
             }
             rotate_flag = true;
         }
+        else if (!std::strcmp(argv[a], "--rebuild")) {
+            if (!rebuilder.parse(next())) {
+                std::fprintf(stderr, "--rebuild needs RATIO, a finite number > 1 (rebuild once the tree's cost exceeds RATIO x the "
+                                     "cost at the last build), not %s\n", argv[a]);
+                return 2;
+            }
+            rebuild_flag = true;
+        }
         else if (!std::strcmp(argv[a], "--motion")) motion_flag = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
@@ -651,6 +704,11 @@ int main(int argc, char** argv) {
     if (rotate_flag && (frames == 0 || move_flag)) {  // refused before anything is loaded
         std::fprintf(stderr, "--rotate %s\n", frames == 0 ? "rotates facets between the frames of a sequence; add --frames N"
                                                           : "and --move both rewrite their facets from an original pose; give one of them");
+        return 2;
+    }
+    if (rebuild_flag && (frames == 0 || !(move_flag || rotate_flag))) {  // refused before anything is loaded
+        std::fprintf(stderr, "--rebuild rebuilds the tree that moves between the frames of a sequence degrade; add %s\n",
+                     frames == 0 ? "--frames N" : "--move or --rotate");
         return 2;
     }
     if (motion_flag && (frames == 0 || upsample)) {  // refused before anything is loaded
@@ -761,7 +819,8 @@ int main(int argc, char** argv) {
             if (const int rc = rotator.bind(scene)) return rc;
         }
         const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out,
-                              move_flag ? &mover : nullptr, motion_flag, rotate_flag ? &rotator : nullptr};
+                              move_flag ? &mover : nullptr, motion_flag, rotate_flag ? &rotator : nullptr,
+                              rebuild_flag ? &rebuilder : nullptr};
         if (clamp_flag && !history_clamp) {
             std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
             return 2;

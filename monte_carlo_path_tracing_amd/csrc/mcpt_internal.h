@@ -184,6 +184,30 @@ int transform_enqueue(const RefitDev& r, const float* rest_v, const float* rest_
                       const double m[12], const double n[9], const double lo[3], const double hi[3], float* out_pos,
                       float* out_nrm, void* stream);
 
+// k_refit_level alone over every level, deepest first, on the dirty bytes the state holds (r.counters[1] cleared
+// first, the dirty bytes after): the tail of refit_enqueue, and how a rebuilt tree gets its boxes
+int refit_levels_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, double margin, void* stream);
+
+// rebuild.hip -- the device side of mcpt_scene_rebuild and mcpt_scene_tree_cost
+constexpr int kRebuildMaxLevels = 15;  // node levels of a rebuilt tree, for every input
+constexpr int kRebuildLeafMax = 2;     // facets per leaf child (chosen by measurement, §4.22)
+// the builder's scratch for a state of F facets (Morton codes, the sorted order, per-node ranges, rocPRIM's temporary
+// storage): allocated on the current device at a state's first rebuild, reused by every later one
+struct RebuildWork;
+int rebuild_work_create(int32_t F, RebuildWork** out);
+void rebuild_work_destroy(RebuildWork* w);
+// builds a tree over out->tri_v's F facets into out's OTHER arrays (bvh4, bvh4q: F nodes; leaf_v, slot_list,
+// slot_dirty: F slots; slot_start: F + 1; node_dirty: F; counters) on `stream`, boxes by refit_levels_enqueue, and
+// waits for the topology (not for the boxes).  Sets out->nnodes, the first node of every level and the tree's
+// bvh4_stack_need (computed top-down on the device); MCPT_E_SCENE if the tree fails its checks or needs more than
+// stack_cap entries -- nothing but `out`'s arrays and the scratch has been written then
+int rebuild_build(RebuildWork* w, RefitDev* out, int leaf_max, int stack_cap, double margin, void* stream,
+                  std::vector<int32_t>* level_first, int32_t* stack_need);
+// the SAH cost of mcpt_scene_tree_cost of a device's 4-wide nodes: per-block partials, then index order.  words:
+// kTreeCostWords doubles of device scratch; *result points at the cost inside them once `stream` has run
+constexpr size_t kTreeCostWords = 1025;
+int tree_cost_enqueue(const BvhNode4* nodes, int32_t nnodes, double* words, void* stream, double** result);
+
 // grid.cpp -- the reference's uniform grid (Myobj.cpp:78-162) for the MCPT_ACCEL_GRID mode
 struct Grid {
     bool ok = false;

@@ -345,9 +345,18 @@ int refit_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, in
         return MCPT_E_INVALID;
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
-    REFIT_HIP_OK(hipMemsetAsync(r.counters + 1, 0, sizeof(unsigned), st));
     hipLaunchKernelGGL(k_refit_scatter, dim3((count + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, r, first, count,
                        dpos, dnrm);
+    return refit_levels_enqueue(r, level_first, nlevels, margin, stream);
+}
+
+int refit_levels_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, double margin, void* stream) {
+    if (nlevels < 1 || level_first[0] != 0 || level_first[nlevels] != r.nnodes) {
+        set_error("refit: levels do not match the device state");
+        return MCPT_E_INVALID;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    REFIT_HIP_OK(hipMemsetAsync(r.counters + 1, 0, sizeof(unsigned), st));
     for (int l = nlevels - 1; l >= 0; l--) {
         const int n0 = level_first[l], n1 = level_first[l + 1];
         if (n1 <= n0) continue;

@@ -4765,6 +4765,18 @@ struct DeviceState {
     RefitDev refit{};
     std::vector<int32_t> level_first;
     DevBuf up_pos, up_nrm;
+    // mcpt_scene_rebuild on this device: the leaf slots of the main tree the state holds (the host
+    // tree's until the first rebuild, F after it); the builder's scratch; two sets of tree arrays sized for F nodes and
+    // F slots, built into in turn (the tree in use is never the one being written); the identity slot_start, the
+    // counters and the cost reduction's words, shared by both sets.  All allocated at the first rebuild (the words at
+    // the first mcpt_scene_tree_cost) and reused.
+    size_t nslots = 0;
+    RebuildWork* rb_work = nullptr;
+    struct RebuildSet {
+        DevBuf bvh4, bvh4q, leaf_v, slot_list, slot_dirty, node_dirty;
+    } rb_set[2];
+    DevBuf rb_slot_start, rb_counters, cost_words;
+    int rb_next = 0;
     // mcpt_scene_pose_save: the previous pose's copies of d.tri_v / d.tri_n (null until the first save or, for a state
     // created after it, from the host copy: the previous pose is then the current one)
     DevBuf prev_v, prev_n;
@@ -4796,6 +4808,9 @@ struct mcpt_scene {
     bool updated = false;
     BvhRefitIndex refit_ix;
     std::vector<int32_t> slot_start, slot_list;
+    // mcpt_scene_rebuild: nodes and leaf slots of the first rebuilt state's main tree (0: never rebuilt), for
+    // mcpt_scene_accel_bytes
+    uint64_t rebuilt_nodes = 0, rebuilt_slots = 0;
     // mcpt_scene_pose_save: host.pos / host.nrm as they were at the last save (empty until the first one)
     bool pose_saved = false;
     std::vector<float> prev_pos, prev_nrm;
@@ -5205,6 +5220,7 @@ int get_device_state(mcpt_scene* sc, int device, DeviceState** out) {
     if ((rc = pack_leaf_codes(b4)) || (rc = pack_leaf_codes(lb4))) return rc;
     d.nbvh4 = (int)b4.size();
     d.nlbvh4 = (int)lb4.size();
+    D->nslots = sc->bvh.leaf_facets.size();
     if ((rc = upload(*D, b4, &d.bvh4))) return rc;
     if ((rc = upload(*D, lb4, &d.lbvh4))) return rc;
     if ((rc = upload(*D, quantize_bvh4(b4), &d.bvh4q))) return rc;
@@ -5612,6 +5628,8 @@ struct AdaptiveRun {
     double* noise;
 };
 
+// mcpt_debug_set_rebuild_leaf_max: process-wide override of the rebuild's leaf size (0: kRebuildLeafMax)
+std::atomic<int> g_rebuild_leaf_max{0};
 // mcpt_debug_set_pick_table: process-wide overrides of the root pick table's rules (0: the default)
 std::atomic<int> g_pick_min_samples{0}, g_pick_window{0};
 // the fewest samples per pixel of a run (and of its windows) at which the table is built: a table pass stages a
@@ -5685,7 +5703,7 @@ int make_plan(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt
     // pixel.  samples_per_launch (if set) sets target = samples_per_launch * npx.
     const long long R = (long long)(p.s1 - p.s0) * p.npx;
     p.accel = (uint64_t)(D.d.nbvh4 + D.d.nlbvh4) * sizeof(BvhNode4) +
-              (uint64_t)(sc->bvh.leaf_facets.size() + sc->lbvh.leaf_facets.size()) * 3 * sizeof(float4);
+              (uint64_t)(D.nslots + sc->lbvh.leaf_facets.size()) * 3 * sizeof(float4);
     p.qf = o->queue_factor > 0 ? o->queue_factor : 2;
     p.nchunks = prep_chunks(D.d.NL);
     p.lstride = 64 * p.nchunks;
@@ -7275,7 +7293,10 @@ void mcpt_scene_destroy(mcpt_scene* sc) {
                                      &D->sc_cum, &D->sc_wsum, &D->sc_last, &D->cull_keys, &D->cull_order, &D->cull_count,
                                      &D->ad_acc[0], &D->ad_acc[1], &D->ad_list[0], &D->ad_list[1], &D->ad_state[0],
                                      &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise, &D->aov, &D->up_pos, &D->up_nrm,
-                                     &D->prev_v, &D->prev_n, &D->rest_v, &D->rest_n};
+                                     &D->prev_v, &D->prev_n, &D->rest_v, &D->rest_n, &D->rb_slot_start, &D->rb_counters,
+                                     &D->cost_words};
+        for (auto& rs : D->rb_set) bufs.insert(bufs.end(), {&rs.bvh4, &rs.bvh4q, &rs.leaf_v, &rs.slot_list, &rs.slot_dirty, &rs.node_dirty});
+        rebuild_work_destroy(D->rb_work);
         for (int k = 0; k < 14; k++) bufs.insert(bufs.end(), {&D->qa[k], &D->qb[k], &D->qs[k]});
         for (int k = 0; k < 9; k++) bufs.push_back(&D->aux[k]);
         for (int k = 0; k < 13; k++) bufs.push_back(&D->sl[k]);
@@ -7293,9 +7314,11 @@ void mcpt_scene_destroy(mcpt_scene* sc) {
 int mcpt_scene_accel_bytes(const mcpt_scene* sc, uint64_t* bytes) {
     if (!sc || !bytes) return MCPT_E_INVALID;
     // 4-wide nodes (128 B) of both BVHs plus their leaf triangles (3 float4 = 48 B)
+    // (after mcpt_scene_rebuild the main tree is the first rebuilt state's)
     auto nodes4 = [](const Bvh& b) { return (uint64_t)collapse_bvh4(b).size(); };
-    *bytes = (nodes4(sc->bvh) + nodes4(sc->lbvh)) * sizeof(BvhNode4) +
-             (uint64_t)(sc->bvh.leaf_facets.size() + sc->lbvh.leaf_facets.size()) * 3 * sizeof(float4);
+    const uint64_t main_nodes = sc->rebuilt_nodes ? sc->rebuilt_nodes : nodes4(sc->bvh);
+    const uint64_t main_slots = sc->rebuilt_nodes ? sc->rebuilt_slots : sc->bvh.leaf_facets.size();
+    *bytes = (main_nodes + nodes4(sc->lbvh)) * sizeof(BvhNode4) + (main_slots + sc->lbvh.leaf_facets.size()) * 3 * sizeof(float4);
     return MCPT_OK;
 }
 
@@ -7389,7 +7412,7 @@ static int update_check_values(const mcpt_scene* sc, int32_t first, int32_t coun
 static int ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
     if (D.refit_ready) return MCPT_OK;
     const DScene& d = D.d;
-    const size_t nslots = sc->bvh.leaf_facets.size();
+    const size_t nslots = D.nslots;
     std::vector<BvhNode4> b4(d.nbvh4);
     HIP_OK(hipMemcpy(b4.data(), d.bvh4, b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
     std::vector<int32_t> lf{0, 1};
@@ -7751,6 +7774,129 @@ int mcpt_scene_host_sync(mcpt_scene* sc) {
     }
     std::lock_guard<std::mutex> lk(sc->mu);
     return host_sync(sc);
+}
+
+// ---- mcpt_scene_rebuild and mcpt_scene_tree_cost (include/mcpt.h; the kernels are rebuild.hip's) ----
+void mcpt_rebuild_stats_init(mcpt_rebuild_stats* st) {
+    if (!st) return;
+    std::memset((void*)st, 0, sizeof *st);
+    st->struct_size = sizeof *st;
+}
+
+// the cost of the main tree `D` holds, on its stream (the current device is D's)
+static int tree_cost_of(DeviceState& D, double* cost) {
+    int rc;
+    if ((rc = ensure(D.cost_words, kTreeCostWords * sizeof(double)))) return rc;
+    double* res = nullptr;
+    if ((rc = tree_cost_enqueue(D.d.bvh4, D.d.nbvh4, (double*)D.cost_words.p, D.stream, &res))) return rc;
+    HIP_OK(hipMemcpyAsync(cost, res, sizeof(double), hipMemcpyDeviceToHost, D.stream));
+    HIP_OK(hipStreamSynchronize(D.stream));
+    return MCPT_OK;
+}
+
+// one device state (the current device is D's): the new tree is built into the set of arrays the state is not using,
+// checked, and only then do the state's pointers change -- together
+static int rebuild_state(mcpt_scene* sc, DeviceState& D, mcpt_rebuild_stats* st) {
+    const size_t F = (size_t)D.d.F;
+    int rc;
+    if (!D.rb_work && (rc = rebuild_work_create(D.d.F, &D.rb_work))) return rc;
+    for (DeviceState::RebuildSet& B : D.rb_set)  // both sets at the first rebuild: nothing grows from call to call
+        if ((rc = ensure(B.bvh4, F * sizeof(BvhNode4))) || (rc = ensure(B.bvh4q, F * sizeof(BvhNode4Q))) ||
+            (rc = ensure(B.leaf_v, 3 * F * sizeof(float4))) || (rc = ensure(B.slot_list, F * sizeof(int32_t))) ||
+            (rc = ensure(B.slot_dirty, F)) || (rc = ensure(B.node_dirty, F)))
+            return rc;
+    if ((rc = ensure(D.rb_slot_start, (F + 1) * sizeof(int32_t))) || (rc = ensure(D.rb_counters, 16 * sizeof(unsigned)))) return rc;
+    DeviceState::RebuildSet& S = D.rb_set[D.rb_next];
+    RefitDev r{};
+    r.F = r.nslots = D.d.F;
+    r.tri_v = const_cast<float*>(reinterpret_cast<const float*>(D.d.tri_v));
+    r.tri_n = const_cast<float*>(D.d.tri_n);
+    r.leaf_v = (float*)S.leaf_v.p;
+    r.bvh4 = (BvhNode4*)S.bvh4.p;
+    r.bvh4q = (BvhNode4Q*)S.bvh4q.p;
+    r.slot_start = (const int32_t*)D.rb_slot_start.p;
+    r.slot_list = (const int32_t*)S.slot_list.p;
+    r.slot_dirty = (uint8_t*)S.slot_dirty.p;
+    r.node_dirty = (uint8_t*)S.node_dirty.p;
+    r.counters = (unsigned*)D.rb_counters.p;
+    // work of other streams (the caller's, a frame sequence's) that still reads the arrays of the set built two
+    // rebuilds ago, or writes tri_v
+    HIP_OK(hipDeviceSynchronize());
+    if (st && (rc = tree_cost_of(D, &st->cost_before))) return rc;
+    std::vector<int32_t> lf;
+    int32_t need = 0;
+    HIP_OK(hipEventRecord(D.ev0, D.stream));
+    const int leaf_max = g_rebuild_leaf_max.load() ? g_rebuild_leaf_max.load() : kRebuildLeafMax;
+    if ((rc = rebuild_build(D.rb_work, &r, leaf_max, kStack, sc->margin, D.stream, &lf, &need))) {
+        (void)hipStreamSynchronize(D.stream);
+        return rc;
+    }
+    HIP_OK(hipEventRecord(D.ev1, D.stream));
+    HIP_OK(hipStreamSynchronize(D.stream));
+    D.d.bvh4 = r.bvh4;
+    D.d.bvh4q = r.bvh4q;
+    D.d.leaf_v = reinterpret_cast<const float4*>(r.leaf_v);
+    D.d.nbvh4 = r.nnodes;
+    D.nslots = F;
+    D.refit = r;
+    D.level_first = std::move(lf);
+    D.refit_ready = true;
+    D.rb_next ^= 1;
+    if (st) {
+        float ms = 0;
+        HIP_OK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
+        st->device_seconds = 1e-3 * ms;
+        st->nodes = r.nnodes;
+        st->levels = (int32_t)D.level_first.size() - 1;
+        st->stack_need = need;
+        if ((rc = tree_cost_of(D, &st->cost_after))) return rc;
+        sc->rebuilt_nodes = (uint64_t)r.nnodes;
+        sc->rebuilt_slots = F;
+    }
+    return MCPT_OK;
+}
+
+int mcpt_scene_rebuild(mcpt_scene* sc, mcpt_rebuild_stats* stats) {
+    if (!sc) {
+        set_error("mcpt_scene_rebuild: NULL scene");
+        return MCPT_E_INVALID;
+    }
+    if (stats && stats->struct_size != sizeof(mcpt_rebuild_stats)) {
+        set_error("mcpt_rebuild_stats.struct_size %u does not match this library's %zu (header / library version mismatch)",
+                  stats->struct_size, sizeof(mcpt_rebuild_stats));
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    mcpt_rebuild_stats st;
+    mcpt_rebuild_stats_init(&st);
+    st.facets = sc->host.F;
+    const std::vector<DeviceState*> devs = device_states(sc);
+    if (!devs.empty() && sc->host.F > 0) {
+        DeviceRestore back;
+        HIP_OK(hipGetDevice(&back.device));
+        for (DeviceState* D : devs) {
+            HIP_OK(hipSetDevice(D->device));
+            if (int rc = rebuild_state(sc, *D, st.device_states == 0 ? &st : nullptr)) return rc;
+            st.device_states++;
+            sc->updated = true;  // the 8-wide trees keep the host tree's topology: refused from here on (bvh8_refused)
+        }
+    }
+    if (stats) *stats = st;
+    return MCPT_OK;
+}
+
+int mcpt_scene_tree_cost(mcpt_scene* sc, int32_t device, double* cost) {
+    if (!sc || !cost) {
+        set_error("mcpt_scene_tree_cost: NULL %s", !sc ? "scene" : "cost");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceRestore back;
+    HIP_OK(hipGetDevice(&back.device));
+    DeviceState* D;
+    int rc;
+    if ((rc = get_device_state(sc, device, &D))) return rc;
+    return tree_cost_of(*D, cost);
 }
 
 int mcpt_scene_camera(const mcpt_scene* sc, mcpt_camera* cam) {
@@ -8217,6 +8363,15 @@ int mcpt_debug_adaptive_active(mcpt_scene* sc, int32_t device, int32_t* pixels, 
     return MCPT_OK;
 }
 
+int mcpt_debug_set_rebuild_leaf_max(int32_t leaf_max) {
+    if (leaf_max < 0 || leaf_max > 4) {
+        set_error("mcpt_debug_set_rebuild_leaf_max: %d is not 0 (the default) or a leaf size in 1..4", leaf_max);
+        return MCPT_E_INVALID;
+    }
+    g_rebuild_leaf_max.store(leaf_max);
+    return MCPT_OK;
+}
+
 int mcpt_debug_set_pick_table(int32_t min_samples, int32_t window_samples) {
     if (min_samples < 0 || window_samples < 0) {
         set_error("mcpt_debug_set_pick_table: negative argument");
@@ -8497,7 +8652,7 @@ static int download_tree(mcpt_scene* sc, int32_t device, bool vertices, DeviceTr
     if ((rc = get_device_state(sc, device, &D))) return rc;
     HIP_OK(hipDeviceSynchronize());
     const DScene& d = D->d;
-    const size_t nslots = sc->bvh.leaf_facets.size();
+    const size_t nslots = D->nslots;
     t->b4.resize(d.nbvh4);
     t->q4.resize(d.nbvh4);
     t->leaf_v.resize(3 * nslots);
