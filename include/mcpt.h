@@ -46,7 +46,9 @@ extern "C" {
                                * MCPT_SEQ_PREV_NORMAL); on-device transforms of facet ranges with a lazily synced
                                * host copy (mcpt_scene_rest_save, mcpt_scene_transform, mcpt_scene_host_pending,
                                * mcpt_scene_host_sync, mcpt_transform_rotation); an on-device rebuild of the main tree
-                               * (mcpt_rebuild_stats, mcpt_scene_rebuild, mcpt_scene_tree_cost);
+                               * (mcpt_rebuild_stats, mcpt_scene_rebuild, mcpt_scene_tree_cost); movable light
+                               * triangles (mcpt_scene_set_lights_movable, mcpt_scene_lights_movable,
+                               * mcpt_light_update_stats, mcpt_scene_light_update_info);
                                * mcpt_stats gains pick_table_roots (appended, guarded by stats_size: stats ABI 2.3);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
@@ -298,13 +300,14 @@ int mcpt_scene_camera(const mcpt_scene* scene, mcpt_camera* cam);
  *
  * Refused with MCPT_E_INVALID and a message, before anything on the host or on any device is modified: a NULL scene
  * or NULL positions; count < 1, first < 0 or first + count > nfacets; a stats struct_size mismatch; a facet of the
- * range that is a light triangle (lights cannot move: the first such facet is named); a non-finite position or normal;
+ * range that is a light triangle (lights cannot move unless mcpt_scene_set_lights_movable, below, switched them to
+ * movable for this handle: the first such facet is named); a non-finite position or normal;
  * a position outside the arena; in the device form a pointer that is not device memory on `device`.
  *
  * An update invalidates the host grid (the next MCPT_ACCEL_GRID render or mcpt_scene_meshing call rebuilds it from the
  * new positions; MCPT_HIT_GRID queries need a new mcpt_scene_meshing call) and the opt-in 8-wide debug trees (refused
- * for the handle from its first update on, include/mcpt_debug.h).  Not covered: light triangles, topology or facet
- * count changes.  A refit tree degrades as geometry moves far: mcpt_scene_tree_cost measures it and mcpt_scene_rebuild
+ * for the handle from its first update on, include/mcpt_debug.h).  Not covered: light triangles (unless switched to movable), topology or
+ * facet count changes.  A refit tree degrades as geometry moves far: mcpt_scene_tree_cost measures it and mcpt_scene_rebuild
  * (below) replaces it.  The temporal accumulation follows moved geometry through the scene's previous pose
  * (mcpt_scene_pose_save below, mcpt_temporal_accumulate_motion). */
 typedef struct {
@@ -432,6 +435,47 @@ typedef struct {
 void mcpt_rebuild_stats_init(mcpt_rebuild_stats* stats);
 int mcpt_scene_rebuild(mcpt_scene* scene, mcpt_rebuild_stats* stats);
 int mcpt_scene_tree_cost(mcpt_scene* scene, int32_t device, double* cost);
+
+/* Movable light triangles.  A per-handle switch, default 0.  While on, mcpt_scene_update[_device] and
+ * mcpt_scene_transform accept ranges that contain light triangles; everything else about those calls is unchanged.
+ * mcpt_scene_update's rule then holds word for word with light facets included: after a successful call the scene
+ * behaves as mcpt_scene_create of the new arrays would -- mcpt_closest_hit (with and without MCPT_HIT_LIGHT_ONLY) and
+ * mcpt_primary_hits bit for bit, mcpt_light_prep's weights_sum, count and pick bit for bit, renders in every mode up to
+ * the order of the fp64 atomics, mcpt_scene_arrays with the new positions and normals and unique normals recomputed as
+ * at load time.  The light table's order, radiances, groups and light_facet do not change, nor do the facet count and
+ * which facets are lights: only the geometry does.  On every device state the light tables (vertices, normals, the
+ * packed and fp32 records, the pair records, the chunk spheres and (S, K), the band constants, the areas and their
+ * running sums) are derived again on the device from the scattered vertices, by the load-time formulas, and the
+ * light-only tree is refit in place with the main scene's box margin; the host copy follows as for any facet
+ * (at once for mcpt_scene_update, at the next sync for a transform on a scene with device states).
+ *
+ * Additional refusal while on (MCPT_E_INVALID, before anything on the host or on any device is modified): a light
+ * triangle whose new vertices a, b, c give |(b - a) x (c - a)| == 0 or non-finite in fp64 (its unique normal would not
+ * be finite).  mcpt_scene_update names the first such facet; the device form and mcpt_scene_transform count the
+ * offenders into the same word as the other value checks.  The arena is the scene's, unchanged.  Switching off later
+ * only restores the refusals.  Light facets are ordinary rows of the previous pose, so mcpt_scene_pose_save and the
+ * motion AOVs follow a directly visible light; the shading that changes under a moved light is the history clamp's
+ * case.  mcpt_scene_rebuild still leaves the light-only tree alone: it keeps its build topology and is only refit.
+ *
+ * mcpt_scene_set_lights_movable takes the scene's lock; with a communicator every rank must make the same call.
+ * MCPT_E_INVALID: a NULL scene (or a NULL `on` of the getter).
+ * mcpt_scene_light_update_info: the numbers of the LAST successful update / transform call on this handle (all zero
+ * before the first, and `lights` 0 for a call whose range held no light).  MCPT_E_INVALID: NULL scene or out, a
+ * struct_size mismatch. */
+int mcpt_scene_set_lights_movable(mcpt_scene* scene, int32_t on);
+int mcpt_scene_lights_movable(const mcpt_scene* scene, int32_t* on);
+typedef struct {
+    uint32_t struct_size;      /* sizeof(mcpt_light_update_stats) of the caller's header (the _init sets it) */
+    int32_t lights;            /* light triangles in the last update / transform call's range (0: none) */
+    int32_t chunks;            /* 64-light chunks whose sphere and (S, K) were recomputed */
+    int32_t groups;            /* <light> groups whose running area sums were recomputed */
+    int64_t light_nodes_refit; /* nodes of the light-only 4-wide tree with a recomputed slot box (first state) */
+    int32_t light_levels;
+    double device_seconds;     /* HIP events around the light stage of the first device state (in addition to
+                                * mcpt_update_stats.device_seconds, which keeps its meaning) */
+} mcpt_light_update_stats;
+void mcpt_light_update_stats_init(mcpt_light_update_stats* stats);
+int mcpt_scene_light_update_info(const mcpt_scene* scene, mcpt_light_update_stats* out);
 
 /* main.cpp:547-588: render samples [sample_begin, sample_end) of an spp-sample frame and ADD
  * sum_k L_k * (1/spp) into out_rgb (caller-owned host buffer, height*width*3 doubles, row 0 =

@@ -108,6 +108,20 @@ int mcpt_debug_bvh4_check_device(mcpt_scene* scene, int32_t device, int64_t out[
 // than the tree has is MCPT_E_INVALID).  Lets a test compare the nodes before and after an update.
 int mcpt_debug_bvh4_download(mcpt_scene* scene, int32_t device, int64_t counts[2], void* nodes, void* qnodes,
                              int32_t* leaf_facets, int64_t cap_nodes, int64_t cap_slots);
+// mcpt_debug_bvh4_check_device's walk over the LIGHT-ONLY tree `device` holds (its nodes, quantized nodes and leaf
+// slots against the host positions; a leaf slot's vertices that differ from the host's count as errors).  The check of
+// the light tree's device-side refit (mcpt_scene_set_lights_movable, include/mcpt.h).
+int mcpt_debug_bvh4_check_device_light(mcpt_scene* scene, int32_t device, int64_t out[6]);
+// Downloads one light table of the state `device` (-1 = current) holds, as raw bytes: which = "lt_v", "lt_n", "lt_pk",
+// "lt_d", "lt_w", "lt_f", "lt_pair", "chunk_sph", "chunk_sk", "l_area", "l_area_cum" (each in the size the state
+// allocated, padding and sentinel records included) or "globals" (light_bound and the band constants the state passes
+// to its kernels by value: 6 doubles band_ctr[3], band_R, band_S, band_K, then the float light_bound and 4 zero
+// bytes).  *bytes = the table's size; out may be NULL (size query), else cap >= *bytes or MCPT_E_INVALID.  Creates the
+// device state if needed.  Lets a test compare an updated state against a fresh one byte for byte.
+int mcpt_debug_light_tables(mcpt_scene* scene, int32_t device, const char* which, void* out, int64_t cap, int64_t* bytes);
+// k_light_area_cum alone over every group of the state `device` holds, `reps` times between two HIP events (the
+// running sums are rewritten with the same values); *seconds = the time of one run.  tools/light_update_bench.py.
+int mcpt_debug_light_area_cum_bench(mcpt_scene* scene, int32_t device, int32_t reps, double* seconds);
 /* After a scene's first mcpt_scene_update the 8-wide trees are stale: MCPT_DEBUG_RAYS_CW8, MCPT_DEBUG_HIT_CW8 and
  * mcpt_debug_bvh8_check are refused for that handle (MCPT_E_INVALID). */
 

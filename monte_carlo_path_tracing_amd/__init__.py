@@ -205,6 +205,15 @@ class RebuildStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
+class LightUpdateStats(C.Structure):
+    """mcpt_light_update_stats (include/mcpt.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("lights", C.c_int32), ("chunks", C.c_int32), ("groups", C.c_int32),
+                ("light_nodes_refit", C.c_int64), ("light_levels", C.c_int32), ("device_seconds", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
 # mcpt_debug_bvh4_download's node layouts (BvhNode4 / BvhNode4Q of the library; leaf children as ~first slot, count)
 BVH4_NODE = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("child", np.int32, 4), ("count", np.int32, 4)])
 BVH4_QNODE = np.dtype([("org", np.float32, 3), ("ex", np.uint32), ("q", np.uint32, 6), ("pad", np.uint32, 2), ("child", np.int32, 4)])
@@ -232,8 +241,10 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_sequence_motion_info",
            "mcpt_scene_rest_save", "mcpt_scene_transform", "mcpt_scene_host_pending", "mcpt_scene_host_sync",
            "mcpt_transform_rotation",
-           "mcpt_rebuild_stats_init", "mcpt_scene_rebuild", "mcpt_scene_tree_cost"]
-DEBUG_EXPORTS = ["mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
+           "mcpt_rebuild_stats_init", "mcpt_scene_rebuild", "mcpt_scene_tree_cost",
+           "mcpt_scene_set_lights_movable", "mcpt_scene_lights_movable", "mcpt_light_update_stats_init",
+           "mcpt_scene_light_update_info"]
+DEBUG_EXPORTS = ["mcpt_debug_bvh4_check_device_light", "mcpt_debug_light_tables", "mcpt_debug_light_area_cum_bench","mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download",
                  "mcpt_debug_set_pick_table", "mcpt_debug_root_picks", "mcpt_debug_set_rebuild_leaf_max"]  # include/mcpt_debug.h
@@ -373,6 +384,12 @@ def lib():
             L.mcpt_rebuild_stats_init.restype = None
             L.mcpt_scene_rebuild.argtypes = [P, C.POINTER(RebuildStats)]
             L.mcpt_scene_tree_cost.argtypes = [P, I, C.POINTER(D)]
+        if hasattr(L, "mcpt_scene_set_lights_movable"):  # and the movable light triangles
+            L.mcpt_scene_set_lights_movable.argtypes = [P, I]
+            L.mcpt_scene_lights_movable.argtypes = [P, C.POINTER(I)]
+            L.mcpt_light_update_stats_init.argtypes = [C.POINTER(LightUpdateStats)]
+            L.mcpt_light_update_stats_init.restype = None
+            L.mcpt_scene_light_update_info.argtypes = [P, C.POINTER(LightUpdateStats)]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -390,7 +407,10 @@ def lib():
                "mcpt_debug_set_pick_table": [I, I],
                "mcpt_debug_set_rebuild_leaf_max": [I],
                "mcpt_debug_root_picks": [P, C.POINTER(Camera), C.POINTER(RenderOpts), ip, dp, ip],
-               "mcpt_debug_bvh4_download": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C"), P, P, P, C.c_int64, C.c_int64]}
+               "mcpt_debug_bvh4_download": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C"), P, P, P, C.c_int64, C.c_int64],
+               "mcpt_debug_bvh4_check_device_light": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
+               "mcpt_debug_light_tables": [P, I, C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64)],
+               "mcpt_debug_light_area_cum_bench": [P, I, I, C.POINTER(D)]}
         for name, argt in dbg.items():
             if hasattr(L, name):
                 getattr(L, name).argtypes = argt
@@ -462,7 +482,7 @@ class Scene:
     def update(self, first, positions, normals=None):
         """mcpt_scene_update: facets [first, first + len(positions)) get new vertex positions (n x 9 floats) and,
         unless normals is None, new vertex normals; the BVH is refit in place on the host and on every device the
-        scene lives on.  Light triangles cannot move.  Returns the call's mcpt_update_stats as a dict."""
+        scene lives on.  Light triangles cannot move unless set_lights_movable() switched them to movable.  Returns the call's mcpt_update_stats as a dict."""
         pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 9)
         nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 9)
         if nrm is not None and nrm.shape != pos.shape:
@@ -480,6 +500,27 @@ class Scene:
         _check(lib().mcpt_scene_update_device(self.h, -1 if device is None else int(device), int(first), int(count),
                                               C.c_void_p(positions_ptr), C.c_void_p(normals_ptr) if normals_ptr else None,
                                               C.byref(st)))
+        return st.as_dict()
+
+    def set_lights_movable(self, on=True):
+        """mcpt_scene_set_lights_movable: while on, update(), update_device() and transform() accept ranges that
+        contain light triangles; the light tables and the light-only tree follow on every device, and the scene
+        behaves as Scene.create of the new arrays would.  Off (the default) restores the refusals."""
+        _check(lib().mcpt_scene_set_lights_movable(self.h, 1 if on else 0))
+
+    @property
+    def lights_movable(self):
+        """mcpt_scene_lights_movable: the switch"""
+        on = C.c_int32(0)
+        _check(lib().mcpt_scene_lights_movable(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def light_update_info(self):
+        """mcpt_scene_light_update_info: the light stage's numbers of the last successful update / transform call as a
+        dict (lights, chunks, groups, light_nodes_refit, light_levels, device_seconds)."""
+        st = LightUpdateStats()
+        lib().mcpt_light_update_stats_init(C.byref(st))
+        _check(lib().mcpt_scene_light_update_info(self.h, C.byref(st)))
         return st.as_dict()
 
     def pose_save(self):
@@ -1527,6 +1568,38 @@ def debug_bvh4_check_device(scene, device=-1):
     out = np.zeros(6, np.int64)
     _check(lib().mcpt_debug_bvh4_check_device(scene.h, int(device), out))
     return dict(zip(("nodes", "tris", "facets", "duplicates", "errors", "depth"), (int(v) for v in out)))
+
+
+def debug_bvh4_check_device_light(scene, device=-1):
+    """Diagnostics: debug_bvh4_check_device's walk over the light-only tree `device` holds (include/mcpt_debug.h)."""
+    out = np.zeros(6, np.int64)
+    _check(lib().mcpt_debug_bvh4_check_device_light(scene.h, int(device), out))
+    return dict(zip(("nodes", "tris", "facets", "duplicates", "errors", "depth"), (int(v) for v in out)))
+
+
+LIGHT_TABLES = ("lt_v", "lt_n", "lt_pk", "lt_d", "lt_w", "lt_f", "lt_pair", "chunk_sph", "chunk_sk", "l_area", "l_area_cum",
+                "globals")
+
+
+def debug_light_tables(scene, which=None, device=-1):
+    """Diagnostics: one light table of the state `device` holds as raw bytes (np.uint8), or with which=None a dict of
+    all of LIGHT_TABLES (include/mcpt_debug.h).  "globals": band_ctr[3], band_R, band_S, band_K (float64), then
+    light_bound (float32) and 4 zero bytes."""
+    if which is None:
+        return {w: debug_light_tables(scene, w, device) for w in LIGHT_TABLES}
+    n = C.c_int64(0)
+    _check(lib().mcpt_debug_light_tables(scene.h, int(device), which.encode(), None, 0, C.byref(n)))
+    out = np.zeros(max(int(n.value), 1), np.uint8)
+    _check(lib().mcpt_debug_light_tables(scene.h, int(device), which.encode(), out.ctypes.data_as(C.c_void_p), out.shape[0],
+                                         C.byref(n)))
+    return out[:int(n.value)]
+
+
+def debug_light_area_cum_bench(scene, reps=20, device=-1):
+    """Diagnostics: seconds of one run of the area-sum kernel over every group (include/mcpt_debug.h)."""
+    s = C.c_double(0.0)
+    _check(lib().mcpt_debug_light_area_cum_bench(scene.h, int(device), int(reps), C.byref(s)))
+    return float(s.value)
 
 
 def debug_bvh4_download(scene, device=-1):

@@ -64,6 +64,38 @@ int64_t host_refresh_ranges(HostScene& s, Bvh& b, const BvhRefitIndex& ix, const
     return static_cast<int64_t>(slots.size());
 }
 
+int64_t host_refresh_lights(HostScene& s, Bvh& lb, const BvhRefitIndex& ix, const std::vector<int32_t>& slot_start,
+                            const std::vector<int32_t>& slot_list, const PendingRanges& ranges, double margin) {
+    std::vector<int32_t> slots;
+    int64_t lights = 0;
+    for (const auto& p : ranges.r) {
+        for (int f = p.first; f < p.second; f++)
+            if (s.light_of[f] >= 0) {
+                s.light_area[s.light_of[f]] = light_triangle_area(s, f);
+                lights++;
+            }
+        slots.insert(slots.end(), slot_list.begin() + slot_start[p.first], slot_list.begin() + slot_start[p.second]);
+    }
+    if (!slots.empty()) refit_bvh(lb, ix, s, slots, margin);
+    return lights;
+}
+
+int first_degenerate_light(const HostScene& s, int32_t first, int32_t count, const float* pos) {
+    for (int32_t i = 0; i < count; i++) {
+        if (s.light_of[first + i] < 0) continue;
+        const float* p = pos + 9 * static_cast<size_t>(i);
+        double ba[3], ca[3];
+        for (int q = 0; q < 3; q++) {
+            ba[q] = static_cast<double>(p[3 + q]) - static_cast<double>(p[q]);
+            ca[q] = static_cast<double>(p[6 + q]) - static_cast<double>(p[q]);
+        }
+        const double n[3] = {ba[1] * ca[2] - ba[2] * ca[1], ba[2] * ca[0] - ba[0] * ca[2], ba[0] * ca[1] - ba[1] * ca[0]};
+        const double l = std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        if (!(l > 0) || !std::isfinite(l)) return first + i;
+    }
+    return -1;
+}
+
 }  // namespace mcpt
 
 extern "C" int mcpt_transform_rotation(const double axis[3], double degrees, const double pivot[3], const double translate[3],

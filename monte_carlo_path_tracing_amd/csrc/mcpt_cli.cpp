@@ -57,6 +57,10 @@
 //   the scene's rest pose is saved once before frame 0 (mcpt_scene_rest_save), and before frame k >= 1 the range is set
 //   to the rest pose rotated by k * DEG degrees about the axis (AX, AY, AZ) through (PX, PY, PZ) by mcpt_scene_transform
 //   (evaluated on the device; the host copy is not touched during the loop); the frame prints a "rotated" line.
+//               [--lights-movable]
+//   --lights-movable (with --frames N and --move or --rotate) switches the scene's light triangles to movable before
+//   frame 0 (mcpt_scene_set_lights_movable), so a range with light triangles is moved like any other: the light tables
+//   and the light-only tree follow on the device.
 //               [--rebuild RATIO]
 //   --rebuild (with --frames N and --move or --rotate) watches the tree the moves degrade: after each frame's move the
 //   tree's cost is read (mcpt_scene_tree_cost), and once it exceeds RATIO (finite, > 1) times the cost at the last build
@@ -576,7 +580,7 @@ int main(int argc, char** argv) {
     bool upsample = false, temporal_upsample = false;
     mcpt_upsample_opts up;
     mcpt_upsample_opts_init(&up);
-    bool move_flag = false, motion_flag = false, rotate_flag = false;
+    bool move_flag = false, motion_flag = false, rotate_flag = false, lights_movable_flag = false;
     Mover mover;
     Rotator rotator;
     bool rebuild_flag = false;
@@ -671,6 +675,7 @@ int main(int argc, char** argv) {
             rebuild_flag = true;
         }
         else if (!std::strcmp(argv[a], "--motion")) motion_flag = true;
+        else if (!std::strcmp(argv[a], "--lights-movable")) lights_movable_flag = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
                 char* e = nullptr;
@@ -708,6 +713,11 @@ int main(int argc, char** argv) {
     }
     if (rebuild_flag && (frames == 0 || !(move_flag || rotate_flag))) {  // refused before anything is loaded
         std::fprintf(stderr, "--rebuild rebuilds the tree that moves between the frames of a sequence degrade; add %s\n",
+                     frames == 0 ? "--frames N" : "--move or --rotate");
+        return 2;
+    }
+    if (lights_movable_flag && (frames == 0 || !(move_flag || rotate_flag))) {  // refused before anything is loaded
+        std::fprintf(stderr, "--lights-movable lets the moves between the frames of a sequence take light triangles along; add %s\n",
                      frames == 0 ? "--frames N" : "--move or --rotate");
         return 2;
     }
@@ -811,6 +821,10 @@ int main(int argc, char** argv) {
         if (adaptive) {
             std::fprintf(stderr, "--frames accumulates plain renders; drop --adaptive\n");
             return 2;
+        }
+        if (lights_movable_flag && mcpt_scene_set_lights_movable(scene, 1) != MCPT_OK) {
+            std::fprintf(stderr, "--lights-movable failed: %s\n", mcpt_last_error());
+            return 1;
         }
         if (move_flag) {
             if (const int rc = mover.bind(scene)) return rc;

@@ -152,6 +152,14 @@ void make_facet_slot_map(const Bvh& b, int F, std::vector<int32_t>& slot_start, 
 int64_t host_refresh_ranges(HostScene& s, Bvh& b, const BvhRefitIndex& ix, const std::vector<int32_t>& slot_start,
                             const std::vector<int32_t>& slot_list, const PendingRanges& ranges, double margin);
 
+// the same for the light triangles of the ranges (a light move): their light_area, then one refit_bvh
+// of the light-only tree `lb` over their slots (slot map and index of `lb`); returns the number of light triangles
+int64_t host_refresh_lights(HostScene& s, Bvh& lb, const BvhRefitIndex& ix, const std::vector<int32_t>& slot_start,
+                            const std::vector<int32_t>& slot_list, const PendingRanges& ranges, double margin);
+// the first light triangle of pos (count facets from `first`, 9 floats each) whose fp64 (b - a) x (c - a) has a zero
+// or non-finite length, or -1
+int first_degenerate_light(const HostScene& s, int32_t first, int32_t count, const float* pos);
+
 // refit.hip -- the device side of mcpt_scene_update: the device pointers of one device state's main tree (owned by
 // render.hip's DeviceState) and the kernels that rewrite them.  Both functions only enqueue on `stream` (a
 // hipStream_t) of the current device.
@@ -187,6 +195,52 @@ int transform_enqueue(const RefitDev& r, const float* rest_v, const float* rest_
 // k_refit_level alone over every level, deepest first, on the dirty bytes the state holds (r.counters[1] cleared
 // first, the dirty bytes after): the tail of refit_enqueue, and how a rebuilt tree gets its boxes
 int refit_levels_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, double margin, void* stream);
+
+// light_tables.hip -- the device side of a light move (mcpt_scene_set_lights_movable): the device
+// pointers of one device state's light tables (owned by render.hip's DeviceState; the layouts are get_device_state's)
+// and the kernels that derive them again from tri_v / tri_n.  Every function only enqueues on `stream`.
+constexpr int kLightRowWords = 8;  // a chunk's scratch row: unrounded S, K, lo[3], hi[3]
+struct LightGlobals {              // the light constants DScene holds by value
+    double band_ctr[3], band_R, band_S, band_K;
+    float light_bound, pad;
+};
+struct LightTabDev {
+    const float* tri_v;          // F * 3 float4
+    const float* tri_n;          // F * 9
+    const int32_t* tri_light;    // F -> light or -1
+    const double* light_sum;     // NL
+    const int32_t* light_group;  // NL -> group
+    const int32_t* grp_range;    // ngroups * (first light, count)
+    float* lt_v;                 // NL * 3 float4
+    double* lt_n;                // NL double4
+    float* lt_pk;                // NL * 3 float4
+    float* lt_d;                 // NL
+    double* lt_w;                // NL * 5 double2
+    float* lt_f;                 // NL * 4 float4
+    float* lt_pair;              // 32 floats per light pair
+    double* l_area;              // NL
+    double* l_area_cum;          // NL
+    float* chunk_sph;            // nchunks float4
+    float* chunk_sk;             // nchunks float2
+    double* chunk_row;           // nchunks * kLightRowWords
+    uint8_t* chunk_dirty;        // nchunks
+    uint8_t* group_dirty;        // ngroups
+    LightGlobals* globals;
+    unsigned* counters;          // the light tree's RefitDev counters: [2] chunks recomputed, [3] groups recomputed
+    int32_t F, NL, nchunks, ngroups;
+};
+// adds to *bad the light triangles of the staged range (dpos: count * 9 floats; tri_light_of_range: count entries)
+// whose (b - a) x (c - a) has a zero or non-finite fp64 length; *bad is not cleared
+int light_validate_enqueue(int32_t count, const float* dpos, const int32_t* tri_light_of_range, unsigned* bad, void* stream);
+// every chunk's sphere, (S, K) and scratch row from the tables as they are (a state's first light move)
+int light_chunks_all_enqueue(const LightTabDev& t, void* stream);
+// the records of the light facets of [first, first + count) from tri_v / tri_n (already scattered), their chunks, the
+// constants, the dirty groups' area sums, then the light-only tree `lr`: its leaf slots of those facets and
+// refit_levels_enqueue with `margin`
+int light_tables_enqueue(const LightTabDev& t, const RefitDev& lr, const int32_t* level_first, int nlevels, int32_t first,
+                         int32_t count, double margin, void* stream);
+// k_light_area_cum alone over the groups whose dirty byte is set (tools/light_update_bench.py times it)
+int light_area_cum_enqueue(const LightTabDev& t, void* stream);
 
 // rebuild.hip -- the device side of mcpt_scene_rebuild and mcpt_scene_tree_cost
 constexpr int kRebuildMaxLevels = 15;  // node levels of a rebuilt tree, for every input

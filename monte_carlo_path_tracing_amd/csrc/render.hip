@@ -4765,6 +4765,16 @@ struct DeviceState {
     RefitDev refit{};
     std::vector<int32_t> level_first;
     DevBuf up_pos, up_nrm;
+    // a light move on this device, built at the state's first one: the light tables' pointers for
+    // light_tables.hip, a second RefitDev over the light-only tree (lbvh4, lbvh4q, lleaf_v; tri_v / tri_n shared with
+    // `refit`) with its own slot map, dirty bytes, counters and levels, a pinned copy of the by-value constants and
+    // the events around the light stage
+    bool light_ready = false;
+    LightTabDev ltab{};
+    RefitDev lrefit{};
+    std::vector<int32_t> llevel_first;
+    LightGlobals* pinned_globals = nullptr;
+    hipEvent_t evl0 = nullptr, evl1 = nullptr;
     // mcpt_scene_rebuild on this device: the leaf slots of the main tree the state holds (the host
     // tree's until the first rebuild, F after it); the builder's scratch; two sets of tree arrays sized for F nodes and
     // F slots, built into in turn (the tree in use is never the one being written); the identity slot_start, the
@@ -4808,6 +4818,12 @@ struct mcpt_scene {
     bool updated = false;
     BvhRefitIndex refit_ix;
     std::vector<int32_t> slot_start, slot_list;
+    // mcpt_scene_set_lights_movable: the switch, the numbers of the last successful update / transform
+    // call, and the same index and slot map for `lbvh`, built at the first light move
+    bool lights_movable = false;
+    mcpt_light_update_stats light_stats{};
+    BvhRefitIndex lrefit_ix;
+    std::vector<int32_t> lslot_start, lslot_list;
     // mcpt_scene_rebuild: nodes and leaf slots of the first rebuilt state's main tree (0: never rebuilt), for
     // mcpt_scene_accel_bytes
     uint64_t rebuilt_nodes = 0, rebuilt_slots = 0;
@@ -4958,6 +4974,17 @@ void ensure_slot_map(mcpt_scene* sc) {
     make_facet_slot_map(sc->bvh, sc->host.F, sc->slot_start, sc->slot_list);
     sc->refit_ix = make_bvh_refit_index(sc->bvh);
 }
+// the same for the light-only tree, built at the handle's first light move
+void ensure_light_slot_map(mcpt_scene* sc) {
+    if (!sc->lslot_start.empty()) return;
+    make_facet_slot_map(sc->lbvh, sc->host.F, sc->lslot_start, sc->lslot_list);
+    sc->lrefit_ix = make_bvh_refit_index(sc->lbvh);
+}
+bool range_has_light(const mcpt_scene* sc, int32_t first, int32_t end) {
+    for (int f = first; f < end; f++)
+        if (sc->host.light_of[f] >= 0) return true;
+    return false;
+}
 
 // puts the thread back on the device it was on when a function that visits device states returns, on every path
 struct DeviceRestore {
@@ -5016,6 +5043,12 @@ int host_sync(mcpt_scene* sc) {
     if (!sc->pending.r.empty()) {
         ensure_slot_map(sc);
         host_refresh_ranges(hs, sc->bvh, sc->refit_ix, sc->slot_start, sc->slot_list, sc->pending, sc->margin);
+        bool lights = false;  // a transform moved light triangles (mcpt_scene_set_lights_movable): areas, light-only tree
+        for (const auto& p : sc->pending.r) lights = lights || range_has_light(sc, p.first, p.second);
+        if (lights) {
+            ensure_light_slot_map(sc);
+            host_refresh_lights(hs, sc->lbvh, sc->lrefit_ix, sc->lslot_start, sc->lslot_list, sc->pending, sc->margin);
+        }
         sc->grid.ok = false;  // as update_apply: rebuilt from the new positions by the next grid-mode call
     }
     if (sc->prev_stale) {
@@ -7303,8 +7336,9 @@ void mcpt_scene_destroy(mcpt_scene* sc) {
         for (DevBuf* b : bufs)
             if (b->p) (void)hipFree(b->p);
         if (D->pinned_count) (void)hipHostFree(D->pinned_count);
+        if (D->pinned_globals) (void)hipHostFree(D->pinned_globals);
         if (D->stream) (void)hipStreamDestroy(D->stream);
-        hipEvent_t evs[] = {D->ev0, D->ev1, D->evp0, D->evp1, D->evr0, D->evr1};
+        hipEvent_t evs[] = {D->ev0, D->ev1, D->evp0, D->evp1, D->evr0, D->evr1, D->evl0, D->evl1};
         for (hipEvent_t e : evs)
             if (e) (void)hipEventDestroy(e);
     }
@@ -7377,6 +7411,7 @@ static int update_check_args(const mcpt_scene* sc, int32_t first, int32_t count,
     return MCPT_OK;
 }
 static int update_check_lights(const mcpt_scene* sc, int32_t first, int32_t count, const char* who = "mcpt_scene_update") {
+    if (sc->lights_movable) return MCPT_OK;  // mcpt_scene_set_lights_movable: light facets move as any other
     for (int f = first; f < first + count; f++)
         if (sc->host.light_of[f] >= 0) {
             set_error("%s: facet %d is a light triangle (light %d); lights cannot move", who, f, sc->host.light_of[f]);
@@ -7407,14 +7442,10 @@ static int update_check_values(const mcpt_scene* sc, int32_t first, int32_t coun
     return MCPT_OK;
 }
 
-// what a device state's first update builds: the CSR facet -> leaf-slot map, the dirty bytes, the counters and the
-// first node of every level; the tree's indices are checked here once, so the kernels need no bounds tests
-static int ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
-    if (D.refit_ready) return MCPT_OK;
-    const DScene& d = D.d;
-    const size_t nslots = D.nslots;
-    std::vector<BvhNode4> b4(d.nbvh4);
-    HIP_OK(hipMemcpy(b4.data(), d.bvh4, b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
+// the first node of every level of a breadth-first 4-wide tree (nodes with packed leaf codes); false if the tree is
+// not in that order or an index is out of range
+static bool bvh4_levels(const std::vector<BvhNode4>& b4, size_t nslots, std::vector<int32_t>* levels) {
+    const int32_t nn = (int32_t)b4.size();
     std::vector<int32_t> lf{0, 1};
     bool ok = !b4.empty();
     while (ok) {
@@ -7425,17 +7456,30 @@ static int ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
                 const int32_t c = b4[n].child[k];
                 if (c == kBvh4Empty) continue;
                 if (c >= 0) {
-                    ok = ok && c == next++ && c < d.nbvh4;
+                    ok = ok && c == next++ && c < nn;
                 } else {
                     const int64_t s0 = ~c >> kLeafBits, cnt = ~c & ((1 << kLeafBits) - 1);
                     ok = ok && s0 + cnt <= (int64_t)nslots;
                 }
             }
         if (next == n1) break;
-        ok = ok && next <= d.nbvh4;
+        ok = ok && next <= nn;
         lf.push_back((int32_t)next);
     }
-    if (!ok || lf.back() != d.nbvh4) {
+    if (!ok || lf.back() != nn) return false;
+    *levels = std::move(lf);
+    return true;
+}
+// what a device state's first update builds: the CSR facet -> leaf-slot map, the dirty bytes, the counters and the
+// first node of every level; the tree's indices are checked here once, so the kernels need no bounds tests
+static int ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
+    if (D.refit_ready) return MCPT_OK;
+    const DScene& d = D.d;
+    const size_t nslots = D.nslots;
+    std::vector<BvhNode4> b4(d.nbvh4);
+    HIP_OK(hipMemcpy(b4.data(), d.bvh4, b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
+    std::vector<int32_t> lf;
+    if (!bvh4_levels(b4, nslots, &lf)) {
         set_error("mcpt_scene_update: device %d's 4-wide tree is not in breadth-first order", D.device);
         return MCPT_E_SCENE;
     }
@@ -7463,6 +7507,144 @@ static int ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
     return MCPT_OK;
 }
 
+// what a device state's first light move builds (after ensure_refit_state): the same for the light-only tree, the
+// light tables' pointers, the light -> group map, the chunk rows (filled here from the tables as they are), the dirty
+// bytes and the small struct of constants.  The current device is D's.
+static int ensure_light_state(mcpt_scene* sc, DeviceState& D) {
+    if (D.light_ready) return MCPT_OK;
+    const DScene& d = D.d;
+    const HostScene& hs = sc->host;
+    const size_t nslots = sc->lbvh.leaf_facets.size();
+    std::vector<BvhNode4> b4(d.nlbvh4);
+    HIP_OK(hipMemcpy(b4.data(), d.lbvh4, b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
+    std::vector<int32_t> lf;
+    if (hs.NL < 1 || !bvh4_levels(b4, nslots, &lf)) {
+        set_error("mcpt_scene_update: device %d's light-only 4-wide tree is not in breadth-first order", D.device);
+        return MCPT_E_SCENE;
+    }
+    ensure_light_slot_map(sc);
+    RefitDev& r = D.lrefit;
+    r.F = d.F;
+    r.nslots = (int32_t)nslots;
+    r.nnodes = d.nlbvh4;
+    r.tri_v = D.refit.tri_v;
+    r.tri_n = D.refit.tri_n;
+    r.leaf_v = const_cast<float*>(reinterpret_cast<const float*>(d.lleaf_v));
+    r.bvh4 = const_cast<BvhNode4*>(d.lbvh4);
+    r.bvh4q = const_cast<BvhNode4Q*>(d.lbvh4q);
+    int rc;
+    if ((rc = upload(D, sc->lslot_start, &r.slot_start)) || (rc = upload(D, sc->lslot_list, &r.slot_list))) return rc;
+    const int nch = prep_chunks(hs.NL), ng = d.ngroups;
+    std::vector<int32_t> lgroup(hs.NL, 0);
+    for (int g = 0; g < ng; g++)
+        for (int l = hs.group_start[g]; l < hs.group_start[g] + hs.group_count[g]; l++) lgroup[l] = g;
+    const std::vector<uint8_t> zs(std::max<size_t>(nslots, 1), 0), zn(std::max<size_t>(b4.size(), 1), 0), zch(nch, 0),
+        zg(std::max(ng, 1), 0);
+    const std::vector<unsigned> zc(16, 0);
+    const std::vector<double> zrow(kLightRowWords * (size_t)nch, 0.0);
+    const std::vector<LightGlobals> zglob(1);
+    const uint8_t *ds, *dn, *dch, *dg;
+    const unsigned* dc;
+    const double* drow;
+    const LightGlobals* dglob;
+    const int32_t* dlg;
+    if ((rc = upload(D, zs, &ds)) || (rc = upload(D, zn, &dn)) || (rc = upload(D, zc, &dc)) || (rc = upload(D, zch, &dch)) ||
+        (rc = upload(D, zg, &dg)) || (rc = upload(D, zrow, &drow)) || (rc = upload(D, zglob, &dglob)) || (rc = upload(D, lgroup, &dlg)))
+        return rc;
+    r.slot_dirty = const_cast<uint8_t*>(ds);
+    r.node_dirty = const_cast<uint8_t*>(dn);
+    r.counters = const_cast<unsigned*>(dc);
+    LightTabDev& t = D.ltab;
+    t.tri_v = D.refit.tri_v;
+    t.tri_n = D.refit.tri_n;
+    t.tri_light = d.tri_light;
+    t.light_sum = d.light_sum;
+    t.light_group = dlg;
+    t.grp_range = reinterpret_cast<const int32_t*>(d.grp_range);
+    t.lt_v = const_cast<float*>(reinterpret_cast<const float*>(d.lt_v));
+    t.lt_n = const_cast<double*>(reinterpret_cast<const double*>(d.lt_n));
+    t.lt_pk = const_cast<float*>(reinterpret_cast<const float*>(d.lt_pk));
+    t.lt_d = const_cast<float*>(d.lt_d);
+    t.lt_w = const_cast<double*>(reinterpret_cast<const double*>(d.lt_w));
+    t.lt_f = const_cast<float*>(reinterpret_cast<const float*>(d.lt_f));
+    t.lt_pair = const_cast<float*>(reinterpret_cast<const float*>(d.lt_pair));
+    t.l_area = const_cast<double*>(d.l_area);
+    t.l_area_cum = const_cast<double*>(d.l_area_cum);
+    t.chunk_sph = const_cast<float*>(reinterpret_cast<const float*>(d.chunk_sph));
+    t.chunk_sk = const_cast<float*>(reinterpret_cast<const float*>(d.chunk_sk));
+    t.chunk_row = const_cast<double*>(drow);
+    t.chunk_dirty = const_cast<uint8_t*>(dch);
+    t.group_dirty = const_cast<uint8_t*>(dg);
+    t.globals = const_cast<LightGlobals*>(dglob);
+    t.counters = r.counters;
+    t.F = d.F;
+    t.NL = hs.NL;
+    t.nchunks = nch;
+    t.ngroups = ng;
+    if (!D.pinned_globals) HIP_OK(hipHostMalloc(&D.pinned_globals, sizeof(LightGlobals)));
+    if (!D.evl0) HIP_OK(hipEventCreate(&D.evl0));
+    if (!D.evl1) HIP_OK(hipEventCreate(&D.evl1));
+    // every chunk's row from the tables as they are: a later move recomputes only its own chunks
+    if ((rc = light_chunks_all_enqueue(t, D.stream))) return rc;
+    HIP_OK(hipStreamSynchronize(D.stream));
+    D.llevel_first = std::move(lf);
+    D.light_ready = true;
+    return MCPT_OK;
+}
+
+// the light stage of an update or transform on one state, after refit_enqueue's scatter on the same stream; the
+// constants land in the state's pinned copy by the time the stream is synchronised
+static int light_stage_enqueue(mcpt_scene* sc, DeviceState& D, int32_t first, int32_t count) {
+    HIP_OK(hipEventRecord(D.evl0, D.stream));
+    if (int rc = light_tables_enqueue(D.ltab, D.lrefit, D.llevel_first.data(), (int)D.llevel_first.size() - 1, first, count,
+                                      sc->margin, D.stream))
+        return rc;
+    HIP_OK(hipEventRecord(D.evl1, D.stream));
+    HIP_OK(hipMemcpyAsync(D.pinned_globals, D.ltab.globals, sizeof(LightGlobals), hipMemcpyDeviceToHost, D.stream));
+    return MCPT_OK;
+}
+// after that synchronisation: the state's by-value constants patched; lst != null: the first state's numbers
+static int light_stage_finish(DeviceState& D, mcpt_light_update_stats* lst) {
+    const LightGlobals& g = *D.pinned_globals;
+    for (int a = 0; a < 3; a++) D.d.band_ctr[a] = g.band_ctr[a];
+    D.d.band_R = g.band_R;
+    D.d.band_S = g.band_S;
+    D.d.band_K = g.band_K;
+    D.d.light_bound = g.light_bound;
+    if (lst) {
+        float ms = 0;
+        unsigned c[4] = {0, 0, 0, 0};
+        HIP_OK(hipEventElapsedTime(&ms, D.evl0, D.evl1));
+        HIP_OK(hipMemcpy(c, D.lrefit.counters, sizeof c, hipMemcpyDeviceToHost));
+        lst->device_seconds = 1e-3 * ms;
+        lst->light_nodes_refit = c[1];
+        lst->chunks = (int32_t)c[2];
+        lst->groups = (int32_t)c[3];
+        lst->light_levels = (int32_t)D.llevel_first.size() - 1;
+    }
+    return MCPT_OK;
+}
+// the numbers of a call with `lights` light triangles in its range, before any device state has added its own:
+// chunks and groups counted on the host (a scene with device states takes the first state's counters instead)
+static mcpt_light_update_stats light_stats_host(const mcpt_scene* sc, int32_t first, int32_t count) {
+    mcpt_light_update_stats st;
+    mcpt_light_update_stats_init(&st);
+    const HostScene& hs = sc->host;
+    std::vector<uint8_t> ch(prep_chunks(hs.NL), 0), gr(std::max<size_t>(hs.group_start.size(), 1), 0);
+    for (int f = first; f < first + count; f++) {
+        const int l = hs.light_of[f];
+        if (l < 0) continue;
+        st.lights++;
+        ch[l >> 6] = 1;
+        // the last group that starts at or before l (groups without triangles share a start with their successor)
+        const auto g = std::upper_bound(hs.group_start.begin(), hs.group_start.end(), l) - hs.group_start.begin();
+        if (g > 0) gr[(size_t)g - 1] = 1;
+    }
+    for (uint8_t b : ch) st.chunks += b;
+    for (uint8_t b : gr) st.groups += b;
+    return st;
+}
+
 // the call after its refusals: the host scene first (it stays the truth for device states made later, for the grid
 // and for the debug checks), then every device state the scene has.  src_device >= 0: dpos / dnrm are device memory
 // there and that device's state reads them directly; every other state gets a staging copy of the host arrays.
@@ -7475,6 +7657,14 @@ static int update_apply(mcpt_scene* sc, int32_t first, int32_t count, const floa
     for (int f = first; f < first + count; f++) unique_normal_of_facet(hs, f);
     const std::vector<int32_t> slots(sc->slot_list.begin() + sc->slot_start[first], sc->slot_list.begin() + sc->slot_start[first + count]);
     refit_bvh(sc->bvh, sc->refit_ix, hs, slots, sc->margin);
+    // light triangles in the range (mcpt_scene_set_lights_movable): their areas and the light-only tree's boxes
+    mcpt_light_update_stats lst = light_stats_host(sc, first, count);
+    if (lst.lights) {
+        ensure_light_slot_map(sc);
+        PendingRanges one;
+        one.add(first, count);
+        host_refresh_lights(hs, sc->lbvh, sc->lrefit_ix, sc->lslot_start, sc->lslot_list, one, sc->margin);
+    }
     sc->grid.ok = false;  // rebuilt from the new positions by the next grid-mode call
     sc->updated = true;   // the 8-wide trees are stale from here on (bvh8_refused)
     mcpt_update_stats st;
@@ -7491,7 +7681,7 @@ static int update_apply(mcpt_scene* sc, int32_t first, int32_t count, const floa
     for (DeviceState* D : devs) {
         HIP_OK(hipSetDevice(D->device));
         int rc;
-        if ((rc = ensure_refit_state(sc, *D))) return rc;
+        if ((rc = ensure_refit_state(sc, *D)) || (lst.lights && (rc = ensure_light_state(sc, *D)))) return rc;
         const float *sp = dpos, *sn = dnrm;
         if (D->device != src_device) {
             if ((rc = ensure(D->up_pos, 36ull * count)) || (nrm && (rc = ensure(D->up_nrm, 36ull * count)))) return rc;
@@ -7507,7 +7697,9 @@ static int update_apply(mcpt_scene* sc, int32_t first, int32_t count, const floa
                                 D->stream)))
             return rc;
         HIP_OK(hipEventRecord(D->ev1, D->stream));
+        if (lst.lights && (rc = light_stage_enqueue(sc, *D, first, count))) return rc;
         HIP_OK(hipStreamSynchronize(D->stream));
+        if (lst.lights && (rc = light_stage_finish(*D, st.device_states == 0 ? &lst : nullptr))) return rc;
         if (st.device_states++ == 0) {
             float ms = 0;
             unsigned n = 0;
@@ -7519,15 +7711,29 @@ static int update_apply(mcpt_scene* sc, int32_t first, int32_t count, const floa
         }
     }
     if (!devs.empty()) HIP_OK(hipSetDevice(cur));
+    sc->light_stats = lst;
     if (stats) *stats = st;
     return MCPT_OK;
+}
+
+// the switch's extra refusal on host arrays: the first degenerate light triangle of the range is named
+static int update_check_light_values(const mcpt_scene* sc, int32_t first, int32_t count, const float* pos,
+                                     const char* who = "mcpt_scene_update") {
+    if (!sc->lights_movable) return MCPT_OK;
+    const int f = first_degenerate_light(sc->host, first, count, pos);
+    if (f < 0) return MCPT_OK;
+    set_error("%s: light triangle %d (light %d) would be degenerate: |(b - a) x (c - a)| is zero or not finite, so it "
+              "has no unique normal", who, f, sc->host.light_of[f]);
+    return MCPT_E_INVALID;
 }
 
 int mcpt_scene_update(mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm, mcpt_update_stats* stats) {
     int rc;
     if ((rc = update_check_args(sc, first, count, pos, stats))) return rc;
     std::lock_guard<std::mutex> lk(sc->mu);
-    if ((rc = update_check_lights(sc, first, count)) || (rc = update_check_values(sc, first, count, pos, nrm))) return rc;
+    if ((rc = update_check_lights(sc, first, count)) || (rc = update_check_values(sc, first, count, pos, nrm)) ||
+        (rc = update_check_light_values(sc, first, count, pos)))
+        return rc;
     if ((rc = host_sync(sc))) return rc;  // the host refit reads every triangle of a touched leaf
     return update_apply(sc, first, count, pos, nrm, -1, nullptr, nullptr, stats);
 }
@@ -7555,13 +7761,22 @@ int mcpt_scene_update_device(mcpt_scene* sc, int32_t device, int32_t first, int3
     update_arena(sc, lo, hi);
     unsigned bad = 0;
     rc = refit_validate_enqueue(v, count, dpos, dnrm, lo, hi, nullptr);
-    hipError_t e = rc ? hipSuccess : hipMemcpy(&bad, word, sizeof bad, hipMemcpyDeviceToHost);
+    const bool lights = sc->lights_movable && range_has_light(sc, first, first + count);
+    void* lof = nullptr;  // the range's rows of light_of, for the degenerate-light count into the same word
+    hipError_t e = hipSuccess;
+    if (!rc && lights) {
+        e = hipMalloc(&lof, 4ull * count);
+        if (e == hipSuccess) e = hipMemcpy(lof, sc->host.light_of.data() + first, 4ull * count, hipMemcpyHostToDevice);
+        if (e == hipSuccess) rc = light_validate_enqueue(count, dpos, (const int32_t*)lof, v.counters, nullptr);
+    }
+    if (!rc && e == hipSuccess) e = hipMemcpy(&bad, word, sizeof bad, hipMemcpyDeviceToHost);
     (void)hipFree(word);
+    if (lof) (void)hipFree(lof);
     if (rc) return rc;
     HIP_OK(e);
     if (bad) {
         set_error("mcpt_scene_update_device: %u values of the range are non-finite or positions outside the arena (the "
-                  "build's box grown by its largest extent)", bad);
+                  "build's box grown by its largest extent)%s", bad, lights ? ", or light triangles that would be degenerate" : "");
         (void)hipSetDevice(cur);
         return MCPT_E_INVALID;
     }
@@ -7570,6 +7785,48 @@ int mcpt_scene_update_device(mcpt_scene* sc, int32_t device, int32_t first, int3
     if (dnrm) HIP_OK(hipMemcpy(hn.data(), dnrm, 36ull * count, hipMemcpyDeviceToHost));
     HIP_OK(hipSetDevice(cur));
     return update_apply(sc, first, count, hp.data(), dnrm ? hn.data() : nullptr, device, dpos, dnrm, stats);
+}
+
+// ---- movable light triangles (include/mcpt.h; the kernels are light_tables.hip's) ----
+int mcpt_scene_set_lights_movable(mcpt_scene* sc, int32_t on) {
+    if (!sc) {
+        set_error("mcpt_scene_set_lights_movable: NULL scene");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    sc->lights_movable = on != 0;
+    return MCPT_OK;
+}
+int mcpt_scene_lights_movable(const mcpt_scene* sc, int32_t* on) {
+    if (!sc || !on) {
+        set_error("mcpt_scene_lights_movable: NULL %s", !sc ? "scene" : "on");
+        return MCPT_E_INVALID;
+    }
+    mcpt_scene* w = const_cast<mcpt_scene*>(sc);
+    std::lock_guard<std::mutex> lk(w->mu);
+    *on = sc->lights_movable ? 1 : 0;
+    return MCPT_OK;
+}
+void mcpt_light_update_stats_init(mcpt_light_update_stats* st) {
+    if (!st) return;
+    std::memset((void*)st, 0, sizeof *st);
+    st->struct_size = sizeof *st;
+}
+int mcpt_scene_light_update_info(const mcpt_scene* sc, mcpt_light_update_stats* out) {
+    if (!sc || !out) {
+        set_error("mcpt_scene_light_update_info: NULL %s", !sc ? "scene" : "out");
+        return MCPT_E_INVALID;
+    }
+    if (out->struct_size != sizeof(mcpt_light_update_stats)) {
+        set_error("mcpt_light_update_stats.struct_size %u does not match this library's %zu (header / library version mismatch)",
+                  out->struct_size, sizeof(mcpt_light_update_stats));
+        return MCPT_E_INVALID;
+    }
+    mcpt_scene* w = const_cast<mcpt_scene*>(sc);
+    std::lock_guard<std::mutex> lk(w->mu);
+    *out = sc->light_stats;
+    out->struct_size = sizeof *out;
+    return MCPT_OK;
 }
 
 // ---- mcpt_scene_pose_save (include/mcpt.h) ----
@@ -7658,6 +7915,7 @@ static int transform_on_devices(mcpt_scene* sc, const std::vector<DeviceState*>&
     mcpt_update_stats_init(&st);
     st.facets = count;
     st.leaf_slots = (int64_t)sc->slot_start[first + count] - sc->slot_start[first];
+    mcpt_light_update_stats lst = light_stats_host(sc, first, count);
     double lo[3], hi[3];
     update_arena(sc, lo, hi);
     int rc;
@@ -7667,7 +7925,8 @@ static int transform_on_devices(mcpt_scene* sc, const std::vector<DeviceState*>&
     for (size_t i = 0; i < devs.size(); i++) {
         DeviceState* D = devs[i];
         HIP_OK(hipSetDevice(D->device));
-        if ((rc = ensure_refit_state(sc, *D)) || (rc = ensure(D->up_pos, 36ull * count)) || (rc = ensure(D->up_nrm, 36ull * count)))
+        if ((rc = ensure_refit_state(sc, *D)) || (rc = ensure(D->up_pos, 36ull * count)) || (rc = ensure(D->up_nrm, 36ull * count)) ||
+            (lst.lights && (rc = ensure_light_state(sc, *D))))
             return rc;
         if (!D->rest_v.p || !D->rest_n.p) {
             set_error("mcpt_scene_transform: device %d holds no rest pose", D->device);
@@ -7679,6 +7938,9 @@ static int transform_on_devices(mcpt_scene* sc, const std::vector<DeviceState*>&
         if ((rc = transform_enqueue(D->refit, (const float*)D->rest_v.p, (const float*)D->rest_n.p, first, count, m, n, lo, hi,
                                     (float*)D->up_pos.p, (float*)D->up_nrm.p, D->stream)))
             return rc;
+        // degenerate light triangles of the staged range count into the same word
+        if (lst.lights && (rc = light_validate_enqueue(count, (const float*)D->up_pos.p, D->d.tri_light + first, D->refit.counters, D->stream)))
+            return rc;
         HIP_OK(hipMemcpyAsync(&bad[i], D->refit.counters, sizeof(unsigned), hipMemcpyDeviceToHost, D->stream));
     }
     unsigned nbad = 0;
@@ -7689,7 +7951,8 @@ static int transform_on_devices(mcpt_scene* sc, const std::vector<DeviceState*>&
     }
     if (nbad) {  // only the staging arrays were written
         set_error("mcpt_scene_transform: %u transformed values of facets [%d, %d) are non-finite or positions outside the "
-                  "arena (the build's box grown by its largest extent)", nbad, first, first + count);
+                  "arena (the build's box grown by its largest extent)%s", nbad, first, first + count,
+                  lst.lights ? ", or light triangles that would be degenerate" : "");
         return MCPT_E_INVALID;
     }
     // the devices are modified from here on, so the marks come first: should a launch below fail, the host copy is
@@ -7706,7 +7969,9 @@ static int transform_on_devices(mcpt_scene* sc, const std::vector<DeviceState*>&
                                 (const float*)D->up_pos.p, (const float*)D->up_nrm.p, sc->margin, D->stream)))
             return rc;
         HIP_OK(hipEventRecord(D->ev1, D->stream));
+        if (lst.lights && (rc = light_stage_enqueue(sc, *D, first, count))) return rc;
         HIP_OK(hipStreamSynchronize(D->stream));
+        if (lst.lights && (rc = light_stage_finish(*D, st.device_states == 0 ? &lst : nullptr))) return rc;
         if (st.device_states++ == 0) {
             float ms = 0;
             unsigned nn = 0;
@@ -7717,6 +7982,7 @@ static int transform_on_devices(mcpt_scene* sc, const std::vector<DeviceState*>&
             st.levels = (int32_t)D->level_first.size() - 1;
         }
     }
+    sc->light_stats = lst;
     if (stats) *stats = st;
     return MCPT_OK;
 }
@@ -7751,7 +8017,9 @@ int mcpt_scene_transform(mcpt_scene* sc, int32_t first, int32_t count, const dou
     std::vector<float> pos(9 * (size_t)count), nrm(9 * (size_t)count);
     transform_facets(sc->rest_pos.data() + 9 * (size_t)first, sc->rest_nrm.data() + 9 * (size_t)first, (size_t)count, m, n, pos.data(),
                      nrm.data());
-    if ((rc = update_check_values(sc, first, count, pos.data(), nrm.data(), who))) return rc;
+    if ((rc = update_check_values(sc, first, count, pos.data(), nrm.data(), who)) ||
+        (rc = update_check_light_values(sc, first, count, pos.data(), who)))
+        return rc;
     return update_apply(sc, first, count, pos.data(), nrm.data(), -1, nullptr, nullptr, stats);
 }
 
@@ -8645,20 +8913,21 @@ struct DeviceTree {
     std::vector<float4> leaf_v, tri_v;
     std::vector<int32_t> leaf_facets;
 };
-static int download_tree(mcpt_scene* sc, int32_t device, bool vertices, DeviceTree* t) {
+static int download_tree(mcpt_scene* sc, int32_t device, bool vertices, DeviceTree* t, bool light_only = false) {
     DeviceState* D;
     int rc;
     if ((rc = host_sync(sc))) return rc;  // the device check compares against host.pos
     if ((rc = get_device_state(sc, device, &D))) return rc;
     HIP_OK(hipDeviceSynchronize());
     const DScene& d = D->d;
-    const size_t nslots = D->nslots;
-    t->b4.resize(d.nbvh4);
-    t->q4.resize(d.nbvh4);
+    const size_t nslots = light_only ? sc->lbvh.leaf_facets.size() : D->nslots;
+    const int nn = light_only ? d.nlbvh4 : d.nbvh4;
+    t->b4.resize(nn);
+    t->q4.resize(nn);
     t->leaf_v.resize(3 * nslots);
-    HIP_OK(hipMemcpy(t->b4.data(), d.bvh4, t->b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(t->q4.data(), d.bvh4q, t->q4.size() * sizeof(BvhNode4Q), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(t->leaf_v.data(), d.leaf_v, t->leaf_v.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(t->b4.data(), light_only ? d.lbvh4 : d.bvh4, t->b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(t->q4.data(), light_only ? d.lbvh4q : d.bvh4q, t->q4.size() * sizeof(BvhNode4Q), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(t->leaf_v.data(), light_only ? d.lleaf_v : d.leaf_v, t->leaf_v.size() * sizeof(float4), hipMemcpyDeviceToHost));
     if (vertices) {
         t->tri_v.resize(3 * (size_t)d.F);
         HIP_OK(hipMemcpy(t->tri_v.data(), d.tri_v, t->tri_v.size() * sizeof(float4), hipMemcpyDeviceToHost));
@@ -8670,7 +8939,10 @@ static int download_tree(mcpt_scene* sc, int32_t device, bool vertices, DeviceTr
     for (size_t q = 0; q < nslots; q++) std::memcpy(&t->leaf_facets[q], &t->leaf_v[3 * q].w, 4);
     return MCPT_OK;
 }
-int mcpt_debug_bvh4_check_device(mcpt_scene* sc, int32_t device, int64_t* out) {
+static int bvh4_check_device(mcpt_scene* sc, int32_t device, bool light_only, int64_t* out);
+int mcpt_debug_bvh4_check_device(mcpt_scene* sc, int32_t device, int64_t* out) { return bvh4_check_device(sc, device, false, out); }
+int mcpt_debug_bvh4_check_device_light(mcpt_scene* sc, int32_t device, int64_t* out) { return bvh4_check_device(sc, device, true, out); }
+static int bvh4_check_device(mcpt_scene* sc, int32_t device, bool light_only, int64_t* out) {
     if (!sc || !out) {
         set_error("invalid argument");
         return MCPT_E_INVALID;
@@ -8678,7 +8950,7 @@ int mcpt_debug_bvh4_check_device(mcpt_scene* sc, int32_t device, int64_t* out) {
     std::lock_guard<std::mutex> lk(sc->mu);
     DeviceTree t;
     int rc;
-    if ((rc = download_tree(sc, device, true, &t))) return rc;
+    if ((rc = download_tree(sc, device, true, &t, light_only))) return rc;
     const std::vector<float>& pos = sc->host.pos;
     bvh4_walk(t.b4, t.q4, t.leaf_facets, pos, out);
     // the device's own copies of the vertices against the host's
@@ -8692,6 +8964,86 @@ int mcpt_debug_bvh4_check_device(mcpt_scene* sc, int32_t device, int64_t* out) {
     for (int f = 0; f < sc->host.F; f++) out[4] += differs(&t.tri_v[3 * (size_t)f], f);
     return MCPT_OK;
 }
+int mcpt_debug_light_tables(mcpt_scene* sc, int32_t device, const char* which, void* out, int64_t cap, int64_t* bytes) {
+    if (!sc || !which || !bytes) {
+        set_error("mcpt_debug_light_tables: invalid argument");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    int rc;
+    if ((rc = get_device_state(sc, device, &D))) return rc;
+    HIP_OK(hipDeviceSynchronize());
+    const DScene& d = D->d;
+    // the sizes get_device_state allocated
+    const size_t NL = (size_t)std::max(d.NL, 1), nch = (size_t)prep_chunks(d.NL), nl_pad = 256 * ((nch + 3) / 4);
+    const std::string w = which;
+    const void* src = nullptr;
+    size_t n = 0;
+    LightGlobals g{};
+    if (w == "lt_v") src = d.lt_v, n = 3 * NL * sizeof(float4);
+    else if (w == "lt_n") src = d.lt_n, n = NL * sizeof(double4);
+    else if (w == "lt_pk") src = d.lt_pk, n = 3 * nl_pad * sizeof(float4);
+    else if (w == "lt_d") src = d.lt_d, n = nl_pad * sizeof(float);
+    else if (w == "lt_w") src = d.lt_w, n = 5 * (nl_pad + kSentinelPad) * sizeof(double2);
+    else if (w == "lt_f") src = d.lt_f, n = 4 * (nl_pad + kSentinelPad) * sizeof(float4);
+    else if (w == "lt_pair") src = d.lt_pair, n = 32 * nch * sizeof(LightPair);
+    else if (w == "chunk_sph") src = d.chunk_sph, n = nch * sizeof(float4);
+    else if (w == "chunk_sk") src = d.chunk_sk, n = nch * sizeof(float2);
+    else if (w == "l_area") src = d.l_area, n = (size_t)d.NL * sizeof(double);
+    else if (w == "l_area_cum") src = d.l_area_cum, n = (size_t)d.NL * sizeof(double);
+    else if (w == "globals") {
+        for (int a = 0; a < 3; a++) g.band_ctr[a] = d.band_ctr[a];
+        g.band_R = d.band_R, g.band_S = d.band_S, g.band_K = d.band_K, g.light_bound = d.light_bound;
+        n = sizeof g;
+    } else {
+        set_error("mcpt_debug_light_tables: no table named '%s'", which);
+        return MCPT_E_INVALID;
+    }
+    *bytes = (int64_t)n;
+    if (!out) return MCPT_OK;
+    if (cap < (int64_t)n) {
+        set_error("mcpt_debug_light_tables: '%s' has %zu bytes, more than the buffer's %lld", which, n, (long long)cap);
+        return MCPT_E_INVALID;
+    }
+    if (src) {
+        if (n) HIP_OK(hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
+    } else {
+        std::memcpy(out, &g, n);
+    }
+    return MCPT_OK;
+}
+
+int mcpt_debug_light_area_cum_bench(mcpt_scene* sc, int32_t device, int32_t reps, double* seconds) {
+    if (!sc || !seconds || reps < 1) {
+        set_error("mcpt_debug_light_area_cum_bench: invalid argument");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    int rc;
+    if ((rc = get_device_state(sc, device, &D))) return rc;
+    if (sc->host.NL < 1) {
+        set_error("mcpt_debug_light_area_cum_bench: the scene has no lights");
+        return MCPT_E_INVALID;
+    }
+    ensure_slot_map(sc);
+    if ((rc = ensure_refit_state(sc, *D)) || (rc = ensure_light_state(sc, *D))) return rc;
+    HIP_OK(hipDeviceSynchronize());
+    for (int k = -1; k < reps; k++) {  // one warm-up run
+        HIP_OK(hipMemsetAsync(D->ltab.group_dirty, 1, (size_t)D->ltab.ngroups, D->stream));
+        if (k == 0) HIP_OK(hipEventRecord(D->evl0, D->stream));
+        if ((rc = light_area_cum_enqueue(D->ltab, D->stream))) return rc;
+    }
+    HIP_OK(hipEventRecord(D->evl1, D->stream));
+    HIP_OK(hipMemsetAsync(D->ltab.group_dirty, 0, (size_t)D->ltab.ngroups, D->stream));
+    HIP_OK(hipStreamSynchronize(D->stream));
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, D->evl0, D->evl1));
+    *seconds = 1e-3 * ms / reps;
+    return MCPT_OK;
+}
+
 int mcpt_debug_bvh4_download(mcpt_scene* sc, int32_t device, int64_t* counts, void* nodes, void* qnodes, int32_t* leaf_facets,
                              int64_t cap_nodes, int64_t cap_slots) {
     if (!sc || !counts) {

@@ -115,6 +115,20 @@ static int run_library(const char* obj, const char* xml, const std::string& out_
             if (host_refresh_ranges(turned, tb, ix, slot_start, slot_list, pend, 1e-5) < covered) return 8;
             const std::vector<BvhNode4> t4 = collapse_bvh4(tb);
             if (quantize_bvh4(t4).size() != t4.size()) return 8;
+            if (hs.NL > 0) {  // the light half of such a move: the areas and the light-only tree's refit
+                Bvh ltree = lb;
+                const BvhRefitIndex lix = make_bvh_refit_index(ltree);
+                std::vector<int32_t> lstart, llist;
+                make_facet_slot_map(ltree, hs.F, lstart, llist);
+                int64_t nl = 0;
+                for (const auto& p : pend.r)
+                    for (int32_t g = p.first; g < p.second; g++) nl += turned.light_of[g] >= 0;
+                if (host_refresh_lights(turned, ltree, lix, lstart, llist, pend, 1e-5) != nl) return 8;
+                const int bad = first_degenerate_light(turned, 0, hs.F, turned.pos.data());
+                if (bad >= hs.F || (bad >= 0 && turned.light_of[bad] < 0)) return 8;
+                const std::vector<BvhNode4> l4 = collapse_bvh4(ltree);
+                if (quantize_bvh4(l4).size() != l4.size()) return 8;
+            }
         }
     }
     const double eye[3] = {hs.has_cam ? hs.cam.eye[0] : 0.0, hs.has_cam ? hs.cam.eye[1] : 0.0,
