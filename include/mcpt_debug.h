@@ -149,6 +149,17 @@ int mcpt_debug_set_rebuild_leaf_max(int32_t leaf_max);
 int mcpt_debug_root_picks(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_render_opts* opts, int32_t* pick,
                           double* weights_sum, int32_t* ambiguous);
 
+/* diagnostics: the Phong functions of csrc/device_math.h on n caller-chosen records, one thread per record, with the
+ * template arguments the render kernels use.  A record is 19 doubles in -- n[3] wi[3] wr[3] kd[3] ks[3] sh u0 k1 k2
+ * -- and 8 doubles out -- brdf[3] pdf dir[3] sample_pdf: brdf_phong(n, wi, wr, kd, ks, sh), phong_pdf of the same
+ * arguments, and sample_phong(n, wr, kd, ks, sh, u0, k1, k2) with its pdf.  variant 0: the MIS / shade() kernels'
+ * forms (brdf_phong<true, false>, sample_phong<false>); variant 1: the BRDF-only kernels' (brdf_phong<false, true>,
+ * sample_phong<true>); phong_pdf is the same function in both.  Needs no scene; runs on the current device (a
+ * host-to-device copy, one launch, a device-to-host copy, a synchronize).  n == 0 does nothing; n < 0, another
+ * variant or a NULL array is MCPT_E_INVALID.  tests/test_phong.py compares the outputs with the oracle's and with a
+ * high-precision evaluation. */
+int mcpt_debug_phong(int32_t n, int32_t variant, const double* in19, double* out8);
+
 #ifdef __cplusplus
 }
 #endif

@@ -247,7 +247,8 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
 DEBUG_EXPORTS = ["mcpt_debug_bvh4_check_device_light", "mcpt_debug_light_tables", "mcpt_debug_light_area_cum_bench","mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download",
-                 "mcpt_debug_set_pick_table", "mcpt_debug_root_picks", "mcpt_debug_set_rebuild_leaf_max"]  # include/mcpt_debug.h
+                 "mcpt_debug_set_pick_table", "mcpt_debug_root_picks", "mcpt_debug_set_rebuild_leaf_max",
+                 "mcpt_debug_phong"]  # include/mcpt_debug.h
 
 
 def lib():
@@ -410,7 +411,8 @@ def lib():
                "mcpt_debug_bvh4_download": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C"), P, P, P, C.c_int64, C.c_int64],
                "mcpt_debug_bvh4_check_device_light": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
                "mcpt_debug_light_tables": [P, I, C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64)],
-               "mcpt_debug_light_area_cum_bench": [P, I, I, C.POINTER(D)]}
+               "mcpt_debug_light_area_cum_bench": [P, I, I, C.POINTER(D)],
+               "mcpt_debug_phong": [I, I, dp, dp]}
         for name, argt in dbg.items():
             if hasattr(L, name):
                 getattr(L, name).argtypes = argt
@@ -1626,6 +1628,16 @@ def debug_tri_filter(tri, ro, rd, tlim=None):
     verdict, tup = np.zeros(n, np.int32), np.zeros(n, np.float32)
     _check(lib().mcpt_debug_tri_filter(n, tri, ro, rd, tl, verdict, tup))
     return verdict, tup
+
+
+def debug_phong(records, variant):
+    """Diagnostics: device_math.h's brdf_phong, phong_pdf and sample_phong on (n, 19) records -- n[3] wi[3] wr[3] kd[3]
+    ks[3] sh u0 k1 k2 -- as the MIS / shade() kernels instantiate them (variant 0) or the BRDF-only kernels (variant 1).
+    Returns an (n, 8) array: brdf[3] pdf dir[3] sample_pdf (include/mcpt_debug.h)."""
+    rec = _d(records, (-1, 19))
+    out = np.zeros((rec.shape[0], 8))
+    _check(lib().mcpt_debug_phong(rec.shape[0], int(variant), rec.reshape(-1), out.reshape(-1)))
+    return out
 
 
 def debug_prep_bench(scene, x1, normal, u, variant=-1, iters=5):

@@ -213,6 +213,13 @@ def sample_phong_ref(ctr, n, wr, kd, ks, ns):
     return o
 
 
+def sample_phong_u(n, wr, kd, ks, ns, u0, u1, u2):
+    """sample_from_phong with explicit uniforms (lobe pick u0, xi1 u1, xi2 u2): direction[3], pdf"""
+    o = np.zeros(4)
+    lib().orc_sample_phong_u(_v(n), _v(wr), _v(kd), _v(ks), ns, u0, u1, u2, o)
+    return o
+
+
 def tone_map(rgb, maxr=380.0, gamma=0.25):
     o = np.zeros(3, np.int32)
     lib().orc_tone_map(_v(rgb), maxr, gamma, o)

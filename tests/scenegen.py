@@ -12,7 +12,7 @@ sys.path.insert(0, str(ROOT / "scenes"))
 import gen_veach_mis as gv  # noqa: E402
 
 
-def _write(outdir, name, obj, mtls, lights, cam):
+def _write(outdir, name, obj, mtls, lights, cam, fovy="20.1143"):
     os.makedirs(outdir, exist_ok=True)
     obj.write(os.path.join(outdir, name + ".obj"), name + ".mtl")
     with open(os.path.join(outdir, name + ".mtl"), "w", newline="\n") as f:
@@ -20,9 +20,9 @@ def _write(outdir, name, obj, mtls, lights, cam):
             f.write("newmtl %s\nKd %.6f %.6f %.6f\nKs %.6f %.6f %.6f\nNs %.6f\n\n" % ((m,) + kd + ks + (ns,)))
     with open(os.path.join(outdir, name + ".xml"), "w", newline="\n") as f:
         eye, look = cam
-        f.write('<camera type="perspective" width="16" height="12" fovy="20.1143">\n'
+        f.write('<camera type="perspective" width="16" height="12" fovy="%s">\n'
                 '\t<eye x="%r" y="%r" z="%r"/>\n\t<lookat x="%r" y="%r" z="%r"/>\n'
-                '\t<up x="0.0" y="1.0" z="0.0"/>\n</camera>\n' % (eye + look))
+                '\t<up x="0.0" y="1.0" z="0.0"/>\n</camera>\n' % ((fovy,) + eye + look))
         for m, rad in lights:
             f.write('<light mtlname="%s" radiance="%.6f,%.6f,%.6f"/>\n' % ((m,) + rad))
     return os.path.join(outdir, name + ".obj"), os.path.join(outdir, name + ".xml")
@@ -232,3 +232,68 @@ def needles(outdir, n=70000, seed=7, length=1.0):
         faces.append(((obj.vert(a), ni), (obj.vert(b), ni), (obj.vert(c), ni)))
     obj.groups.append(("needles", "floor", faces))
     return _write(outdir, "needles", obj, mtls, [], CAM)
+
+
+# ---- material swatch: the Phong material classes the other scenes never render (tests/test_swatch.py) ----
+SWATCH_TILES = [  # (name, Kd, Ks, Ns): the classes of tests/phonggen.py that a frame can show (no black, no Ns < 0)
+    ("diffuse", (0.5, 0.5, 0.5), (0.0, 0.0, 0.0), 1.0),
+    ("specular", (0.0, 0.0, 0.0), (0.5, 0.5, 0.5), 50.0),
+    ("plates", (0.07, 0.09, 0.13), (0.1, 0.2, 0.3), 120.0),
+    ("kszero", (0.2, 0.2, 0.2), (0.3, 0.0, 0.2), 50.0),
+    ("tinykd", (1e-6, 1e-6, 1e-6), (0.5, 0.5, 0.5), 50.0),
+    ("ns0", (0.07, 0.09, 0.13), (0.1, 0.2, 0.3), 0.0),
+    ("nshalf", (0.07, 0.09, 0.13), (0.1, 0.2, 0.3), 0.5),
+    ("ns1", (0.07, 0.09, 0.13), (0.1, 0.2, 0.3), 1.0),
+    ("ns5000", (0.07, 0.09, 0.13), (0.1, 0.2, 0.3), 5000.0),
+    ("spec1e6", (0.0, 0.0, 0.0), (0.5, 0.5, 0.5), 1e6),
+    ("ns2e6", (0.07, 0.09, 0.13), (0.1, 0.2, 0.3), 2e6),
+    ("diff1e6", (0.5, 0.5, 0.5), (0.0, 0.0, 0.0), 1e6),
+]
+SWATCH_SLABS = [("slab_px", (0.5, 0.5, 0.5), (0.0, 0.0, 0.0), 1.0), ("slab_nx", (0.0, 0.0, 0.0), (0.5, 0.5, 0.5), 50.0)]
+# the reference takes tan(fovy / 360) of the XML's fovy (main.cpp's camera): 120 gives a half angle of 19 degrees
+SWATCH_CAM, SWATCH_FOVY = ((0.0, 4.0, 3.0), (0.0, 0.3, 0.0)), "120.0"
+
+
+def material_swatch(outdir):
+    """A 4 x 3 grid of unit tiles, one Phong material class each (SWATCH_TILES), between two upright slabs whose large
+    inner faces have the normals exactly +x (diffuse) and -x (specular only), under a 16 x 8 sphere light (224
+    triangles) and a down-facing light quad: 226 lights, so the main prep path, the root cache and the exact fallback
+    run.  The tiles abut, and the slabs close the grid's x ends from below the tiles to above them: every -x-facing
+    side of a material with a diffuse part (the reference's cosine-lobe frame for n = -e_x exactly is 0 / 0, a NaN
+    direction) is either covered by its neighbour or, on the +x slab's outer side, faces nothing a ray can leave
+    from.  The -x slab has Kd = 0: its cosine lobe is picked for u0 == 0 only."""
+    obj, mtls = gv.Obj(), []
+    ex, ey, ez = (1.0, 0.0, 0.0), (0.0, 1.0, 0.0), (0.0, 0.0, 1.0)
+    for k, (name, kd, ks, ns) in enumerate(SWATCH_TILES):
+        i, j = k % 4, k // 4
+        obj.box("tile_" + name, name, (i - 1.5, -0.1, j - 1.0), [(ex, 0.5), (ey, 0.1), (ez, 0.5)])
+        mtls.append((name, kd, ks, ns))
+    for (name, kd, ks, ns), x in zip(SWATCH_SLABS, (-2.125, 2.125)):  # inner faces at x = -2 and x = 2 exactly
+        obj.box(name, name, (x, 1.0, 0.0), [(ex, 0.125), (ey, 1.5), (ez, 1.5)])
+        mtls.append((name, kd, ks, ns))
+    obj.sphere("bulb", "bulb", (-0.4, 2.6, -0.3), 0.35, 16, 8)
+    n = obj.normal((0.0, -1.0, 0.0))
+    q = [obj.vert(p) for p in ((0.3, 3.2, 0.2), (1.3, 3.2, 0.2), (1.3, 3.2, 1.2), (0.3, 3.2, 1.2))]
+    obj.groups.append(("quad", "quad", [((q[0], n), (q[1], n), (q[2], n)), ((q[0], n), (q[2], n), (q[3], n))]))
+    mtls += [("bulb", (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.0), ("quad", (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.0)]
+    return _write(outdir, "swatch", obj, mtls, [("bulb", (20.0, 18.0, 15.0)), ("quad", (6.0, 7.0, 8.0))], SWATCH_CAM,
+                  SWATCH_FOVY)
+
+
+def swatch_owners(oscene, cam):
+    """per pixel of the oracle's primary hits: the material index (-1: no hit) and whether the facet's normal is
+    exactly +-e_x; plus the material names in the MTL's order"""
+    import numpy as np
+    from oracle import pyoracle as po
+
+    _, mat, _, un = oscene.facets()
+    owner = np.full(cam.width * cam.height, -1)
+    xface = np.zeros(cam.width * cam.height, bool)
+    for i in range(cam.height):  # the oracle's pixel order: row i, column j, pixel i * width + j
+        for j in range(cam.width):
+            e, d = po.camera_ray(cam, i, j)
+            f, _ = oscene.closest_hit(e, d)
+            if f >= 0:
+                owner[i * cam.width + j] = mat[f]
+                xface[i * cam.width + j] = abs(un[f][0]) == 1.0 and un[f][1] == 0.0 and un[f][2] == 0.0
+    return owner, xface
