@@ -160,6 +160,12 @@ int mcpt_debug_root_picks(mcpt_scene* scene, const mcpt_camera* cam, const mcpt_
  * high-precision evaluation. */
 int mcpt_debug_phong(int32_t n, int32_t variant, const double* in19, double* out8);
 
+/* diagnostics: the bytes of device memory the library's self-owning buffers hold at this moment, process-wide and over
+ * all devices -- every scene's uploaded arrays and work buffers, counted where a buffer is allocated and where it is
+ * freed.  0 in a process that never made a device state; back to its earlier value once the scenes made since are
+ * destroyed (tests/test_device_memory.py).  Needs no device. */
+int64_t mcpt_debug_device_bytes_live(void);
+
 #ifdef __cplusplus
 }
 #endif

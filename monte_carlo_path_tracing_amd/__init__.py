@@ -248,7 +248,7 @@ DEBUG_EXPORTS = ["mcpt_debug_bvh4_check_device_light", "mcpt_debug_light_tables"
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download",
                  "mcpt_debug_set_pick_table", "mcpt_debug_root_picks", "mcpt_debug_set_rebuild_leaf_max",
-                 "mcpt_debug_phong"]  # include/mcpt_debug.h
+                 "mcpt_debug_phong", "mcpt_debug_device_bytes_live"]  # include/mcpt_debug.h
 
 
 def lib():
@@ -412,10 +412,12 @@ def lib():
                "mcpt_debug_bvh4_check_device_light": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
                "mcpt_debug_light_tables": [P, I, C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64)],
                "mcpt_debug_light_area_cum_bench": [P, I, I, C.POINTER(D)],
-               "mcpt_debug_phong": [I, I, dp, dp]}
+               "mcpt_debug_phong": [I, I, dp, dp], "mcpt_debug_device_bytes_live": []}
         for name, argt in dbg.items():
             if hasattr(L, name):
                 getattr(L, name).argtypes = argt
+        if hasattr(L, "mcpt_debug_device_bytes_live"):
+            L.mcpt_debug_device_bytes_live.restype = C.c_int64
         L.mcpt_tone_map.argtypes = [dp, I, I, D, D, u8]
         L.mcpt_write_bmp.argtypes = [C.c_char_p, u8, I, I]
         L.mcpt_comm_unique_id.argtypes = [C.c_char_p]
@@ -1489,6 +1491,12 @@ def debug_set_pick_table(min_samples=0, window_samples=0):
     """mcpt_debug_set_pick_table (include/mcpt_debug.h): process-wide overrides of the root pick table's rules,
     0 = the library's default."""
     _check(lib().mcpt_debug_set_pick_table(int(min_samples), int(window_samples)))
+
+
+def debug_device_bytes_live():
+    """mcpt_debug_device_bytes_live (include/mcpt_debug.h): the bytes of device memory the library's buffers hold now,
+    over all scenes and devices; back to its earlier value once the scenes made since are destroyed."""
+    return int(lib().mcpt_debug_device_bytes_live())
 
 
 def debug_set_rebuild_leaf_max(leaf_max=0):

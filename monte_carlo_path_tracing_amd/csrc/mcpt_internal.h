@@ -161,7 +161,7 @@ int64_t host_refresh_lights(HostScene& s, Bvh& lb, const BvhRefitIndex& ix, cons
 int first_degenerate_light(const HostScene& s, int32_t first, int32_t count, const float* pos);
 
 // refit.hip -- the device side of mcpt_scene_update: the device pointers of one device state's main tree (owned by
-// render.hip's DeviceState) and the kernels that rewrite them.  Both functions only enqueue on `stream` (a
+// scene_state.h's DeviceState) and the kernels that rewrite them.  Both functions only enqueue on `stream` (a
 // hipStream_t) of the current device.
 struct RefitDev {
     float* tri_v;               // F * 3 float4
@@ -197,7 +197,7 @@ int transform_enqueue(const RefitDev& r, const float* rest_v, const float* rest_
 int refit_levels_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, double margin, void* stream);
 
 // light_tables.hip -- the device side of a light move (mcpt_scene_set_lights_movable): the device
-// pointers of one device state's light tables (owned by render.hip's DeviceState; the layouts are get_device_state's)
+// pointers of one device state's light tables (owned by scene_state.h's DeviceState; the layouts are get_device_state's)
 // and the kernels that derive them again from tri_v / tri_n.  Every function only enqueues on `stream`.
 constexpr int kLightRowWords = 8;  // a chunk's scratch row: unrounded S, K, lo[3], hi[3]
 struct LightGlobals {              // the light constants DScene holds by value

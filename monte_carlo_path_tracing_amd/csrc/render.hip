@@ -52,76 +52,13 @@
 #include "mcpt.h"
 #include "mcpt_debug.h"
 #include "mcpt_internal.h"
+#include "scene_state.h"
 
 using namespace mcpt;
 
 // ============================================================================================
-// device scene
+// device scene (LightPair and DScene: scene_state.h)
 // ============================================================================================
-// two consecutive light triangles (2q, 2q+1) for the lane-per-node cull, every field as an (A, B)
-// float pair so that one v_pk_fma_f32 with a scalar operand serves both lights: nl = unique normal,
-// d = float(nl . p0 + 1e-8) (the threshold folded in), p[3k+i] = coordinate i of vertex k.  Padding
-// lights (index >= N_L) have nl = 0, d = 1e30 (light-side culled).  128 B = two s_load_dwordx16.
-struct LightPair {
-    float2 nl[3];
-    float2 d;      // nl . p0 + 1e-8 of both lights
-    float2 p[9];
-    float pad[6];
-};
-
-struct DScene {
-    int F, NL;
-    const float4* tri_v;      // F*3, original facet order
-    const float* tri_n;       // F*9 vertex normals
-    const int* tri_mat;       // F
-    const int* tri_light;     // F -> light index or -1
-    const float* mtl;         // M*7
-    const double* light_rad;  // NL*3
-    const double* light_sum;  // NL
-    const int* light_facet;   // NL
-    const float4* lt_v;       // NL*3 light vertices (reference order); .w = float(unique normal)
-    float light_bound;        // max |coordinate| over light vertices
-    const double4* lt_n;      // NL: unique normal xyz, w = RadianceRGB::sum()
-    const float4* lt_pk;      // NL*3: (p0.x, p1.x, p2.x, nl.x), (.. .y), (.. .z) -- packed cheap stages
-    const float* lt_d;        // NL: float(nl . p0)
-    const double2* lt_w;      // NL*5: p0, p1, p2 (fp64), 2 RadianceRGB::sum()
-    const float4* lt_f;       // NL*4: fp32 records of MCPT_RENDER_PRECISION_FP32 (LightF32: p0, p1, p2 with the
-                              // area normal in .w, then 2 RadianceRGB::sum() as fp64 bits)
-    const struct LightPair* lt_pair;  // 32*nchunks light pairs for k_prep_cull_lanes (scalar loads)
-    // exact-pick band: per 64-light chunk a bounding sphere (centre, radius) of its
-    // vertices and (max sum L, max sum L / shortest edge) of its lights; the same over the whole table
-    const float4* chunk_sph;  // nchunks
-    const float2* chunk_sk;   // nchunks
-    double band_ctr[3], band_R, band_S, band_K;
-    const float4* leaf_v;     // per leaf slot: 3 float4 (w of the first = facet id bits)
-    const BvhNode4* bvh4;     // 4-wide collapse of bvh (same leaves), breadth-first node order
-    const BvhNode4* lbvh4;
-    const BvhNode4Q* bvh4q;   // the same trees as 64-B compressed nodes (k_rays_persistent)
-    const BvhNode4Q* lbvh4q;
-    int nbvh4, nlbvh4;        // node counts
-    const float4* lleaf_v;
-    // 8-wide compressed trees (BvhNode8Q, k_rays_cw8) and their triangle slots (3 float4 each, w of the
-    // first = facet id bits; unused slots are never read); null when a tree does not fit the 24-bit base
-    const BvhNode8Q* bvh8;
-    const BvhNode8Q* lbvh8;
-    const float4* tri8_v;
-    const float4* ltri8_v;
-    // select_a_point_from_lights (MCPT_MODE_SHADE_AREA): the lightsRadiance map in name order --
-    // RadianceRGB::sum() per light and its running sum, the light-table run of its triangles -- and
-    // the triangles' areas (Mylight.cpp:66-69) with their running sum within their light
-    int ngroups;
-    const double* grp_sum;
-    const double* grp_cum;
-    const int2* grp_range;    // (first light-table index, count)
-    const double* l_area;
-    const double* l_area_cum;
-    // reference uniform grid (MCPT_ACCEL_GRID; null until mcpt_scene_meshing / a grid render)
-    const int* g_start;       // CSR cell -> facets
-    const int* g_tri;
-    double g_mn[3], g_inv_d;
-    int g_lim[3], g_gd[3];
-};
-
 __device__ inline d3 cam_dir(const CamFrame& f, int i, int j) {  // main.cpp:563-564
     d3 delta = mk3(-f.pixellen * (i - (f.H - 1) / 2.0), f.pixellen * (j - (f.W - 1) / 2.0), 0);
     return normalized(cols_mul(f.U, f.V, f.N, add(delta, mk3(0, 0, f.wlen))));
@@ -137,8 +74,6 @@ __device__ inline d3 cam_dir_at(const CamFrame& f, double y, double x) {
 // BVH traversal: fp32 slab tests on conservatively enlarged boxes (prune only), fp64 reference
 // triangle test on every candidate.  Stack in LDS, [depth][thread] layout (conflict-free).
 // ============================================================================================
-constexpr int kStack = 48;
-constexpr int kLeafBits = kBvh4LeafBits;  // (5) leaf code ~((first slot << kLeafBits) | count)
 constexpr int kRayBlock = 256;
 constexpr int kRayLds = 16;  // LDS stack entries per lane of trace4_ww (16 KB per 256 lanes)
 // k_mis_rays: the first kRayTop nodes of the traversed BVH4 (breadth-first numbering: its top
@@ -2043,7 +1978,6 @@ __device__ v4u struct_load_b128(__amdgpu_buffer_rsrc_t r, int vindex, int voffse
 constexpr int kLtW = 80;  // bytes per light record in lt_w (the descriptor's stride)
 // the light-record descriptor for k_prep_pk2 / prep_select: stride kLtW, the whole padded table
 // plus the sentinel records (lt_w has nl_pad + kSentinelPad records)
-constexpr int kSentinelPad = 64;
 __device__ inline __amdgpu_buffer_rsrc_t light_record_rsrc(const DScene& S, int ngroups4) {
     return __builtin_amdgcn_make_buffer_rsrc((void*)S.lt_w, kLtW, (ngroups4 * 256 + kSentinelPad) * kLtW, kBufFlags);
 }
@@ -4720,129 +4654,19 @@ __global__ __launch_bounds__(kTraceBlock) void k_trace_batch_cw8(DScene S, int n
 // ============================================================================================
 // host side
 // ============================================================================================
-#define HIP_OK(x)                                                                              \
-    do {                                                                                       \
-        hipError_t e_ = (x);                                                                   \
-        if (e_ != hipSuccess) {                                                                \
-            set_error("%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return MCPT_E_DEVICE;                                                              \
-        }                                                                                      \
-    } while (0)
-
-namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-
-struct DeviceState {
-    int device = -1;
-    DScene d{};
-    std::vector<void*> allocs;
-    hipStream_t stream = nullptr;
-    // reusable work buffers
-    DevBuf hit_f, hit_tbg, root_pnw, root_kind, fb, rank_fb, stats, work, qa[14], qb[14], qs[14], aux[9], sl[13], cache_bt, cache_lst, cache_info, cache_w, masks;
-    DevBuf cull_keys, cull_order, cull_count;  // the cull's node order (CullOrder)
-    DevBuf exact, exact_scr, slack;  // exact pick: list, k_prep_exact's scratch, per-node slack
-    DevBuf lit_slot, lit_pool;        // exact pick: roots' literal sums per pixel (RootLit)
-    DevBuf sc_cum, sc_wsum, sc_last;  // small-table root-point cache (SmallCache)
-    DevBuf pick_tab, pick_wsum;       // the root pick table of a run's window (PickTable)
-    // adaptive sampling: half sums A / B, active lists and state bytes (ping-pong), per-block survivor counts
-    // (+ the total), the library's own count / noise maps
-    DevBuf ad_acc[2], ad_list[2], ad_state[2], ad_blk, ad_count, ad_noise;
-    int ad_last_list = -1, ad_last_n = 0;  // the last active list built (mcpt_debug_adaptive_active)
-    DevBuf aov;  // mcpt_render_aovs: the four maps of a host call (10 doubles per pixel)
-    DevBuf ray_o, ray_d;  // mcpt_render_rays: a host call's origins and directions
-    int spill_cap = 0;  // nodes the spill stack qs holds (grown on demand)
-    bool bvh8_tried = false;  // ensure_bvh8 ran on this device
-    DevBuf g_start, g_tri;  // the scene's uniform grid (MCPT_ACCEL_GRID), version grid_version
-    int grid_version = 0;
-    // mcpt_scene_update on this device: what refit.hip's kernels need beside the scene's own arrays (built at the
-    // device state's first update: the facet -> leaf-slot map, the dirty bytes, the counters and the first node of
-    // every level of the breadth-first 4-wide tree) and the staging copies of a host call's arrays
-    bool refit_ready = false;
-    RefitDev refit{};
-    std::vector<int32_t> level_first;
-    DevBuf up_pos, up_nrm;
-    // a light move on this device, built at the state's first one: the light tables' pointers for
-    // light_tables.hip, a second RefitDev over the light-only tree (lbvh4, lbvh4q, lleaf_v; tri_v / tri_n shared with
-    // `refit`) with its own slot map, dirty bytes, counters and levels, a pinned copy of the by-value constants and
-    // the events around the light stage
-    bool light_ready = false;
-    LightTabDev ltab{};
-    RefitDev lrefit{};
-    std::vector<int32_t> llevel_first;
-    LightGlobals* pinned_globals = nullptr;
-    hipEvent_t evl0 = nullptr, evl1 = nullptr;
-    // mcpt_scene_rebuild on this device: the leaf slots of the main tree the state holds (the host
-    // tree's until the first rebuild, F after it); the builder's scratch; two sets of tree arrays sized for F nodes and
-    // F slots, built into in turn (the tree in use is never the one being written); the identity slot_start, the
-    // counters and the cost reduction's words, shared by both sets.  All allocated at the first rebuild (the words at
-    // the first mcpt_scene_tree_cost) and reused.
-    size_t nslots = 0;
-    RebuildWork* rb_work = nullptr;
-    struct RebuildSet {
-        DevBuf bvh4, bvh4q, leaf_v, slot_list, slot_dirty, node_dirty;
-    } rb_set[2];
-    DevBuf rb_slot_start, rb_counters, cost_words;
-    int rb_next = 0;
-    // mcpt_scene_pose_save: the previous pose's copies of d.tri_v / d.tri_n (null until the first save or, for a state
-    // created after it, from the host copy: the previous pose is then the current one)
-    DevBuf prev_v, prev_n;
-    // mcpt_scene_rest_save: the rest pose's copies of d.tri_v / d.tri_n, the source of every mcpt_scene_transform
-    DevBuf rest_v, rest_n;
-    unsigned* pinned_count = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, evp0 = nullptr, evp1 = nullptr, evr0 = nullptr, evr1 = nullptr;
-};
-
-}  // namespace
-
-struct mcpt_scene {
-    HostScene host;
-    Bvh bvh, lbvh;
-    Bvh8 bvh8, lbvh8;  // 8-wide compressed trees of bvh / lbvh (k_rays_cw8), built on first use (ensure_bvh8)
-    bool bvh8_built = false;
-    std::mutex bvh8_mu;
-    Grid grid;             // Myobj::cal_scene_boundingbox(eye) + meshing(n0) (mcpt_scene_meshing)
-    int grid_version = 0;  // bumped by every rebuild; devices re-upload on mismatch
-    std::vector<std::unique_ptr<DeviceState>> devs;
-    std::mutex devs_mu;             // devs (render_multi creates device states on its worker threads)
-    std::vector<int> comm_devices;  // distinct devices of the cached ncclCommInitAll communicators
-    std::vector<void*> comms;
-    std::mutex mu;
-    // mcpt_scene_update: the build's bounding box, largest axis extent and box margin (Builder::margin) stay the
-    // scene's for good; `updated` once a call succeeded (the 8-wide trees are then stale and refused); the refit
-    // index of `bvh` and the facet -> leaf-slot map, both built at the first update
-    double build_lo[3] = {0, 0, 0}, build_hi[3] = {0, 0, 0}, build_ext = 0, margin = 0;
-    bool updated = false;
-    BvhRefitIndex refit_ix;
-    std::vector<int32_t> slot_start, slot_list;
-    // mcpt_scene_set_lights_movable: the switch, the numbers of the last successful update / transform
-    // call, and the same index and slot map for `lbvh`, built at the first light move
-    bool lights_movable = false;
-    mcpt_light_update_stats light_stats{};
-    BvhRefitIndex lrefit_ix;
-    std::vector<int32_t> lslot_start, lslot_list;
-    // mcpt_scene_rebuild: nodes and leaf slots of the first rebuilt state's main tree (0: never rebuilt), for
-    // mcpt_scene_accel_bytes
-    uint64_t rebuilt_nodes = 0, rebuilt_slots = 0;
-    // mcpt_scene_pose_save: host.pos / host.nrm as they were at the last save (empty until the first one)
-    bool pose_saved = false;
-    std::vector<float> prev_pos, prev_nrm;
-    // mcpt_scene_rest_save / mcpt_scene_transform: the rest pose (host.pos / host.nrm at the save);
-    // the facet ranges of host.pos / host.nrm / host.unique_n / bvh that are behind the devices, and whether prev_pos /
-    // prev_nrm are (a pose_save while ranges were pending); host_sync brings all of it up to date from the first
-    // device state.  host_mu guards pending and prev_stale and the sync itself: every read or write of the two takes it
-    // (transform, pose_save, host_pending, host_sync), so render_multi's workers, which create device states and so
-    // sync without holding `mu`, see a consistent list.  It does NOT order a render against a concurrent transform of
-    // the same handle: as for an update, one render or update at a time per handle is the caller's rule (`mu`)
-    bool rest_saved = false;
-    std::vector<float> rest_pos, rest_nrm;
-    PendingRanges pending;
-    bool prev_stale = false;
-    std::mutex host_mu;
-};
+// shared with scene_edit.hip and tree_debug.hip (scene_state.h), as are the mcpt:: functions further down
+std::atomic<int64_t> mcpt::g_device_bytes_live{0};
+// mcpt_debug_set_rebuild_leaf_max: process-wide override of the rebuild's leaf size (0: kRebuildLeafMax)
+std::atomic<int> mcpt::g_rebuild_leaf_max{0};
+int mcpt::prep_chunks(int NL) { return std::max(1, (NL + 63) / 64); }
+int mcpt::ensure(DevBuf& b, size_t bytes) {
+    if (b.bytes >= bytes && b.p) return MCPT_OK;
+    HIP_OK(b.release());
+    HIP_OK(hipMalloc(&b.p, std::max<size_t>(bytes, 256)));
+    b.bytes = std::max<size_t>(bytes, 256);
+    g_device_bytes_live += (int64_t)b.bytes;
+    return MCPT_OK;
+}
 
 namespace {
 
@@ -4854,30 +4678,12 @@ std::vector<double> soa3(const double* v, int n) {
     return o;
 }
 
-int ensure(DevBuf& b, size_t bytes) {
-    if (b.bytes >= bytes && b.p) return MCPT_OK;
-    if (b.p) HIP_OK(hipFree(b.p));
-    b.p = nullptr;
-    HIP_OK(hipMalloc(&b.p, std::max<size_t>(bytes, 256)));
-    b.bytes = std::max<size_t>(bytes, 256);
-    return MCPT_OK;
-}
 // the cull's node-order scratch for up to n nodes
 int cull_order_bufs(DeviceState& D, size_t n, CullOrder* co) {
     int rc;
     if ((rc = ensure(D.cull_keys, n)) || (rc = ensure(D.cull_order, 4 * n)) || (rc = ensure(D.cull_count, 8 * kCullBuckets)))
         return rc;
     *co = CullOrder{(unsigned char*)D.cull_keys.p, (int*)D.cull_order.p, (unsigned*)D.cull_count.p};
-    return MCPT_OK;
-}
-
-template <class T>
-int upload(DeviceState& D, const std::vector<T>& v, const T** out) {
-    void* p = nullptr;
-    HIP_OK(hipMalloc(&p, std::max<size_t>(v.size() * sizeof(T), 64)));
-    D.allocs.push_back(p);  // owned by D from here on, even if the copy fails
-    if (!v.empty()) HIP_OK(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    *out = static_cast<const T*>(p);
     return MCPT_OK;
 }
 
@@ -4966,105 +4772,12 @@ std::vector<float4> leaf_vertices(const HostScene& s, const Bvh& b) {
     return v;
 }
 
-int prep_chunks(int NL);
-
-// the facet -> leaf-slot map and the binary tree's refit index, built at the handle's first update or transform
-void ensure_slot_map(mcpt_scene* sc) {
-    if (!sc->slot_start.empty()) return;
-    make_facet_slot_map(sc->bvh, sc->host.F, sc->slot_start, sc->slot_list);
-    sc->refit_ix = make_bvh_refit_index(sc->bvh);
-}
-// the same for the light-only tree, built at the handle's first light move
-void ensure_light_slot_map(mcpt_scene* sc) {
-    if (!sc->lslot_start.empty()) return;
-    make_facet_slot_map(sc->lbvh, sc->host.F, sc->lslot_start, sc->lslot_list);
-    sc->lrefit_ix = make_bvh_refit_index(sc->lbvh);
-}
-bool range_has_light(const mcpt_scene* sc, int32_t first, int32_t end) {
-    for (int f = first; f < end; f++)
-        if (sc->host.light_of[f] >= 0) return true;
-    return false;
-}
-
-// puts the thread back on the device it was on when a function that visits device states returns, on every path
-struct DeviceRestore {
-    int device = -1;
-    ~DeviceRestore() {
-        if (device >= 0) (void)hipSetDevice(device);
-    }
-};
-
-// mcpt_scene_host_sync: the host copy brought up to date from the first device state (every state holds the same
-// arrays) -- the pending ranges of tri_v / tri_n into host.pos / host.nrm, then update_apply's host half over them,
-// and the previous pose as a whole if a pose_save left it stale.  Every reader of host.pos, host.nrm, host.unique_n,
-// the binary tree's boxes, prev_pos or prev_nrm calls this first; a no-op when nothing is pending.
-int host_sync(mcpt_scene* sc) {
-    std::lock_guard<std::mutex> lk(sc->host_mu);
-    if (sc->pending.r.empty() && !sc->prev_stale) return MCPT_OK;
-    DeviceState* D = nullptr;
-    {
-        std::lock_guard<std::mutex> dl(sc->devs_mu);
-        if (!sc->devs.empty()) D = sc->devs.front().get();
-    }
-    if (!D) {
-        set_error("the host copy is behind the devices but the scene has no device state");
-        return MCPT_E_DEVICE;
-    }
-    DeviceRestore back;
-    HIP_OK(hipGetDevice(&back.device));
-    HIP_OK(hipSetDevice(D->device));
-    HostScene& hs = sc->host;
-    // every copy lands in a buffer of its own first: a copy that fails leaves the host copy as it was, still pending
-    std::vector<std::vector<float4>> dv(sc->pending.r.size());
-    std::vector<std::vector<float>> dn(sc->pending.r.size());
-    for (size_t i = 0; i < sc->pending.r.size(); i++) {
-        const size_t f0 = (size_t)sc->pending.r[i].first, n = (size_t)sc->pending.r[i].second - f0;
-        dv[i].resize(3 * n);
-        dn[i].resize(9 * n);
-        HIP_OK(hipMemcpy(dv[i].data(), D->d.tri_v + 3 * f0, 3 * n * sizeof(float4), hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(dn[i].data(), D->d.tri_n + 9 * f0, 9 * n * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    std::vector<float4> pv;
-    std::vector<float> pn;
-    if (sc->prev_stale && hs.F > 0) {  // the device copies change only at a pose_save: they are still that pose
-        pv.resize(3 * (size_t)hs.F);
-        pn.resize(hs.nrm.size());
-        HIP_OK(hipMemcpy(pv.data(), D->prev_v.p, pv.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(pn.data(), D->prev_n.p, pn.size() * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    auto unpack = [](const std::vector<float4>& v, float* out) {
-        for (size_t i = 0; i < v.size(); i++) out[3 * i] = v[i].x, out[3 * i + 1] = v[i].y, out[3 * i + 2] = v[i].z;
-    };
-    for (size_t i = 0; i < sc->pending.r.size(); i++) {
-        const size_t f0 = (size_t)sc->pending.r[i].first;
-        unpack(dv[i], hs.pos.data() + 9 * f0);
-        std::copy(dn[i].begin(), dn[i].end(), hs.nrm.begin() + 9 * f0);
-    }
-    if (!sc->pending.r.empty()) {
-        ensure_slot_map(sc);
-        host_refresh_ranges(hs, sc->bvh, sc->refit_ix, sc->slot_start, sc->slot_list, sc->pending, sc->margin);
-        bool lights = false;  // a transform moved light triangles (mcpt_scene_set_lights_movable): areas, light-only tree
-        for (const auto& p : sc->pending.r) lights = lights || range_has_light(sc, p.first, p.second);
-        if (lights) {
-            ensure_light_slot_map(sc);
-            host_refresh_lights(hs, sc->lbvh, sc->lrefit_ix, sc->lslot_start, sc->lslot_list, sc->pending, sc->margin);
-        }
-        sc->grid.ok = false;  // as update_apply: rebuilt from the new positions by the next grid-mode call
-    }
-    if (sc->prev_stale) {
-        sc->prev_pos.resize(hs.pos.size());
-        unpack(pv, sc->prev_pos.data());
-        sc->prev_nrm = std::move(pn);
-    }
-    sc->pending.r.clear();
-    sc->prev_stale = false;
-    return MCPT_OK;
-}
+}  // namespace
 
 // the device's scene state, created (scene, light tables and BVHs uploaded) on first use.  Thread-safe
 // for distinct devices: render_multi's workers create theirs concurrently (the lookup and the insertion
 // hold devs_mu, the uploads do not)
-int get_device_state(mcpt_scene* sc, int device, DeviceState** out) {
+int mcpt::get_device_state(mcpt_scene* sc, int device, DeviceState** out) {
     if (device < 0) HIP_OK(hipGetDevice(&device));
     {
         std::lock_guard<std::mutex> lk(sc->devs_mu);
@@ -5259,24 +4972,18 @@ int get_device_state(mcpt_scene* sc, int device, DeviceState** out) {
     if ((rc = upload(*D, quantize_bvh4(b4), &d.bvh4q))) return rc;
     if ((rc = upload(*D, quantize_bvh4(lb4), &d.lbvh4q))) return rc;
     if ((rc = upload(*D, leaf_vertices(s, sc->lbvh), &d.lleaf_v))) return rc;
-    if (sc->pose_saved) {  // a state created after mcpt_scene_pose_save: its previous pose from the host copy
+    // a state created after mcpt_scene_pose_save or mcpt_scene_rest_save: its previous / rest pose from the host copy
+    auto pose_from_host = [&](const std::vector<float>& pos, const std::vector<float>& nrm, DevBuf& dv, DevBuf& dn) -> int {
         std::vector<float4> pv(tv.size());
-        for (int f = 0; f < s.F; f++)
-            for (int k = 0; k < 3; k++)
-                pv[3 * f + k] = make_float4(sc->prev_pos[9 * f + 3 * k], sc->prev_pos[9 * f + 3 * k + 1], sc->prev_pos[9 * f + 3 * k + 2], 0.f);
-        if ((rc = ensure(D->prev_v, pv.size() * sizeof(float4))) || (rc = ensure(D->prev_n, std::max<size_t>(s.nrm.size(), 1) * sizeof(float))))
-            return rc;
-        HIP_OK(hipMemcpy(D->prev_v.p, pv.data(), pv.size() * sizeof(float4), hipMemcpyHostToDevice));
-        if (!sc->prev_nrm.empty()) HIP_OK(hipMemcpy(D->prev_n.p, sc->prev_nrm.data(), sc->prev_nrm.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (sc->rest_saved) {  // and one created after mcpt_scene_rest_save: its rest pose likewise
-        std::vector<float4> rv(tv.size());
-        for (size_t i = 0; i < 3 * (size_t)s.F; i++) rv[i] = make_float4(sc->rest_pos[3 * i], sc->rest_pos[3 * i + 1], sc->rest_pos[3 * i + 2], 0.f);
-        if ((rc = ensure(D->rest_v, rv.size() * sizeof(float4))) || (rc = ensure(D->rest_n, std::max<size_t>(s.nrm.size(), 1) * sizeof(float))))
-            return rc;
-        HIP_OK(hipMemcpy(D->rest_v.p, rv.data(), rv.size() * sizeof(float4), hipMemcpyHostToDevice));
-        if (!sc->rest_nrm.empty()) HIP_OK(hipMemcpy(D->rest_n.p, sc->rest_nrm.data(), sc->rest_nrm.size() * sizeof(float), hipMemcpyHostToDevice));
-    }
+        for (size_t i = 0; i < 3 * (size_t)s.F; i++) pv[i] = make_float4(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], 0.f);
+        if (int re = ensure(dv, pv.size() * sizeof(float4))) return re;
+        if (int re = ensure(dn, std::max<size_t>(s.nrm.size(), 1) * sizeof(float))) return re;
+        HIP_OK(hipMemcpy(dv.p, pv.data(), pv.size() * sizeof(float4), hipMemcpyHostToDevice));
+        if (!nrm.empty()) HIP_OK(hipMemcpy(dn.p, nrm.data(), nrm.size() * sizeof(float), hipMemcpyHostToDevice));
+        return MCPT_OK;
+    };
+    if (sc->pose_saved && (rc = pose_from_host(sc->prev_pos, sc->prev_nrm, D->prev_v, D->prev_n))) return rc;
+    if (sc->rest_saved && (rc = pose_from_host(sc->rest_pos, sc->rest_nrm, D->rest_v, D->rest_n))) return rc;
     HIP_OK(hipStreamCreateWithFlags(&D->stream, hipStreamNonBlocking));
     HIP_OK(hipHostMalloc(&D->pinned_count, 64 + kCtrlBytes));
     HIP_OK(hipEventCreate(&D->ev0));
@@ -5290,6 +4997,8 @@ int get_device_state(mcpt_scene* sc, int device, DeviceState** out) {
     sc->devs.push_back(std::move(D));
     return MCPT_OK;
 }
+
+namespace {
 
 int alloc_aux(DevBuf* b, int cap, Aux& a) {
     const size_t c = (size_t)cap;
@@ -5374,10 +5083,7 @@ int alloc_slots(DevBuf* b, int rcap, Slots& T, hipStream_t st, bool grow, int rp
     }
     HIP_OK(hipMemcpyAsync(nt.ctrl, c.data(), kCtrlBytes, hipMemcpyHostToDevice, st));
     HIP_OK(hipStreamSynchronize(st));
-    for (int k = 0; k < kSlotArrays; k++) {
-        if (b[k].p) HIP_OK(hipFree(b[k].p));
-        b[k] = nb[k];
-    }
+    for (int k = 0; k < kSlotArrays; k++) b[k] = std::move(nb[k]);
     T = nt;
     return MCPT_OK;
 }
@@ -5413,7 +5119,6 @@ int validate_camera(const mcpt_camera* cam) {
     return MCPT_OK;
 }
 
-int prep_chunks(int NL) { return std::max(1, (NL + 63) / 64); }
 size_t prep_lds_bytes(int nchunks) { return 4 * ((size_t)nchunks * sizeof(double) + kPrepQueue * sizeof(int)); }
 // per-wave LDS bytes of k_prep_pk2: batch totals + uint16 candidate list, 16-byte aligned
 int prep_list_wave_bytes(int nchunks) { return (int)((nchunks * 8 + nchunks * 64 * 2 + 15) / 16 * 16); }
@@ -5565,19 +5270,21 @@ int use_grid(mcpt_scene* sc, DeviceState& D, const double eye[3], int n0) {
 // the 8-wide trees (k_rays_cw8, MCPT_DEBUG_RAYS_CW8 / MCPT_DEBUG_HIT_CW8, mcpt_debug_bvh8_check): built on the
 // host on first use (1.2 s for the 1 M-triangle scene, so only runs that ask for them pay it) and uploaded to
 // a device on its first use there; a tree whose reserved node slots exceed the 24-bit stack base stays null
-void ensure_bvh8_host(mcpt_scene* sc) {
+}  // namespace
+void mcpt::ensure_bvh8_host(mcpt_scene* sc) {
     std::lock_guard<std::mutex> lk(sc->bvh8_mu);
     if (sc->bvh8_built) return;
     sc->bvh8 = build_bvh8(sc->host, sc->bvh);
     sc->lbvh8 = build_bvh8(sc->host, sc->lbvh);
     sc->bvh8_built = true;
 }
-int bvh8_refused(const mcpt_scene* sc) {
+int mcpt::bvh8_refused(const mcpt_scene* sc) {
     if (!sc->updated) return MCPT_OK;
     set_error("the 8-wide trees are not refit by mcpt_scene_update: MCPT_DEBUG_RAYS_CW8, MCPT_DEBUG_HIT_CW8 and "
               "mcpt_debug_bvh8_check are refused for a scene handle after its first update");
     return MCPT_E_INVALID;
 }
+namespace {
 int ensure_bvh8(mcpt_scene* sc, DeviceState* D) {
     if (int rc = bvh8_refused(sc)) return rc;
     ensure_bvh8_host(sc);
@@ -5590,12 +5297,15 @@ int ensure_bvh8(mcpt_scene* sc, DeviceState* D) {
     // so its error is reported each time instead of a later "no 8-wide tree"; only success marks the device tried
     // (a tree too large for the 24-bit stack base then stays null by design)
     struct Undo {
-        DScene& d;
+        DeviceState& D;
+        const size_t nallocs;  // the attempt's uploads go again: D.allocs trimmed back to its size at entry
         bool armed = true;
         ~Undo() {
-            if (armed) d.bvh8 = d.lbvh8 = nullptr, d.tri8_v = d.ltri8_v = nullptr;
+            if (!armed) return;
+            D.d.bvh8 = D.d.lbvh8 = nullptr, D.d.tri8_v = D.d.ltri8_v = nullptr;
+            D.allocs.resize(nallocs);
         }
-    } undo{d};
+    } undo{*D, D->allocs.size()};
     for (int t = 0; t < 2; t++) {
         const Bvh8& b8 = t == 0 ? sc->bvh8 : sc->lbvh8;
         // trace_cw8 / k_rays_cw8 push at most one node group per level: a tree deeper than kStack could drop one
@@ -5661,8 +5371,6 @@ struct AdaptiveRun {
     double* noise;
 };
 
-// mcpt_debug_set_rebuild_leaf_max: process-wide override of the rebuild's leaf size (0: kRebuildLeafMax)
-std::atomic<int> g_rebuild_leaf_max{0};
 // mcpt_debug_set_pick_table: process-wide overrides of the root pick table's rules (0: the default)
 std::atomic<int> g_pick_min_samples{0}, g_pick_window{0};
 // the fewest samples per pixel of a run (and of its windows) at which the table is built: a table pass stages a
@@ -6113,10 +5821,7 @@ struct WavefrontRun {
         if (spill_n > 0 && qs.p)
             hipLaunchKernelGGL(k_queue_move, dim3((unsigned)((spill_n + 255) / 256)), dim3(256), 0, st, qs, 0, nq, 0, (int)spill_n);
         HIP_OK(hipStreamSynchronize(st));
-        for (int k = 0; k < 14; k++) {
-            if (D.qs[k].p) HIP_OK(hipFree(D.qs[k].p));
-            D.qs[k] = nb[k];
-        }
+        for (int k = 0; k < 14; k++) D.qs[k] = std::move(nb[k]);
         D.spill_cap = ncap;
         qs = nq;
         return MCPT_OK;
@@ -6724,7 +6429,8 @@ int check_opts(const mcpt_render_opts* o) {
 
 // the caller's framebuffer must be device memory of `device` (fp64 hardware atomics are lost on
 // host / managed memory, and a host pointer the runtime does not know would fault the GPU)
-int check_device_buffer(const void* p, int device, const char* name = "dev_out_rgb") {
+}  // namespace
+int mcpt::check_device_buffer(const void* p, int device, const char* name) {
     hipPointerAttribute_t a;
     if (hipPointerGetAttributes(&a, p) != hipSuccess) {
         (void)hipGetLastError();
@@ -6741,6 +6447,7 @@ int check_device_buffer(const void* p, int device, const char* name = "dev_out_r
     }
     return MCPT_OK;
 }
+namespace {
 
 // shard k of n of [s0, s1): contiguous and balanced (sizes differ by at most one sample)
 void shard_range(int s0, int s1, int k, int n, int* a, int* b) {
@@ -7317,32 +7024,7 @@ int mcpt_scene_create(const mcpt_scene_desc* d, mcpt_scene** out) {
 void mcpt_scene_destroy(mcpt_scene* sc) {
     if (!sc) return;
     comm_all_destroy(sc->comms);
-    for (auto& D : sc->devs) {
-        (void)hipSetDevice(D->device);
-        for (void* p : D->allocs) (void)hipFree(p);
-        std::vector<DevBuf*> bufs = {&D->hit_f, &D->hit_tbg, &D->fb, &D->rank_fb, &D->stats, &D->work, &D->cache_bt, &D->cache_lst,
-                                     &D->cache_info, &D->cache_w, &D->masks, &D->g_start, &D->g_tri, &D->root_pnw,
-                                     &D->root_kind, &D->exact, &D->exact_scr, &D->slack, &D->lit_slot, &D->lit_pool,
-                                     &D->sc_cum, &D->sc_wsum, &D->sc_last, &D->cull_keys, &D->cull_order, &D->cull_count,
-                                     &D->ad_acc[0], &D->ad_acc[1], &D->ad_list[0], &D->ad_list[1], &D->ad_state[0],
-                                     &D->ad_state[1], &D->ad_blk, &D->ad_count, &D->ad_noise, &D->aov, &D->up_pos, &D->up_nrm,
-                                     &D->prev_v, &D->prev_n, &D->rest_v, &D->rest_n, &D->rb_slot_start, &D->rb_counters,
-                                     &D->cost_words};
-        for (auto& rs : D->rb_set) bufs.insert(bufs.end(), {&rs.bvh4, &rs.bvh4q, &rs.leaf_v, &rs.slot_list, &rs.slot_dirty, &rs.node_dirty});
-        rebuild_work_destroy(D->rb_work);
-        for (int k = 0; k < 14; k++) bufs.insert(bufs.end(), {&D->qa[k], &D->qb[k], &D->qs[k]});
-        for (int k = 0; k < 9; k++) bufs.push_back(&D->aux[k]);
-        for (int k = 0; k < 13; k++) bufs.push_back(&D->sl[k]);
-        for (DevBuf* b : bufs)
-            if (b->p) (void)hipFree(b->p);
-        if (D->pinned_count) (void)hipHostFree(D->pinned_count);
-        if (D->pinned_globals) (void)hipHostFree(D->pinned_globals);
-        if (D->stream) (void)hipStreamDestroy(D->stream);
-        hipEvent_t evs[] = {D->ev0, D->ev1, D->evp0, D->evp1, D->evr0, D->evr1, D->evl0, D->evl1};
-        for (hipEvent_t e : evs)
-            if (e) (void)hipEventDestroy(e);
-    }
-    delete sc;
+    delete sc;  // every device state frees what it holds (~DeviceState)
 }
 
 int mcpt_scene_accel_bytes(const mcpt_scene* sc, uint64_t* bytes) {
@@ -7381,790 +7063,6 @@ int mcpt_scene_arrays(const mcpt_scene* sc, float* pos, float* nrm, int32_t* mat
     if (lrad) std::copy(h.light_rad.begin(), h.light_rad.end(), lrad);
     if (un) std::copy(h.unique_n.begin(), h.unique_n.end(), un);
     return MCPT_OK;
-}
-
-// ---- mcpt_scene_update (include/mcpt.h; the kernels are refit.hip's) ----
-void mcpt_update_stats_init(mcpt_update_stats* st) {
-    if (!st) return;
-    std::memset((void*)st, 0, sizeof *st);
-    st->struct_size = sizeof *st;
-}
-
-// every refusal that needs neither the values nor a device
-// `data`: the call's required pointer argument and its name in the message
-static int update_check_args(const mcpt_scene* sc, int32_t first, int32_t count, const void* data, const mcpt_update_stats* stats,
-                             const char* who = "mcpt_scene_update", const char* data_name = "positions") {
-    if (!sc || !data) {
-        set_error("%s: NULL %s", who, !sc ? "scene" : data_name);
-        return MCPT_E_INVALID;
-    }
-    if (count < 1 || first < 0 || (int64_t)first + count > sc->host.F) {
-        set_error("%s: facets [%d, %lld) are not a non-empty range of the scene's %d facets", who, first,
-                  (long long)first + count, sc->host.F);
-        return MCPT_E_INVALID;
-    }
-    if (stats && stats->struct_size != sizeof(mcpt_update_stats)) {
-        set_error("mcpt_update_stats.struct_size %u does not match this library's %zu (header / library version mismatch)",
-                  stats->struct_size, sizeof(mcpt_update_stats));
-        return MCPT_E_INVALID;
-    }
-    return MCPT_OK;
-}
-static int update_check_lights(const mcpt_scene* sc, int32_t first, int32_t count, const char* who = "mcpt_scene_update") {
-    if (sc->lights_movable) return MCPT_OK;  // mcpt_scene_set_lights_movable: light facets move as any other
-    for (int f = first; f < first + count; f++)
-        if (sc->host.light_of[f] >= 0) {
-            set_error("%s: facet %d is a light triangle (light %d); lights cannot move", who, f, sc->host.light_of[f]);
-            return MCPT_E_INVALID;
-        }
-    return MCPT_OK;
-}
-// the arena: the build's box grown by its largest axis extent on every side
-static void update_arena(const mcpt_scene* sc, double lo[3], double hi[3]) {
-    for (int a = 0; a < 3; a++) lo[a] = sc->build_lo[a] - sc->build_ext, hi[a] = sc->build_hi[a] + sc->build_ext;
-}
-static int update_check_values(const mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm,
-                               const char* who = "mcpt_scene_update") {
-    double lo[3], hi[3];
-    update_arena(sc, lo, hi);
-    for (size_t i = 0; i < 9 * (size_t)count; i++) {
-        const int f = first + (int)(i / 9), a = (int)(i % 3);
-        if (!std::isfinite(pos[i]) || (nrm && !std::isfinite(nrm[i]))) {
-            set_error("%s: facet %d has a non-finite %s", who, f, std::isfinite(pos[i]) ? "normal" : "position");
-            return MCPT_E_INVALID;
-        }
-        if (pos[i] < lo[a] || pos[i] > hi[a]) {
-            set_error("%s: facet %d has a position outside the arena (axis %d: %g not in [%g, %g], the "
-                      "build's box grown by its largest extent)", who, f, a, (double)pos[i], lo[a], hi[a]);
-            return MCPT_E_INVALID;
-        }
-    }
-    return MCPT_OK;
-}
-
-// the first node of every level of a breadth-first 4-wide tree (nodes with packed leaf codes); false if the tree is
-// not in that order or an index is out of range
-static bool bvh4_levels(const std::vector<BvhNode4>& b4, size_t nslots, std::vector<int32_t>* levels) {
-    const int32_t nn = (int32_t)b4.size();
-    std::vector<int32_t> lf{0, 1};
-    bool ok = !b4.empty();
-    while (ok) {
-        const int32_t n0 = lf[lf.size() - 2], n1 = lf.back();
-        int64_t next = n1;  // breadth-first order: the inner children of a level are the next level, in order
-        for (int32_t n = n0; n < n1 && ok; n++)
-            for (int k = 0; k < 4; k++) {
-                const int32_t c = b4[n].child[k];
-                if (c == kBvh4Empty) continue;
-                if (c >= 0) {
-                    ok = ok && c == next++ && c < nn;
-                } else {
-                    const int64_t s0 = ~c >> kLeafBits, cnt = ~c & ((1 << kLeafBits) - 1);
-                    ok = ok && s0 + cnt <= (int64_t)nslots;
-                }
-            }
-        if (next == n1) break;
-        ok = ok && next <= nn;
-        lf.push_back((int32_t)next);
-    }
-    if (!ok || lf.back() != nn) return false;
-    *levels = std::move(lf);
-    return true;
-}
-// what a device state's first update builds: the CSR facet -> leaf-slot map, the dirty bytes, the counters and the
-// first node of every level; the tree's indices are checked here once, so the kernels need no bounds tests
-static int ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
-    if (D.refit_ready) return MCPT_OK;
-    const DScene& d = D.d;
-    const size_t nslots = D.nslots;
-    std::vector<BvhNode4> b4(d.nbvh4);
-    HIP_OK(hipMemcpy(b4.data(), d.bvh4, b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
-    std::vector<int32_t> lf;
-    if (!bvh4_levels(b4, nslots, &lf)) {
-        set_error("mcpt_scene_update: device %d's 4-wide tree is not in breadth-first order", D.device);
-        return MCPT_E_SCENE;
-    }
-    RefitDev& r = D.refit;
-    r.F = d.F;
-    r.nslots = (int32_t)nslots;
-    r.nnodes = d.nbvh4;
-    r.tri_v = const_cast<float*>(reinterpret_cast<const float*>(d.tri_v));
-    r.tri_n = const_cast<float*>(d.tri_n);
-    r.leaf_v = const_cast<float*>(reinterpret_cast<const float*>(d.leaf_v));
-    r.bvh4 = const_cast<BvhNode4*>(d.bvh4);
-    r.bvh4q = const_cast<BvhNode4Q*>(d.bvh4q);
-    int rc;
-    if ((rc = upload(D, sc->slot_start, &r.slot_start)) || (rc = upload(D, sc->slot_list, &r.slot_list))) return rc;
-    const std::vector<uint8_t> zs(std::max<size_t>(nslots, 1), 0), zn(std::max<size_t>(b4.size(), 1), 0);
-    const std::vector<unsigned> zc(16, 0);
-    const uint8_t *ds, *dn;
-    const unsigned* dc;
-    if ((rc = upload(D, zs, &ds)) || (rc = upload(D, zn, &dn)) || (rc = upload(D, zc, &dc))) return rc;
-    r.slot_dirty = const_cast<uint8_t*>(ds);
-    r.node_dirty = const_cast<uint8_t*>(dn);
-    r.counters = const_cast<unsigned*>(dc);
-    D.level_first = std::move(lf);
-    D.refit_ready = true;
-    return MCPT_OK;
-}
-
-// what a device state's first light move builds (after ensure_refit_state): the same for the light-only tree, the
-// light tables' pointers, the light -> group map, the chunk rows (filled here from the tables as they are), the dirty
-// bytes and the small struct of constants.  The current device is D's.
-static int ensure_light_state(mcpt_scene* sc, DeviceState& D) {
-    if (D.light_ready) return MCPT_OK;
-    const DScene& d = D.d;
-    const HostScene& hs = sc->host;
-    const size_t nslots = sc->lbvh.leaf_facets.size();
-    std::vector<BvhNode4> b4(d.nlbvh4);
-    HIP_OK(hipMemcpy(b4.data(), d.lbvh4, b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
-    std::vector<int32_t> lf;
-    if (hs.NL < 1 || !bvh4_levels(b4, nslots, &lf)) {
-        set_error("mcpt_scene_update: device %d's light-only 4-wide tree is not in breadth-first order", D.device);
-        return MCPT_E_SCENE;
-    }
-    ensure_light_slot_map(sc);
-    RefitDev& r = D.lrefit;
-    r.F = d.F;
-    r.nslots = (int32_t)nslots;
-    r.nnodes = d.nlbvh4;
-    r.tri_v = D.refit.tri_v;
-    r.tri_n = D.refit.tri_n;
-    r.leaf_v = const_cast<float*>(reinterpret_cast<const float*>(d.lleaf_v));
-    r.bvh4 = const_cast<BvhNode4*>(d.lbvh4);
-    r.bvh4q = const_cast<BvhNode4Q*>(d.lbvh4q);
-    int rc;
-    if ((rc = upload(D, sc->lslot_start, &r.slot_start)) || (rc = upload(D, sc->lslot_list, &r.slot_list))) return rc;
-    const int nch = prep_chunks(hs.NL), ng = d.ngroups;
-    std::vector<int32_t> lgroup(hs.NL, 0);
-    for (int g = 0; g < ng; g++)
-        for (int l = hs.group_start[g]; l < hs.group_start[g] + hs.group_count[g]; l++) lgroup[l] = g;
-    const std::vector<uint8_t> zs(std::max<size_t>(nslots, 1), 0), zn(std::max<size_t>(b4.size(), 1), 0), zch(nch, 0),
-        zg(std::max(ng, 1), 0);
-    const std::vector<unsigned> zc(16, 0);
-    const std::vector<double> zrow(kLightRowWords * (size_t)nch, 0.0);
-    const std::vector<LightGlobals> zglob(1);
-    const uint8_t *ds, *dn, *dch, *dg;
-    const unsigned* dc;
-    const double* drow;
-    const LightGlobals* dglob;
-    const int32_t* dlg;
-    if ((rc = upload(D, zs, &ds)) || (rc = upload(D, zn, &dn)) || (rc = upload(D, zc, &dc)) || (rc = upload(D, zch, &dch)) ||
-        (rc = upload(D, zg, &dg)) || (rc = upload(D, zrow, &drow)) || (rc = upload(D, zglob, &dglob)) || (rc = upload(D, lgroup, &dlg)))
-        return rc;
-    r.slot_dirty = const_cast<uint8_t*>(ds);
-    r.node_dirty = const_cast<uint8_t*>(dn);
-    r.counters = const_cast<unsigned*>(dc);
-    LightTabDev& t = D.ltab;
-    t.tri_v = D.refit.tri_v;
-    t.tri_n = D.refit.tri_n;
-    t.tri_light = d.tri_light;
-    t.light_sum = d.light_sum;
-    t.light_group = dlg;
-    t.grp_range = reinterpret_cast<const int32_t*>(d.grp_range);
-    t.lt_v = const_cast<float*>(reinterpret_cast<const float*>(d.lt_v));
-    t.lt_n = const_cast<double*>(reinterpret_cast<const double*>(d.lt_n));
-    t.lt_pk = const_cast<float*>(reinterpret_cast<const float*>(d.lt_pk));
-    t.lt_d = const_cast<float*>(d.lt_d);
-    t.lt_w = const_cast<double*>(reinterpret_cast<const double*>(d.lt_w));
-    t.lt_f = const_cast<float*>(reinterpret_cast<const float*>(d.lt_f));
-    t.lt_pair = const_cast<float*>(reinterpret_cast<const float*>(d.lt_pair));
-    t.l_area = const_cast<double*>(d.l_area);
-    t.l_area_cum = const_cast<double*>(d.l_area_cum);
-    t.chunk_sph = const_cast<float*>(reinterpret_cast<const float*>(d.chunk_sph));
-    t.chunk_sk = const_cast<float*>(reinterpret_cast<const float*>(d.chunk_sk));
-    t.chunk_row = const_cast<double*>(drow);
-    t.chunk_dirty = const_cast<uint8_t*>(dch);
-    t.group_dirty = const_cast<uint8_t*>(dg);
-    t.globals = const_cast<LightGlobals*>(dglob);
-    t.counters = r.counters;
-    t.F = d.F;
-    t.NL = hs.NL;
-    t.nchunks = nch;
-    t.ngroups = ng;
-    if (!D.pinned_globals) HIP_OK(hipHostMalloc(&D.pinned_globals, sizeof(LightGlobals)));
-    if (!D.evl0) HIP_OK(hipEventCreate(&D.evl0));
-    if (!D.evl1) HIP_OK(hipEventCreate(&D.evl1));
-    // every chunk's row from the tables as they are: a later move recomputes only its own chunks
-    if ((rc = light_chunks_all_enqueue(t, D.stream))) return rc;
-    HIP_OK(hipStreamSynchronize(D.stream));
-    D.llevel_first = std::move(lf);
-    D.light_ready = true;
-    return MCPT_OK;
-}
-
-// the light stage of an update or transform on one state, after refit_enqueue's scatter on the same stream; the
-// constants land in the state's pinned copy by the time the stream is synchronised
-static int light_stage_enqueue(mcpt_scene* sc, DeviceState& D, int32_t first, int32_t count) {
-    HIP_OK(hipEventRecord(D.evl0, D.stream));
-    if (int rc = light_tables_enqueue(D.ltab, D.lrefit, D.llevel_first.data(), (int)D.llevel_first.size() - 1, first, count,
-                                      sc->margin, D.stream))
-        return rc;
-    HIP_OK(hipEventRecord(D.evl1, D.stream));
-    HIP_OK(hipMemcpyAsync(D.pinned_globals, D.ltab.globals, sizeof(LightGlobals), hipMemcpyDeviceToHost, D.stream));
-    return MCPT_OK;
-}
-// after that synchronisation: the state's by-value constants patched; lst != null: the first state's numbers
-static int light_stage_finish(DeviceState& D, mcpt_light_update_stats* lst) {
-    const LightGlobals& g = *D.pinned_globals;
-    for (int a = 0; a < 3; a++) D.d.band_ctr[a] = g.band_ctr[a];
-    D.d.band_R = g.band_R;
-    D.d.band_S = g.band_S;
-    D.d.band_K = g.band_K;
-    D.d.light_bound = g.light_bound;
-    if (lst) {
-        float ms = 0;
-        unsigned c[4] = {0, 0, 0, 0};
-        HIP_OK(hipEventElapsedTime(&ms, D.evl0, D.evl1));
-        HIP_OK(hipMemcpy(c, D.lrefit.counters, sizeof c, hipMemcpyDeviceToHost));
-        lst->device_seconds = 1e-3 * ms;
-        lst->light_nodes_refit = c[1];
-        lst->chunks = (int32_t)c[2];
-        lst->groups = (int32_t)c[3];
-        lst->light_levels = (int32_t)D.llevel_first.size() - 1;
-    }
-    return MCPT_OK;
-}
-// the numbers of a call with `lights` light triangles in its range, before any device state has added its own:
-// chunks and groups counted on the host (a scene with device states takes the first state's counters instead)
-static mcpt_light_update_stats light_stats_host(const mcpt_scene* sc, int32_t first, int32_t count) {
-    mcpt_light_update_stats st;
-    mcpt_light_update_stats_init(&st);
-    const HostScene& hs = sc->host;
-    std::vector<uint8_t> ch(prep_chunks(hs.NL), 0), gr(std::max<size_t>(hs.group_start.size(), 1), 0);
-    for (int f = first; f < first + count; f++) {
-        const int l = hs.light_of[f];
-        if (l < 0) continue;
-        st.lights++;
-        ch[l >> 6] = 1;
-        // the last group that starts at or before l (groups without triangles share a start with their successor)
-        const auto g = std::upper_bound(hs.group_start.begin(), hs.group_start.end(), l) - hs.group_start.begin();
-        if (g > 0) gr[(size_t)g - 1] = 1;
-    }
-    for (uint8_t b : ch) st.chunks += b;
-    for (uint8_t b : gr) st.groups += b;
-    return st;
-}
-
-// the call after its refusals: the host scene first (it stays the truth for device states made later, for the grid
-// and for the debug checks), then every device state the scene has.  src_device >= 0: dpos / dnrm are device memory
-// there and that device's state reads them directly; every other state gets a staging copy of the host arrays.
-static int update_apply(mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm, int src_device,
-                        const float* dpos, const float* dnrm, mcpt_update_stats* stats) {
-    HostScene& hs = sc->host;
-    ensure_slot_map(sc);  // first update of the handle: the facet -> leaf-slot map and the binary tree's index
-    std::copy(pos, pos + 9 * (size_t)count, hs.pos.begin() + 9 * (size_t)first);
-    if (nrm) std::copy(nrm, nrm + 9 * (size_t)count, hs.nrm.begin() + 9 * (size_t)first);
-    for (int f = first; f < first + count; f++) unique_normal_of_facet(hs, f);
-    const std::vector<int32_t> slots(sc->slot_list.begin() + sc->slot_start[first], sc->slot_list.begin() + sc->slot_start[first + count]);
-    refit_bvh(sc->bvh, sc->refit_ix, hs, slots, sc->margin);
-    // light triangles in the range (mcpt_scene_set_lights_movable): their areas and the light-only tree's boxes
-    mcpt_light_update_stats lst = light_stats_host(sc, first, count);
-    if (lst.lights) {
-        ensure_light_slot_map(sc);
-        PendingRanges one;
-        one.add(first, count);
-        host_refresh_lights(hs, sc->lbvh, sc->lrefit_ix, sc->lslot_start, sc->lslot_list, one, sc->margin);
-    }
-    sc->grid.ok = false;  // rebuilt from the new positions by the next grid-mode call
-    sc->updated = true;   // the 8-wide trees are stale from here on (bvh8_refused)
-    mcpt_update_stats st;
-    mcpt_update_stats_init(&st);
-    st.facets = count;
-    st.leaf_slots = (int64_t)slots.size();
-    std::vector<DeviceState*> devs;
-    {
-        std::lock_guard<std::mutex> lk(sc->devs_mu);
-        for (auto& D : sc->devs) devs.push_back(D.get());
-    }
-    int cur = 0;
-    if (!devs.empty()) HIP_OK(hipGetDevice(&cur));
-    for (DeviceState* D : devs) {
-        HIP_OK(hipSetDevice(D->device));
-        int rc;
-        if ((rc = ensure_refit_state(sc, *D)) || (lst.lights && (rc = ensure_light_state(sc, *D)))) return rc;
-        const float *sp = dpos, *sn = dnrm;
-        if (D->device != src_device) {
-            if ((rc = ensure(D->up_pos, 36ull * count)) || (nrm && (rc = ensure(D->up_nrm, 36ull * count)))) return rc;
-            HIP_OK(hipMemcpy(D->up_pos.p, pos, 36ull * count, hipMemcpyHostToDevice));
-            if (nrm) HIP_OK(hipMemcpy(D->up_nrm.p, nrm, 36ull * count, hipMemcpyHostToDevice));
-            sp = (const float*)D->up_pos.p;
-            sn = nrm ? (const float*)D->up_nrm.p : nullptr;
-        }
-        // work of other streams (the caller's, a frame sequence's) that still reads or writes these arrays
-        HIP_OK(hipDeviceSynchronize());
-        HIP_OK(hipEventRecord(D->ev0, D->stream));
-        if ((rc = refit_enqueue(D->refit, D->level_first.data(), (int)D->level_first.size() - 1, first, count, sp, sn, sc->margin,
-                                D->stream)))
-            return rc;
-        HIP_OK(hipEventRecord(D->ev1, D->stream));
-        if (lst.lights && (rc = light_stage_enqueue(sc, *D, first, count))) return rc;
-        HIP_OK(hipStreamSynchronize(D->stream));
-        if (lst.lights && (rc = light_stage_finish(*D, st.device_states == 0 ? &lst : nullptr))) return rc;
-        if (st.device_states++ == 0) {
-            float ms = 0;
-            unsigned n = 0;
-            HIP_OK(hipEventElapsedTime(&ms, D->ev0, D->ev1));
-            HIP_OK(hipMemcpy(&n, D->refit.counters + 1, sizeof n, hipMemcpyDeviceToHost));
-            st.device_seconds = 1e-3 * ms;
-            st.nodes_refit = n;
-            st.levels = (int32_t)D->level_first.size() - 1;
-        }
-    }
-    if (!devs.empty()) HIP_OK(hipSetDevice(cur));
-    sc->light_stats = lst;
-    if (stats) *stats = st;
-    return MCPT_OK;
-}
-
-// the switch's extra refusal on host arrays: the first degenerate light triangle of the range is named
-static int update_check_light_values(const mcpt_scene* sc, int32_t first, int32_t count, const float* pos,
-                                     const char* who = "mcpt_scene_update") {
-    if (!sc->lights_movable) return MCPT_OK;
-    const int f = first_degenerate_light(sc->host, first, count, pos);
-    if (f < 0) return MCPT_OK;
-    set_error("%s: light triangle %d (light %d) would be degenerate: |(b - a) x (c - a)| is zero or not finite, so it "
-              "has no unique normal", who, f, sc->host.light_of[f]);
-    return MCPT_E_INVALID;
-}
-
-int mcpt_scene_update(mcpt_scene* sc, int32_t first, int32_t count, const float* pos, const float* nrm, mcpt_update_stats* stats) {
-    int rc;
-    if ((rc = update_check_args(sc, first, count, pos, stats))) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    if ((rc = update_check_lights(sc, first, count)) || (rc = update_check_values(sc, first, count, pos, nrm)) ||
-        (rc = update_check_light_values(sc, first, count, pos)))
-        return rc;
-    if ((rc = host_sync(sc))) return rc;  // the host refit reads every triangle of a touched leaf
-    return update_apply(sc, first, count, pos, nrm, -1, nullptr, nullptr, stats);
-}
-
-int mcpt_scene_update_device(mcpt_scene* sc, int32_t device, int32_t first, int32_t count, const float* dpos, const float* dnrm,
-                             mcpt_update_stats* stats) {
-    int rc;
-    if ((rc = update_check_args(sc, first, count, dpos, stats))) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    if ((rc = update_check_lights(sc, first, count))) return rc;
-    if ((rc = host_sync(sc))) return rc;  // as mcpt_scene_update
-    int cur;
-    HIP_OK(hipGetDevice(&cur));
-    if (device < 0) device = cur;
-    if ((rc = check_device_buffer(dpos, device, "dev_positions")) || (dnrm && (rc = check_device_buffer(dnrm, device, "dev_normals"))))
-        return rc;
-    HIP_OK(hipSetDevice(device));
-    // the value checks: one word counted on the device and read back before anything is modified
-    HIP_OK(hipDeviceSynchronize());  // the caller's streams may still be writing the arrays
-    RefitDev v{};
-    void* word = nullptr;
-    HIP_OK(hipMalloc(&word, 64));
-    v.counters = (unsigned*)word;
-    double lo[3], hi[3];
-    update_arena(sc, lo, hi);
-    unsigned bad = 0;
-    rc = refit_validate_enqueue(v, count, dpos, dnrm, lo, hi, nullptr);
-    const bool lights = sc->lights_movable && range_has_light(sc, first, first + count);
-    void* lof = nullptr;  // the range's rows of light_of, for the degenerate-light count into the same word
-    hipError_t e = hipSuccess;
-    if (!rc && lights) {
-        e = hipMalloc(&lof, 4ull * count);
-        if (e == hipSuccess) e = hipMemcpy(lof, sc->host.light_of.data() + first, 4ull * count, hipMemcpyHostToDevice);
-        if (e == hipSuccess) rc = light_validate_enqueue(count, dpos, (const int32_t*)lof, v.counters, nullptr);
-    }
-    if (!rc && e == hipSuccess) e = hipMemcpy(&bad, word, sizeof bad, hipMemcpyDeviceToHost);
-    (void)hipFree(word);
-    if (lof) (void)hipFree(lof);
-    if (rc) return rc;
-    HIP_OK(e);
-    if (bad) {
-        set_error("mcpt_scene_update_device: %u values of the range are non-finite or positions outside the arena (the "
-                  "build's box grown by its largest extent)%s", bad, lights ? ", or light triangles that would be degenerate" : "");
-        (void)hipSetDevice(cur);
-        return MCPT_E_INVALID;
-    }
-    std::vector<float> hp(9 * (size_t)count), hn(dnrm ? 9 * (size_t)count : 0);
-    HIP_OK(hipMemcpy(hp.data(), dpos, 36ull * count, hipMemcpyDeviceToHost));
-    if (dnrm) HIP_OK(hipMemcpy(hn.data(), dnrm, 36ull * count, hipMemcpyDeviceToHost));
-    HIP_OK(hipSetDevice(cur));
-    return update_apply(sc, first, count, hp.data(), dnrm ? hn.data() : nullptr, device, dpos, dnrm, stats);
-}
-
-// ---- movable light triangles (include/mcpt.h; the kernels are light_tables.hip's) ----
-int mcpt_scene_set_lights_movable(mcpt_scene* sc, int32_t on) {
-    if (!sc) {
-        set_error("mcpt_scene_set_lights_movable: NULL scene");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    sc->lights_movable = on != 0;
-    return MCPT_OK;
-}
-int mcpt_scene_lights_movable(const mcpt_scene* sc, int32_t* on) {
-    if (!sc || !on) {
-        set_error("mcpt_scene_lights_movable: NULL %s", !sc ? "scene" : "on");
-        return MCPT_E_INVALID;
-    }
-    mcpt_scene* w = const_cast<mcpt_scene*>(sc);
-    std::lock_guard<std::mutex> lk(w->mu);
-    *on = sc->lights_movable ? 1 : 0;
-    return MCPT_OK;
-}
-void mcpt_light_update_stats_init(mcpt_light_update_stats* st) {
-    if (!st) return;
-    std::memset((void*)st, 0, sizeof *st);
-    st->struct_size = sizeof *st;
-}
-int mcpt_scene_light_update_info(const mcpt_scene* sc, mcpt_light_update_stats* out) {
-    if (!sc || !out) {
-        set_error("mcpt_scene_light_update_info: NULL %s", !sc ? "scene" : "out");
-        return MCPT_E_INVALID;
-    }
-    if (out->struct_size != sizeof(mcpt_light_update_stats)) {
-        set_error("mcpt_light_update_stats.struct_size %u does not match this library's %zu (header / library version mismatch)",
-                  out->struct_size, sizeof(mcpt_light_update_stats));
-        return MCPT_E_INVALID;
-    }
-    mcpt_scene* w = const_cast<mcpt_scene*>(sc);
-    std::lock_guard<std::mutex> lk(w->mu);
-    *out = sc->light_stats;
-    out->struct_size = sizeof *out;
-    return MCPT_OK;
-}
-
-// ---- mcpt_scene_pose_save (include/mcpt.h) ----
-int mcpt_scene_pose_save(mcpt_scene* sc) {
-    if (!sc) {
-        set_error("mcpt_scene_pose_save: NULL scene");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    if (std::lock_guard<std::mutex> hl(sc->host_mu); sc->pending.r.empty()) {
-        sc->prev_pos = sc->host.pos;
-        sc->prev_nrm = sc->host.nrm;
-        sc->prev_stale = false;
-    } else {
-        // the host copy is behind the devices (mcpt_scene_transform) and a frame loop must not pay for a sync here:
-        // the device copies below are the pose, and host_sync refreshes prev_pos / prev_nrm from the first state's
-        sc->prev_stale = true;
-    }
-    sc->pose_saved = true;
-    std::vector<DeviceState*> devs;
-    {
-        std::lock_guard<std::mutex> dl(sc->devs_mu);
-        for (auto& D : sc->devs) devs.push_back(D.get());
-    }
-    if (devs.empty()) return MCPT_OK;
-    int cur = 0;
-    HIP_OK(hipGetDevice(&cur));
-    for (DeviceState* D : devs) {
-        HIP_OK(hipSetDevice(D->device));
-        const size_t vb = 3 * (size_t)std::max(D->d.F, 1) * sizeof(float4), nb = 9 * (size_t)D->d.F * sizeof(float);
-        int rc;
-        if ((rc = ensure(D->prev_v, vb)) || (rc = ensure(D->prev_n, std::max<size_t>(nb, 4)))) return rc;
-        // device to device on the state's stream: ordered after the refits (mcpt_scene_update) and before the motion
-        // AOVs, which run there too
-        HIP_OK(hipMemcpyAsync(D->prev_v.p, D->d.tri_v, vb, hipMemcpyDeviceToDevice, D->stream));
-        if (nb) HIP_OK(hipMemcpyAsync(D->prev_n.p, D->d.tri_n, nb, hipMemcpyDeviceToDevice, D->stream));
-        HIP_OK(hipStreamSynchronize(D->stream));
-    }
-    HIP_OK(hipSetDevice(cur));
-    return MCPT_OK;
-}
-
-// ---- mcpt_scene_rest_save, mcpt_scene_transform and the lazily synced host copy (include/mcpt.h, DESIGN.md §4.21;
-// the kernel is refit.hip's, the host arithmetic and the pending ranges host_mirror.cpp's) ----
-static std::vector<DeviceState*> device_states(mcpt_scene* sc) {
-    std::vector<DeviceState*> devs;
-    std::lock_guard<std::mutex> lk(sc->devs_mu);
-    for (auto& D : sc->devs) devs.push_back(D.get());
-    return devs;
-}
-
-int mcpt_scene_rest_save(mcpt_scene* sc) {
-    if (!sc) {
-        set_error("mcpt_scene_rest_save: NULL scene");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    int rc;
-    if ((rc = host_sync(sc))) return rc;
-    sc->rest_pos = sc->host.pos;
-    sc->rest_nrm = sc->host.nrm;
-    sc->rest_saved = true;
-    const std::vector<DeviceState*> devs = device_states(sc);
-    if (devs.empty()) return MCPT_OK;
-    DeviceRestore back;
-    HIP_OK(hipGetDevice(&back.device));
-    for (DeviceState* D : devs) {
-        HIP_OK(hipSetDevice(D->device));
-        const size_t vb = 3 * (size_t)std::max(D->d.F, 1) * sizeof(float4), nb = 9 * (size_t)D->d.F * sizeof(float);
-        if ((rc = ensure(D->rest_v, vb)) || (rc = ensure(D->rest_n, std::max<size_t>(nb, 4)))) return rc;
-        // device to device on the state's stream, as mcpt_scene_pose_save: ordered after the refits
-        HIP_OK(hipMemcpyAsync(D->rest_v.p, D->d.tri_v, vb, hipMemcpyDeviceToDevice, D->stream));
-        if (nb) HIP_OK(hipMemcpyAsync(D->rest_n.p, D->d.tri_n, nb, hipMemcpyDeviceToDevice, D->stream));
-        HIP_OK(hipStreamSynchronize(D->stream));
-    }
-    return MCPT_OK;
-}
-
-// the call after the refusals that need no values, on a scene with device states: every state transforms the range
-// from its own rest copy into its staging arrays and counts the offenders; the counts are read back before anything
-// is modified; then refit_enqueue as for an update.  The host copy only gets the range marked as behind.
-static int transform_on_devices(mcpt_scene* sc, const std::vector<DeviceState*>& devs, int32_t first, int32_t count,
-                                const double m[12], const double n[9], mcpt_update_stats* stats) {
-    ensure_slot_map(sc);
-    mcpt_update_stats st;
-    mcpt_update_stats_init(&st);
-    st.facets = count;
-    st.leaf_slots = (int64_t)sc->slot_start[first + count] - sc->slot_start[first];
-    mcpt_light_update_stats lst = light_stats_host(sc, first, count);
-    double lo[3], hi[3];
-    update_arena(sc, lo, hi);
-    int rc;
-    DeviceRestore back;
-    HIP_OK(hipGetDevice(&back.device));
-    std::vector<unsigned> bad(devs.size(), 0);
-    for (size_t i = 0; i < devs.size(); i++) {
-        DeviceState* D = devs[i];
-        HIP_OK(hipSetDevice(D->device));
-        if ((rc = ensure_refit_state(sc, *D)) || (rc = ensure(D->up_pos, 36ull * count)) || (rc = ensure(D->up_nrm, 36ull * count)) ||
-            (lst.lights && (rc = ensure_light_state(sc, *D))))
-            return rc;
-        if (!D->rest_v.p || !D->rest_n.p) {
-            set_error("mcpt_scene_transform: device %d holds no rest pose", D->device);
-            return MCPT_E_DEVICE;
-        }
-        // work of other streams (the caller's, a frame sequence's) that still reads or writes these arrays
-        HIP_OK(hipDeviceSynchronize());
-        HIP_OK(hipEventRecord(D->ev0, D->stream));
-        if ((rc = transform_enqueue(D->refit, (const float*)D->rest_v.p, (const float*)D->rest_n.p, first, count, m, n, lo, hi,
-                                    (float*)D->up_pos.p, (float*)D->up_nrm.p, D->stream)))
-            return rc;
-        // degenerate light triangles of the staged range count into the same word
-        if (lst.lights && (rc = light_validate_enqueue(count, (const float*)D->up_pos.p, D->d.tri_light + first, D->refit.counters, D->stream)))
-            return rc;
-        HIP_OK(hipMemcpyAsync(&bad[i], D->refit.counters, sizeof(unsigned), hipMemcpyDeviceToHost, D->stream));
-    }
-    unsigned nbad = 0;
-    for (size_t i = 0; i < devs.size(); i++) {
-        HIP_OK(hipSetDevice(devs[i]->device));
-        HIP_OK(hipStreamSynchronize(devs[i]->stream));
-        nbad = std::max(nbad, bad[i]);
-    }
-    if (nbad) {  // only the staging arrays were written
-        set_error("mcpt_scene_transform: %u transformed values of facets [%d, %d) are non-finite or positions outside the "
-                  "arena (the build's box grown by its largest extent)%s", nbad, first, first + count,
-                  lst.lights ? ", or light triangles that would be degenerate" : "");
-        return MCPT_E_INVALID;
-    }
-    // the devices are modified from here on, so the marks come first: should a launch below fail, the host copy is
-    // still known to be behind (host.pos / host.nrm / host.unique_n and the binary tree follow at the next host_sync)
-    {
-        std::lock_guard<std::mutex> hl(sc->host_mu);
-        sc->pending.add(first, count);
-    }
-    sc->grid.ok = false;  // stale from here on, as after an update
-    sc->updated = true;   // the 8-wide trees are stale from here on (bvh8_refused)
-    for (DeviceState* D : devs) {
-        HIP_OK(hipSetDevice(D->device));
-        if ((rc = refit_enqueue(D->refit, D->level_first.data(), (int)D->level_first.size() - 1, first, count,
-                                (const float*)D->up_pos.p, (const float*)D->up_nrm.p, sc->margin, D->stream)))
-            return rc;
-        HIP_OK(hipEventRecord(D->ev1, D->stream));
-        if (lst.lights && (rc = light_stage_enqueue(sc, *D, first, count))) return rc;
-        HIP_OK(hipStreamSynchronize(D->stream));
-        if (lst.lights && (rc = light_stage_finish(*D, st.device_states == 0 ? &lst : nullptr))) return rc;
-        if (st.device_states++ == 0) {
-            float ms = 0;
-            unsigned nn = 0;
-            HIP_OK(hipEventElapsedTime(&ms, D->ev0, D->ev1));
-            HIP_OK(hipMemcpy(&nn, D->refit.counters + 1, sizeof nn, hipMemcpyDeviceToHost));
-            st.device_seconds = 1e-3 * ms;
-            st.nodes_refit = nn;
-            st.levels = (int32_t)D->level_first.size() - 1;
-        }
-    }
-    sc->light_stats = lst;
-    if (stats) *stats = st;
-    return MCPT_OK;
-}
-
-int mcpt_scene_transform(mcpt_scene* sc, int32_t first, int32_t count, const double m[12], const double normal_m[9],
-                         mcpt_update_stats* stats) {
-    static const char* who = "mcpt_scene_transform";
-    int rc;
-    if ((rc = update_check_args(sc, first, count, m, stats, who, "m"))) return rc;
-    std::lock_guard<std::mutex> lk(sc->mu);
-    if ((rc = update_check_lights(sc, first, count, who))) return rc;
-    double n[9];
-    for (int i = 0; i < 12; i++)
-        if (!std::isfinite(m[i])) {
-            set_error("%s: m[%d] is not finite", who, i);
-            return MCPT_E_INVALID;
-        }
-    for (int i = 0; i < 9; i++) {
-        n[i] = normal_m ? normal_m[i] : m[4 * (i / 3) + i % 3];
-        if (!std::isfinite(n[i])) {
-            set_error("%s: normal_m[%d] is not finite", who, i);
-            return MCPT_E_INVALID;
-        }
-    }
-    if (!sc->rest_saved) {
-        set_error("%s: the scene has no rest pose yet (call mcpt_scene_rest_save first)", who);
-        return MCPT_E_INVALID;
-    }
-    const std::vector<DeviceState*> devs = device_states(sc);
-    if (!devs.empty()) return transform_on_devices(sc, devs, first, count, m, n, stats);
-    // no device state yet: the rule on the host, then an ordinary update (nothing is left pending)
-    std::vector<float> pos(9 * (size_t)count), nrm(9 * (size_t)count);
-    transform_facets(sc->rest_pos.data() + 9 * (size_t)first, sc->rest_nrm.data() + 9 * (size_t)first, (size_t)count, m, n, pos.data(),
-                     nrm.data());
-    if ((rc = update_check_values(sc, first, count, pos.data(), nrm.data(), who)) ||
-        (rc = update_check_light_values(sc, first, count, pos.data(), who)))
-        return rc;
-    return update_apply(sc, first, count, pos.data(), nrm.data(), -1, nullptr, nullptr, stats);
-}
-
-int mcpt_scene_host_pending(const mcpt_scene* sc, int64_t* facets) {
-    if (!sc || !facets) {
-        set_error("mcpt_scene_host_pending: NULL %s", !sc ? "scene" : "facets");
-        return MCPT_E_INVALID;
-    }
-    mcpt_scene* w = const_cast<mcpt_scene*>(sc);
-    std::lock_guard<std::mutex> lk(w->mu);
-    std::lock_guard<std::mutex> hl(w->host_mu);
-    *facets = sc->pending.facets();
-    return MCPT_OK;
-}
-
-int mcpt_scene_host_sync(mcpt_scene* sc) {
-    if (!sc) {
-        set_error("mcpt_scene_host_sync: NULL scene");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    return host_sync(sc);
-}
-
-// ---- mcpt_scene_rebuild and mcpt_scene_tree_cost (include/mcpt.h; the kernels are rebuild.hip's) ----
-void mcpt_rebuild_stats_init(mcpt_rebuild_stats* st) {
-    if (!st) return;
-    std::memset((void*)st, 0, sizeof *st);
-    st->struct_size = sizeof *st;
-}
-
-// the cost of the main tree `D` holds, on its stream (the current device is D's)
-static int tree_cost_of(DeviceState& D, double* cost) {
-    int rc;
-    if ((rc = ensure(D.cost_words, kTreeCostWords * sizeof(double)))) return rc;
-    double* res = nullptr;
-    if ((rc = tree_cost_enqueue(D.d.bvh4, D.d.nbvh4, (double*)D.cost_words.p, D.stream, &res))) return rc;
-    HIP_OK(hipMemcpyAsync(cost, res, sizeof(double), hipMemcpyDeviceToHost, D.stream));
-    HIP_OK(hipStreamSynchronize(D.stream));
-    return MCPT_OK;
-}
-
-// one device state (the current device is D's): the new tree is built into the set of arrays the state is not using,
-// checked, and only then do the state's pointers change -- together
-static int rebuild_state(mcpt_scene* sc, DeviceState& D, mcpt_rebuild_stats* st) {
-    const size_t F = (size_t)D.d.F;
-    int rc;
-    if (!D.rb_work && (rc = rebuild_work_create(D.d.F, &D.rb_work))) return rc;
-    for (DeviceState::RebuildSet& B : D.rb_set)  // both sets at the first rebuild: nothing grows from call to call
-        if ((rc = ensure(B.bvh4, F * sizeof(BvhNode4))) || (rc = ensure(B.bvh4q, F * sizeof(BvhNode4Q))) ||
-            (rc = ensure(B.leaf_v, 3 * F * sizeof(float4))) || (rc = ensure(B.slot_list, F * sizeof(int32_t))) ||
-            (rc = ensure(B.slot_dirty, F)) || (rc = ensure(B.node_dirty, F)))
-            return rc;
-    if ((rc = ensure(D.rb_slot_start, (F + 1) * sizeof(int32_t))) || (rc = ensure(D.rb_counters, 16 * sizeof(unsigned)))) return rc;
-    DeviceState::RebuildSet& S = D.rb_set[D.rb_next];
-    RefitDev r{};
-    r.F = r.nslots = D.d.F;
-    r.tri_v = const_cast<float*>(reinterpret_cast<const float*>(D.d.tri_v));
-    r.tri_n = const_cast<float*>(D.d.tri_n);
-    r.leaf_v = (float*)S.leaf_v.p;
-    r.bvh4 = (BvhNode4*)S.bvh4.p;
-    r.bvh4q = (BvhNode4Q*)S.bvh4q.p;
-    r.slot_start = (const int32_t*)D.rb_slot_start.p;
-    r.slot_list = (const int32_t*)S.slot_list.p;
-    r.slot_dirty = (uint8_t*)S.slot_dirty.p;
-    r.node_dirty = (uint8_t*)S.node_dirty.p;
-    r.counters = (unsigned*)D.rb_counters.p;
-    // work of other streams (the caller's, a frame sequence's) that still reads the arrays of the set built two
-    // rebuilds ago, or writes tri_v
-    HIP_OK(hipDeviceSynchronize());
-    if (st && (rc = tree_cost_of(D, &st->cost_before))) return rc;
-    std::vector<int32_t> lf;
-    int32_t need = 0;
-    HIP_OK(hipEventRecord(D.ev0, D.stream));
-    const int leaf_max = g_rebuild_leaf_max.load() ? g_rebuild_leaf_max.load() : kRebuildLeafMax;
-    if ((rc = rebuild_build(D.rb_work, &r, leaf_max, kStack, sc->margin, D.stream, &lf, &need))) {
-        (void)hipStreamSynchronize(D.stream);
-        return rc;
-    }
-    HIP_OK(hipEventRecord(D.ev1, D.stream));
-    HIP_OK(hipStreamSynchronize(D.stream));
-    D.d.bvh4 = r.bvh4;
-    D.d.bvh4q = r.bvh4q;
-    D.d.leaf_v = reinterpret_cast<const float4*>(r.leaf_v);
-    D.d.nbvh4 = r.nnodes;
-    D.nslots = F;
-    D.refit = r;
-    D.level_first = std::move(lf);
-    D.refit_ready = true;
-    D.rb_next ^= 1;
-    if (st) {
-        float ms = 0;
-        HIP_OK(hipEventElapsedTime(&ms, D.ev0, D.ev1));
-        st->device_seconds = 1e-3 * ms;
-        st->nodes = r.nnodes;
-        st->levels = (int32_t)D.level_first.size() - 1;
-        st->stack_need = need;
-        if ((rc = tree_cost_of(D, &st->cost_after))) return rc;
-        sc->rebuilt_nodes = (uint64_t)r.nnodes;
-        sc->rebuilt_slots = F;
-    }
-    return MCPT_OK;
-}
-
-int mcpt_scene_rebuild(mcpt_scene* sc, mcpt_rebuild_stats* stats) {
-    if (!sc) {
-        set_error("mcpt_scene_rebuild: NULL scene");
-        return MCPT_E_INVALID;
-    }
-    if (stats && stats->struct_size != sizeof(mcpt_rebuild_stats)) {
-        set_error("mcpt_rebuild_stats.struct_size %u does not match this library's %zu (header / library version mismatch)",
-                  stats->struct_size, sizeof(mcpt_rebuild_stats));
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    mcpt_rebuild_stats st;
-    mcpt_rebuild_stats_init(&st);
-    st.facets = sc->host.F;
-    const std::vector<DeviceState*> devs = device_states(sc);
-    if (!devs.empty() && sc->host.F > 0) {
-        DeviceRestore back;
-        HIP_OK(hipGetDevice(&back.device));
-        for (DeviceState* D : devs) {
-            HIP_OK(hipSetDevice(D->device));
-            if (int rc = rebuild_state(sc, *D, st.device_states == 0 ? &st : nullptr)) return rc;
-            st.device_states++;
-            sc->updated = true;  // the 8-wide trees keep the host tree's topology: refused from here on (bvh8_refused)
-        }
-    }
-    if (stats) *stats = st;
-    return MCPT_OK;
-}
-
-int mcpt_scene_tree_cost(mcpt_scene* sc, int32_t device, double* cost) {
-    if (!sc || !cost) {
-        set_error("mcpt_scene_tree_cost: NULL %s", !sc ? "scene" : "cost");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    DeviceRestore back;
-    HIP_OK(hipGetDevice(&back.device));
-    DeviceState* D;
-    int rc;
-    if ((rc = get_device_state(sc, device, &D))) return rc;
-    return tree_cost_of(*D, cost);
 }
 
 int mcpt_scene_camera(const mcpt_scene* sc, mcpt_camera* cam) {
@@ -8631,6 +7529,8 @@ int mcpt_debug_adaptive_active(mcpt_scene* sc, int32_t device, int32_t* pixels, 
     return MCPT_OK;
 }
 
+int64_t mcpt_debug_device_bytes_live(void) { return g_device_bytes_live.load(); }
+
 int mcpt_debug_set_rebuild_leaf_max(int32_t leaf_max) {
     if (leaf_max < 0 || leaf_max > 4) {
         set_error("mcpt_debug_set_rebuild_leaf_max: %d is not 0 (the default) or a leaf size in 1..4", leaf_max);
@@ -8721,12 +7621,11 @@ int mcpt_closest_hit(mcpt_scene* sc, int32_t n, const double* ro, const double* 
         if ((rc = use_grid(sc, *D, sc->grid.eye, sc->grid.n0))) return rc;
     }
     const int light_only = (flags & MCPT_HIT_LIGHT_ONLY) != 0;
-    void *dro, *drd, *dex, *df, *dt;
-    HIP_OK(hipMalloc(&dro, 24ull * n));
-    HIP_OK(hipMalloc(&drd, 24ull * n));
-    HIP_OK(hipMalloc(&dex, 4ull * n));
-    HIP_OK(hipMalloc(&df, 4ull * n));
-    HIP_OK(hipMalloc(&dt, 24ull * n));
+    DevBuf bro, brd, bex, bf, bt;  // the call's own: freed on every path
+    if ((rc = ensure(bro, 24ull * n)) || (rc = ensure(brd, 24ull * n)) || (rc = ensure(bex, 4ull * n)) || (rc = ensure(bf, 4ull * n)) ||
+        (rc = ensure(bt, 24ull * n)))
+        return rc;
+    void *dro = bro.p, *drd = brd.p, *dex = bex.p, *df = bf.p, *dt = bt.p;
     HIP_OK(hipMemcpy(dro, ro, 24ull * n, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(drd, rd, 24ull * n, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(dex, ex, 4ull * n, hipMemcpyHostToDevice));
@@ -8746,11 +7645,6 @@ int mcpt_closest_hit(mcpt_scene* sc, int32_t n, const double* ro, const double* 
     HIP_OK(hipStreamSynchronize(D->stream));
     HIP_OK(hipMemcpy(facet, df, 4ull * n, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(tbg, dt, 24ull * n, hipMemcpyDeviceToHost));
-    (void)hipFree(dro);
-    (void)hipFree(drd);
-    (void)hipFree(dex);
-    (void)hipFree(df);
-    (void)hipFree(dt);
     return MCPT_OK;
 }
 
@@ -8775,373 +7669,17 @@ int mcpt_debug_light_literal(mcpt_scene* sc, const double* x1, const double* nrm
     if ((rc = get_device_state(sc, -1, &D))) return rc;
     const int NL = D->d.NL;
     if (NL == 0) return MCPT_OK;
-    void* dout;
-    HIP_OK(hipMalloc(&dout, 160ull * NL));
+    DevBuf bout;
+    if ((rc = ensure(bout, 160ull * NL))) return rc;
+    void* dout = bout.p;
     hipLaunchKernelGGL(k_light_literal, dim3((NL + 255) / 256), dim3(256), 0, D->stream, D->d, mk3(x1[0], x1[1], x1[2]),
                        mk3(nrm[0], nrm[1], nrm[2]), (double*)dout);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(D->stream));
     HIP_OK(hipMemcpy(out, dout, 160ull * NL, hipMemcpyDeviceToHost));
-    (void)hipFree(dout);
     return MCPT_OK;
 }
 
-// host-only check of an 8-wide tree (include/mcpt_debug.h): every facet of the binary tree is reached exactly
-// once, and every reached triangle's vertices lie inside the decoded box of every slot on its path (the
-// traversal prunes with those boxes, so this is what keeps its hits the binary tree's)
-// references beyond the first of each facet in a binary tree's leaf list (spatial splits repeat facets)
-static int64_t dup_refs(const Bvh& b) {
-    std::vector<int32_t> f(b.leaf_facets);
-    std::sort(f.begin(), f.end());
-    return (int64_t)(f.size() - (std::unique(f.begin(), f.end()) - f.begin()));
-}
-// A facet may sit in several leaves (spatial splits, each reference with its triangle clipped to one side):
-// then its references' regions (the intersection of the slot boxes on each one's path) must together cover
-// the triangle -- checked at the vertices, edge points and interior points; a facet with one reference
-// needs all three vertices inside every box on its path.
-struct RefRegion {
-    int32_t f;
-    float lo[3], hi[3];
-};
-static int64_t check_coverage(const std::vector<float>& pos, std::vector<RefRegion>& refs) {
-    std::sort(refs.begin(), refs.end(), [](const RefRegion& x, const RefRegion& y) { return x.f < y.f; });
-    int64_t bad = 0;
-    static const double kW[][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {.5, .5, 0}, {0, .5, .5}, {.5, 0, .5}, {1. / 3, 1. / 3, 1. / 3},
-                                   {.8, .1, .1}, {.1, .8, .1}, {.1, .1, .8}, {.25, .75, 0}, {.75, .25, 0}, {0, .25, .75},
-                                   {0, .75, .25}, {.25, 0, .75}, {.75, 0, .25}};
-    for (size_t i = 0; i < refs.size();) {
-        size_t j = i;
-        while (j < refs.size() && refs[j].f == refs[i].f) j++;
-        const float* v = &pos[9 * (size_t)refs[i].f];
-        const int npts = j - i == 1 ? 3 : (int)(sizeof(kW) / sizeof(kW[0]));
-        for (int w = 0; w < npts; w++) {
-            float x[3];
-            for (int a = 0; a < 3; a++)
-                x[a] = j - i == 1 ? v[3 * w + a] : (float)(kW[w][0] * v[a] + kW[w][1] * v[3 + a] + kW[w][2] * v[6 + a]);
-            bool in = false;
-            for (size_t r = i; r < j && !in; r++)
-                in = x[0] >= refs[r].lo[0] && x[0] <= refs[r].hi[0] && x[1] >= refs[r].lo[1] && x[1] <= refs[r].hi[1] &&
-                     x[2] >= refs[r].lo[2] && x[2] <= refs[r].hi[2];
-            if (!in) bad++;
-        }
-        i = j;
-    }
-    return bad;
-}
-// the 4-wide tree every traversal kernel reads (collapse_bvh4 of the binary tree) and its quantized form
-// (quantize_bvh4), walked on the host: every facet of the binary tree reached, each reference's triangle
-// covered by the slot boxes on its path (check_coverage), and every quantized slot box containing its fp32
-// box (the conservative rounding the persistent traversal relies on)
-// the walk itself, over any copy of a tree: nodes with unpacked leaf children (~first slot, count), their quantized
-// forms, the facet of every leaf slot and the positions (9 floats per facet) the triangles are checked with
-static void bvh4_walk(const std::vector<BvhNode4>& b4, const std::vector<BvhNode4Q>& q4, const std::vector<int32_t>& leaf_facets,
-                      const std::vector<float>& pos, int64_t* out) {
-    const int F = (int)(pos.size() / 9);
-    int64_t nodes = 0, tris = 0, dup = 0, bad = 0, maxd = 0;
-    std::vector<int> seen(F, 0);
-    std::vector<RefRegion> refs;
-    RefRegion cur{0, {-FLT_MAX, -FLT_MAX, -FLT_MAX}, {FLT_MAX, FLT_MAX, FLT_MAX}};
-    std::function<void(int32_t, int)> walk = [&](int32_t ni, int depth) {
-        if (ni < 0 || (size_t)ni >= b4.size()) {
-            bad++;
-            return;
-        }
-        nodes++;
-        maxd = std::max<int64_t>(maxd, depth);
-        const BvhNode4& n = b4[ni];
-        const BvhNode4Q& q = q4[ni];
-        for (int k = 0; k < 4; k++) {
-            if (n.child[k] == kBvh4Empty || (n.child[k] < 0 && n.count[k] == 0)) continue;
-            const RefRegion saved = cur;
-            for (int a = 0; a < 3; a++) {
-                cur.lo[a] = std::max(cur.lo[a], n.lo[a][k]), cur.hi[a] = std::min(cur.hi[a], n.hi[a][k]);
-                const uint32_t bits = ((q.ex >> (8 * a)) & 0xffu) << 23;
-                float sc_;
-                std::memcpy(&sc_, &bits, 4);
-                const float ql = std::fmaf((float)((q.q[2 * a] >> (8 * k)) & 0xffu), sc_, q.org[a]);
-                const float qh = std::fmaf((float)((q.q[2 * a + 1] >> (8 * k)) & 0xffu), sc_, q.org[a]);
-                if (!(ql <= n.lo[a][k] && qh >= n.hi[a][k])) bad++;
-            }
-            if (n.child[k] >= 0) {
-                walk(n.child[k], depth + 1);
-            } else {
-                const int32_t first = ~n.child[k];
-                for (int32_t j = first; j < first + n.count[k]; j++) {
-                    if (j < 0 || (size_t)j >= leaf_facets.size() || leaf_facets[j] < 0 || leaf_facets[j] >= F) {
-                        bad++;
-                        continue;
-                    }
-                    const int f = leaf_facets[j];
-                    tris++;
-                    if (seen[f]++) dup++;
-                    cur.f = f;
-                    refs.push_back(cur);
-                }
-            }
-            cur = saved;
-        }
-    };
-    if (!b4.empty()) walk(0, 1);
-    bad += check_coverage(pos, refs);
-    std::vector<int32_t> distinct(leaf_facets);
-    std::sort(distinct.begin(), distinct.end());
-    out[0] = nodes;
-    out[1] = tris - dup;  // distinct facets reached
-    out[2] = (int64_t)(std::unique(distinct.begin(), distinct.end()) - distinct.begin());
-    out[3] = dup;
-    out[4] = bad;
-    out[5] = maxd;
-}
-int mcpt_debug_bvh4_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
-    if (!sc || !out) {
-        set_error("invalid argument");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    if (int rs = host_sync(sc)) return rs;
-    const Bvh& bb = light_only ? sc->lbvh : sc->bvh;
-    const std::vector<BvhNode4> b4 = collapse_bvh4(bb);
-    bvh4_walk(b4, quantize_bvh4(b4), bb.leaf_facets, sc->host.pos, out);
-    return MCPT_OK;
-}
-
-// what `device` holds of the main tree: nodes with their leaf codes unpacked, quantized nodes, the facet and the
-// vertices of every leaf slot, the facet array's vertices
-struct DeviceTree {
-    std::vector<BvhNode4> b4;
-    std::vector<BvhNode4Q> q4;
-    std::vector<float4> leaf_v, tri_v;
-    std::vector<int32_t> leaf_facets;
-};
-static int download_tree(mcpt_scene* sc, int32_t device, bool vertices, DeviceTree* t, bool light_only = false) {
-    DeviceState* D;
-    int rc;
-    if ((rc = host_sync(sc))) return rc;  // the device check compares against host.pos
-    if ((rc = get_device_state(sc, device, &D))) return rc;
-    HIP_OK(hipDeviceSynchronize());
-    const DScene& d = D->d;
-    const size_t nslots = light_only ? sc->lbvh.leaf_facets.size() : D->nslots;
-    const int nn = light_only ? d.nlbvh4 : d.nbvh4;
-    t->b4.resize(nn);
-    t->q4.resize(nn);
-    t->leaf_v.resize(3 * nslots);
-    HIP_OK(hipMemcpy(t->b4.data(), light_only ? d.lbvh4 : d.bvh4, t->b4.size() * sizeof(BvhNode4), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(t->q4.data(), light_only ? d.lbvh4q : d.bvh4q, t->q4.size() * sizeof(BvhNode4Q), hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(t->leaf_v.data(), light_only ? d.lleaf_v : d.leaf_v, t->leaf_v.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    if (vertices) {
-        t->tri_v.resize(3 * (size_t)d.F);
-        HIP_OK(hipMemcpy(t->tri_v.data(), d.tri_v, t->tri_v.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    }
-    for (BvhNode4& n : t->b4)
-        for (int k = 0; k < 4; k++)
-            if (n.child[k] < 0) n.child[k] = ~(~n.child[k] >> kLeafBits);  // pack_leaf_codes kept count[k]
-    t->leaf_facets.resize(nslots);
-    for (size_t q = 0; q < nslots; q++) std::memcpy(&t->leaf_facets[q], &t->leaf_v[3 * q].w, 4);
-    return MCPT_OK;
-}
-static int bvh4_check_device(mcpt_scene* sc, int32_t device, bool light_only, int64_t* out);
-int mcpt_debug_bvh4_check_device(mcpt_scene* sc, int32_t device, int64_t* out) { return bvh4_check_device(sc, device, false, out); }
-int mcpt_debug_bvh4_check_device_light(mcpt_scene* sc, int32_t device, int64_t* out) { return bvh4_check_device(sc, device, true, out); }
-static int bvh4_check_device(mcpt_scene* sc, int32_t device, bool light_only, int64_t* out) {
-    if (!sc || !out) {
-        set_error("invalid argument");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    DeviceTree t;
-    int rc;
-    if ((rc = download_tree(sc, device, true, &t, light_only))) return rc;
-    const std::vector<float>& pos = sc->host.pos;
-    bvh4_walk(t.b4, t.q4, t.leaf_facets, pos, out);
-    // the device's own copies of the vertices against the host's
-    auto differs = [&](const float4* v, int f) {
-        int64_t n = 0;
-        for (int k = 0; k < 3; k++) n += std::memcmp(&v[k].x, &pos[9 * (size_t)f + 3 * k], 12) != 0;
-        return n;
-    };
-    for (size_t q = 0; q < t.leaf_facets.size(); q++)
-        if (t.leaf_facets[q] >= 0 && t.leaf_facets[q] < sc->host.F) out[4] += differs(&t.leaf_v[3 * q], t.leaf_facets[q]);
-    for (int f = 0; f < sc->host.F; f++) out[4] += differs(&t.tri_v[3 * (size_t)f], f);
-    return MCPT_OK;
-}
-int mcpt_debug_light_tables(mcpt_scene* sc, int32_t device, const char* which, void* out, int64_t cap, int64_t* bytes) {
-    if (!sc || !which || !bytes) {
-        set_error("mcpt_debug_light_tables: invalid argument");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    DeviceState* D;
-    int rc;
-    if ((rc = get_device_state(sc, device, &D))) return rc;
-    HIP_OK(hipDeviceSynchronize());
-    const DScene& d = D->d;
-    // the sizes get_device_state allocated
-    const size_t NL = (size_t)std::max(d.NL, 1), nch = (size_t)prep_chunks(d.NL), nl_pad = 256 * ((nch + 3) / 4);
-    const std::string w = which;
-    const void* src = nullptr;
-    size_t n = 0;
-    LightGlobals g{};
-    if (w == "lt_v") src = d.lt_v, n = 3 * NL * sizeof(float4);
-    else if (w == "lt_n") src = d.lt_n, n = NL * sizeof(double4);
-    else if (w == "lt_pk") src = d.lt_pk, n = 3 * nl_pad * sizeof(float4);
-    else if (w == "lt_d") src = d.lt_d, n = nl_pad * sizeof(float);
-    else if (w == "lt_w") src = d.lt_w, n = 5 * (nl_pad + kSentinelPad) * sizeof(double2);
-    else if (w == "lt_f") src = d.lt_f, n = 4 * (nl_pad + kSentinelPad) * sizeof(float4);
-    else if (w == "lt_pair") src = d.lt_pair, n = 32 * nch * sizeof(LightPair);
-    else if (w == "chunk_sph") src = d.chunk_sph, n = nch * sizeof(float4);
-    else if (w == "chunk_sk") src = d.chunk_sk, n = nch * sizeof(float2);
-    else if (w == "l_area") src = d.l_area, n = (size_t)d.NL * sizeof(double);
-    else if (w == "l_area_cum") src = d.l_area_cum, n = (size_t)d.NL * sizeof(double);
-    else if (w == "globals") {
-        for (int a = 0; a < 3; a++) g.band_ctr[a] = d.band_ctr[a];
-        g.band_R = d.band_R, g.band_S = d.band_S, g.band_K = d.band_K, g.light_bound = d.light_bound;
-        n = sizeof g;
-    } else {
-        set_error("mcpt_debug_light_tables: no table named '%s'", which);
-        return MCPT_E_INVALID;
-    }
-    *bytes = (int64_t)n;
-    if (!out) return MCPT_OK;
-    if (cap < (int64_t)n) {
-        set_error("mcpt_debug_light_tables: '%s' has %zu bytes, more than the buffer's %lld", which, n, (long long)cap);
-        return MCPT_E_INVALID;
-    }
-    if (src) {
-        if (n) HIP_OK(hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
-    } else {
-        std::memcpy(out, &g, n);
-    }
-    return MCPT_OK;
-}
-
-int mcpt_debug_light_area_cum_bench(mcpt_scene* sc, int32_t device, int32_t reps, double* seconds) {
-    if (!sc || !seconds || reps < 1) {
-        set_error("mcpt_debug_light_area_cum_bench: invalid argument");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    DeviceState* D;
-    int rc;
-    if ((rc = get_device_state(sc, device, &D))) return rc;
-    if (sc->host.NL < 1) {
-        set_error("mcpt_debug_light_area_cum_bench: the scene has no lights");
-        return MCPT_E_INVALID;
-    }
-    ensure_slot_map(sc);
-    if ((rc = ensure_refit_state(sc, *D)) || (rc = ensure_light_state(sc, *D))) return rc;
-    HIP_OK(hipDeviceSynchronize());
-    for (int k = -1; k < reps; k++) {  // one warm-up run
-        HIP_OK(hipMemsetAsync(D->ltab.group_dirty, 1, (size_t)D->ltab.ngroups, D->stream));
-        if (k == 0) HIP_OK(hipEventRecord(D->evl0, D->stream));
-        if ((rc = light_area_cum_enqueue(D->ltab, D->stream))) return rc;
-    }
-    HIP_OK(hipEventRecord(D->evl1, D->stream));
-    HIP_OK(hipMemsetAsync(D->ltab.group_dirty, 0, (size_t)D->ltab.ngroups, D->stream));
-    HIP_OK(hipStreamSynchronize(D->stream));
-    float ms = 0;
-    HIP_OK(hipEventElapsedTime(&ms, D->evl0, D->evl1));
-    *seconds = 1e-3 * ms / reps;
-    return MCPT_OK;
-}
-
-int mcpt_debug_bvh4_download(mcpt_scene* sc, int32_t device, int64_t* counts, void* nodes, void* qnodes, int32_t* leaf_facets,
-                             int64_t cap_nodes, int64_t cap_slots) {
-    if (!sc || !counts) {
-        set_error("invalid argument");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    DeviceTree t;
-    int rc;
-    if ((rc = download_tree(sc, device, false, &t))) return rc;
-    counts[0] = (int64_t)t.b4.size();
-    counts[1] = (int64_t)t.leaf_facets.size();
-    if (((nodes || qnodes) && cap_nodes < counts[0]) || (leaf_facets && cap_slots < counts[1])) {
-        set_error("mcpt_debug_bvh4_download: the tree has %lld nodes and %lld leaf slots, more than the buffers hold",
-                  (long long)counts[0], (long long)counts[1]);
-        return MCPT_E_INVALID;
-    }
-    if (nodes) std::memcpy(nodes, t.b4.data(), t.b4.size() * sizeof(BvhNode4));
-    if (qnodes) std::memcpy(qnodes, t.q4.data(), t.q4.size() * sizeof(BvhNode4Q));
-    if (leaf_facets) std::copy(t.leaf_facets.begin(), t.leaf_facets.end(), leaf_facets);
-    return MCPT_OK;
-}
-
-int mcpt_debug_bvh8_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
-    if (!sc || !out) {
-        set_error("invalid argument");
-        return MCPT_E_INVALID;
-    }
-    std::lock_guard<std::mutex> lk(sc->mu);
-    if (int rc = bvh8_refused(sc)) return rc;
-    ensure_bvh8_host(sc);
-    const Bvh8& b = light_only ? sc->lbvh8 : sc->bvh8;
-    const Bvh& bb = light_only ? sc->lbvh : sc->bvh;
-    const HostScene& hs = sc->host;
-    int64_t nodes = 0, tris = 0, dup = 0, bad = 0, maxd = 0;
-    std::vector<int> seen(hs.F, 0);
-    struct Box {
-        float lo[3], hi[3];
-    };
-    std::vector<Box> path;
-    std::vector<RefRegion> refs;
-    auto decode = [](const BvhNode8Q& n, int a, int k, bool hi) {
-        const uint32_t w = hi ? n.qhi[a][k >> 2] : n.qlo[a][k >> 2];
-        const uint32_t bits = ((n.ex >> (8 * a)) & 0xffu) << 23;
-        float sc_;
-        std::memcpy(&sc_, &bits, 4);
-        return std::fmaf((float)((w >> (8 * (k & 3))) & 0xffu), sc_, n.org[a]);
-    };
-    std::function<void(int32_t, int)> walk = [&](int32_t ni, int depth) {
-        if (ni < 0 || (size_t)ni >= b.nodes.size()) {
-            bad++;
-            return;
-        }
-        nodes++;
-        maxd = std::max<int64_t>(maxd, depth);
-        const BvhNode8Q& n = b.nodes[ni];
-        const uint32_t imask = n.ex >> 24;
-        for (int k = 0; k < 8; k++) {
-            Box bx;
-            for (int a = 0; a < 3; a++) bx.lo[a] = decode(n, a, k, false), bx.hi[a] = decode(n, a, k, true);
-            path.push_back(bx);
-            if (imask & (1u << k)) {
-                walk(n.base_inner + k, depth + 1);
-            } else {
-                for (int j = 0; j < 2; j++) {
-                    if (!(n.tvalid & (1u << (2 * k + j)))) continue;
-                    const int64_t q = (int64_t)n.base_tri + 2 * k + j;
-                    if (q < 0 || (size_t)q >= b.tri_facets.size() || b.tri_facets[q] < 0 || b.tri_facets[q] >= hs.F) {
-                        bad++;
-                        continue;
-                    }
-                    const int f = b.tri_facets[q];
-                    tris++;
-                    if (seen[f]++) dup++;
-                    RefRegion r{f, {-FLT_MAX, -FLT_MAX, -FLT_MAX}, {FLT_MAX, FLT_MAX, FLT_MAX}};
-                    for (const Box& p : path)
-                        for (int a = 0; a < 3; a++) r.lo[a] = std::max(r.lo[a], p.lo[a]), r.hi[a] = std::min(r.hi[a], p.hi[a]);
-                    refs.push_back(r);
-                }
-            }
-            path.pop_back();
-        }
-    };
-    if (!b.nodes.empty()) walk(0, 1);
-    bad += check_coverage(hs.pos, refs);
-    out[0] = nodes;
-    out[1] = tris - dup;  // distinct facets reached
-    out[2] = (int64_t)bb.leaf_facets.size() - dup_refs(bb);
-    out[3] = dup;
-    out[4] = bad;
-    out[5] = maxd;
-    return MCPT_OK;
-}
-
-// the 4-wide tree every traversal kernel reads (collapse_bvh4 of the binary tree) and its quantized form
-// (quantize_bvh4), walked on the host: every facet of the binary tree reached exactly once, each vertex
-// inside every ancestor slot's box, and every quantized slot box containing its fp32 box (the conservative
-// rounding the persistent traversal relies on)
 int mcpt_debug_tri_filter(int32_t n, const float* tri, const double* ro, const double* rd, const float* tlim,
                           int32_t* verdict, float* tup) {
     if (n < 0 || (n > 0 && (!tri || !ro || !rd || !tlim || !verdict || !tup))) return MCPT_E_INVALID;
