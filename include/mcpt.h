@@ -48,7 +48,9 @@ extern "C" {
                                * mcpt_scene_host_sync, mcpt_transform_rotation); an on-device rebuild of the main tree
                                * (mcpt_rebuild_stats, mcpt_scene_rebuild, mcpt_scene_tree_cost); movable light
                                * triangles (mcpt_scene_set_lights_movable, mcpt_scene_lights_movable,
-                               * mcpt_light_update_stats, mcpt_scene_light_update_info);
+                               * mcpt_light_update_stats, mcpt_scene_light_update_info); in-place re-lighting
+                               * (mcpt_relight_stats, mcpt_scene_set_light_radiance and its _device form,
+                               * mcpt_scene_set_materials, mcpt_scene_light_groups);
                                * mcpt_stats gains pick_table_roots (appended, guarded by stats_size: stats ABI 2.3);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
@@ -476,6 +478,58 @@ typedef struct {
 } mcpt_light_update_stats;
 void mcpt_light_update_stats_init(mcpt_light_update_stats* stats);
 int mcpt_scene_light_update_info(const mcpt_scene* scene, mcpt_light_update_stats* out);
+
+/* In-place re-lighting: new radiances for a range of the light table, new rows of the material table.
+ * No reference interface corresponds.  The rule is mcpt_scene_update's: after a successful call the scene behaves as
+ * mcpt_scene_create of the new arrays WITH THE SCENE'S CURRENT LIGHT GROUPING PASSED AS light_group would -- every light
+ * table byte for byte, mcpt_light_prep bit for bit, renders in every mode up to the order of the fp64 atomics,
+ * mcpt_scene_arrays with the new radiances and materials -- on the host copy and on every device the scene lives on.
+ * The grouping is part of the rule because mcpt_scene_create without light_group infers the groups from runs of equal
+ * radiance: a re-light never regroups, even when two neighbouring groups end up with equal radiances.  Unchanged too:
+ * the light table's order, light_facet, which facets are lights, the facet, material and group counts, material_id,
+ * every tree and all geometry.  The calls work whether mcpt_scene_set_lights_movable is on or off, take the scene's
+ * lock (one render or edit at a time per handle), and with a communicator every rank must make the same call.
+ *
+ * mcpt_scene_set_light_radiance: lights [first_light, first_light + count) of the light table get the radiances rgb
+ * (count * 3 doubles).  As mcpt_scene_create forms them: a light's sum is (r + g) + b in fp64, a group's sum is the sum
+ * of its FIRST light, and the groups' running sum is added in group order.  On every device state the rows of the
+ * radiance and sum tables, the radiance words of the light records, the (S, K) of the 64-light chunks of the range,
+ * the band constants and the groups' sums are derived again by kernels on the state's stream, which is synchronised
+ * once at the end of the call; neither refit state is needed or built.  A zero radiance is allowed and switches the light off.
+ * mcpt_scene_set_light_radiance_device: the same from count * 3 doubles of device memory on `device` (< 0: the current
+ * one); the values are checked by a kernel that counts the offenders, read back before any modifying kernel is
+ * enqueued; the host copy follows inside the call by one device-to-host copy (nothing is left pending).
+ * mcpt_scene_set_materials: rows [first_material, first_material + count) of the material table get mtl (count * 7
+ * floats: Kd[3] Ks[3] Ns), on the host copy and by one asynchronous copy on each device state's stream.
+ * mcpt_scene_light_groups: group[l] = the index of light l's group (nlights entries, ascending): exactly what
+ * mcpt_scene_desc.light_group takes, so a caller can build the fresh scene of the rule.
+ *
+ * count == 0 succeeds and does nothing.  Refused with MCPT_E_INVALID and a message that names the first offender,
+ * before anything on the host or on any device is modified: a NULL scene; count < 0, a first index < 0 or a range that
+ * ends behind the table; a NULL array with count > 0; a stats struct_size mismatch; a radiance component or a Kd / Ks /
+ * Ns value that is negative or not finite (the device form reports how many); in the device form a pointer that is not
+ * device memory on `device`.
+ *
+ * Not covered: reassigning facets to materials, turning a facet into a light or back, changing the light, material or
+ * group counts, the lights of the opt-in 8-wide debug trees, and the history of a surface whose shading changed (the
+ * history clamp's case, as for a moved light). */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mcpt_relight_stats) of the caller's header (mcpt_relight_stats_init sets it) */
+    int32_t lights;         /* lights given a radiance (count of a radiance call, else 0) */
+    int32_t chunks;         /* 64-light chunks of the range: their (S, K) were recomputed */
+    int32_t groups;         /* groups whose first light is in the range: their sum was rewritten */
+    int32_t materials;      /* material rows written (count of mcpt_scene_set_materials, else 0) */
+    int32_t device_states;  /* device states brought up to date (0: none existed yet) */
+    double device_seconds;  /* HIP events around the stage on the first device state (0 if none) */
+} mcpt_relight_stats;
+void mcpt_relight_stats_init(mcpt_relight_stats* stats);
+int mcpt_scene_set_light_radiance(mcpt_scene* scene, int32_t first_light, int32_t count, const double* rgb,
+                                  mcpt_relight_stats* stats);
+int mcpt_scene_set_light_radiance_device(mcpt_scene* scene, int32_t device, int32_t first_light, int32_t count,
+                                         const void* dev_rgb, mcpt_relight_stats* stats);
+int mcpt_scene_set_materials(mcpt_scene* scene, int32_t first_material, int32_t count, const float* mtl,
+                             mcpt_relight_stats* stats);
+int mcpt_scene_light_groups(const mcpt_scene* scene, int32_t* group);
 
 /* main.cpp:547-588: render samples [sample_begin, sample_end) of an spp-sample frame and ADD
  * sum_k L_k * (1/spp) into out_rgb (caller-owned host buffer, height*width*3 doubles, row 0 =

@@ -114,7 +114,8 @@ int mcpt_debug_bvh4_download(mcpt_scene* scene, int32_t device, int64_t counts[2
 int mcpt_debug_bvh4_check_device_light(mcpt_scene* scene, int32_t device, int64_t out[6]);
 // Downloads one light table of the state `device` (-1 = current) holds, as raw bytes: which = "lt_v", "lt_n", "lt_pk",
 // "lt_d", "lt_w", "lt_f", "lt_pair", "chunk_sph", "chunk_sk", "l_area", "l_area_cum" (each in the size the state
-// allocated, padding and sentinel records included) or "globals" (light_bound and the band constants the state passes
+// allocated, padding and sentinel records included), the tables a re-light writes beside those (mcpt_scene_set_light_radiance,
+// mcpt_scene_set_materials): "light_rad", "light_sum", "grp_sum", "grp_cum", "mtl", or "globals" (light_bound and the band constants the state passes
 // to its kernels by value: 6 doubles band_ctr[3], band_R, band_S, band_K, then the float light_bound and 4 zero
 // bytes).  *bytes = the table's size; out may be NULL (size query), else cap >= *bytes or MCPT_E_INVALID.  Creates the
 // device state if needed.  Lets a test compare an updated state against a fresh one byte for byte.

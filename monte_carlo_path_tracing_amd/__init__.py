@@ -24,7 +24,7 @@ __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_rays", 
            "UpsampleOpts", "upsample", "upsample_device", "camera_scaled",
            "upsample_phase", "camera_phase_rays", "temporal_upsample", "temporal_upsample_device",
            "MotionBuffers", "render_motion_aovs", "render_motion_aovs_device", "temporal_accumulate_motion",
-           "temporal_accumulate_motion_device", "transform_rotation",
+           "temporal_accumulate_motion_device", "transform_rotation", "RelightStats",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -214,6 +214,15 @@ class LightUpdateStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
 
 
+class RelightStats(C.Structure):
+    """mcpt_relight_stats (include/mcpt.h)"""
+    _fields_ = [("struct_size", C.c_uint32), ("lights", C.c_int32), ("chunks", C.c_int32), ("groups", C.c_int32),
+                ("materials", C.c_int32), ("device_states", C.c_int32), ("device_seconds", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "struct_size"}
+
+
 # mcpt_debug_bvh4_download's node layouts (BvhNode4 / BvhNode4Q of the library; leaf children as ~first slot, count)
 BVH4_NODE = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("child", np.int32, 4), ("count", np.int32, 4)])
 BVH4_QNODE = np.dtype([("org", np.float32, 3), ("ex", np.uint32), ("q", np.uint32, 6), ("pad", np.uint32, 2), ("child", np.int32, 4)])
@@ -243,7 +252,9 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_transform_rotation",
            "mcpt_rebuild_stats_init", "mcpt_scene_rebuild", "mcpt_scene_tree_cost",
            "mcpt_scene_set_lights_movable", "mcpt_scene_lights_movable", "mcpt_light_update_stats_init",
-           "mcpt_scene_light_update_info"]
+           "mcpt_scene_light_update_info",
+           "mcpt_relight_stats_init", "mcpt_scene_set_light_radiance", "mcpt_scene_set_light_radiance_device",
+           "mcpt_scene_set_materials", "mcpt_scene_light_groups"]
 DEBUG_EXPORTS = ["mcpt_debug_bvh4_check_device_light", "mcpt_debug_light_tables", "mcpt_debug_light_area_cum_bench","mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download",
@@ -391,6 +402,13 @@ def lib():
             L.mcpt_light_update_stats_init.argtypes = [C.POINTER(LightUpdateStats)]
             L.mcpt_light_update_stats_init.restype = None
             L.mcpt_scene_light_update_info.argtypes = [P, C.POINTER(LightUpdateStats)]
+        if hasattr(L, "mcpt_scene_set_light_radiance"):  # and the in-place re-lighting
+            L.mcpt_relight_stats_init.argtypes = [C.POINTER(RelightStats)]
+            L.mcpt_relight_stats_init.restype = None
+            L.mcpt_scene_set_light_radiance.argtypes = [P, I, I, P, C.POINTER(RelightStats)]
+            L.mcpt_scene_set_light_radiance_device.argtypes = [P, I, I, I, P, C.POINTER(RelightStats)]
+            L.mcpt_scene_set_materials.argtypes = [P, I, I, P, C.POINTER(RelightStats)]
+            L.mcpt_scene_light_groups.argtypes = [P, ip]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -526,6 +544,44 @@ class Scene:
         lib().mcpt_light_update_stats_init(C.byref(st))
         _check(lib().mcpt_scene_light_update_info(self.h, C.byref(st)))
         return st.as_dict()
+
+    def _relight(self, call, *args):
+        st = RelightStats()
+        lib().mcpt_relight_stats_init(C.byref(st))
+        _check(call(self.h, *args, C.byref(st)))
+        return st.as_dict()
+
+    def set_light_radiance(self, first_light, radiance):
+        """mcpt_scene_set_light_radiance: lights [first_light, first_light + n) of the light table get the radiances
+        `radiance` (n x 3), on the host copy and on every device the scene lives on; the scene then behaves as
+        Scene.create of the new arrays with light_group=self.light_groups() would (a re-light never regroups).  Zero
+        switches a light off.  Returns the call's mcpt_relight_stats as a dict."""
+        rgb = _d(radiance).reshape(-1, 3)
+        return self._relight(lib().mcpt_scene_set_light_radiance, int(first_light), rgb.shape[0], rgb.ctypes.data_as(C.c_void_p))
+
+    def set_light_radiance_device(self, first_light, count, ptr, device=None):
+        """mcpt_scene_set_light_radiance_device: the same from count x 3 doubles of device memory on `device`."""
+        return self._relight(lib().mcpt_scene_set_light_radiance_device, -1 if device is None else int(device), int(first_light),
+                             int(count), C.c_void_p(ptr))
+
+    def set_group_radiance(self, g, rgb):
+        """every light of group g (an index of light_groups()) set to the one colour rgb"""
+        ls = np.flatnonzero(self.light_groups() == int(g))
+        if ls.size == 0:
+            raise MCPTError("Scene.set_group_radiance: the scene has no lights in group %d" % int(g))
+        return self.set_light_radiance(int(ls[0]), np.tile(_d(rgb, (1, 3)), (ls.size, 1)))
+
+    def set_materials(self, first, materials):
+        """mcpt_scene_set_materials: rows [first, first + n) of the material table get `materials` (n x 7: Kd[3] Ks[3]
+        Ns), on the host copy and on every device the scene lives on.  Returns the call's mcpt_relight_stats as a dict."""
+        mtl = np.ascontiguousarray(materials, np.float32).reshape(-1, 7)
+        return self._relight(lib().mcpt_scene_set_materials, int(first), mtl.shape[0], mtl.ctypes.data_as(C.c_void_p))
+
+    def light_groups(self):
+        """mcpt_scene_light_groups: the group index of every light (ascending): what Scene.create's light_group takes"""
+        g = np.zeros(max(self.nlights, 1), np.int32)
+        _check(lib().mcpt_scene_light_groups(self.h, g))
+        return g[:self.nlights]
 
     def pose_save(self):
         """mcpt_scene_pose_save: the current vertex positions and normals become the scene's previous pose, on the host
@@ -1589,14 +1645,18 @@ def debug_bvh4_check_device_light(scene, device=-1):
 
 LIGHT_TABLES = ("lt_v", "lt_n", "lt_pk", "lt_d", "lt_w", "lt_f", "lt_pair", "chunk_sph", "chunk_sk", "l_area", "l_area_cum",
                 "globals")
+# and what a re-light writes beside them (Scene.set_light_radiance, Scene.set_materials)
+RELIGHT_TABLES = LIGHT_TABLES + ("light_rad", "light_sum", "grp_sum", "grp_cum", "mtl")
 
 
 def debug_light_tables(scene, which=None, device=-1):
     """Diagnostics: one light table of the state `device` holds as raw bytes (np.uint8), or with which=None a dict of
-    all of LIGHT_TABLES (include/mcpt_debug.h).  "globals": band_ctr[3], band_R, band_S, band_K (float64), then
+    all of LIGHT_TABLES (include/mcpt_debug.h); a tuple of names (RELIGHT_TABLES) gives a dict of those.  "globals": band_ctr[3], band_R, band_S, band_K (float64), then
     light_bound (float32) and 4 zero bytes."""
     if which is None:
         return {w: debug_light_tables(scene, w, device) for w in LIGHT_TABLES}
+    if isinstance(which, (tuple, list)):
+        return {w: debug_light_tables(scene, w, device) for w in which}
     n = C.c_int64(0)
     _check(lib().mcpt_debug_light_tables(scene.h, int(device), which.encode(), None, 0, C.byref(n)))
     out = np.zeros(max(int(n.value), 1), np.uint8)

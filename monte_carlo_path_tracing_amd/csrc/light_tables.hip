@@ -18,6 +18,12 @@
 //   k_light_leaf_scatter one thread per facet of the range: the facet's slots of the light-only tree's leaf array
 //                        from tri_v, and their dirty bytes (refit.hip's k_refit_level does the rest).
 // No block waits on another; kernel boundaries on the stream are the only synchronisation.
+//
+// A re-light (mcpt_scene_set_light_radiance) reuses k_light_chunks and k_light_globals after its own
+//   k_light_radiance_validate (device form, before anything is modified) one thread per component: negative or not finite;
+//   k_light_radiance     one thread per light of the range: light_rad, light_sum, the radiance words of lt_n / lt_w /
+//                        lt_f, a group's grp_sum at its first light; marks the chunk (and that group) dirty;
+//   k_light_group_cum    one thread: the running fp64 sum of grp_sum in group order.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -331,7 +337,80 @@ __global__ __launch_bounds__(kLtBlock) void k_light_leaf_scatter(RefitDev r, int
     }
 }
 
+// ---- a re-light (mcpt_scene_set_light_radiance) ----
+
+// one thread per value of the staged radiances: negative or not finite (a NaN fails v >= 0)
+__global__ __launch_bounds__(kLtBlock) void k_light_radiance_validate(int64_t n, const double* __restrict__ rgb, unsigned* bad) {
+    const int64_t i = (int64_t)blockIdx.x * kLtBlock + threadIdx.x;
+    if (i >= n) return;
+    const double v = rgb[i];
+    if (!(v >= 0) || !isfinite(v)) atomicAdd(bad, 1u);  // only a refused call gets here
+}
+
+// one thread per light of the range: everything mcpt_scene_create derives from the radiance of ONE light, by its
+// formulas (the sum is (r + g) + b).  The chunk's (S, K) and the constants follow in k_light_chunks / k_light_globals,
+// grp_cum in k_light_group_cum.  Geometry words, pair records, padding and sentinel records are not touched.
+__global__ __launch_bounds__(kLtBlock) void k_light_radiance(LightTabDev t, int first, int count, const double* __restrict__ rgb) {
+    const int i = (int)(blockIdx.x * kLtBlock + threadIdx.x);
+    if (i >= count) return;
+    const int l = first + i;
+    const double r = rgb[3 * (size_t)i], g = rgb[3 * (size_t)i + 1], b = rgb[3 * (size_t)i + 2];
+    const double lsum = r + g + b;
+    t.light_rad[3 * (size_t)l] = r;
+    t.light_rad[3 * (size_t)l + 1] = g;
+    t.light_rad[3 * (size_t)l + 2] = b;
+    t.light_sum[l] = lsum;
+    t.lt_n[4 * (size_t)l + 3] = lsum;                          // double4 .w
+    t.lt_w[2 * (5 * (size_t)l + 4) + 1] = 2.0 * lsum;          // double2 [5l + 4].y
+    t.lt_f[4 * (4 * (size_t)l + 2) + 1] = (float)(2.0 * lsum);  // float4 [4l + 2].y
+    t.chunk_dirty[l >> 6] = 1;
+    const int grp = t.light_group[l];
+    if (t.grp_range[2 * grp] == l) {  // a group's sum is its first light's, as create takes it
+        t.grp_sum[grp] = lsum;
+        t.group_dirty[grp] = 1;
+    }
+}
+
+// grp_cum: the running fp64 sum of grp_sum in group order, added serially by one thread (the order is part of the
+// rule, as for k_light_area_cum; a scene has a handful of groups)
+__global__ __launch_bounds__(64) void k_light_group_cum(LightTabDev t) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double run = 0;
+    for (int g = 0; g < t.ngroups; g++) {
+        run += t.grp_sum[g];
+        t.grp_cum[g] = run;
+    }
+}
+
 }  // namespace
+
+int light_radiance_validate_enqueue(int64_t n, const double* drgb, unsigned* bad, void* stream) {
+    if (n < 1 || !drgb || !bad) {
+        set_error("light tables: bad validation arguments");
+        return MCPT_E_INVALID;
+    }
+    hipLaunchKernelGGL(k_light_radiance_validate, dim3((unsigned)((n + kLtBlock - 1) / kLtBlock)), dim3(kLtBlock), 0,
+                       static_cast<hipStream_t>(stream), n, drgb, bad);
+    LT_HIP_OK(hipGetLastError());
+    return MCPT_OK;
+}
+
+int light_radiance_enqueue(const LightTabDev& t, int32_t first, int32_t count, const double* drgb, bool groups, void* stream) {
+    if (first < 0 || count < 1 || (int64_t)first + count > t.NL || t.nchunks != (t.NL + 63) / 64 || t.ngroups < 1 || !drgb ||
+        !t.light_rad || !t.grp_sum || !t.grp_cum) {
+        set_error("light tables: range or tables do not match the device state");
+        return MCPT_E_INVALID;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_light_radiance, dim3((count + kLtBlock - 1) / kLtBlock), dim3(kLtBlock), 0, st, t, first, count, drgb);
+    hipLaunchKernelGGL(k_light_chunks, dim3(t.nchunks), dim3(64), 0, st, t, 0);
+    hipLaunchKernelGGL(k_light_globals, dim3(1), dim3(kLtBlock), 0, st, t);
+    if (groups) hipLaunchKernelGGL(k_light_group_cum, dim3(1), dim3(64), 0, st, t);
+    LT_HIP_OK(hipGetLastError());
+    LT_HIP_OK(hipMemsetAsync(t.chunk_dirty, 0, (size_t)t.nchunks, st));
+    LT_HIP_OK(hipMemsetAsync(t.group_dirty, 0, (size_t)t.ngroups, st));
+    return MCPT_OK;
+}
 
 int light_validate_enqueue(int32_t count, const float* dpos, const int32_t* tri_light_of_range, unsigned* bad, void* stream) {
     if (count < 1 || !dpos || !tri_light_of_range || !bad) {

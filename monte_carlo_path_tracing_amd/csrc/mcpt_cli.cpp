@@ -70,6 +70,11 @@
 //   facets: before each frame's move the scene's pose is saved (mcpt_scene_pose_save), the frame renders the motion AOVs
 //   (mcpt_render_motion_aovs) and accumulates with mcpt_temporal_accumulate_motion (mcpt_sequence_set_motion in the device
 //   sequence), so a moved surface keeps its history instead of restarting it every frame.  Not with --upsample.
+//               [--dim GROUP:FACTOR]... [--tint MATERIAL:R,G,B]...
+//   --dim and --tint (with --frames N, with or without --device-sequence, with --move / --rotate or alone) re-light the
+//   scene in place: before frame k >= 1 the radiance of every light of GROUP (mcpt_scene_light_groups) is multiplied by
+//   FACTOR once more (mcpt_scene_set_light_radiance; 0 switches the group off), and before frame 1 row MATERIAL of the
+//   material table gets Kd = (R, G, B) (mcpt_scene_set_materials).  Each prints a "dimmed" / "tinted" line.
 //   --devices renders on several GPUs of this node: the sample range is split into one contiguous shard
 //   per listed device, rendered concurrently, and summed by ONE RCCL reduce into the first device
 //   (mcpt_render_opts.devices; the reference itself is single-threaded, README.md:418).
@@ -288,6 +293,102 @@ struct Rebuilder {
     }
 };
 
+// --dim GROUP:FACTOR (repeatable) and --tint MATERIAL:R,G,B (repeatable), with --frames N: before frame k >= 1 every light
+// of GROUP (an index of mcpt_scene_light_groups) gets its radiance multiplied by FACTOR once more, each step an fp64
+// multiply of the previous value (mcpt_scene_set_light_radiance); before frame 1 row MATERIAL of the material table
+// gets Kd = (R, G, B) (mcpt_scene_set_materials).  Nothing is rebuilt and no geometry moves.
+struct Relighter {
+    struct Dim {
+        int32_t group;
+        double factor;
+        int32_t l0 = 0, l1 = 0;  // the group's run of the light table
+    };
+    struct Tint {
+        int32_t material;
+        float kd[3];
+    };
+    std::vector<Dim> dims;
+    std::vector<Tint> tints;
+    std::vector<double> rad;  // the light table's radiances as the steps so far left them
+    bool parse_dim(const char* arg) {
+        Dim d{};
+        char tail = 0;
+        if (std::sscanf(arg, "%d:%lf%c", &d.group, &d.factor, &tail) != 2 || d.group < 0 || !std::isfinite(d.factor) || d.factor < 0) return false;
+        dims.push_back(d);
+        return true;
+    }
+    bool parse_tint(const char* arg) {
+        Tint t{};
+        char tail = 0;
+        if (std::sscanf(arg, "%d:%f,%f,%f%c", &t.material, &t.kd[0], &t.kd[1], &t.kd[2], &tail) != 4 || t.material < 0) return false;
+        for (float v : t.kd)
+            if (!std::isfinite(v) || v < 0) return false;
+        tints.push_back(t);
+        return true;
+    }
+    // the groups and rows against the scene
+    int bind(mcpt_scene* scene) {
+        int32_t nm = 0, nl = 0;
+        mcpt_scene_counts(scene, nullptr, &nm, &nl);
+        std::vector<int32_t> group(nl > 0 ? nl : 1, -1);
+        rad.assign(3 * (size_t)(nl > 0 ? nl : 1), 0.0);
+        if (nl > 0) {
+            mcpt_scene_light_groups(scene, group.data());
+            mcpt_scene_arrays(scene, nullptr, nullptr, nullptr, nullptr, nullptr, rad.data(), nullptr);
+        }
+        for (Dim& d : dims) {
+            d.l0 = d.l1 = 0;
+            for (int32_t l = 0; l < nl; l++)
+                if (group[l] == d.group) {
+                    if (d.l1 == d.l0) d.l0 = l;
+                    d.l1 = l + 1;
+                }
+            if (d.l1 == d.l0) {
+                std::fprintf(stderr, "--dim: the scene has no light group %d (its %d light triangles are in groups 0..%d)\n", d.group, nl,
+                             nl > 0 ? group[nl - 1] : -1);
+                return 2;
+            }
+        }
+        for (const Tint& t : tints)
+            if (t.material >= nm) {
+                std::fprintf(stderr, "--tint: material %d is not one of the scene's %d\n", t.material, nm);
+                return 2;
+            }
+        return 0;
+    }
+    int apply(mcpt_scene* scene, int k) {
+        if (k < 1) return 0;
+        mcpt_relight_stats rs;
+        mcpt_relight_stats_init(&rs);
+        for (const Dim& d : dims) {
+            for (size_t i = 3 * (size_t)d.l0; i < 3 * (size_t)d.l1; i++) rad[i] *= d.factor;
+            if (mcpt_scene_set_light_radiance(scene, d.l0, d.l1 - d.l0, rad.data() + 3 * (size_t)d.l0, &rs) != MCPT_OK) {
+                std::fprintf(stderr, "--dim failed: %s\n", mcpt_last_error());
+                return 1;
+            }
+            std::printf("  dimmed light group %d by %g (step %d): %d lights in %d chunks, %.3f ms device\n", d.group, d.factor, k, rs.lights,
+                        rs.chunks, rs.device_seconds * 1e3);
+        }
+        if (k == 1 && !tints.empty()) {
+            int32_t nm = 0;
+            mcpt_scene_counts(scene, nullptr, &nm, nullptr);
+            std::vector<float> mtl(7 * (size_t)nm);
+            mcpt_scene_arrays(scene, nullptr, nullptr, nullptr, mtl.data(), nullptr, nullptr, nullptr);
+            for (const Tint& t : tints) {
+                float* row = mtl.data() + 7 * (size_t)t.material;
+                std::memcpy(row, t.kd, sizeof t.kd);
+                if (mcpt_scene_set_materials(scene, t.material, 1, row, &rs) != MCPT_OK) {
+                    std::fprintf(stderr, "--tint failed: %s\n", mcpt_last_error());
+                    return 1;
+                }
+                std::printf("  tinted material %d: Kd = (%g, %g, %g), %.3f ms device\n", t.material, t.kd[0], t.kd[1], t.kd[2],
+                            rs.device_seconds * 1e3);
+            }
+        }
+        return 0;
+    }
+};
+
 struct SequenceArgs {
     int frames, spp, mode, flags;
     double orbit;
@@ -298,6 +399,7 @@ struct SequenceArgs {
     bool motion;  // --motion
     Rotator* rotate;  // --rotate, or null
     Rebuilder* rebuild;  // --rebuild, or null
+    Relighter* relight;  // --dim / --tint, or null
 };
 
 // --frames: render, accumulate (and filter) frame after frame; the history ping-pongs between two sets of buffers
@@ -357,6 +459,7 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
         if (a.move && a.move->apply(scene, k)) return 1;
         if (a.rotate && a.rotate->apply(scene, k)) return 1;
         if (a.rebuild && a.rebuild->apply(scene, k)) return 1;
+        if (a.relight && a.relight->apply(scene, k)) return 1;
         if (mcpt_camera_orbit(&cam0, k * a.orbit, &cur.cam) != MCPT_OK) {
             std::fprintf(stderr, "%s\n", mcpt_last_error());
             return 1;
@@ -493,7 +596,7 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
             break;
         }
         if ((a.move && a.move->apply(scene, k)) || (a.rotate && a.rotate->apply(scene, k)) ||
-            (a.rebuild && a.rebuild->apply(scene, k))) {
+            (a.rebuild && a.rebuild->apply(scene, k)) || (a.relight && a.relight->apply(scene, k))) {
             rc = 1;
             break;
         }
@@ -585,6 +688,7 @@ int main(int argc, char** argv) {
     Rotator rotator;
     bool rebuild_flag = false;
     Rebuilder rebuilder;
+    Relighter relighter;
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -674,6 +778,18 @@ int main(int argc, char** argv) {
             }
             rebuild_flag = true;
         }
+        else if (!std::strcmp(argv[a], "--dim")) {
+            if (!relighter.parse_dim(next())) {
+                std::fprintf(stderr, "--dim needs GROUP:FACTOR (a light group and a finite factor >= 0 per frame), not %s\n", argv[a]);
+                return 2;
+            }
+        }
+        else if (!std::strcmp(argv[a], "--tint")) {
+            if (!relighter.parse_tint(next())) {
+                std::fprintf(stderr, "--tint needs MATERIAL:R,G,B (a row of the material table and a finite Kd >= 0), not %s\n", argv[a]);
+                return 2;
+            }
+        }
         else if (!std::strcmp(argv[a], "--motion")) motion_flag = true;
         else if (!std::strcmp(argv[a], "--lights-movable")) lights_movable_flag = true;
         else if (!std::strcmp(argv[a], "--devices")) {
@@ -719,6 +835,11 @@ int main(int argc, char** argv) {
     if (lights_movable_flag && (frames == 0 || !(move_flag || rotate_flag))) {  // refused before anything is loaded
         std::fprintf(stderr, "--lights-movable lets the moves between the frames of a sequence take light triangles along; add %s\n",
                      frames == 0 ? "--frames N" : "--move or --rotate");
+        return 2;
+    }
+    const bool relight_flag = !relighter.dims.empty() || !relighter.tints.empty();
+    if (relight_flag && frames == 0) {  // refused before anything is loaded
+        std::fprintf(stderr, "--dim and --tint re-light the scene between the frames of a sequence; add --frames N\n");
         return 2;
     }
     if (motion_flag && (frames == 0 || upsample)) {  // refused before anything is loaded
@@ -832,9 +953,12 @@ int main(int argc, char** argv) {
         if (rotate_flag) {
             if (const int rc = rotator.bind(scene)) return rc;
         }
+        if (relight_flag) {
+            if (const int rc = relighter.bind(scene)) return rc;
+        }
         const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out,
                               move_flag ? &mover : nullptr, motion_flag, rotate_flag ? &rotator : nullptr,
-                              rebuild_flag ? &rebuilder : nullptr};
+                              rebuild_flag ? &rebuilder : nullptr, relight_flag ? &relighter : nullptr};
         if (clamp_flag && !history_clamp) {
             std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
             return 2;

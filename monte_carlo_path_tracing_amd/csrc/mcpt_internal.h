@@ -208,7 +208,8 @@ struct LightTabDev {
     const float* tri_v;          // F * 3 float4
     const float* tri_n;          // F * 9
     const int32_t* tri_light;    // F -> light or -1
-    const double* light_sum;     // NL
+    double* light_rad;           // NL * 3 (written by a re-light only)
+    double* light_sum;           // NL
     const int32_t* light_group;  // NL -> group
     const int32_t* grp_range;    // ngroups * (first light, count)
     float* lt_v;                 // NL * 3 float4
@@ -220,13 +221,15 @@ struct LightTabDev {
     float* lt_pair;              // 32 floats per light pair
     double* l_area;              // NL
     double* l_area_cum;          // NL
+    double* grp_sum;             // ngroups (a re-light)
+    double* grp_cum;             // ngroups (a re-light)
     float* chunk_sph;            // nchunks float4
     float* chunk_sk;             // nchunks float2
     double* chunk_row;           // nchunks * kLightRowWords
     uint8_t* chunk_dirty;        // nchunks
     uint8_t* group_dirty;        // ngroups
     LightGlobals* globals;
-    unsigned* counters;          // the light tree's RefitDev counters: [2] chunks recomputed, [3] groups recomputed
+    unsigned* counters;          // the tables' own 16 words: [2] chunks recomputed, [3] groups recomputed
     int32_t F, NL, nchunks, ngroups;
 };
 // adds to *bad the light triangles of the staged range (dpos: count * 9 floats; tri_light_of_range: count entries)
@@ -241,6 +244,14 @@ int light_tables_enqueue(const LightTabDev& t, const RefitDev& lr, const int32_t
                          int32_t count, double margin, void* stream);
 // k_light_area_cum alone over the groups whose dirty byte is set (tools/light_update_bench.py times it)
 int light_area_cum_enqueue(const LightTabDev& t, void* stream);
+// a re-light (mcpt_scene_set_light_radiance).  light_radiance_validate_enqueue adds to *bad the values
+// of drgb (n doubles) that are negative or not finite; *bad is not cleared.  light_radiance_enqueue gives lights
+// [first, first + count) the radiances drgb (count * 3 doubles of device memory): their rows of light_rad / light_sum,
+// the radiance words of lt_n / lt_w / lt_f and the grp_sum of every group whose first light is in the range, then the
+// dirty chunks' (S, K) and rows, the constants, grp_cum when `groups` (a group's first light is in the range), and
+// the dirty bytes cleared.  No geometry field and no tree is touched.
+int light_radiance_validate_enqueue(int64_t n, const double* drgb, unsigned* bad, void* stream);
+int light_radiance_enqueue(const LightTabDev& t, int32_t first, int32_t count, const double* drgb, bool groups, void* stream);
 
 // rebuild.hip -- the device side of mcpt_scene_rebuild and mcpt_scene_tree_cost
 constexpr int kRebuildMaxLevels = 15;  // node levels of a rebuilt tree, for every input

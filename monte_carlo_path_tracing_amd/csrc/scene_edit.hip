@@ -1,6 +1,7 @@
 // Scene editing: everything that changes a loaded scene's geometry in place and keeps the host copy, the device
 // states and their trees in step -- mcpt_scene_update[_device], movable lights, mcpt_scene_pose_save / _rest_save,
-// mcpt_scene_transform with the lazily synced host copy, mcpt_scene_rebuild and mcpt_scene_tree_cost (include/mcpt.h).
+// mcpt_scene_transform with the lazily synced host copy, mcpt_scene_rebuild and mcpt_scene_tree_cost -- and what its
+// lights and surfaces look like: mcpt_scene_set_light_radiance[_device], mcpt_scene_set_materials (include/mcpt.h).
 // Host code only: the kernels are refit.hip's, light_tables.hip's and rebuild.hip's.  Locks are taken in the order
 // mu, host_mu, devs_mu; every function that visits device states leaves the caller's device current (DeviceRestore).
 #include <algorithm>
@@ -231,19 +232,18 @@ int mcpt::ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
     return MCPT_OK;
 }
 
-// what a device state's first light move builds (after ensure_refit_state): the same for the light-only tree, the
+// the tables' half of what a device state's first light move builds, and all a re-light needs: the
 // light tables' pointers, the light -> group map, the chunk rows (filled here from the tables as they are), the dirty
-// bytes and the small struct of constants.  The current device is D's.
-int mcpt::ensure_light_state(mcpt_scene* sc, DeviceState& D) {
-    if (D.lrefit.ready) return MCPT_OK;
+// bytes, the counters and the small struct of constants.  Needs neither refit state.  The current device is D's.
+int mcpt::ensure_light_tables(mcpt_scene* sc, DeviceState& D) {
+    if (D.ltab_ready) return MCPT_OK;
     const DScene& d = D.d;
     const HostScene& hs = sc->host;
-    ensure_slot_map(sc, true);
-    int rc;  // a scene without lights has no light-only tree to refit: refused as a tree of no nodes
-    if ((rc = build_tree_refit(D, D.lrefit, d.lbvh4, d.lbvh4q, hs.NL < 1 ? 0 : d.nlbvh4, d.lleaf_v, sc->lbvh.leaf_facets.size(),
-                               sc->lslots, "light-only ")))
-        return rc;
-    const RefitDev& r = D.lrefit.dev;
+    if (hs.NL < 1) {
+        set_error("the scene has no lights");
+        return MCPT_E_INVALID;
+    }
+    int rc;
     const int nch = prep_chunks(hs.NL), ng = d.ngroups;
     std::vector<int32_t> lgroup(hs.NL, 0);
     for (int g = 0; g < ng; g++)
@@ -251,14 +251,18 @@ int mcpt::ensure_light_state(mcpt_scene* sc, DeviceState& D) {
     const std::vector<uint8_t> zch(nch, 0), zg(std::max(ng, 1), 0);
     const std::vector<double> zrow(kLightRowWords * (size_t)nch, 0.0);
     const std::vector<LightGlobals> zglob(1);
+    const std::vector<unsigned> zc(16, 0);
     LightTabDev& t = D.ltab;
     if ((rc = upload(D, zch, &t.chunk_dirty)) || (rc = upload(D, zg, &t.group_dirty)) || (rc = upload(D, zrow, &t.chunk_row)) ||
-        (rc = upload(D, zglob, &t.globals)) || (rc = upload(D, lgroup, &t.light_group)))
+        (rc = upload(D, zglob, &t.globals)) || (rc = upload(D, lgroup, &t.light_group)) || (rc = upload(D, zc, &t.counters)))
         return rc;
-    t.tri_v = D.refit.dev.tri_v;
-    t.tri_n = D.refit.dev.tri_n;
+    t.tri_v = reinterpret_cast<const float*>(d.tri_v);
+    t.tri_n = d.tri_n;
     t.tri_light = d.tri_light;
-    t.light_sum = d.light_sum;
+    t.light_rad = const_cast<double*>(d.light_rad);
+    t.light_sum = const_cast<double*>(d.light_sum);
+    t.grp_sum = const_cast<double*>(d.grp_sum);
+    t.grp_cum = const_cast<double*>(d.grp_cum);
     t.grp_range = reinterpret_cast<const int32_t*>(d.grp_range);
     t.lt_v = const_cast<float*>(reinterpret_cast<const float*>(d.lt_v));
     t.lt_n = const_cast<double*>(reinterpret_cast<const double*>(d.lt_n));
@@ -271,7 +275,6 @@ int mcpt::ensure_light_state(mcpt_scene* sc, DeviceState& D) {
     t.l_area_cum = const_cast<double*>(d.l_area_cum);
     t.chunk_sph = const_cast<float*>(reinterpret_cast<const float*>(d.chunk_sph));
     t.chunk_sk = const_cast<float*>(reinterpret_cast<const float*>(d.chunk_sk));
-    t.counters = r.counters;
     t.F = d.F;
     t.NL = hs.NL;
     t.nchunks = nch;
@@ -282,6 +285,21 @@ int mcpt::ensure_light_state(mcpt_scene* sc, DeviceState& D) {
     // every chunk's row from the tables as they are: a later move recomputes only its own chunks
     if ((rc = light_chunks_all_enqueue(t, D.stream))) return rc;
     HIP_OK(hipStreamSynchronize(D.stream));
+    D.ltab_ready = true;
+    return MCPT_OK;
+}
+
+// what a device state's first light move builds (after ensure_refit_state): build_tree_refit's state for the
+// light-only tree, then the tables' half above.  The current device is D's.
+int mcpt::ensure_light_state(mcpt_scene* sc, DeviceState& D) {
+    if (D.lrefit.ready) return MCPT_OK;
+    const DScene& d = D.d;
+    ensure_slot_map(sc, true);
+    int rc;  // a scene without lights has no light-only tree to refit: refused as a tree of no nodes
+    if ((rc = build_tree_refit(D, D.lrefit, d.lbvh4, d.lbvh4q, sc->host.NL < 1 ? 0 : d.nlbvh4, d.lleaf_v, sc->lbvh.leaf_facets.size(),
+                               sc->lslots, "light-only ")) ||
+        (rc = ensure_light_tables(sc, D)))
+        return rc;
     D.lrefit.ready = true;
     return MCPT_OK;
 }
@@ -313,7 +331,8 @@ static int light_stage_finish(DeviceState& D, mcpt_light_update_stats* lst) {
         float ms = 0;
         unsigned c[4] = {0, 0, 0, 0};
         HIP_OK(hipEventElapsedTime(&ms, D.evl0, D.evl1));
-        HIP_OK(hipMemcpy(c, D.lrefit.dev.counters, sizeof c, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(c, D.lrefit.dev.counters, 2 * sizeof(unsigned), hipMemcpyDeviceToHost));  // [1]: the tree's
+        HIP_OK(hipMemcpy(c + 2, D.ltab.counters + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost));  // [2], [3]: the tables'
         lst->device_seconds = 1e-3 * ms;
         lst->light_nodes_refit = c[1];
         lst->chunks = (int32_t)c[2];
@@ -514,6 +533,180 @@ int mcpt_scene_light_update_info(const mcpt_scene* sc, mcpt_light_update_stats* 
     std::lock_guard<std::mutex> lk(w->mu);
     *out = sc->light_stats;
     out->struct_size = sizeof *out;
+    return MCPT_OK;
+}
+
+// ---- in-place re-lighting (include/mcpt.h; the kernels are light_tables.hip's) ----
+void mcpt_relight_stats_init(mcpt_relight_stats* st) { stats_init(st); }
+
+// the refusals of the three setters that need no values: `n` rows of `what`, and the call's array
+static int relight_check_args(const char* who, const mcpt_scene* sc, int32_t first, int32_t count, int32_t n, const char* what,
+                              const void* data, const char* data_name, const mcpt_relight_stats* stats) {
+    if (int rn = refuse_null(who, sc)) return rn;
+    if (count < 0 || first < 0 || (int64_t)first + count > n) {
+        set_error("%s: %s [%d, %lld) are not a range of the scene's %d", who, what, first, (long long)first + count, n);
+        return MCPT_E_INVALID;
+    }
+    if (count > 0 && !data) {
+        set_error("%s: NULL %s", who, data_name);
+        return MCPT_E_INVALID;
+    }
+    return check_struct_size(stats, "mcpt_relight_stats");
+}
+static bool relight_value_ok(double v) { return v >= 0 && std::isfinite(v); }
+
+// a state's events for a stage that needs no light tables (mcpt_scene_set_materials on a scene without lights)
+static int ensure_light_events(DeviceState& D) {
+    if (!D.evl0) HIP_OK(hipEventCreate(&D.evl0));
+    if (!D.evl1) HIP_OK(hipEventCreate(&D.evl1));
+    return MCPT_OK;
+}
+
+// mcpt_scene_set_light_radiance after its refusals: the host copy first (it stays the truth for device states made
+// later), then every device state.  src_device >= 0: drgb is device memory there and that device's state reads it
+// directly; every other state gets a staging copy of rgb.
+static int relight_apply(mcpt_scene* sc, int32_t first, int32_t count, const double* rgb, int src_device, const double* drgb,
+                         mcpt_relight_stats* stats) {
+    HostScene& hs = sc->host;
+    mcpt_relight_stats st;
+    mcpt_relight_stats_init(&st);
+    st.lights = count;
+    st.chunks = (first + count - 1) / 64 - first / 64 + 1;
+    std::copy(rgb, rgb + 3 * (size_t)count, hs.light_rad.begin() + 3 * (size_t)first);
+    for (int l = first; l < first + count; l++) hs.light_sum[l] = hs.light_rad[3 * (size_t)l] + hs.light_rad[3 * (size_t)l + 1] + hs.light_rad[3 * (size_t)l + 2];
+    for (size_t g = 0; g < hs.group_start.size(); g++)  // a group without triangles keeps the sum it was loaded with
+        if (hs.group_count[g] > 0 && hs.group_start[g] >= first && hs.group_start[g] < first + count) {
+            hs.group_rsum[g] = hs.light_sum[hs.group_start[g]];
+            st.groups++;
+        }
+    const std::vector<DeviceState*> devs = device_states(sc);
+    DeviceRestore back;
+    if (!devs.empty()) HIP_OK(hipGetDevice(&back.device));
+    for (DeviceState* D : devs) {
+        HIP_OK(hipSetDevice(D->device));
+        int rc;
+        if ((rc = ensure_light_tables(sc, *D))) return rc;
+        const double* src = drgb;
+        if (D->device != src_device) {
+            if ((rc = ensure(D->up_rad, 24ull * count))) return rc;
+            HIP_OK(hipMemcpy(D->up_rad.p, rgb, 24ull * count, hipMemcpyHostToDevice));
+            src = (const double*)D->up_rad.p;
+        }
+        // work of other streams (the caller's, a frame sequence's) that still reads these tables
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipEventRecord(D->evl0, D->stream));
+        if ((rc = light_radiance_enqueue(D->ltab, first, count, src, st.groups > 0, D->stream))) return rc;
+        HIP_OK(hipEventRecord(D->evl1, D->stream));
+        HIP_OK(hipMemcpyAsync(D->pinned_globals, D->ltab.globals, sizeof(LightGlobals), hipMemcpyDeviceToHost, D->stream));
+        HIP_OK(hipStreamSynchronize(D->stream));
+        if ((rc = light_stage_finish(*D, nullptr))) return rc;  // the state's by-value constants: band_S, band_K
+        if (st.device_states++ == 0) {
+            float ms = 0;
+            HIP_OK(hipEventElapsedTime(&ms, D->evl0, D->evl1));
+            st.device_seconds = 1e-3 * ms;
+        }
+    }
+    if (stats) *stats = st;
+    return MCPT_OK;
+}
+
+int mcpt_scene_set_light_radiance(mcpt_scene* sc, int32_t first, int32_t count, const double* rgb, mcpt_relight_stats* stats) {
+    static const char* who = "mcpt_scene_set_light_radiance";
+    if (int rc = relight_check_args(who, sc, first, count, sc ? sc->host.NL : 0, "lights", rgb, "rgb", stats)) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    for (size_t i = 0; i < 3 * (size_t)count; i++)
+        if (!relight_value_ok(rgb[i])) {
+            set_error("%s: light %d has a negative or non-finite radiance (component %d: %g)", who, first + (int)(i / 3), (int)(i % 3), rgb[i]);
+            return MCPT_E_INVALID;
+        }
+    if (count == 0) {
+        stats_init(stats);
+        return MCPT_OK;
+    }
+    return relight_apply(sc, first, count, rgb, -1, nullptr, stats);
+}
+
+int mcpt_scene_set_light_radiance_device(mcpt_scene* sc, int32_t device, int32_t first, int32_t count, const void* drgb,
+                                         mcpt_relight_stats* stats) {
+    static const char* who = "mcpt_scene_set_light_radiance_device";
+    int rc;
+    if ((rc = relight_check_args(who, sc, first, count, sc ? sc->host.NL : 0, "lights", drgb, "dev_rgb", stats))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (count == 0) {
+        stats_init(stats);
+        return MCPT_OK;
+    }
+    DeviceRestore back;
+    HIP_OK(hipGetDevice(&back.device));
+    if (device < 0) device = back.device;
+    if ((rc = check_device_buffer(drgb, device, "dev_rgb"))) return rc;
+    HIP_OK(hipSetDevice(device));
+    HIP_OK(hipDeviceSynchronize());  // the caller's streams may still be writing the array
+    // the offenders counted into one word before anything is modified, as mcpt_scene_update_device counts its own
+    DevBuf word;
+    unsigned bad = 0;
+    if ((rc = ensure(word, 64))) return rc;
+    HIP_OK(hipMemset(word.p, 0, sizeof(unsigned)));
+    if ((rc = light_radiance_validate_enqueue(3 * (int64_t)count, (const double*)drgb, (unsigned*)word.p, nullptr))) return rc;
+    HIP_OK(hipMemcpy(&bad, word.p, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad) {
+        set_error("%s: %u radiance components of lights [%d, %d) are negative or not finite", who, bad, first, first + count);
+        return MCPT_E_INVALID;
+    }
+    std::vector<double> h(3 * (size_t)count);  // the host copy follows by this one copy of the range
+    HIP_OK(hipMemcpy(h.data(), drgb, 24ull * count, hipMemcpyDeviceToHost));
+    HIP_OK(hipSetDevice(back.device));
+    return relight_apply(sc, first, count, h.data(), device, (const double*)drgb, stats);
+}
+
+int mcpt_scene_set_materials(mcpt_scene* sc, int32_t first, int32_t count, const float* mtl, mcpt_relight_stats* stats) {
+    static const char* who = "mcpt_scene_set_materials";
+    if (int rc = relight_check_args(who, sc, first, count, sc ? sc->host.M : 0, "materials", mtl, "mtl", stats)) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    for (size_t i = 0; i < 7 * (size_t)count; i++)
+        if (!relight_value_ok(mtl[i])) {
+            const int c = (int)(i % 7);
+            set_error("%s: material %d has a negative or non-finite %s (%g)", who, first + (int)(i / 7), c < 3 ? "Kd" : c < 6 ? "Ks" : "Ns",
+                      (double)mtl[i]);
+            return MCPT_E_INVALID;
+        }
+    mcpt_relight_stats st;
+    mcpt_relight_stats_init(&st);
+    if (count > 0) {
+        HostScene& hs = sc->host;
+        st.materials = count;
+        std::copy(mtl, mtl + 7 * (size_t)count, hs.mtl.begin() + 7 * (size_t)first);
+        const std::vector<DeviceState*> devs = device_states(sc);
+        DeviceRestore back;
+        if (!devs.empty()) HIP_OK(hipGetDevice(&back.device));
+        for (DeviceState* D : devs) {
+            HIP_OK(hipSetDevice(D->device));
+            if (int rc = ensure_light_events(*D)) return rc;
+            HIP_OK(hipDeviceSynchronize());  // work of other streams that still reads the table
+            HIP_OK(hipEventRecord(D->evl0, D->stream));
+            // from the host copy, which outlives the copy (the stream is synchronised below)
+            HIP_OK(hipMemcpyAsync(const_cast<float*>(D->d.mtl) + 7 * (size_t)first, hs.mtl.data() + 7 * (size_t)first, 28ull * count,
+                                  hipMemcpyHostToDevice, D->stream));
+            HIP_OK(hipEventRecord(D->evl1, D->stream));
+            HIP_OK(hipStreamSynchronize(D->stream));
+            if (st.device_states++ == 0) {
+                float ms = 0;
+                HIP_OK(hipEventElapsedTime(&ms, D->evl0, D->evl1));
+                st.device_seconds = 1e-3 * ms;
+            }
+        }
+    }
+    if (stats) *stats = st;
+    return MCPT_OK;
+}
+
+int mcpt_scene_light_groups(const mcpt_scene* sc, int32_t* group) {
+    if (int rn = refuse_null("mcpt_scene_light_groups", sc, group, "group")) return rn;
+    mcpt_scene* w = const_cast<mcpt_scene*>(sc);
+    std::lock_guard<std::mutex> lk(w->mu);
+    const HostScene& hs = sc->host;
+    for (size_t g = 0; g < hs.group_start.size(); g++)
+        for (int l = hs.group_start[g]; l < hs.group_start[g] + hs.group_count[g]; l++) group[l] = (int32_t)g;
     return MCPT_OK;
 }
 

@@ -156,7 +156,12 @@ struct DeviceState {
     // light_tables.hip, a second TreeRefit over the light-only tree (lbvh4, lbvh4q, lleaf_v; tri_v / tri_n shared with
     // `refit`) with its own slot map, dirty bytes, counters and levels, a pinned copy of the by-value constants and
     // the events around the light stage
+    // A re-light needs the tables' half of that alone -- ltab with the chunk rows, the dirty bytes, the
+    // constants' struct, the counters, the pinned copy and the events (ltab_ready) -- and never the light-only tree's;
+    // up_rad stages a host call's radiances.
     LightTabDev ltab{};
+    bool ltab_ready = false;
+    DevBuf up_rad;
     TreeRefit lrefit;
     LightGlobals* pinned_globals = nullptr;
     hipEvent_t evl0 = nullptr, evl1 = nullptr;
@@ -285,6 +290,7 @@ std::vector<DeviceState*> device_states(mcpt_scene* sc);
 int host_sync(mcpt_scene* sc);
 void ensure_slot_map(mcpt_scene* sc, bool light_tree);
 int ensure_refit_state(mcpt_scene* sc, DeviceState& D);
+int ensure_light_tables(mcpt_scene* sc, DeviceState& D);
 int ensure_light_state(mcpt_scene* sc, DeviceState& D);
 
 }  // namespace mcpt

@@ -223,6 +223,11 @@ int mcpt_debug_light_tables(mcpt_scene* sc, int32_t device, const char* which, v
     else if (w == "chunk_sk") src = d.chunk_sk, n = nch * sizeof(float2);
     else if (w == "l_area") src = d.l_area, n = (size_t)d.NL * sizeof(double);
     else if (w == "l_area_cum") src = d.l_area_cum, n = (size_t)d.NL * sizeof(double);
+    else if (w == "light_rad") src = d.light_rad, n = 3 * (size_t)d.NL * sizeof(double);
+    else if (w == "light_sum") src = d.light_sum, n = (size_t)d.NL * sizeof(double);
+    else if (w == "grp_sum") src = d.grp_sum, n = (size_t)d.ngroups * sizeof(double);
+    else if (w == "grp_cum") src = d.grp_cum, n = (size_t)d.ngroups * sizeof(double);
+    else if (w == "mtl") src = d.mtl, n = 7 * (size_t)sc->host.M * sizeof(float);
     else if (w == "globals") {
         for (int a = 0; a < 3; a++) g.band_ctr[a] = d.band_ctr[a];
         g.band_R = d.band_R, g.band_S = d.band_S, g.band_K = d.band_K, g.light_bound = d.light_bound;
