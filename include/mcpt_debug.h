@@ -21,8 +21,13 @@ enum {
     MCPT_DEBUG_RAYS_CW8 = 1 << 21,
     MCPT_DEBUG_FUSED_CULL = 1 << 22,
     MCPT_DEBUG_NO_EXACT_DEFER = 1 << 23,
-    MCPT_DEBUG_NO_PICK_TABLE = 1 << 24
+    MCPT_DEBUG_NO_PICK_TABLE = 1 << 24,
+    MCPT_DEBUG_REEVAL_PICK = 1 << 25
 };
+/* MCPT_DEBUG_REEVAL_PICK: k_prep_pk2 keeps no batch weights in LDS, so every node's pick evaluates the 64 candidates of
+ * its picked batch again (the only form before the stash).  By default the weights of a node's first batches stay in the
+ * idle tail of the wave's candidate-list region and a whole picked batch among them is read back; sums, picks, margins
+ * and frames are the same either way (tests/test_prep_stash_pick.py). */
 /* MCPT_DEBUG_NO_PICK_TABLE: cached roots search their pixel's cached row in every generation (k_prep_pick_g)
  * instead of looking their pick up in the run's root pick table (k_root_pick_table + k_pick_lookup; sums, picks,
  * exact-list membership and frames are the same either way). */
@@ -63,10 +68,16 @@ int mcpt_debug_set_collective_lib(const char* path);
  * node, small light sets); 17 k_prep_cull_lanes (lane per node, light table in scalar registers)
  * + k_prep_pk2's fp64 phase (the renderer's form: the cull's lanes take the nodes bucketed by their
  * tangent-plane chunk classes and skip the work a class decides, k_cull_classify); 18 variant 17 without
- * that order and without the chunk classes (its candidate words must be identical).  Other values:
+ * that order and without the chunk classes (its candidate words must be identical); 19 variant 17 with
+ * MCPT_DEBUG_REEVAL_PICK (every pick re-evaluates its batch; sums and picks must be identical).  Other values:
  * MCPT_E_DEVICE (invalid value). */
 int mcpt_debug_prep_bench(mcpt_scene* scene, int32_t n, const double* x1, const double* normal, const double* u,
                           int32_t variant, int32_t iters, double* ms_per_launch, double* weights_sum, int32_t* pick);
+/* diagnostics: how the n nodes of the last mcpt_debug_prep_bench call (process-wide; its untimed first launch) got
+ * their picks in k_prep_pk2: *from_stash nodes read the picked batch's weights back from LDS, *reevaluated nodes
+ * evaluated the batch again (a batch beyond the stashed ones, a partial last batch, or variant 19).  Nodes without a
+ * pick (weights_sum below 1e-8) count in neither; variants that do not run k_prep_pk2 report 0, 0. */
+int mcpt_debug_prep_pick_counts(int64_t* from_stash, int64_t* reevaluated);
 
 /* diagnostics: mcpt_light_prep with every point through the exact fallback alone (k_prep_exact: the
  * reference's literal cull chain and weights, Mylight.cpp:335-413, summed in index order, and the

@@ -80,6 +80,7 @@ DEBUG_RAYS_CW8 = 1 << 21  # the persistent traversal walks the 8-wide compressed
 DEBUG_FUSED_CULL = 1 << 22  # MIS children's prep: cheap stages inside k_prep_pk2 (variant 8) instead of k_prep_cull_lanes
 DEBUG_NO_EXACT_DEFER = 1 << 23  # k_prep_exact recomputes same-launch duplicate roots instead of deferring them
 DEBUG_NO_PICK_TABLE = 1 << 24  # cached roots search their pixel's cached row (k_prep_pick_g) instead of the root pick table
+DEBUG_REEVAL_PICK = 1 << 25  # k_prep_pk2 stashes no batch weights: every pick evaluates its picked batch again
 DEBUG_HIT_CW8 = 1 << 8  # mcpt_closest_hit: trace through the 8-wide trees
 
 
@@ -259,7 +260,7 @@ DEBUG_EXPORTS = ["mcpt_debug_bvh4_check_device_light", "mcpt_debug_light_tables"
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download",
                  "mcpt_debug_set_pick_table", "mcpt_debug_root_picks", "mcpt_debug_set_rebuild_leaf_max",
-                 "mcpt_debug_phong", "mcpt_debug_device_bytes_live"]  # include/mcpt_debug.h
+                 "mcpt_debug_phong", "mcpt_debug_device_bytes_live", "mcpt_debug_prep_pick_counts"]  # include/mcpt_debug.h
 
 
 def lib():
@@ -430,7 +431,8 @@ def lib():
                "mcpt_debug_bvh4_check_device_light": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
                "mcpt_debug_light_tables": [P, I, C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64)],
                "mcpt_debug_light_area_cum_bench": [P, I, I, C.POINTER(D)],
-               "mcpt_debug_phong": [I, I, dp, dp], "mcpt_debug_device_bytes_live": []}
+               "mcpt_debug_phong": [I, I, dp, dp], "mcpt_debug_device_bytes_live": [],
+               "mcpt_debug_prep_pick_counts": [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]}
         for name, argt in dbg.items():
             if hasattr(L, name):
                 getattr(L, name).argtypes = argt
@@ -1715,6 +1717,14 @@ def debug_prep_bench(scene, x1, normal, u, variant=-1, iters=5):
     ms, ws, pick = C.c_double(), np.zeros(n), np.zeros(n, np.int32)
     _check(lib().mcpt_debug_prep_bench(scene.h, n, x1, normal, u, int(variant), int(iters), C.byref(ms), ws, pick))
     return ms.value, ws, pick
+
+
+def debug_prep_pick_counts():
+    """Diagnostics: (nodes whose pick read the stashed batch weights, nodes that re-evaluated their picked batch) of the
+    last debug_prep_bench call (include/mcpt_debug.h)."""
+    a, b = C.c_int64(), C.c_int64()
+    _check(lib().mcpt_debug_prep_pick_counts(C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def primary_hits(scene, camera):

@@ -799,7 +799,9 @@ __device__ inline void block_count(unsigned long long* ca, unsigned a, unsigned 
 // ray counts (rays, light_rays), which every wavefront workgroup adds to -- one line per 8 workgroups
 // round robin instead of one word for all (the host sums the shards)
 constexpr int kStatShards = 8;
-constexpr int kStatBytes = 128 * (1 + kStatShards);
+// then one more line: k_prep_pk2's picks served from the stash / by re-evaluation (mcpt_debug_prep_pick_counts)
+constexpr int kStatPickStash = 16 * (1 + kStatShards), kStatPickReeval = kStatPickStash + 1;
+constexpr int kStatBytes = 128 * (2 + kStatShards);
 template <class P_>
 __device__ inline unsigned long long* ray_stats(const P_& P) {
     return P.stats + 16 * (1 + (blockIdx.x & (kStatShards - 1)));
@@ -2083,14 +2085,30 @@ struct PrepCache {
     int exact_counts;
     int* maybe;  // nodes whose slack the whole-table bound cannot clear (band_candidate), for k_prep_band
     int* exact;  // k_prep_pick: roots inside the cached band go straight to the exact list
+    int reeval;  // MCPT_DEBUG_REEVAL_PICK: k_prep_pk2 stashes no batch weights, every pick re-evaluates its batch
 };
+
+// k_prep_pk2's same-box A/B switch (profiles/prep_stash_ab.txt).  MCPT_PREP_STASH: the batch loop keeps the weights
+// of a node's first m batches in the idle tail of the wave's list region (m = the whole 64-double rows between the
+// padded list's end and the region's end, at most nb), and the pick reads a whole picked batch below m back instead
+// of evaluating its 64 candidates again.
+#ifndef MCPT_PREP_STASH
+#define MCPT_PREP_STASH 1
+#endif
+#ifndef MCPT_PICK_DIAG
+#define MCPT_PICK_DIAG 0  // 1: every render call logs how its full-prep nodes got their picks (stash / re-evaluated)
+#endif
 
 // inverse-CDF pick from the batch totals bt[0, nb) and candidate list lst (LDS or global): returns
 // weights_sum and the picked light (-1 if weights_sum < eps) and the pick's margin (pick_margin; +inf
-// without a pick).  u_of() gives dim 1 when needed.
+// without a pick).  u_of() gives dim 1 when needed.  stash: the weights of the batches [0, m) as the batch
+// loop computed them (k_prep_pk2's stash rows, -1 for a culled lane); a picked whole batch below m is read
+// back from it instead of being evaluated again (*stashed = 1), any other picked batch is re-evaluated
+// (*stashed = 2; untouched without a picked batch).
 template <bool kF32 = false, class U>
 __device__ inline double prep_select(const double* bt, const unsigned short* lst, int nb, int ncand, int lane,
-                                     __amdgpu_buffer_rsrc_t rw, d3 x1, U u_of, int* pick_out, double* margin_out) {
+                                     __amdgpu_buffer_rsrc_t rw, d3 x1, U u_of, int* pick_out, double* margin_out,
+                                     const double* stash = nullptr, int m = 0, int* stashed = nullptr) {
     double wsum = 0;
     int pick = -1;
     int kb = -1;
@@ -2136,7 +2154,15 @@ __device__ inline double prep_select(const double* bt, const unsigned short* lst
         const int lj = act ? (int)lst[k] : 0;
         bool ok;
         double w;
-        if (kF32) {  // the same packed evaluation as the batch (both halves this candidate)
+        // A partial last batch is never read back: its re-evaluation gives the idle lanes light 0 where the
+        // batch loop gave them the sentinel record, so atan2_pos_prep's wave-uniform path may differ between the two.
+        const bool from_stash = MCPT_PREP_STASH && !kF32 && kb < m && 64 * kb + 64 <= ncand;  // wave-uniform
+        if (stashed) *stashed = from_stash ? 1 : 2;
+        if (from_stash) {
+            const double v = stash[k];
+            ok = !(v < 0.0);
+            w = ok ? v : 0.0;
+        } else if (kF32) {  // the same packed evaluation as the batch (both halves this candidate)
             bool ok1;
             double w1;
             prep_weight_f32x2(rw, lj, lj, node_f32(x1), &w, &w1, &ok, &ok1);
@@ -2513,6 +2539,9 @@ __global__ __launch_bounds__(256, kMinWavesPerSimd) void k_prep_pk2(DScene S, ui
     const unsigned short sentinel = (unsigned short)(ngroups4 * 256);
     unsigned long long cand_acc = 0, c1_acc = 0, full_acc = 0, pad_acc = 0;
     unsigned bad_acc = 0;  // per lane: culled lanes of phase B, padding included
+    // the stash (MCPT_PREP_STASH): only the picking fp64 instances; C.reeval (MCPT_DEBUG_REEVAL_PICK) switches it off
+    constexpr bool kStash = MCPT_PREP_STASH && !kBuild && !kF32;
+    unsigned stash_acc = 0, reeval_acc = 0;  // nodes whose pick read the stash / re-evaluated its batch (wave-uniform)
     int grab = 0, left = 0;
     while (true) {
         if (left == 0) {
@@ -2600,6 +2629,9 @@ __global__ __launch_bounds__(256, kMinWavesPerSimd) void k_prep_pk2(DScene S, ui
         double sacc = 0;  // flagged slivers' error terms (this lane's candidates)
         int ndeg = 0;     // near-degenerate slivers (this lane's)
         const NodeF32 xf = node_f32(x1);
+        // the stash rows follow the padded list: row b = the 64 weights of batch b, for the m first batches
+        double* stash = reinterpret_cast<double*>(lst + 64 * nb);
+        const int m = kStash && !C.reeval ? min(nb, (nchunks - nb) >> 2) : 0;
         for (int b0 = 0; b0 < nb; b0 += 4) {
             double w4[4];
             if (kF32) {  // batches (b0, b0+1) and (b0+2, b0+3) as the two halves of packed fp32 evaluations
@@ -2633,6 +2665,7 @@ __global__ __launch_bounds__(256, kMinWavesPerSimd) void k_prep_pk2(DScene S, ui
                     const int k = 64 * (b0 + i) + lane;
                     double l2;
                     const WeightBx r = prep_weight_buf_bx(rw, (int)lst[k], x1, &l2);  // w = 0 if culled
+                    if (kStash && b0 + i < m) stash[k] = r.ok ? r.w : -1.0;  // wave-uniform; read back by the pick
                     if (kBuild) {  // in-batch inclusive prefix, culled with the sign bit (PrepCache::w)
                         const double sc = wave_incl_scan(r.ok ? r.w : 0.0, lane);
                         if (k < ncand) C.w[(size_t)(qpixel ? qpixel[node] : node) * C.lstride + k] = r.ok ? sc : copysign(sc, -1.0);
@@ -2685,7 +2718,10 @@ __global__ __launch_bounds__(256, kMinWavesPerSimd) void k_prep_pk2(DScene S, ui
         }
         int pick;
         double margin;
-        const double wsum = prep_select<kF32>(bt, lst, nb, ncand, lane, rw, x1, u_of, &pick, &margin);
+        int served = 0;
+        const double wsum = prep_select<kF32>(bt, lst, nb, ncand, lane, rw, x1, u_of, &pick, &margin, stash, m, &served);
+        stash_acc += served == 1;
+        reeval_acc += served == 2;
         if (lane == 0) {
             wsum_out[node] = wsum;
             pick_out[node] = pick;
@@ -2707,6 +2743,8 @@ __global__ __launch_bounds__(256, kMinWavesPerSimd) void k_prep_pk2(DScene S, ui
             if (cand_acc) atomicAdd(stats + 5, cand_acc);
             if (c1_acc) atomicAdd(stats + 6, c1_acc);
             if (full_acc) atomicAdd(stats + 7, full_acc);
+            if (stash_acc) atomicAdd(stats + kStatPickStash, (unsigned long long)stash_acc);
+            if (reeval_acc) atomicAdd(stats + kStatPickReeval, (unsigned long long)reeval_acc);
         }
     }
 }
@@ -5356,7 +5394,7 @@ int validate_render(const mcpt_render_opts* o) {
     if (o->flags & ~(MCPT_RENDER_NO_BACKFACE_STATS | MCPT_RENDER_FRESH_PDF | MCPT_RENDER_PRECISION_FP32 |
                      MCPT_RENDER_PIXEL_JITTER | MCPT_DEBUG_SPLIT_BRDF | MCPT_DEBUG_NO_ROOT_CACHE | MCPT_DEBUG_COUNT_TRAVERSAL |
                      MCPT_DEBUG_SHARD_RANKS | MCPT_DEBUG_RAYS_PERSIST | MCPT_DEBUG_RAYS_CW8 | MCPT_DEBUG_FUSED_CULL |
-                     MCPT_DEBUG_NO_EXACT_DEFER | MCPT_DEBUG_NO_PICK_TABLE)) {
+                     MCPT_DEBUG_NO_EXACT_DEFER | MCPT_DEBUG_NO_PICK_TABLE | MCPT_DEBUG_REEVAL_PICK)) {
         set_error("unknown mcpt_render_opts.flags bits 0x%x", (unsigned)o->flags);
         return MCPT_E_INVALID;
     }
@@ -6038,6 +6076,7 @@ struct WavefrontRun {
         int root_off = INT_MAX;
         cx.slack = B.slack;
         cx.maybe = B.maybe_list;
+        cx.reeval = (o->flags & MCPT_DEBUG_REEVAL_PICK) != 0;
         if (pl.exact_pick) {
             HIP_OK(hipMemsetAsync(B.exact_list, 0, 4, st));
             HIP_OK(hipMemsetAsync(B.maybe_list, 0, 4, st));
@@ -6321,6 +6360,10 @@ int fill_stats(const RenderPlan& p, const Bound& B, DeviceState& D, const Counte
         fprintf(stderr, "trace diag: %llu visits over %llu wave node-iterations (lane use %.3f), %llu tests over %llu wave "
                         "leaf-iterations (lane use %.3f)\n", hs[8], hs[14], hs[8] / (64.0 * std::max<unsigned long long>(hs[14], 1)),
                 hs[9], hs[15], hs[9] / (64.0 * std::max<unsigned long long>(hs[15], 1)));
+#endif
+#if MCPT_PICK_DIAG  // untimed instrumented runs: how k_prep_pk2's full-prep nodes got their picks (profiles/prep_stash_ab.txt)
+    fprintf(stderr, "pick diag: %llu full-prep nodes, %llu picks from the stash, %llu re-evaluated\n", hs[7],
+            hs[kStatPickStash], hs[kStatPickReeval]);
 #endif
 #if MCPT_BAND_DIAG
     fprintf(stderr, "exact diag (10 ns ticks summed over nodes): lists %llu literal %llu lists+literal+sum %llu pick %llu\n",
@@ -7694,6 +7737,8 @@ int mcpt_debug_tri_filter(int32_t n, const float* tri, const double* ro, const d
     return MCPT_OK;
 }
 
+// mcpt_debug_prep_pick_counts: the counts of the last mcpt_debug_prep_bench call's first launch
+static std::atomic<int64_t> g_pick_stash{0}, g_pick_reeval{0};
 int mcpt_debug_prep_bench(mcpt_scene* sc, int32_t n, const double* x1, const double* nrm, const double* u,
                           int32_t variant, int32_t iters, double* ms, double* wsum, int32_t* pick) {
     if (!sc || n <= 0 || !x1 || !nrm || !u || iters <= 0 || !ms || !wsum || !pick) {
@@ -7720,14 +7765,23 @@ int mcpt_debug_prep_bench(mcpt_scene* sc, int32_t n, const double* x1, const dou
     if ((rc = ensure(D->work, 256))) return rc;
     CullOrder co{};
     if ((rc = cull_order_bufs(*D, (size_t)n, &co))) return rc;
+    PrepCache cx{};
+    if (variant == 19) {  // variant 17 with MCPT_DEBUG_REEVAL_PICK
+        variant = 17;
+        cx.reeval = 1;
+    }
+    // the untimed first launch counts (a statistics block of its own); the timed ones run without statistics
+    void* dst;
+    HIP_OK(hipMalloc(&dst, kStatBytes));
+    HIP_OK(hipMemsetAsync(dst, 0, kStatBytes, D->stream));
     HIP_OK(launch_prep(variant, D->d, 0, n, (const double*)dp, (const double*)dn, n, nullptr, nullptr, nullptr,
-                       (const double*)du, (double*)dw, (int*)dk, nullptr, nullptr, (unsigned*)D->work.p, D->stream,
-                       PrepCache{}, (uint64_t*)dm, true, false, co));
+                       (const double*)du, (double*)dw, (int*)dk, nullptr, (unsigned long long*)dst, (unsigned*)D->work.p,
+                       D->stream, cx, (uint64_t*)dm, true, false, co));
     HIP_OK(hipEventRecord(D->ev0, D->stream));
     for (int it = 0; it < iters; it++)
         HIP_OK(launch_prep(variant, D->d, 0, n, (const double*)dp, (const double*)dn, n, nullptr, nullptr, nullptr,
                            (const double*)du, (double*)dw, (int*)dk, nullptr, nullptr, (unsigned*)D->work.p, D->stream,
-                       PrepCache{}, (uint64_t*)dm, true, false, co));
+                           cx, (uint64_t*)dm, true, false, co));
     HIP_OK(hipEventRecord(D->ev1, D->stream));
     HIP_OK(hipEventSynchronize(D->ev1));
     float t = 0;
@@ -7736,8 +7790,24 @@ int mcpt_debug_prep_bench(mcpt_scene* sc, int32_t n, const double* x1, const dou
     HIP_OK(hipMemcpy(wsum, dw, 8ull * n, hipMemcpyDeviceToHost));
     HIP_OK(hipMemcpy(pick, dk, 4ull * n, hipMemcpyDeviceToHost));
     for (int k = 0; k < n; k++) pick[k] = pick[k] >= 0 ? sc->host.light_facet[pick[k]] : -1;
-    void* bufs[] = {dp, dn, du, dw, dk, dm};
+    {
+        unsigned long long hc[2] = {0, 0};
+        HIP_OK(hipMemcpy(hc, (unsigned long long*)dst + kStatPickStash, sizeof hc, hipMemcpyDeviceToHost));
+        g_pick_stash = (int64_t)hc[0];
+        g_pick_reeval = (int64_t)hc[1];
+    }
+    void* bufs[] = {dp, dn, du, dw, dk, dm, dst};
     for (void* b : bufs) (void)hipFree(b);
+    return MCPT_OK;
+}
+
+int mcpt_debug_prep_pick_counts(int64_t* from_stash, int64_t* reevaluated) {
+    if (!from_stash || !reevaluated) {
+        set_error("null argument");
+        return MCPT_E_INVALID;
+    }
+    *from_stash = g_pick_stash;
+    *reevaluated = g_pick_reeval;
     return MCPT_OK;
 }
 
