@@ -50,7 +50,11 @@ extern "C" {
                                * triangles (mcpt_scene_set_lights_movable, mcpt_scene_lights_movable,
                                * mcpt_light_update_stats, mcpt_scene_light_update_info); in-place re-lighting
                                * (mcpt_relight_stats, mcpt_scene_set_light_radiance and its _device form,
-                               * mcpt_scene_set_materials, mcpt_scene_light_groups);
+                               * mcpt_scene_set_materials, mcpt_scene_light_groups); anti-lag by temporal gradients
+                               * (mcpt_gradient_opts, mcpt_gradient_phase, mcpt_gradient_rays and its _device form,
+                               * mcpt_temporal_gradient and its _device form, mcpt_temporal_accumulate_antilag and its
+                               * _device form, mcpt_sequence_set_antilag, mcpt_sequence_antilag_info, the selectors
+                               * MCPT_SEQ_GRADIENT_LAMBDA and MCPT_SEQ_GRADIENT_RAW);
                                * mcpt_stats gains pick_table_roots (appended, guarded by stats_size: stats ABI 2.3);
                                * 2.2.0: mcpt_stats gains comm_init_seconds, device_setup_seconds and
                                * device_seconds[MCPT_STATS_MAX_DEVICES] (appended): where a multi-device call's
@@ -456,8 +460,9 @@ int mcpt_scene_tree_cost(mcpt_scene* scene, int32_t device, double* cost);
  * be finite).  mcpt_scene_update names the first such facet; the device form and mcpt_scene_transform count the
  * offenders into the same word as the other value checks.  The arena is the scene's, unchanged.  Switching off later
  * only restores the refusals.  Light facets are ordinary rows of the previous pose, so mcpt_scene_pose_save and the
- * motion AOVs follow a directly visible light; the shading that changes under a moved light is the history clamp's
- * case.  mcpt_scene_rebuild still leaves the light-only tree alone: it keeps its build topology and is only refit.
+ * motion AOVs follow a directly visible light; the shading that changes under a moved light is the anti-lag's case
+ * (mcpt_temporal_accumulate_antilag).  mcpt_scene_rebuild still leaves the light-only tree alone: it keeps its build
+ * topology and is only refit.
  *
  * mcpt_scene_set_lights_movable takes the scene's lock; with a communicator every rank must make the same call.
  * MCPT_E_INVALID: a NULL scene (or a NULL `on` of the getter).
@@ -512,7 +517,7 @@ int mcpt_scene_light_update_info(const mcpt_scene* scene, mcpt_light_update_stat
  *
  * Not covered: reassigning facets to materials, turning a facet into a light or back, changing the light, material or
  * group counts, the lights of the opt-in 8-wide debug trees, and the history of a surface whose shading changed (the
- * history clamp's case, as for a moved light). */
+ * anti-lag's case, mcpt_temporal_accumulate_antilag, as for a moved light). */
 typedef struct {
     uint32_t struct_size;   /* sizeof(mcpt_relight_stats) of the caller's header (mcpt_relight_stats_init sets it) */
     int32_t lights;         /* lights given a radiance (count of a radiance call, else 0) */
@@ -843,8 +848,8 @@ int mcpt_temporal_accumulate_clamped_device(const mcpt_temporal_opts* opts, cons
  * Everything else reads the current guides: depth_p > 0 decides whether p has a source at all, `blend`, the moments,
  * the fast history and the box of the clamp, and the spatial estimate of the variance.  With Xm = X and Nm = N (a
  * scene that did not move) the outputs are those of the plain or clamped call bit for bit.  What it does not do: no
- * screen-space motion vectors come out, lights do not move, and shading that changes on a static surface is still the
- * clamp's job.
+ * screen-space motion vectors come out, lights do not move, and shading that changes on a static surface is the
+ * anti-lag's job (mcpt_temporal_accumulate_antilag below) or, without it, the clamp's.
  * Host arrays in, host arrays out; the arguments are those of the two forms above.  motion: both arrays are required.
  * clamp == NULL selects the plain rule; prev_fast, out_fast and out_shift must then be NULL.  With clamp, prev_fast
  * belongs to the previous state, out_fast is required and out_shift may be NULL.  Refused with MCPT_E_INVALID before
@@ -866,6 +871,103 @@ int mcpt_temporal_accumulate_motion_device(const mcpt_temporal_opts* opts, const
                                            const double* dev_prev_fast, double* dev_out_color, double* dev_out_moments,
                                            double* dev_out_fast, double* dev_out_shift, double* dev_out_variance,
                                            double* device_seconds);
+
+/* Anti-lag by temporal gradients (Schied et al. 2018, "Gradient Estimation for Temporally Stable Real-Time Path
+ * Tracing"; opt-in, no counterpart in the reference; every form above is unchanged).  The accumulation reprojects
+ * geometry, but radiance that changed on a surface that did not move -- a dimmed light, a moved lamp's shadow, a
+ * re-tinted wall -- is blended at alpha for about 1 / alpha frames.  The remedy: a sparse subset of the PREVIOUS frame's
+ * samples is traced again, with the previous camera and the previous seed, in the CURRENT scene.  The counter RNG is
+ * keyed by (seed, pixel, sample), so the two radiances differ only by what changed in the scene: their difference is a
+ * noise-free measure of that change, and the blend weight is raised where it is large.
+ *   options  mcpt_gradient_opts: the stratum s (one gradient sample per s x s block of the previous frame's pixels), the
+ *            radius r (a window of (2 r + 1)^2 strata) and a scale on the ratio
+ *   phase    (a, b) with 0 <= a, b < s picks the sample pixel (s I + a, s J + b) of stratum (I, J).  The phase of frame
+ *            k (mcpt_gradient_phase) is mcpt_upsample_phase's rule for s in 1..8: k' = k mod s^2, a = k' mod s,
+ *            b = (a + k' div s) mod s -- a bijection onto the s^2 phases
+ *   rays     mcpt_gradient_rays(cam, s, a, b): height*width rays.  Every origin is the pulled-back eye.  The direction of
+ *            pixel (i, j) is mcpt_camera_rays(cam, jitter = 0)'s direction bit for bit (the same device function) when
+ *            i mod s == a and j mod s == b; every other direction is (0, 0, 0), which mcpt_render_rays treats as a miss
+ *            that traces nothing.  mcpt_render_rays over these arrays with seed S therefore adds, at index p of a
+ *            selected pixel, the radiance mcpt_render(cam, seed S) gives pixel p, and nothing anywhere else
+ *   gradient mcpt_temporal_gradient: prev_raw is the previous frame's raw render, regrad the radiance along the gradient
+ *            rays (both h*w*3); out_lambda is hs*ws with hs = (h + s - 1) / s, ws = (w + s - 1) / s (integer division),
+ *            overwritten.  For stratum (I, J) with sample pixel q = (s I + a, s J + b): if q lies inside the frame,
+ *            num(I, J) = sum over c of |regrad_c(q) - prev_raw_c(q)| and den(I, J) = sum over c of
+ *            fmax(regrad_c(q), prev_raw_c(q)), c = r, g, b in this order starting from the first term; otherwise both
+ *            are 0.  Num and Den are the sums of num and den over the strata (I + di, J + dj) with |di|, |dj| <= r that
+ *            lie inside the grid, rows top to bottom and columns left to right, starting from 0.
+ *            Lambda(I, J) = 0 when !(Den > 0); otherwise x = scale * Num / Den and Lambda = x < 1 ? x : 1, so a NaN
+ *            gives 1.  fp64, with no contraction
+ *   accumulation  mcpt_temporal_accumulate_antilag: mcpt_temporal_accumulate_motion's rule word for word (with motion ==
+ *            NULL the current guides are used, which is the plain or the clamped rule), with these substitutions for a
+ *            pixel that has history:
+ *            lookup        qi = min(max((int)floor(ys + 0.5), 0), h - 1) and qj likewise from xs and w, (ys, xs) the
+ *                          `source` step's coordinates; L = lambda[(qi / s) * ws + qj / s] (integer divisions);
+ *                          l = L > 0 ? (L < 1 ? L : 1) : 0
+ *            blend         n = min(n' + 1, max_history), A0 = max(alpha, 1 / n), A = A0 + l * (1 - A0); colour, m1, m2
+ *                          and g are blended with this A exactly as before (g = (1 - A)^2 g' + A^2); the stored
+ *                          history length is n_out = (1 - l) * n + l
+ *            fast history  Af0 = max(alpha_fast, 1 / n) with the same n (not n_out), Af = Af0 + l * (1 - Af0)
+ *            Everything else -- the box, the shift, the variance with n_out and g, the spatial estimate -- is unchanged.
+ *            With lambda == 0 everywhere every output equals the plain, clamped or motion call's BIT FOR BIT:
+ *            A0 + 0 * (1 - A0) = A0 and 1 * n + 0 = n.
+ * What the gradient sees: a change of radiance along the previous camera's own rays -- re-lit lights, edited materials,
+ * moved lights, moved occluders and moved geometry.  What it does not see: view-dependent change from camera motion
+ * (the rays are the previous camera's); that stays the clamp's job.  The samples are not forward-projected and the
+ * gradient is not filtered beyond the window sum.  Single device. */
+typedef struct {
+    uint32_t struct_size; /* sizeof(mcpt_gradient_opts) of the caller's header; a mismatch is MCPT_E_INVALID */
+    int32_t stratum;      /* default 3, 1..8: one gradient sample per stratum x stratum block of pixels */
+    int32_t radius;       /* default 1, 0..3: Num and Den are summed over (2 radius + 1)^2 strata */
+    int32_t device;       /* HIP device ordinal (-1 = current) */
+    double scale;         /* default 1, finite and > 0: multiplier on Num / Den */
+} mcpt_gradient_opts;
+/* zero-fills *opts and sets struct_size and the defaults above (device = -1) */
+void mcpt_gradient_opts_init(mcpt_gradient_opts* opts);
+/* Host helper: the phase of frame `frame_index` at `stratum` (1..8).  MCPT_E_INVALID for a NULL pointer or a stratum
+ * outside 1..8. */
+int mcpt_gradient_phase(int32_t stratum, uint64_t frame_index, int32_t* a, int32_t* b);
+/* The gradient rays of `cam` (see `rays` above) to host arrays, height*width*3 doubles each, computed on `device`
+ * (-1 = current).  MCPT_E_INVALID before any device work: a NULL pointer, an invalid camera, a frame of more than 2^28
+ * pixels, a stratum outside 1..8, a phase outside [0, stratum). */
+int mcpt_gradient_rays(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device, double* origin,
+                       double* dir);
+/* same with origin and dir in DEVICE memory on `device` */
+int mcpt_gradient_rays_device(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device,
+                              double* dev_origin, double* dev_dir);
+/* Host arrays in, host array out (see `gradient` above).  device_seconds (device time of the kernel, HIP events) may be
+ * NULL.  Refused with MCPT_E_INVALID before any device work: a NULL opts, a struct_size mismatch, a stratum, radius or
+ * scale out of range, a phase outside [0, stratum), width or height < 1 or a frame of more than 2^28 pixels, a NULL
+ * array, out_lambda aliasing an input. */
+int mcpt_temporal_gradient(const mcpt_gradient_opts* opts, int32_t width, int32_t height, int32_t a, int32_t b,
+                           const double* prev_raw, const double* regrad, double* out_lambda, double* device_seconds);
+/* same with the three arrays in DEVICE memory on opts->device */
+int mcpt_temporal_gradient_device(const mcpt_gradient_opts* opts, int32_t width, int32_t height, int32_t a, int32_t b,
+                                  const double* dev_prev_raw, const double* dev_regrad, double* dev_out_lambda,
+                                  double* device_seconds);
+/* Host arrays in, host arrays out; the arguments are mcpt_temporal_accumulate_motion's plus gradient (read for its
+ * stratum only, but checked whole) and lambda (the hs*ws map of mcpt_temporal_gradient at that stratum).  motion may be
+ * NULL (the current guides are then used); clamp may be NULL as in the motion call.  Refused with MCPT_E_INVALID before
+ * any device work: everything the motion call refuses (a NULL motion struct excepted), a NULL gradient or lambda, a
+ * struct_size mismatch, a stratum, radius or scale out of range, an output aliasing lambda. */
+int mcpt_temporal_accumulate_antilag(const mcpt_temporal_opts* opts, const mcpt_temporal_clamp_opts* clamp,
+                                     const mcpt_camera* prev_cam, int32_t width, int32_t height, const double* color,
+                                     const mcpt_aov_buffers* guides, const mcpt_motion_buffers* motion,
+                                     const mcpt_aov_buffers* prev_guides, const double* prev_color,
+                                     const double* prev_moments, const double* prev_fast, double* out_color,
+                                     double* out_moments, double* out_fast, double* out_shift, double* out_variance,
+                                     double* device_seconds, const mcpt_gradient_opts* gradient, const double* lambda);
+/* same with every array in DEVICE memory on opts->device (the option structs, prev_cam and device_seconds stay host
+ * pointers) */
+int mcpt_temporal_accumulate_antilag_device(const mcpt_temporal_opts* opts, const mcpt_temporal_clamp_opts* clamp,
+                                            const mcpt_camera* prev_cam, int32_t width, int32_t height,
+                                            const double* dev_color, const mcpt_aov_buffers* dev_guides,
+                                            const mcpt_motion_buffers* dev_motion, const mcpt_aov_buffers* dev_prev_guides,
+                                            const double* dev_prev_color, const double* dev_prev_moments,
+                                            const double* dev_prev_fast, double* dev_out_color, double* dev_out_moments,
+                                            double* dev_out_fast, double* dev_out_shift, double* dev_out_variance,
+                                            double* device_seconds, const mcpt_gradient_opts* gradient,
+                                            const double* dev_lambda);
 
 /* Guided upsampling (joint bilateral upsampling, Kopf et al. 2007; no counterpart in the reference): trace at 1 / f of
  * the shown size and reconstruct the full-size frame from the low-size radiance and full-size guides.  A camera's
@@ -1174,6 +1276,35 @@ int mcpt_sequence_motion_info(mcpt_sequence* seq, double* motion_seconds);
 /* the last frame's motion AOVs (h*w*3 each), for mcpt_sequence_read and mcpt_sequence_device_buffer; refused while
  * motion is off (and until a frame has run with it) */
 enum { MCPT_SEQ_PREV_POSITION = 9, MCPT_SEQ_PREV_NORMAL = 10 };
+/* Anti-lag in a sequence created by mcpt_sequence_create: gradient != NULL makes every frame from the next one on keep
+ * its raw frame and its seed (a device-to-device copy), and -- when a history exists and the previous frame kept its raw
+ * frame -- run the gradient pass before its render: the phase from frame_index (mcpt_gradient_phase), mcpt_gradient_rays
+ * of the PREVIOUS camera, mcpt_render_rays_device over them (the sequence's mode, spp and flags, n = width * height, the
+ * PREVIOUS seed) into a zeroed buffer, mcpt_temporal_gradient's kernel against the kept raw frame and a deterministic
+ * reduction of Lambda's mean and maximum (per-block partials in a fixed order, then index order; no floating-point
+ * atomics).  The frame then accumulates by mcpt_temporal_accumulate_antilag's rule, with motion when that is on and
+ * with the clamp when the sequence was created with it.  When the pass does not run (the first frame, the first frame
+ * after a reset or after the switch) Lambda is zero-filled and the frame is the plain rule's bit for bit.  NULL switches
+ * it off: the frames are then those of a sequence that never had it.  The buffers (two ray arrays, the gradient raw
+ * frame, the kept raw frame, a Lambda map of one double a pixel -- enough for stratum 1 -- and the reduction's words,
+ * whose number does not depend on the frame or the stratum) are an allocation of their own, made at the first
+ * switch-on.  mcpt_sequence_info and the stats argument of a frame describe the main render only.
+ * mcpt_sequence_reset drops the kept raw frame.  MCPT_E_INVALID: a NULL handle, a sequence created by
+ * mcpt_sequence_create_upsampled or mcpt_sequence_create_temporal_upsampled, a base with MCPT_RENDER_PIXEL_JITTER or
+ * MCPT_ACCEL_GRID (mcpt_render_rays refuses both), invalid options (mcpt_temporal_gradient's checks; the device field is
+ * ignored). */
+int mcpt_sequence_set_antilag(mcpt_sequence* seq, const mcpt_gradient_opts* gradient);
+/* the last frame's anti-lag stage: *ran 1 when the gradient pass ran, else 0; the phase (a, b); trace_seconds the
+ * gradient render's mcpt_stats.seconds (0 when it did not run); kernel_seconds the ray, gradient and reduction kernels
+ * alone (HIP events; the buffers' zero fills are outside them; when the pass did not run: the reduction); Lambda's
+ * mean and maximum over the hs*ws strata.  Any output may be NULL.  MCPT_E_INVALID: a NULL handle, a last frame that
+ * ran without anti-lag, no frame since create / reset / a failed frame. */
+int mcpt_sequence_antilag_info(mcpt_sequence* seq, int32_t* ran, int32_t* a, int32_t* b, double* trace_seconds,
+                               double* kernel_seconds, double* lambda_mean, double* lambda_max);
+/* the last frame's Lambda (hs*ws doubles at the stratum it ran with) and, only when the gradient pass ran, the radiance
+ * along the gradient rays (h*w*3; 0 off the selected pixels); refused while anti-lag is off (and until a frame has run
+ * with it) */
+enum { MCPT_SEQ_GRADIENT_LAMBDA = 11, MCPT_SEQ_GRADIENT_RAW = 12 };
 
 /* Multi-process communicator (see mcpt_comm above): ncclGetUniqueId / ncclCommInitRank /
  * ncclCommDestroy.  device -1 = the current device. */

@@ -25,6 +25,8 @@ __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_rays", 
            "upsample_phase", "camera_phase_rays", "temporal_upsample", "temporal_upsample_device",
            "MotionBuffers", "render_motion_aovs", "render_motion_aovs_device", "temporal_accumulate_motion",
            "temporal_accumulate_motion_device", "transform_rotation", "RelightStats",
+           "GradientOpts", "gradient_phase", "gradient_rays", "temporal_gradient", "temporal_accumulate_antilag",
+           "temporal_accumulate_antilag_device", "SEQ_ANTILAG_BUFFERS",
            "tone_map", "write_bmp", "MODE_MIS", "MODE_BRDF", "MODE_SHADE", "MODE_SHADE_AREA", "ACCEL_BVH", "ACCEL_GRID", "Stats", "MCPTError", "LIB_PATH", "lib"]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -120,6 +122,12 @@ class TemporalClampOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_int32), ("alpha_fast", C.c_double), ("sigma", C.c_double)]
 
 
+class GradientOpts(C.Structure):
+    """mcpt_gradient_opts: the temporal gradient's parameters (include/mcpt.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("stratum", C.c_int32), ("radius", C.c_int32), ("device", C.c_int32),
+                ("scale", C.c_double)]
+
+
 class UpsampleOpts(C.Structure):
     """mcpt_upsample_opts: the guided upsampling's parameters (include/mcpt.h)."""
     _fields_ = [("struct_size", C.c_uint32), ("factor", C.c_int32), ("sigma_normal", C.c_double),
@@ -149,6 +157,8 @@ SEQ_BUFFERS = {"raw": (0, (3,)), "accumulated": (1, (3,)), "moments": (2, (4,)),
                "fast": (5, (3,)), "shift": (6, ()), "rgb8": (7, (3,)), "upsampled": (8, (3,))}
 # and of a sequence with motion: MCPT_SEQ_PREV_POSITION, MCPT_SEQ_PREV_NORMAL
 SEQ_MOTION_BUFFERS = {"prev_position": (9, (3,)), "prev_normal": (10, (3,))}
+# and of a sequence with anti-lag: MCPT_SEQ_GRADIENT_LAMBDA (hs x ws at the stratum), MCPT_SEQ_GRADIENT_RAW
+SEQ_ANTILAG_BUFFERS = {"gradient_lambda": (11, ()), "gradient_raw": (12, (3,))}
 
 
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64)
@@ -255,7 +265,10 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_scene_set_lights_movable", "mcpt_scene_lights_movable", "mcpt_light_update_stats_init",
            "mcpt_scene_light_update_info",
            "mcpt_relight_stats_init", "mcpt_scene_set_light_radiance", "mcpt_scene_set_light_radiance_device",
-           "mcpt_scene_set_materials", "mcpt_scene_light_groups"]
+           "mcpt_scene_set_materials", "mcpt_scene_light_groups",
+           "mcpt_gradient_opts_init", "mcpt_gradient_phase", "mcpt_gradient_rays", "mcpt_gradient_rays_device",
+           "mcpt_temporal_gradient", "mcpt_temporal_gradient_device", "mcpt_temporal_accumulate_antilag",
+           "mcpt_temporal_accumulate_antilag_device", "mcpt_sequence_set_antilag", "mcpt_sequence_antilag_info"]
 DEBUG_EXPORTS = ["mcpt_debug_bvh4_check_device_light", "mcpt_debug_light_tables", "mcpt_debug_light_area_cum_bench","mcpt_debug_prep_bench", "mcpt_debug_tri_filter", "mcpt_debug_light_prep_exact", "mcpt_debug_light_literal",
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download",
@@ -410,6 +423,19 @@ def lib():
             L.mcpt_scene_set_light_radiance_device.argtypes = [P, I, I, I, P, C.POINTER(RelightStats)]
             L.mcpt_scene_set_materials.argtypes = [P, I, I, P, C.POINTER(RelightStats)]
             L.mcpt_scene_light_groups.argtypes = [P, ip]
+        if hasattr(L, "mcpt_temporal_gradient"):  # and the anti-lag by temporal gradients
+            L.mcpt_gradient_opts_init.argtypes = [C.POINTER(GradientOpts)]
+            L.mcpt_gradient_opts_init.restype = None
+            L.mcpt_gradient_phase.argtypes = [I, C.c_uint64, C.POINTER(I), C.POINTER(I)]
+            L.mcpt_gradient_rays.argtypes = [C.POINTER(Camera), I, I, I, I, P, P]
+            L.mcpt_gradient_rays_device.argtypes = L.mcpt_gradient_rays.argtypes
+            L.mcpt_temporal_gradient.argtypes = [C.POINTER(GradientOpts), I, I, I, I, P, P, P, C.POINTER(D)]
+            L.mcpt_temporal_gradient_device.argtypes = L.mcpt_temporal_gradient.argtypes
+            L.mcpt_temporal_accumulate_antilag.argtypes = L.mcpt_temporal_accumulate_motion.argtypes + [C.POINTER(GradientOpts), P]
+            L.mcpt_temporal_accumulate_antilag_device.argtypes = L.mcpt_temporal_accumulate_antilag.argtypes
+            L.mcpt_sequence_set_antilag.argtypes = [P, C.POINTER(GradientOpts)]
+            L.mcpt_sequence_antilag_info.argtypes = [P, C.POINTER(I), C.POINTER(I), C.POINTER(I), C.POINTER(D), C.POINTER(D),
+                                                     C.POINTER(D), C.POINTER(D)]
         L.mcpt_closest_hit.argtypes = [P, I, dp, dp, ip, I, ip, dp]
         L.mcpt_light_prep.argtypes = [P, I, dp, dp, dp, dp, ip, ip]
         L.mcpt_primary_hits.argtypes = [P, C.POINTER(Camera), ip, dp]
@@ -1328,6 +1354,120 @@ def temporal_accumulate_motion_device(width, height, color_ptr, aov_ptrs, motion
     return sec.value
 
 
+GRADIENT_OPTS = ("stratum", "radius", "scale", "device")
+
+
+def _gradient_opts(stratum=None, radius=None, scale=None, device=None):
+    g = GradientOpts()
+    lib().mcpt_gradient_opts_init(C.byref(g))
+    for k, v in (("stratum", stratum), ("radius", radius), ("scale", scale), ("device", device)):
+        if v is not None:
+            setattr(g, k, type(getattr(g, k))(v))
+    return g
+
+
+def gradient_phase(stratum, frame_index):
+    """mcpt_gradient_phase: the phase (a, b) of frame `frame_index` at `stratum` (1..8), upsample_phase's rule:
+    k = frame_index mod stratum^2, a = k mod stratum, b = (a + k div stratum) mod stratum."""
+    a, b = C.c_int32(), C.c_int32()
+    _check(lib().mcpt_gradient_phase(int(stratum), int(frame_index), C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def gradient_rays(camera, stratum, a, b, device=None):
+    """mcpt_gradient_rays: (origin, dir), H*W x 3 each in pixel order: camera_rays(camera)'s rays at the pixels (i, j)
+    with i mod stratum == a and j mod stratum == b bit for bit, a zero direction (a miss for render_rays) everywhere else
+    -- what an anti-lag gradient pass traces, with the previous frame's camera and seed."""
+    n = max(camera.width * camera.height, 1)
+    origin, dir = np.zeros((n, 3)), np.zeros((n, 3))
+    _check(lib().mcpt_gradient_rays(C.byref(camera), int(stratum), int(a), int(b), -1 if device is None else int(device),
+                                    origin.ctypes.data, dir.ctypes.data))
+    return origin, dir
+
+
+def temporal_gradient(prev_raw, regrad, a, b, stratum=3, radius=1, scale=1.0, device=None):
+    """mcpt_temporal_gradient (include/mcpt.h states the rule): prev_raw H x W x 3 is the previous frame's raw render,
+    regrad H x W x 3 the radiance along gradient_rays of the previous camera with the previous seed in the current scene
+    (0 off the selected pixels).  Returns (Lambda, ceil(H / stratum) x ceil(W / stratum), in [0, 1]; the device seconds)."""
+    prev_raw, regrad = _d(prev_raw), _d(regrad)
+    H, W = prev_raw.shape[:2]
+    assert prev_raw.shape == (H, W, 3) and regrad.shape == (H, W, 3)
+    g = _gradient_opts(stratum, radius, scale, device)
+    s = max(int(g.stratum), 1)
+    lam, sec = np.zeros(((H + s - 1) // s, (W + s - 1) // s)), C.c_double()
+    _check(lib().mcpt_temporal_gradient(C.byref(g), W, H, int(a), int(b), prev_raw.ctypes.data, regrad.ctypes.data,
+                                        lam.ctypes.data, C.byref(sec)))
+    return lam, sec.value
+
+
+def temporal_accumulate_antilag(color, aovs, lam, prev=None, motion=None, clamp=None, stratum=3, **opts):
+    """Temporal accumulation with anti-lag (mcpt_temporal_accumulate_antilag; include/mcpt.h states the rule): as
+    temporal_accumulate (clamp=None) or temporal_accumulate_clamped, with motion (the dict of render_motion_aovs) as
+    temporal_accumulate_motion, and the blend weights raised by `lam`, the map temporal_gradient returned at `stratum`.
+    prev and the return value are those of the form chosen.  With lam == 0 the outputs are that form's bit for bit."""
+    color = _d(color)
+    H, W = color.shape[:2]
+    assert color.shape == (H, W, 3)
+    keys = ("albedo", "normal", "position", "depth")
+    g = {k: _d(aovs[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys}
+    b = AovBuffers(*[g[k].ctypes.data for k in keys])
+    mb = None
+    if motion is not None:
+        mo = {k: _d(motion[k], (H, W, 3)) for k in ("prev_position", "prev_normal")}
+        mb = MotionBuffers(mo["prev_position"].ctypes.data, mo["prev_normal"].ctypes.data)
+    go = _gradient_opts(stratum)
+    s = max(int(go.stratum), 1)
+    lam = _d(lam, ((H + s - 1) // s, (W + s - 1) // s))
+    pc = pb = pcol = pmom = pfast = None
+    if prev is not None:
+        pcam, paov, pcol, pmom = prev[:4]
+        pg = {k: _d(paov[k], (H, W) if k == "depth" else (H, W, 3)) for k in keys[1:]}
+        pb = AovBuffers(None, *[pg[k].ctypes.data for k in keys[1:]])
+        pcol, pmom = _d(pcol, (H, W, 3)), _d(pmom, (H, W, 4))
+        if clamp is not None:
+            pfast = _d(prev[4], (H, W, 3))
+        pc = C.byref(pcam)
+    out, mom, var, sec = np.zeros((H, W, 3)), np.zeros((H, W, 4)), np.zeros((H, W)), C.c_double()
+    fast, shift = (np.zeros((H, W, 3)), np.zeros((H, W))) if clamp is not None else (None, None)
+    o = _temporal_opts(opts)
+    c = _clamp_opts(clamp) if clamp is not None else None
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _check(lib().mcpt_temporal_accumulate_antilag(
+        C.byref(o), None if c is None else C.byref(c), pc, W, H, color.ctypes.data, C.byref(b), None if mb is None else C.byref(mb),
+        None if pb is None else C.byref(pb), ptr(pcol), ptr(pmom), ptr(pfast), out.ctypes.data, mom.ctypes.data, ptr(fast),
+        ptr(shift), var.ctypes.data, C.byref(sec), C.byref(go), lam.ctypes.data))
+    if clamp is None:
+        return out, mom, var, sec.value
+    return out, mom, fast, var, shift, sec.value
+
+
+def temporal_accumulate_antilag_device(width, height, color_ptr, aov_ptrs, lambda_ptr, out_color_ptr, out_moments_ptr,
+                                       out_fast_ptr=None, out_variance_ptr=None, out_shift_ptr=None, prev=None, motion_ptrs=None,
+                                       clamp=None, stratum=3, **opts):
+    """temporal_accumulate_antilag over device buffers, as temporal_accumulate_motion_device: lambda_ptr the device
+    pointer of the Lambda map at `stratum`; motion_ptrs None or a dict of the prev_position and prev_normal pointers.
+    Returns the device seconds."""
+    b = AovBuffers(*[int(aov_ptrs[k]) for k in ("albedo", "normal", "position", "depth")])
+    mb = None if motion_ptrs is None else MotionBuffers(int(motion_ptrs["prev_position"]), int(motion_ptrs["prev_normal"]))
+    opt = lambda p: None if p is None else C.c_void_p(int(p))
+    pc = pb = pcol = pmom = pfast = None
+    if prev is not None:
+        pcam, paov, pcol, pmom = prev[:4]
+        pb = AovBuffers(None, *[int(paov[k]) for k in ("normal", "position", "depth")])
+        pc, pcol, pmom = C.byref(pcam), opt(pcol), opt(pmom)
+        if clamp is not None:
+            pfast = opt(prev[4])
+    sec = C.c_double()
+    o, go = _temporal_opts(opts), _gradient_opts(stratum)
+    c = _clamp_opts(clamp) if clamp is not None else None
+    _check(lib().mcpt_temporal_accumulate_antilag_device(
+        C.byref(o), None if c is None else C.byref(c), pc, int(width), int(height), opt(color_ptr), C.byref(b),
+        None if mb is None else C.byref(mb), None if pb is None else C.byref(pb), pcol, pmom, pfast, opt(out_color_ptr),
+        opt(out_moments_ptr), opt(out_fast_ptr), opt(out_shift_ptr), opt(out_variance_ptr), C.byref(sec), C.byref(go),
+        opt(lambda_ptr)))
+    return sec.value
+
+
 class TemporalAccumulator:
     """The history of a frame sequence over a static scene: push(camera, color, aovs) accumulates one frame onto
     what the earlier pushes left and returns (accumulated colour, variance of its luminance); the unfiltered
@@ -1336,7 +1476,8 @@ class TemporalAccumulator:
     clamp: None (the default: plain accumulation), True or a dict of radius / alpha_fast / sigma for history clamping
     (temporal_accumulate_clamped); then a push also leaves `fast` (the fast history), `shift` and `clamped`, the share
     of pixels with shift != 0.  push(..., motion=render_motion_aovs(scene, camera)) follows geometry moved by
-    Scene.update since the last Scene.pose_save (temporal_accumulate_motion)."""
+    Scene.update since the last Scene.pose_save (temporal_accumulate_motion).  push(..., lam=Lambda, stratum=s) raises
+    the blend weights by the temporal gradient's map (temporal_accumulate_antilag), with or without motion and clamp."""
 
     def __init__(self, clamp=None, **opts):
         if clamp is False:
@@ -1348,10 +1489,19 @@ class TemporalAccumulator:
         self.state, self.moments, self.seconds, self.kept = None, None, 0.0, 0.0
         self.fast, self.shift, self.clamped = None, None, 0.0
 
-    def push(self, camera, color, aovs, motion=None):
+    def push(self, camera, color, aovs, motion=None, lam=None, stratum=3):
         cam = Camera.from_buffer_copy(camera)
         keep = {k: np.array(aovs[k], dtype=np.float64) for k in ("albedo", "normal", "position", "depth")}
-        if self.clamp is None:
+        if lam is not None:
+            r = temporal_accumulate_antilag(color, keep, lam, self.state, motion, self.clamp, stratum, **self.opts)
+            if self.clamp is None:
+                out, mom, var, self.seconds = r
+                self.state = (cam, keep, out, mom)
+            else:
+                out, mom, self.fast, var, self.shift, self.seconds = r
+                self.state = (cam, keep, out, mom, self.fast)
+                self.clamped = float((self.shift != 0).mean())
+        elif self.clamp is None:
             if motion is None:
                 out, mom, var, self.seconds = temporal_accumulate(color, keep, self.state, **self.opts)
             else:
@@ -1394,10 +1544,17 @@ class FrameSequence:
     temporal_accumulate_motion's rule, following geometry moved by Scene.update since the caller's last Scene.pose_save
     (the sequence never saves the pose); read("prev_position") / read("prev_normal") and motion_info() then work, and
     set_motion() switches it from the next frame on.
+    antilag=True or a dict of stratum / radius / scale (not with upsample, jitter or grid): every frame keeps its raw
+    frame and seed, the next one traces a 1 / stratum^2 subset of those samples again in the scene as it then is
+    (gradient_rays, render_rays with the kept seed), turns the difference into Lambda (temporal_gradient) and accumulates
+    by temporal_accumulate_antilag's rule, so that history made stale by an edit of the scene is dropped at once;
+    read("gradient_lambda") / read("gradient_raw") and antilag_info() then work, and set_antilag() switches it from the
+    next frame on.
     After a frame: `info` (SequenceInfo: stage device times, kept, mean_history, clamped) and `stats` (the render's)."""
 
     def __init__(self, scene, width, height, spp, mode="mis", denoise=True, clamp=None, device=None, accel="bvh", flags=0,
-                 tone_max=None, tone_gamma=None, upsample=None, temporal_upsample=False, motion=False, **temporal_opts):
+                 tone_max=None, tone_gamma=None, upsample=None, temporal_upsample=False, motion=False, antilag=None,
+                 **temporal_opts):
         self.h = None
         self._destroy = lib().mcpt_sequence_destroy
         if clamp is False:
@@ -1445,8 +1602,38 @@ class FrameSequence:
         self.width, self.height, self.spp, self.denoise, self.clamp = o.width, o.height, o.spp, bool(denoise), clamp
         self.info, self.stats = None, None
         self.motion = False
+        self.antilag = None
         if motion:
             self.set_motion(True)
+        if antilag is not None and antilag is not False:
+            self.set_antilag(antilag)
+
+    def set_antilag(self, antilag):
+        """mcpt_sequence_set_antilag: from the next frame on, run the gradient pass and accumulate by the anti-lag rule
+        (True for the defaults, or a dict of stratum / radius / scale), or not (None or False); refused by an upsampled
+        sequence and with jitter or the grid."""
+        if antilag is None or antilag is False:
+            _check(lib().mcpt_sequence_set_antilag(self.h, None))
+            self.antilag = None
+            return
+        d = {} if antilag is True else dict(antilag)
+        unknown = set(d) - set(GRADIENT_OPTS[:3])
+        if unknown:
+            raise TypeError("unknown antilag option %r (one of %s)" % (sorted(unknown)[0], ", ".join(GRADIENT_OPTS[:3])))
+        g = _gradient_opts(d.get("stratum"), d.get("radius"), d.get("scale"))
+        _check(lib().mcpt_sequence_set_antilag(self.h, C.byref(g)))
+        self.antilag = g
+
+    def antilag_info(self):
+        """mcpt_sequence_antilag_info of the last frame: dict of ran (the gradient pass ran), phase (a, b), trace_seconds
+        (the gradient render), kernel_seconds (the ray, gradient and reduction kernels), lambda_mean and lambda_max;
+        antilag only."""
+        r, a, b = C.c_int32(), C.c_int32(), C.c_int32()
+        t, k, m, x = C.c_double(), C.c_double(), C.c_double(), C.c_double()
+        _check(lib().mcpt_sequence_antilag_info(self.h, C.byref(r), C.byref(a), C.byref(b), C.byref(t), C.byref(k), C.byref(m),
+                                                C.byref(x)))
+        return dict(ran=bool(r.value), phase=(a.value, b.value), trace_seconds=t.value, kernel_seconds=k.value,
+                    lambda_mean=m.value, lambda_max=x.value)
 
     def set_motion(self, on):
         """mcpt_sequence_set_motion: from the next frame on, accumulate with (True) or without (False) object motion;
@@ -1469,15 +1656,20 @@ class FrameSequence:
         _check(lib().mcpt_sequence_frame(self.h, C.byref(camera), int(seed), None if out is None else out.ctypes.data,
                                          C.byref(info), C.byref(st)))
         self.info, self.stats = info, st
+        self._lambda_stratum = int(self.antilag.stratum) if self.antilag is not None else 0  # what gradient_lambda is sized by
         return out
 
     def read(self, name):
         """The last frame's buffer `name` as a float64 array: raw, accumulated, filtered, fast (H x W x 3), moments
         (H x W x 4), variance, shift (H x W); with upsample=F also upsampled (F H x F W x 3); with motion=True also
-        prev_position and prev_normal (H x W x 3)."""
-        what, tail = SEQ_BUFFERS.get(name, SEQ_MOTION_BUFFERS.get(name, (-1, ())))
+        prev_position and prev_normal (H x W x 3); with antilag also gradient_lambda (ceil(H / s) x ceil(W / s)) and,
+        when the gradient pass ran, gradient_raw (H x W x 3)."""
+        what, tail = SEQ_BUFFERS.get(name, SEQ_MOTION_BUFFERS.get(name, SEQ_ANTILAG_BUFFERS.get(name, (-1, ()))))
         f = self.factor if name == "upsampled" or (self.temporal_upsample and name != "raw") else 1
         out = np.zeros((f * self.height, f * self.width) + tail)
+        if name == "gradient_lambda":  # at the stratum the last frame ran with, whatever set_antilag set since
+            s = max(getattr(self, "_lambda_stratum", 0), 1)
+            out = np.zeros(((self.height + s - 1) // s, (self.width + s - 1) // s))
         _check(lib().mcpt_sequence_read(self.h, what, out.ctypes.data))
         return out
 
@@ -1485,7 +1677,8 @@ class FrameSequence:
         """The device pointer (int) of the last frame's buffer `name` (read()'s names and rgb8), valid until the next
         frame, reset or close."""
         p = C.c_void_p()
-        _check(lib().mcpt_sequence_device_buffer(self.h, SEQ_BUFFERS.get(name, SEQ_MOTION_BUFFERS.get(name, (-1, ())))[0], C.byref(p)))
+        what = SEQ_BUFFERS.get(name, SEQ_MOTION_BUFFERS.get(name, SEQ_ANTILAG_BUFFERS.get(name, (-1, ()))))[0]
+        _check(lib().mcpt_sequence_device_buffer(self.h, what, C.byref(p)))
         return p.value
 
     def upsample_info(self):

@@ -70,6 +70,13 @@
 //   facets: before each frame's move the scene's pose is saved (mcpt_scene_pose_save), the frame renders the motion AOVs
 //   (mcpt_render_motion_aovs) and accumulates with mcpt_temporal_accumulate_motion (mcpt_sequence_set_motion in the device
 //   sequence), so a moved surface keeps its history instead of restarting it every frame.  Not with --upsample.
+//               [--antilag] [--antilag-stratum S]
+//   --antilag (with --frames N, with or without --device-sequence; meant for --dim, --tint, --move and --rotate) drops
+//   history that an edit of the scene made stale: every frame from the second on traces one sample pixel per S x S
+//   block (S = 3, or --antilag-stratum S in 1..8) of the previous frame again, with that frame's camera and seed in the
+//   scene as it is now (mcpt_gradient_rays, mcpt_render_rays), turns the difference into Lambda (mcpt_temporal_gradient)
+//   and accumulates with mcpt_temporal_accumulate_antilag (mcpt_sequence_set_antilag in the device sequence); the frame
+//   prints an "anti-lag" line.  Not with --jitter, --grid or --upsample.
 //               [--dim GROUP:FACTOR]... [--tint MATERIAL:R,G,B]...
 //   --dim and --tint (with --frames N, with or without --device-sequence, with --move / --rotate or alone) re-light the
 //   scene in place: before frame k >= 1 the radiance of every light of GROUP (mcpt_scene_light_groups) is multiplied by
@@ -83,6 +90,7 @@
 //   reference's, default) otherwise.
 //   --progress prints the share of camera samples dispatched (the reference prints per-row progress
 //   and updates its EasyX window, main.cpp:539-592) through mcpt_render_opts.progress.
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -400,7 +408,13 @@ struct SequenceArgs {
     Rotator* rotate;  // --rotate, or null
     Rebuilder* rebuild;  // --rebuild, or null
     Relighter* relight;  // --dim / --tint, or null
+    int antilag;  // --antilag: the stratum, or 0
 };
+
+void print_antilag(int stratum, int a, int b, double mean, double mx, double trace_seconds) {
+    std::printf("  anti-lag: stratum %d, phase (%d, %d), Lambda mean %.4f, max %.4f, %.3f ms gradient render\n", stratum, a, b, mean, mx,
+                trace_seconds * 1e3);
+}
 
 // --frames: render, accumulate (and filter) frame after frame; the history ping-pongs between two sets of buffers
 // the full-size guides of `cam` scaled by up.factor, then mcpt_upsample of the low frame `low` into `full`; prints the
@@ -450,6 +464,12 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
     }
     std::vector<double> hdr, variance(npx), filtered(3 * npx), shift(clamp ? npx : 0), upsampled;
     std::vector<double> prev_position(a.motion ? 3 * npx : 0), prev_normal(a.motion ? 3 * npx : 0);
+    // --antilag: the previous frame's raw render, the gradient rays and their radiance, Lambda
+    mcpt_gradient_opts go;
+    mcpt_gradient_opts_init(&go);
+    if (a.antilag) go.stratum = a.antilag;
+    const size_t nlam = a.antilag ? (size_t)((H + go.stratum - 1) / go.stratum) * ((W + go.stratum - 1) / go.stratum) : 0;
+    std::vector<double> prev_raw, ray_o(a.antilag ? 3 * npx : 0), ray_d(a.antilag ? 3 * npx : 0), regrad, lambda(nlam);
     for (int k = 0; k < a.frames; k++) {
         Frame &cur = fr[k & 1], &prev = fr[(k & 1) ^ 1];
         if (a.motion && mcpt_scene_pose_save(scene) != MCPT_OK) {
@@ -464,11 +484,33 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
             std::fprintf(stderr, "%s\n", mcpt_last_error());
             return 1;
         }
+        if (a.antilag) {  // the previous frame's samples again, in the scene as it is now
+            std::fill(lambda.begin(), lambda.end(), 0.0);
+            if (k) {
+                int32_t pa = 0, pb = 0;
+                mcpt_render_opts gr;
+                mcpt_render_opts_init(&gr);
+                gr.spp = a.spp, gr.mode = a.mode, gr.seed = a.seed + k - 1, gr.flags = a.flags;
+                mcpt_stats gst{};
+                regrad.assign(3 * npx, 0.0);
+                if (mcpt_gradient_phase(go.stratum, (uint64_t)k, &pa, &pb) != MCPT_OK ||
+                    mcpt_gradient_rays(&prev.cam, go.stratum, pa, pb, -1, ray_o.data(), ray_d.data()) != MCPT_OK ||
+                    mcpt_render_rays(scene, &gr, (int32_t)npx, ray_o.data(), ray_d.data(), regrad.data(), &gst) != MCPT_OK ||
+                    mcpt_temporal_gradient(&go, W, H, pa, pb, prev_raw.data(), regrad.data(), lambda.data(), nullptr) != MCPT_OK) {
+                    std::fprintf(stderr, "anti-lag gradient failed: %s\n", mcpt_last_error());
+                    return 1;
+                }
+                double sum = 0, mx = 0;
+                for (double v : lambda) sum += v, mx = v > mx ? v : mx;
+                print_antilag(go.stratum, pa, pb, sum / (double)nlam, mx, gst.seconds);
+            }
+        }
         mcpt_stats st{};
         if (render(scene, cur.cam, a.spp, a.mode, a.seed + k, a.progress, a.grid, a.flags, devices, hdr, &st) != MCPT_OK) {
             std::fprintf(stderr, "render failed: %s\n", mcpt_last_error());
             return 1;
         }
+        if (a.antilag) prev_raw = hdr;
         const mcpt_aov_buffers aov{cur.albedo.data(), cur.normal.data(), cur.position.data(), cur.depth.data()};
         const mcpt_aov_buffers paov{prev.albedo.data(), prev.normal.data(), prev.position.data(), prev.depth.data()};
         mcpt_render_opts ao;
@@ -484,7 +526,14 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
             return 1;
         }
         double tsec = 0;
-        const int rc = a.motion ? mcpt_temporal_accumulate_motion(&tp, clamp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov, &mo,
+        const int rc = a.antilag ? mcpt_temporal_accumulate_antilag(&tp, clamp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov,
+                                                                    a.motion ? &mo : nullptr, k ? &paov : nullptr,
+                                                                    k ? prev.color.data() : nullptr, k ? prev.moments.data() : nullptr,
+                                                                    clamp && k ? prev.fast.data() : nullptr, cur.color.data(),
+                                                                    cur.moments.data(), clamp ? cur.fast.data() : nullptr,
+                                                                    clamp ? shift.data() : nullptr, variance.data(), &tsec, &go,
+                                                                    lambda.data())
+                       : a.motion ? mcpt_temporal_accumulate_motion(&tp, clamp, k ? &prev.cam : nullptr, W, H, hdr.data(), &aov, &mo,
                                                                   k ? &paov : nullptr, k ? prev.color.data() : nullptr,
                                                                   k ? prev.moments.data() : nullptr,
                                                                   clamp && k ? prev.fast.data() : nullptr, cur.color.data(),
@@ -583,6 +632,14 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
         mcpt_sequence_destroy(seq);
         return 1;
     }
+    mcpt_gradient_opts go;
+    mcpt_gradient_opts_init(&go);
+    if (a.antilag) go.stratum = a.antilag;
+    if (a.antilag && mcpt_sequence_set_antilag(seq, &go) != MCPT_OK) {
+        std::fprintf(stderr, "sequence setup failed: %s\n", mcpt_last_error());
+        mcpt_sequence_destroy(seq);
+        return 1;
+    }
     std::vector<uint8_t> rgb8(3 * npx);
     std::vector<double> shown;
     int rc = 0;
@@ -605,6 +662,16 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
             std::fprintf(stderr, "frame %d failed: %s\n", k, mcpt_last_error());
             rc = 1;
             break;
+        }
+        if (a.antilag) {
+            int32_t ran = 0, pa = 0, pb = 0;
+            double tsec = 0, mean = 0, mx = 0;
+            if (mcpt_sequence_antilag_info(seq, &ran, &pa, &pb, &tsec, nullptr, &mean, &mx) != MCPT_OK) {
+                std::fprintf(stderr, "%s\n", mcpt_last_error());
+                rc = 1;
+                break;
+            }
+            if (ran) print_antilag(go.stratum, pa, pb, mean, mx, tsec);
         }
         std::printf("frame %d: orbit %g deg, seed %llu, %.3f s render, %.3f ms accumulate, %.1f%% of the pixels kept their "
                     "history (mean length %.2f)", k, k * a.orbit, (unsigned long long)(a.seed + k), fi.render_seconds,
@@ -684,6 +751,8 @@ int main(int argc, char** argv) {
     mcpt_upsample_opts up;
     mcpt_upsample_opts_init(&up);
     bool move_flag = false, motion_flag = false, rotate_flag = false, lights_movable_flag = false;
+    bool antilag_flag = false, antilag_stratum_flag = false;
+    int antilag_stratum = 3;
     Mover mover;
     Rotator rotator;
     bool rebuild_flag = false;
@@ -791,6 +860,8 @@ int main(int argc, char** argv) {
             }
         }
         else if (!std::strcmp(argv[a], "--motion")) motion_flag = true;
+        else if (!std::strcmp(argv[a], "--antilag")) antilag_flag = true;
+        else if (!std::strcmp(argv[a], "--antilag-stratum")) antilag_stratum = std::atoi(next()), antilag_stratum_flag = true;
         else if (!std::strcmp(argv[a], "--lights-movable")) lights_movable_flag = true;
         else if (!std::strcmp(argv[a], "--devices")) {
             for (const char* p = next(); *p;) {
@@ -846,6 +917,22 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "--motion %s\n", frames == 0 ? "follows moved facets through the history of a sequence; add --frames N"
                                                           : "is not supported with upsampling; drop --upsample");
         return 2;
+    }
+    if (antilag_stratum_flag && !antilag_flag) {  // refused before anything is loaded
+        std::fprintf(stderr, "--antilag-stratum sets the stratum of --antilag; add --antilag\n");
+        return 2;
+    }
+    if (antilag_flag) {  // refused before anything is loaded
+        const char* why = frames == 0 ? "drops stale history in a sequence; add --frames N"
+                          : antilag_stratum < 1 || antilag_stratum > 8 ? "needs an --antilag-stratum in 1..8"
+                          : (flags & MCPT_RENDER_PIXEL_JITTER) ? "traces its gradient samples through the pixels' centres; drop --jitter"
+                          : grid     ? "traces its gradient samples over the BVH; drop --grid"
+                          : upsample ? "is not supported with upsampling; drop --upsample"
+                                     : nullptr;
+        if (why) {
+            std::fprintf(stderr, "--antilag %s\n", why);
+            return 2;
+        }
     }
     if (temporal_upsample) {  // refused before anything is loaded
         const char* why = !upsample          ? "accumulates at --upsample F times the traced size; add --upsample F"
@@ -958,7 +1045,8 @@ int main(int argc, char** argv) {
         }
         const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out,
                               move_flag ? &mover : nullptr, motion_flag, rotate_flag ? &rotator : nullptr,
-                              rebuild_flag ? &rebuilder : nullptr, relight_flag ? &relighter : nullptr};
+                              rebuild_flag ? &rebuilder : nullptr, relight_flag ? &relighter : nullptr,
+                              antilag_flag ? antilag_stratum : 0};
         if (clamp_flag && !history_clamp) {
             std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
             return 2;

@@ -299,12 +299,30 @@ struct TemporalClampIo {  // the clamped rule's extra arguments
     double* out_fast;
     double* out_shift;  // required here: the kernels pass "has a history" through it (the public form's scratch)
 };
+struct TemporalAntilagIo {  // the anti-lag rule's extra arguments
+    const mcpt_gradient_opts* gradient;
+    const double* lambda;  // hs * ws at gradient->stratum
+};
 int temporal_check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, bool clamped);
 // io == nullptr: mcpt_temporal_accumulate's rule, else mcpt_temporal_accumulate_clamped's; motion != nullptr: either
-// in mcpt_temporal_accumulate_motion's form (both arrays required)
+// in mcpt_temporal_accumulate_motion's form (both arrays required); antilag != nullptr: any of them in
+// mcpt_temporal_accumulate_antilag's form
 int temporal_enqueue(const mcpt_temporal_opts* o, const mcpt_camera* prev_cam, int32_t W, int32_t H, const double* dC,
                      const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut,
-                     double* dOutM, double* dOutV, const TemporalClampIo* io, const mcpt_motion_buffers* motion = nullptr);
+                     double* dOutM, double* dOutV, const TemporalClampIo* io, const mcpt_motion_buffers* motion = nullptr,
+                     const TemporalAntilagIo* antilag = nullptr);
+
+// temporal_gradient.hip -- the temporal gradient in the same form.  gradient_check_opts: mcpt_gradient_opts' checks.
+// temporal_gradient_enqueue: every check of mcpt_temporal_gradient_device that needs no device, then its kernel on the
+// null stream.  lambda_stats_enqueue: the mean and the maximum of n values of Lambda -- per-block partials in a fixed
+// lane and wave order, then one pass over the partials in index order -- into words[0] (mean) and words[1] (max);
+// words: lambda_stats_words() doubles of device scratch, enough for every n (the number of partials is bounded, and
+// not monotone in n).
+int gradient_check_opts(const mcpt_gradient_opts* o);
+int temporal_gradient_enqueue(const mcpt_gradient_opts* o, int32_t W, int32_t H, int32_t a, int32_t b, const double* dPrev,
+                              const double* dRegrad, double* dLambda);
+size_t lambda_stats_words();
+int lambda_stats_enqueue(const double* dLambda, size_t n, double* words);
 int denoise_check_opts(const mcpt_denoise_opts* o);
 // tmp: 8 * W * H doubles of scratch (two colour + variance buffers)
 int denoise_enqueue(const mcpt_denoise_opts* o, int32_t W, int32_t H, const double* dC, const double* dV,
@@ -332,6 +350,8 @@ int temporal_upsample_enqueue(const mcpt_temporal_opts* tp, const mcpt_upsample_
 // render.hip -- mcpt_camera_phase_rays_device's checks that need no device, then its kernel on the null stream of the
 // current device
 int camera_phase_rays_enqueue(const mcpt_camera* full_cam, int32_t factor, int32_t a, int32_t b, double* dOrigin, double* dDir);
+// the same for mcpt_gradient_rays_device
+int gradient_rays_enqueue(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, double* dOrigin, double* dDir);
 
 // render.hip -- k_motion_aovs alone, on the primary-hit tables the scene's state on `device` holds from its last
 // mcpt_render_aovs[_device] call, which must have been for a W x H camera (the frame sequence calls it right after the

@@ -1256,6 +1256,17 @@ __global__ __launch_bounds__(256) void k_camera_phase_rays(CamFrame cam, int f, 
     dir[3 * (size_t)r] = rd.x, dir[3 * (size_t)r + 1] = rd.y, dir[3 * (size_t)r + 2] = rd.z;
 }
 
+// mcpt_gradient_rays: every pixel of the frame gets a ray; pixels (i, j) with i mod s == a and j mod s == b the
+// pixel-centre ray, by the same function, every other a zero direction (a miss that traces nothing)
+__global__ __launch_bounds__(256) void k_gradient_rays(CamFrame cam, int s, int a, int b, double* origin, double* dir) {
+    const int p = blockIdx.x * 256 + (int)threadIdx.x;
+    if (p >= cam.W * cam.H) return;
+    d3 rd = {0.0, 0.0, 0.0};
+    if ((p / cam.W) % s == a && (p % cam.W) % s == b) rd = pixel_ray_dir(cam, 0, p, 0, false);
+    origin[3 * (size_t)p] = cam.eye.x, origin[3 * (size_t)p + 1] = cam.eye.y, origin[3 * (size_t)p + 2] = cam.eye.z;
+    dir[3 * (size_t)p] = rd.x, dir[3 * (size_t)p + 1] = rd.y, dir[3 * (size_t)p + 2] = rd.z;
+}
+
 // moves nodes [sb, sb + m) of src to [db, db + m) of dst (every field a generation carries into the
 // next: point, normal, wo, throughput, facet, pixel, sample, node id) -- the spill stack's push and
 // pop when a generation is larger than its children buffer can take (WavefrontRun::balance_spill)
@@ -6957,6 +6968,40 @@ int camera_phase_rays_enqueue(const mcpt_camera* cam, int32_t f, int32_t a, int3
     return MCPT_OK;
 }
 
+// every check of mcpt_gradient_rays[_device] that needs no device
+static int gradient_rays_check(const mcpt_camera* cam, int32_t s, int32_t a, int32_t b, const double* dOrigin, const double* dDir) {
+    if (!cam || !dOrigin || !dDir) {
+        set_error("mcpt_gradient_rays: null argument: %s", !cam ? "cam" : !dOrigin ? "origin" : "dir");
+        return MCPT_E_INVALID;
+    }
+    int rc;
+    if ((rc = validate_camera(cam))) return rc;
+    if ((long long)cam->width * cam->height > (1ll << 28)) {
+        set_error("mcpt_gradient_rays: invalid frame size: width %d, height %d (a frame may hold 2^28 pixels)", cam->width,
+                  cam->height);
+        return MCPT_E_INVALID;
+    }
+    if (s < 1 || s > 8) {
+        set_error("mcpt_gradient_rays: stratum %d is outside 1..8", s);
+        return MCPT_E_INVALID;
+    }
+    if (a < 0 || a >= s || b < 0 || b >= s) {
+        set_error("mcpt_gradient_rays: invalid phase (%d, %d): both must lie in [0, stratum = %d)", a, b, s);
+        return MCPT_E_INVALID;
+    }
+    return MCPT_OK;
+}
+
+int gradient_rays_enqueue(const mcpt_camera* cam, int32_t s, int32_t a, int32_t b, double* dOrigin, double* dDir) {
+    int rc;
+    if ((rc = gradient_rays_check(cam, s, a, b, dOrigin, dDir))) return rc;
+    const CamFrame cf = cam_setup(*cam);
+    const int npx = cam->width * cam->height;
+    hipLaunchKernelGGL(k_gradient_rays, dim3((npx + 255) / 256), dim3(256), 0, 0, cf, s, a, b, dOrigin, dDir);
+    HIP_OK(hipGetLastError());
+    return MCPT_OK;
+}
+
 }  // namespace mcpt
 
 // ============================================================================================
@@ -7363,6 +7408,55 @@ int mcpt_camera_phase_rays(const mcpt_camera* full_cam, int32_t factor, int32_t 
 int mcpt_camera_phase_rays_device(const mcpt_camera* full_cam, int32_t factor, int32_t a, int32_t b, int32_t device,
                                   double* dev_origin, double* dev_dir) {
     return camera_phase_rays(full_cam, factor, a, b, device, dev_origin, dev_dir, false);
+}
+
+// both forms of mcpt_gradient_rays; host: origin and dir are host arrays
+static int gradient_rays(const mcpt_camera* cam, int32_t s, int32_t a, int32_t b, int32_t device, double* origin, double* dir,
+                         bool host) {
+    int rc;
+    if ((rc = gradient_rays_check(cam, s, a, b, origin, dir))) return rc;
+    struct Restore {  // the caller's current device
+        int prev = -1;
+        ~Restore() {
+            if (prev >= 0) (void)hipSetDevice(prev);
+        }
+    } restore;
+    if (device >= 0) {
+        HIP_OK(hipGetDevice(&restore.prev));
+        HIP_OK(hipSetDevice(device));
+    }
+    if (!host) {
+        int cur = 0;
+        HIP_OK(hipGetDevice(&cur));
+        if ((rc = check_device_buffer(origin, cur, "dev_origin")) || (rc = check_device_buffer(dir, cur, "dev_dir"))) return rc;
+        // the caller's arrays may still be in use by work on other streams (e.g. torch's)
+        HIP_OK(hipDeviceSynchronize());
+        if ((rc = gradient_rays_enqueue(cam, s, a, b, origin, dir))) return rc;
+        HIP_OK(hipStreamSynchronize(nullptr));
+        return MCPT_OK;
+    }
+    const size_t n = (size_t)cam->width * cam->height, bytes = 3 * n * sizeof(double);
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() {
+            if (p) (void)hipFree(p);
+        }
+    } buf;
+    HIP_OK(hipMalloc(&buf.p, 2 * bytes));
+    double* d = (double*)buf.p;
+    if ((rc = gradient_rays_enqueue(cam, s, a, b, d, d + 3 * n))) return rc;
+    HIP_OK(hipMemcpy(origin, d, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dir, d + 3 * n, bytes, hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+int mcpt_gradient_rays(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device, double* origin, double* dir) {
+    return gradient_rays(cam, stratum, a, b, device, origin, dir, true);
+}
+
+int mcpt_gradient_rays_device(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device, double* dev_origin,
+                              double* dev_dir) {
+    return gradient_rays(cam, stratum, a, b, device, dev_origin, dev_dir, false);
 }
 
 void mcpt_adaptive_opts_init(mcpt_adaptive_opts* a) {

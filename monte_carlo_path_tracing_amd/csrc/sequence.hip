@@ -24,6 +24,13 @@
 // (mcpt_internal.h: k_motion_aovs on the primary-hit tables the AOVs just built) into two maps allocated at the first
 // set_motion(on), and temporal_enqueue takes them (mcpt_temporal_accumulate_motion's rule).
 //
+// With mcpt_sequence_set_antilag a plain sequence's frame adds the gradient pass BEFORE its render (so the frame's AOVs
+// and motion AOVs still see the primary-hit tables of the frame's own camera): gradient_rays_enqueue of the previous
+// camera, mcpt_render_rays_device with the previous seed, temporal_gradient_enqueue against the raw frame the previous
+// frame kept and lambda_stats_enqueue (mcpt_internal.h); temporal_enqueue then takes Lambda
+// (mcpt_temporal_accumulate_antilag's rule) and the frame ends by keeping its raw frame (a device-to-device copy).  The
+// buffers are an allocation of their own, made at the first switch-on.
+//
 // The tone map's loads are plain: lane k reads values 4 k .. 4 k + 3 (32 consecutive bytes, a wave 2 KB), stores
 // are one dword per lane.  pow is the device library's; -ffp-contract=off as everywhere.  The statistics read the
 // moments' n (every fourth double) and the shift once: thread t of a block takes the chunk's pixels t, t + 256, ...
@@ -39,6 +46,7 @@
 #include "denoise_common.h"
 #include "mcpt.h"
 #include "mcpt_internal.h"
+#include "scene_state.h"  // DevBuf: the anti-lag allocation is counted by mcpt_debug_device_bytes_live
 
 using mcpt::set_error;
 using mcpt_dn::check_device_array;
@@ -221,18 +229,35 @@ struct mcpt_sequence {
     mcpt_motion_buffers mo{};
     hipEvent_t ev_motion = nullptr;  // between the AOVs and the motion AOVs
     double motion_seconds = 0;
+    // anti-lag (mcpt_sequence_set_antilag): the gradient rays, the gradient raw frame, the kept raw frame, Lambda (sized
+    // for stratum 1) and the reduction's words, an allocation of their own made at the first switch-on; antilag: the
+    // next frame runs with it; last_antilag: the last frame did, last_ran: and its gradient pass ran
+    bool antilag = false, last_antilag = false, last_ran = false;
+    mcpt_gradient_opts go{}, last_go{};
+    mcpt::DevBuf al_mem;
+    double *al_ray_o = nullptr, *al_ray_d = nullptr, *al_raw = nullptr, *al_kept = nullptr, *al_lambda = nullptr, *al_words = nullptr;
+    double* al_host = nullptr;  // pinned: Lambda's mean and maximum
+    hipEvent_t ev_al[4] = {nullptr, nullptr, nullptr, nullptr};  // the ray kernel, then (after the trace) gradient + reduction
+    bool kept_valid = false;  // al_kept holds the raw frame of set[cur ^ 1], rendered with kept_seed
+    uint64_t kept_seed = 0;
+    int al_a = 0, al_b = 0;
+    double al_trace_seconds = 0, al_kernel_seconds = 0, al_mean = 0, al_max = 0;
 };
 
 namespace {
 
 void release(mcpt_sequence* s) {
     if (!s) return;
-    if (s->mem || s->host_stats || s->ev[0] || s->motion_mem || s->ev_motion) {
+    if (s->mem || s->host_stats || s->ev[0] || s->motion_mem || s->ev_motion || s->al_mem.p || s->al_host || s->ev_al[0]) {
         int cur = 0;
         const bool sw = hipGetDevice(&cur) == hipSuccess && cur != s->device && hipSetDevice(s->device) == hipSuccess;
         if (s->mem) (void)hipFree(s->mem);
         if (s->motion_mem) (void)hipFree(s->motion_mem);
         if (s->ev_motion) (void)hipEventDestroy(s->ev_motion);
+        (void)s->al_mem.release();
+        if (s->al_host) (void)hipHostFree(s->al_host);
+        for (hipEvent_t e : s->ev_al)
+            if (e) (void)hipEventDestroy(e);
         if (s->host_stats) (void)hipHostFree(s->host_stats);
         for (hipEvent_t e : s->ev)
             if (e) (void)hipEventDestroy(e);
@@ -288,6 +313,25 @@ int locate(mcpt_sequence* s, int32_t what, bool allow_rgb8, const void** dev, si
             }
             p = what == MCPT_SEQ_PREV_POSITION ? s->mo.prev_position : s->mo.prev_normal, b = 3 * n * d;
             break;
+        case MCPT_SEQ_GRADIENT_LAMBDA:
+        case MCPT_SEQ_GRADIENT_RAW: {
+            const char* name = what == MCPT_SEQ_GRADIENT_LAMBDA ? "MCPT_SEQ_GRADIENT_LAMBDA" : "MCPT_SEQ_GRADIENT_RAW";
+            if (!s->antilag || (s->has_last && !s->last_antilag)) {
+                set_error("%s: %s", name, !s->antilag ? "anti-lag is off for this sequence (mcpt_sequence_set_antilag)"
+                                                      : "the last frame ran before anti-lag was switched on");
+                return MCPT_E_INVALID;
+            }
+            if (what == MCPT_SEQ_GRADIENT_RAW && s->has_last && !s->last_ran) {
+                set_error("%s: the last frame's gradient pass did not run (no history, or the previous frame kept no raw frame)", name);
+                return MCPT_E_INVALID;
+            }
+            if (what == MCPT_SEQ_GRADIENT_RAW) p = s->al_raw, b = 3 * n * d;
+            else {
+                const size_t st = s->last_go.stratum > 0 ? s->last_go.stratum : 1;
+                p = s->al_lambda, b = ((s->opts.height + st - 1) / st) * ((s->opts.width + st - 1) / st) * d;
+            }
+            break;
+        }
         case MCPT_SEQ_RGB8:
             if (allow_rgb8) {
                 p = s->rgb8, b = 3 * s->NPX;
@@ -709,6 +753,34 @@ int mcpt_sequence_frame(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed,
     Scratch S;  // restores the caller's device
     if ((rc = select_device(s->device, S, &device))) return rc;
     s->has_last = false;  // the shared buffers are about to be overwritten
+    const bool antilag = s->antilag;
+    const mcpt_gradient_opts go = s->go;
+    bool ran = false;
+    int32_t pa = 0, pb = 0;
+    mcpt_stats gst{};
+    if (antilag) {
+        const size_t gs = go.stratum, nlam = ((H + gs - 1) / gs) * ((W + gs - 1) / gs);
+        if ((rc = mcpt_gradient_phase(go.stratum, s->frame_index, &pa, &pb))) return rc;
+        if (s->has_prev && s->kept_valid) {  // the previous frame's samples again, in the scene as it is now
+            DN_HIP_OK(hipEventRecord(s->ev_al[0], nullptr));
+            if ((rc = mcpt::gradient_rays_enqueue(&P.cam, go.stratum, pa, pb, s->al_ray_o, s->al_ray_d))) return rc;
+            DN_HIP_OK(hipEventRecord(s->ev_al[1], nullptr));
+            DN_HIP_OK(hipMemsetAsync(s->al_raw, 0, 3 * npx * sizeof(double), nullptr));
+            mcpt_render_opts gr = s->base;
+            gr.seed = s->kept_seed;
+            gr.stats_size = sizeof gst;
+            if ((rc = mcpt_render_rays_device(s->scene, &gr, (int32_t)npx, s->al_ray_o, s->al_ray_d, s->al_raw, &gst))) return rc;
+            DN_HIP_OK(hipSetDevice(device));
+            DN_HIP_OK(hipEventRecord(s->ev_al[2], nullptr));
+            if ((rc = mcpt::temporal_gradient_enqueue(&go, W, H, pa, pb, s->al_kept, s->al_raw, s->al_lambda))) return rc;
+            ran = true;
+        } else {
+            DN_HIP_OK(hipMemsetAsync(s->al_lambda, 0, nlam * sizeof(double), nullptr));
+            DN_HIP_OK(hipEventRecord(s->ev_al[2], nullptr));
+        }
+        if ((rc = mcpt::lambda_stats_enqueue(s->al_lambda, nlam, s->al_words))) return rc;
+        DN_HIP_OK(hipEventRecord(s->ev_al[3], nullptr));
+    }
     DN_HIP_OK(hipMemsetAsync(s->raw, 0, 3 * npx * sizeof(double), nullptr));
     mcpt_render_opts ro = s->base;
     ro.seed = seed;
@@ -729,9 +801,10 @@ int mcpt_sequence_frame(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed,
     DN_HIP_OK(hipEventRecord(s->ev[1], nullptr));
     const mcpt::TemporalClampIo io{&s->tc, s->has_prev ? P.fast : nullptr, C.fast, s->shift};
     const bool hp = s->has_prev;
+    const mcpt::TemporalAntilagIo al{&go, s->al_lambda};
     if ((rc = mcpt::temporal_enqueue(&s->tp, hp ? &P.cam : nullptr, W, H, s->raw, &C.g, hp ? &P.g : nullptr, hp ? P.color : nullptr,
                                      hp ? P.moments : nullptr, C.color, C.moments, s->variance, s->opts.clamp ? &io : nullptr,
-                                     motion ? &s->mo : nullptr)))
+                                     motion ? &s->mo : nullptr, antilag ? &al : nullptr)))
         return rc;
     StatsOut* dres = nullptr;
     if ((rc = enqueue_stats(C.moments, s->shift, npx, s->stats_words, &dres))) return rc;
@@ -758,6 +831,11 @@ int mcpt_sequence_frame(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed,
     DN_HIP_OK(hipMemcpyAsync(s->host_stats, dres, sizeof(StatsOut), hipMemcpyDeviceToHost, nullptr));
     if (s->factor) DN_HIP_OK(hipMemcpyAsync(hfall, s->fallbacks, sizeof *hfall, hipMemcpyDeviceToHost, nullptr));
     if (out_rgb8) DN_HIP_OK(hipMemcpyAsync(out_rgb8, s->rgb8, 3 * s->NPX, hipMemcpyDeviceToHost, nullptr));
+    if (antilag) {  // the next frame's gradient pass compares against this frame's raw render
+        s->kept_valid = false;
+        DN_HIP_OK(hipMemcpyAsync(s->al_kept, s->raw, 3 * npx * sizeof(double), hipMemcpyDeviceToDevice, nullptr));
+        DN_HIP_OK(hipMemcpyAsync(s->al_host, s->al_words, 2 * sizeof(double), hipMemcpyDeviceToHost, nullptr));
+    }
     DN_HIP_OK(hipStreamSynchronize(nullptr));
     float ms[4] = {0, 0, 0, 0};
     for (int k = 0; k < 3; k++) DN_HIP_OK(hipEventElapsedTime(&ms[k], s->ev[k], s->ev[k + 1]));
@@ -769,6 +847,19 @@ int mcpt_sequence_frame(mcpt_sequence* s, const mcpt_camera* cam, uint64_t seed,
         s->motion_seconds = mm * 1e-3;
     }
     s->last_motion = motion;
+    if (antilag) {
+        float k0 = 0, k1 = 0;
+        if (ran) DN_HIP_OK(hipEventElapsedTime(&k0, s->ev_al[0], s->ev_al[1]));
+        DN_HIP_OK(hipEventElapsedTime(&k1, s->ev_al[2], s->ev_al[3]));
+        s->al_a = pa, s->al_b = pb;
+        s->al_trace_seconds = ran ? gst.seconds : 0.0;
+        s->al_kernel_seconds = (k0 + k1) * 1e-3;  // without the pass: the reduction alone
+        s->al_mean = s->al_host[0], s->al_max = s->al_host[1];
+        s->kept_seed = seed;
+        s->last_go = go;
+    }
+    s->kept_valid = antilag;
+    s->last_antilag = antilag, s->last_ran = ran;
     if (s->factor) {
         float g = 0, u = 0;
         DN_HIP_OK(hipEventElapsedTime(&g, s->ev[3], s->ev[5]));
@@ -813,6 +904,71 @@ int mcpt_sequence_set_motion(mcpt_sequence* s, int32_t on) {
         s->mo.prev_position = s->motion_mem, s->mo.prev_normal = s->motion_mem + 3 * s->npx;
     }
     s->motion = on != 0;
+    return MCPT_OK;
+}
+
+int mcpt_sequence_set_antilag(mcpt_sequence* s, const mcpt_gradient_opts* g) {
+    if (!s) {
+        set_error("null mcpt_sequence");
+        return MCPT_E_INVALID;
+    }
+    if (s->factor || s->tu) {
+        set_error("mcpt_sequence_set_antilag: anti-lag is not supported in a sequence created by %s (use mcpt_sequence_create)",
+                  s->tu ? "mcpt_sequence_create_temporal_upsampled" : "mcpt_sequence_create_upsampled");
+        return MCPT_E_INVALID;
+    }
+    if (!g) {
+        s->antilag = false;
+        return MCPT_OK;
+    }
+    if ((s->base.flags & MCPT_RENDER_PIXEL_JITTER) || s->base.accel == MCPT_ACCEL_GRID) {
+        set_error("mcpt_sequence_set_antilag: %s is not supported (the gradient samples are traced by mcpt_render_rays, which "
+                  "refuses it)", (s->base.flags & MCPT_RENDER_PIXEL_JITTER) ? "MCPT_RENDER_PIXEL_JITTER" : "MCPT_ACCEL_GRID");
+        return MCPT_E_INVALID;
+    }
+    int rc;
+    if ((rc = mcpt::gradient_check_opts(g))) return rc;
+    if (!s->al_mem.p) {
+        int device;
+        Scratch S;  // restores the caller's device
+        if ((rc = select_device(s->device, S, &device))) return rc;
+        for (auto& e : s->ev_al)
+            if (!e) DN_HIP_OK(hipEventCreate(&e));
+        if (!s->al_host) DN_HIP_OK(hipHostMalloc((void**)&s->al_host, 2 * sizeof(double)));
+        const size_t npx = s->npx;
+        if ((rc = mcpt::ensure(s->al_mem, (13 * npx + mcpt::lambda_stats_words()) * sizeof(double)))) return rc;
+        double* q = (double*)s->al_mem.p;
+        s->al_ray_o = q, s->al_ray_d = q + 3 * npx, s->al_raw = q + 6 * npx, s->al_kept = q + 9 * npx, s->al_lambda = q + 12 * npx;
+        s->al_words = q + 13 * npx;
+    }
+    if (!s->antilag) s->kept_valid = false;  // frames since the switch-off kept nothing
+    s->go = *g;
+    s->go.device = s->device;
+    s->antilag = true;
+    return MCPT_OK;
+}
+
+int mcpt_sequence_antilag_info(mcpt_sequence* s, int32_t* ran, int32_t* a, int32_t* b, double* trace_seconds, double* kernel_seconds,
+                               double* lambda_mean, double* lambda_max) {
+    if (!s) {
+        set_error("null mcpt_sequence");
+        return MCPT_E_INVALID;
+    }
+    if (!s->has_last) {
+        set_error("the sequence holds no frame (none since create, reset or a failed frame)");
+        return MCPT_E_INVALID;
+    }
+    if (!s->last_antilag) {
+        set_error("mcpt_sequence_antilag_info: the last frame ran without anti-lag (mcpt_sequence_set_antilag)");
+        return MCPT_E_INVALID;
+    }
+    if (ran) *ran = s->last_ran ? 1 : 0;
+    if (a) *a = s->al_a;
+    if (b) *b = s->al_b;
+    if (trace_seconds) *trace_seconds = s->al_trace_seconds;
+    if (kernel_seconds) *kernel_seconds = s->al_kernel_seconds;
+    if (lambda_mean) *lambda_mean = s->al_mean;
+    if (lambda_max) *lambda_max = s->al_max;
     return MCPT_OK;
 }
 
@@ -865,6 +1021,7 @@ int mcpt_sequence_reset(mcpt_sequence* s) {
         return MCPT_E_INVALID;
     }
     s->has_prev = s->has_last = false;
+    s->kept_valid = false;
     s->frame_index = 0;
     return MCPT_OK;
 }

@@ -1,6 +1,6 @@
-// Temporal accumulation for gfx950 (mcpt_temporal_accumulate, mcpt_temporal_accumulate_clamped and
-// mcpt_temporal_accumulate_motion, include/mcpt.h states the rules in full) and the host helper mcpt_camera_orbit.  No
-// counterpart in the reference.
+// Temporal accumulation for gfx950 (mcpt_temporal_accumulate, mcpt_temporal_accumulate_clamped,
+// mcpt_temporal_accumulate_motion and mcpt_temporal_accumulate_antilag, include/mcpt.h states the rules in full) and the
+// host helper mcpt_camera_orbit.  No counterpart in the reference.
 //
 //   k_temporal_accumulate  lane per pixel : reproject, gather the four taps of the previous history, blend,
 //                                           and the temporal variance where the history is long enough; the
@@ -16,6 +16,11 @@
 // The <*, true> instantiations (mcpt_temporal_accumulate_motion) take the reprojected point and the normal of the tap tests
 // from the motion AOVs (the surface point's previous position and normal) instead of the current guides: three
 // substitutions, two more pointers in TpParams, 6 doubles more read per pixel; everything else is the same code.
+//
+// The <*, *, true> instantiations (mcpt_temporal_accumulate_antilag) read one double more per pixel with a history -- the
+// Lambda of the stratum its source falls in (temporal_gradient.hip writes that map) -- and raise the blend weights by
+// it: one pointer and two ints more in TpParams.  The <*, *, false> instantiations are the code they were (DESIGN.md
+// 4.25 compares their resource usage).
 //
 // Everything is fp64 with -ffp-contract=off, so a numpy restatement of the rule reproduces the output to
 // rounding (tests/test_temporal.py).  A block is 64 x 4 pixels as in denoise.hip: the centre's loads and the
@@ -56,11 +61,14 @@ struct TpParams {
     double *outF, *outS;  // outS: k_temporal_accumulate<true> leaves "has a history" (1 or 0), k_temporal_clamp the shift
     // the motion call only: the previous position and normal of every pixel's surface point
     const double *mX, *mN;
+    // the anti-lag call only: the hs x ws map of Lambda, its stratum and its row length
+    const double* lam;
+    int stratum, lam_ws;
 };
 
 __device__ inline bool temporal_variance_applies(const TpParams& P, double n, double g) { return n > P.var_n && g < 1.0; }
 
-template <bool FAST, bool MOTION>
+template <bool FAST, bool MOTION, bool ANTILAG>
 __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
     const int x = blockIdx.x * kBx + threadIdx.x, y = blockIdx.y * kBy + threadIdx.y;
     if (x >= P.W || y >= P.H) return;
@@ -71,6 +79,7 @@ __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
     double wsum = 0.0, h0 = 0.0, h1 = 0.0, h2 = 0.0, m1 = 0.0, m2 = 0.0, hn = 0.0, hg = 0.0;
     double f0 = 0.0, f1 = 0.0, f2 = 0.0;  // FAST: the fast history's gather
     bool source = false;
+    double lam = 0.0;  // ANTILAG: the source stratum's Lambda, clamped to [0, 1]
     if (P.has_prev && depth > 0) {
         // MOTION: the source and the taps' normal and plane tests take the point where it was a frame ago
         const double* pn = MOTION ? P.mN : P.N;
@@ -89,6 +98,11 @@ __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
                 const int i0 = (int)fi, j0 = (int)fj;
                 const double fy = ys - fi, fx = xs - fj;
                 const double plane = P.plane_max * depth;
+                if (ANTILAG) {  // the stratum of the nearest previous pixel
+                    const int li = min(max((int)floor(ys + 0.5), 0), P.H - 1), lj = min(max((int)floor(xs + 0.5), 0), P.W - 1);
+                    const double L = P.lam[(size_t)(li / P.stratum) * P.lam_ws + lj / P.stratum];
+                    lam = L > 0 ? (L < 1 ? L : 1.0) : 0.0;
+                }
 #pragma unroll
                 for (int t = 0; t < 4; t++) {
                     const int di = t >> 1, dj = t & 1, qi = i0 + di, qj = j0 + dj;
@@ -119,9 +133,15 @@ __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
     }
     double o0 = c0, o1 = c1, o2 = c2, om1 = l, om2 = l * l, on = 1.0, og = 1.0;
     const bool history = source && wsum >= P.min_weight;
+    double nb = 1.0;  // the history length the blend weights are taken from (ANTILAG: on is then n_out)
     if (history) {
-        on = fmin(hn / wsum + 1.0, P.max_history);
-        const double A = fmax(P.alpha, 1.0 / on), B = 1.0 - A;
+        nb = on = fmin(hn / wsum + 1.0, P.max_history);
+        double A = fmax(P.alpha, 1.0 / on);
+        if (ANTILAG) {
+            A = A + lam * (1.0 - A);
+            on = (1.0 - lam) * nb + lam;
+        }
+        const double B = 1.0 - A;
         o0 = B * (h0 / wsum) + A * c0;
         o1 = B * (h1 / wsum) + A * c1;
         o2 = B * (h2 / wsum) + A * c2;
@@ -134,7 +154,9 @@ __global__ __launch_bounds__(kBx* kBy) void k_temporal_accumulate(TpParams P) {
     if (FAST) {  // the variance waits for the clamped colour and the corrected moments (k_temporal_clamp)
         double F0 = c0, F1 = c1, F2 = c2;
         if (history) {
-            const double A = fmax(P.alpha_fast, 1.0 / on), B = 1.0 - A;
+            double A = fmax(P.alpha_fast, 1.0 / nb);
+            if (ANTILAG) A = A + lam * (1.0 - A);
+            const double B = 1.0 - A;
             F0 = B * (f0 / wsum) + A * c0;
             F1 = B * (f1 / wsum) + A * c1;
             F2 = B * (f2 / wsum) + A * c2;
@@ -231,6 +253,12 @@ struct ClampArgs {
     double *outf, *outs;
 };
 
+// the anti-lag call's extra arguments (g == nullptr: every other call)
+struct AntilagArgs {
+    const mcpt_gradient_opts* g;
+    const double* lam;
+};
+
 // the option structs' checks (c is looked at only when clamped); mcpt::temporal_check_opts is this function
 int check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* c, bool clamped) {
     if (!o) {
@@ -303,9 +331,17 @@ int check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* c, b
 int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* color, const mcpt_aov_buffers* g,
                const mcpt_aov_buffers* pg, const double* pcol, const double* pmom, const double* out, const double* outm,
                const double* outv, bool* has_prev, bool clamped = false, const ClampArgs& ca = ClampArgs{},
-               bool with_motion = false, const mcpt_motion_buffers* mo = nullptr) {
+               bool with_motion = false, const mcpt_motion_buffers* mo = nullptr, bool antilag = false,
+               const AntilagArgs& al = AntilagArgs{}) {
     int orc;
     if ((orc = check_opts(o, ca.clamp, clamped))) return orc;
+    if (antilag) {
+        if (!al.g || !al.lam) {
+            set_error("null argument: %s", !al.g ? "gradient" : "lambda");
+            return MCPT_E_INVALID;
+        }
+        if ((orc = mcpt::gradient_check_opts(al.g))) return orc;
+    }
     if (W < 1 || H < 1 || (long long)W * H > (1ll << 28)) {
         set_error("invalid frame size: width %d, height %d", W, H);
         return MCPT_E_INVALID;
@@ -356,6 +392,7 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
     }
     // an output overlapping an input would be read by other pixels after it is written
     const size_t npx = (size_t)W * H;
+    const size_t nlam = antilag ? (size_t)((H + al.g->stratum - 1) / al.g->stratum) * ((W + al.g->stratum - 1) / al.g->stratum) : 0;
     const Range ins[] = {{"color", color, 3 * npx},
                          {"guides.albedo", g->albedo, 3 * npx},
                          {"guides.normal", g->normal, 3 * npx},
@@ -368,7 +405,8 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
                          {"prev_moments", pmom, 4 * npx},
                          {"prev_fast", ca.pfast, 3 * npx},
                          {"motion.prev_position", with_motion ? mo->prev_position : nullptr, 3 * npx},
-                         {"motion.prev_normal", with_motion ? mo->prev_normal : nullptr, 3 * npx}},
+                         {"motion.prev_normal", with_motion ? mo->prev_normal : nullptr, 3 * npx},
+                         {"lambda", antilag ? al.lam : nullptr, nlam}},
                 outs[] = {{"out_color", out, 3 * npx}, {"out_moments", outm, 4 * npx}, {"out_variance", outv, npx},
                           {"out_fast", ca.outf, 3 * npx}, {"out_shift", ca.outs, npx}};  // NULL: overlaps nothing
     for (const auto& w : outs)
@@ -391,7 +429,7 @@ int check_call(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H,
 // mo (the motion call): its two device arrays
 int enqueue_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* dC, const mcpt_aov_buffers* g,
                        const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut, double* dOutM,
-                       double* dOutV, const ClampArgs* ca, const mcpt_motion_buffers* mo = nullptr) {
+                       double* dOutV, const ClampArgs* ca, const mcpt_motion_buffers* mo = nullptr, const AntilagArgs* al = nullptr) {
     TpParams P{};
     P.W = W, P.H = H;
     P.has_prev = pc != nullptr;
@@ -414,14 +452,23 @@ int enqueue_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W
     const DnParams D{W, H, 0.0, o->sigma_normal, o->sigma_plane, o->sigma_albedo, g->albedo, g->normal, g->position, g->depth};
     const dim3 grid((W + kBx - 1) / kBx, (H + kBy - 1) / kBy), block(kBx, kBy);
     if (mo) P.mX = mo->prev_position, P.mN = mo->prev_normal;
+    if (al) P.lam = al->lam, P.stratum = al->g->stratum, P.lam_ws = (W + al->g->stratum - 1) / al->g->stratum;
     if (ca) {
-        if (mo) hipLaunchKernelGGL((k_temporal_accumulate<true, true>), grid, block, 0, nullptr, P);
-        else hipLaunchKernelGGL((k_temporal_accumulate<true, false>), grid, block, 0, nullptr, P);
+        if (al) {
+            if (mo) hipLaunchKernelGGL((k_temporal_accumulate<true, true, true>), grid, block, 0, nullptr, P);
+            else hipLaunchKernelGGL((k_temporal_accumulate<true, false, true>), grid, block, 0, nullptr, P);
+        } else {
+            if (mo) hipLaunchKernelGGL((k_temporal_accumulate<true, true, false>), grid, block, 0, nullptr, P);
+            else hipLaunchKernelGGL((k_temporal_accumulate<true, false, false>), grid, block, 0, nullptr, P);
+        }
         DN_HIP_OK(hipGetLastError());
         if (P.has_prev) hipLaunchKernelGGL(k_temporal_clamp, grid, block, 0, nullptr, P);  // else no pixel has a history
+    } else if (al) {
+        if (mo) hipLaunchKernelGGL((k_temporal_accumulate<false, true, true>), grid, block, 0, nullptr, P);
+        else hipLaunchKernelGGL((k_temporal_accumulate<false, false, true>), grid, block, 0, nullptr, P);
     } else {
-        if (mo) hipLaunchKernelGGL((k_temporal_accumulate<false, true>), grid, block, 0, nullptr, P);
-        else hipLaunchKernelGGL((k_temporal_accumulate<false, false>), grid, block, 0, nullptr, P);
+        if (mo) hipLaunchKernelGGL((k_temporal_accumulate<false, true, false>), grid, block, 0, nullptr, P);
+        else hipLaunchKernelGGL((k_temporal_accumulate<false, false, false>), grid, block, 0, nullptr, P);
     }
     DN_HIP_OK(hipGetLastError());
     if (dOutV) {
@@ -434,12 +481,13 @@ int enqueue_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W
 // the same, timed with two events and waited for
 int run_accumulate(const mcpt_temporal_opts* o, const mcpt_camera* pc, int W, int H, const double* dC, const mcpt_aov_buffers* g,
                    const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut, double* dOutM,
-                   double* dOutV, Scratch& S, double* seconds, const ClampArgs* ca = nullptr, const mcpt_motion_buffers* mo = nullptr) {
+                   double* dOutV, Scratch& S, double* seconds, const ClampArgs* ca = nullptr, const mcpt_motion_buffers* mo = nullptr,
+                   const AntilagArgs* al = nullptr) {
     int rc;
     DN_HIP_OK(hipEventCreate(&S.e0));
     DN_HIP_OK(hipEventCreate(&S.e1));
     DN_HIP_OK(hipEventRecord(S.e0, nullptr));
-    if ((rc = enqueue_accumulate(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, ca, mo))) return rc;
+    if ((rc = enqueue_accumulate(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, ca, mo, al))) return rc;
     DN_HIP_OK(hipEventRecord(S.e1, nullptr));
     DN_HIP_OK(hipEventSynchronize(S.e1));
     float ms = 0;
@@ -459,17 +507,21 @@ int temporal_check_opts(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_o
 
 int temporal_enqueue(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* dC,
                      const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM, double* dOut,
-                     double* dOutM, double* dOutV, const TemporalClampIo* io, const mcpt_motion_buffers* motion) {
+                     double* dOutM, double* dOutV, const TemporalClampIo* io, const mcpt_motion_buffers* motion,
+                     const TemporalAntilagIo* antilag) {
     int rc;
     bool has_prev = false;
     const ClampArgs ca = io ? ClampArgs{io->clamp, io->prev_fast, io->out_fast, io->out_shift} : ClampArgs{};
-    if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev, io != nullptr, ca, motion != nullptr, motion)))
+    const AntilagArgs al = antilag ? AntilagArgs{antilag->gradient, antilag->lambda} : AntilagArgs{};
+    if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev, io != nullptr, ca, motion != nullptr, motion,
+                         antilag != nullptr, al)))
         return rc;
     if (io && !io->out_shift) {  // the kernels pass "has a history" through it: the caller's scratch
         set_error("null argument: out_shift (required by the caller-owned form)");
         return MCPT_E_INVALID;
     }
-    return enqueue_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, io ? &ca : nullptr, motion);
+    return enqueue_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, io ? &ca : nullptr, motion,
+                              antilag ? &al : nullptr);
 }
 
 int temporal_spatial_enqueue(const mcpt_temporal_opts* o, int32_t W, int32_t H, const mcpt_aov_buffers* g, const double* dOutC,
@@ -509,11 +561,11 @@ void mcpt_temporal_opts_init(mcpt_temporal_opts* o) {
 static int accumulate_device(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* dC,
                              const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* dpC, const double* dpM,
                              double* dOut, double* dOutM, double* dOutV, double* seconds, const ClampArgs* ca,
-                             bool with_motion = false, const mcpt_motion_buffers* mo = nullptr) {
+                             bool with_motion = false, const mcpt_motion_buffers* mo = nullptr, const AntilagArgs* al = nullptr) {
     int rc;
     bool has_prev = false;
     if ((rc = check_call(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, &has_prev, ca != nullptr, ca ? *ca : ClampArgs{},
-                         with_motion, mo)))
+                         with_motion, mo, al != nullptr, al ? *al : AntilagArgs{})))
         return rc;
     Scratch S;
     int device;
@@ -534,6 +586,7 @@ static int accumulate_device(const mcpt_temporal_opts* o, const mcpt_camera* pc,
     if (with_motion && ((rc = check_device_array(mo->prev_position, device, "dev_motion.prev_position")) ||
                         (rc = check_device_array(mo->prev_normal, device, "dev_motion.prev_normal"))))
         return rc;
+    if (al && (rc = check_device_array(al->lam, device, "dev_lambda"))) return rc;
     ClampArgs dca{};
     if (ca) {
         if ((rc = check_device_array(ca->outf, device, "dev_out_fast")) ||
@@ -549,26 +602,29 @@ static int accumulate_device(const mcpt_temporal_opts* o, const mcpt_camera* pc,
     // the caller's arrays may still be written by work on other streams (e.g. torch's)
     DN_HIP_OK(hipDeviceSynchronize());
     return run_accumulate(o, has_prev ? pc : nullptr, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, S, seconds, ca ? &dca : nullptr,
-                          with_motion ? mo : nullptr);
+                          with_motion ? mo : nullptr, al);
 }
 
 // the host forms
 static int accumulate_host(const mcpt_temporal_opts* o, const mcpt_camera* pc, int32_t W, int32_t H, const double* color,
                            const mcpt_aov_buffers* g, const mcpt_aov_buffers* pg, const double* pcol, const double* pmom,
                            double* out, double* outm, double* outv, double* seconds, const ClampArgs* ca,
-                           bool with_motion = false, const mcpt_motion_buffers* mo = nullptr) {
+                           bool with_motion = false, const mcpt_motion_buffers* mo = nullptr, const AntilagArgs* al = nullptr) {
     int rc;
     bool has_prev = false;
     if ((rc = check_call(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, &has_prev, ca != nullptr, ca ? *ca : ClampArgs{},
-                         with_motion, mo)))
+                         with_motion, mo, al != nullptr, al ? *al : AntilagArgs{})))
         return rc;
     Scratch S;
     int device;
     if ((rc = select_device(o->device, S, &device))) return rc;
     const size_t npx = (size_t)W * H, B = sizeof(double);
     // colour 3, guides 3 + 3 + 3 + 1, out colour 3, moments 4, variance 1, then the previous state 3 + 3 + 1 + 3 + 4,
-    // then the clamped call's fast history 3, shift 1 and previous fast history 3, then the motion call's two maps 3 + 3
-    DN_HIP_OK(hipMalloc(&S.p, ((has_prev ? 35 : 21) + (ca ? 7 : 0) + (with_motion ? 6 : 0)) * npx * B));
+    // then the clamped call's fast history 3, shift 1 and previous fast history 3, then the motion call's two maps 3 + 3,
+    // then the anti-lag call's Lambda (hs * ws)
+    const size_t nlam = al ? (size_t)((H + al->g->stratum - 1) / al->g->stratum) * ((W + al->g->stratum - 1) / al->g->stratum) : 0;
+    const size_t nfix = ((has_prev ? 35 : 21) + (ca ? 7 : 0) + (with_motion ? 6 : 0)) * npx;
+    DN_HIP_OK(hipMalloc(&S.p, (nfix + nlam) * B));
     double* dC = S.p;
     const mcpt_aov_buffers dg{dC + 3 * npx, dC + 6 * npx, dC + 9 * npx, dC + 12 * npx};
     double* dOut = dC + 13 * npx;
@@ -606,8 +662,13 @@ static int accumulate_host(const mcpt_temporal_opts* o, const mcpt_camera* pc, i
         DN_HIP_OK(hipMemcpy(dmo.prev_position, mo->prev_position, 3 * npx * B, hipMemcpyHostToDevice));
         DN_HIP_OK(hipMemcpy(dmo.prev_normal, mo->prev_normal, 3 * npx * B, hipMemcpyHostToDevice));
     }
+    AntilagArgs dal{};
+    if (al) {
+        dal.g = al->g, dal.lam = S.p + nfix;
+        DN_HIP_OK(hipMemcpy(S.p + nfix, al->lam, nlam * B, hipMemcpyHostToDevice));
+    }
     if ((rc = run_accumulate(o, has_prev ? pc : nullptr, W, H, dC, &dg, &dpg, dpC, dpM, dOut, dOutM, outv ? dOutV : nullptr, S,
-                             seconds, ca ? &dca : nullptr, with_motion ? &dmo : nullptr)))
+                             seconds, ca ? &dca : nullptr, with_motion ? &dmo : nullptr, al ? &dal : nullptr)))
         return rc;
     if (ca) {
         DN_HIP_OK(hipMemcpy(ca->outf, dca.outf, 3 * npx * B, hipMemcpyDeviceToHost));
@@ -687,6 +748,35 @@ int mcpt_temporal_accumulate_motion(const mcpt_temporal_opts* o, const mcpt_temp
     if ((rc = motion_clamp_args(clamp, pfast, outf, outs))) return rc;
     const ClampArgs ca{clamp, pfast, outf, outs};
     return accumulate_host(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, seconds, clamp ? &ca : nullptr, true, mo);
+}
+
+// the anti-lag call: the motion call's arguments (motion may be NULL) and the Lambda map
+int mcpt_temporal_accumulate_antilag_device(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, const mcpt_camera* pc,
+                                            int32_t W, int32_t H, const double* dC, const mcpt_aov_buffers* g,
+                                            const mcpt_motion_buffers* mo, const mcpt_aov_buffers* pg, const double* dpC,
+                                            const double* dpM, const double* dpF, double* dOut, double* dOutM, double* dOutF,
+                                            double* dOutS, double* dOutV, double* seconds, const mcpt_gradient_opts* gradient,
+                                            const double* dLambda) {
+    int rc;
+    if ((rc = motion_clamp_args(clamp, dpF, dOutF, dOutS))) return rc;
+    const ClampArgs ca{clamp, dpF, dOutF, dOutS};
+    const AntilagArgs al{gradient, dLambda};
+    return accumulate_device(o, pc, W, H, dC, g, pg, dpC, dpM, dOut, dOutM, dOutV, seconds, clamp ? &ca : nullptr, mo != nullptr, mo,
+                             &al);
+}
+
+int mcpt_temporal_accumulate_antilag(const mcpt_temporal_opts* o, const mcpt_temporal_clamp_opts* clamp, const mcpt_camera* pc,
+                                     int32_t W, int32_t H, const double* color, const mcpt_aov_buffers* g,
+                                     const mcpt_motion_buffers* mo, const mcpt_aov_buffers* pg, const double* pcol,
+                                     const double* pmom, const double* pfast, double* out, double* outm, double* outf,
+                                     double* outs, double* outv, double* seconds, const mcpt_gradient_opts* gradient,
+                                     const double* lambda) {
+    int rc;
+    if ((rc = motion_clamp_args(clamp, pfast, outf, outs))) return rc;
+    const ClampArgs ca{clamp, pfast, outf, outs};
+    const AntilagArgs al{gradient, lambda};
+    return accumulate_host(o, pc, W, H, color, g, pg, pcol, pmom, out, outm, outv, seconds, clamp ? &ca : nullptr, mo != nullptr, mo,
+                           &al);
 }
 
 int mcpt_camera_orbit(const mcpt_camera* in, double degrees, mcpt_camera* out) {
