@@ -300,9 +300,13 @@ int mcpt_scene_camera(const mcpt_scene* scene, mcpt_camera* cam);
  * kernels, level by level; no rebuild, no light-table upload, no new buffers.  The call takes the scene's lock (one
  * render or update at a time per handle); with a communicator every rank must make the same update call.
  *
- * The arena: the scene keeps the bounding box and the box margin (1e-5 of the largest axis extent `ext` + 1e-6) of its
- * build; positions must stay inside that box grown by `ext` on every side, which keeps the traversals' fp32 plane
- * arithmetic inside the margin.
+ * The arena: the scene keeps the bounding box and the box margin of its build; positions must stay inside that box
+ * grown by its largest axis extent `ext` on every side.  The margin is 1e-5 * ext + 1e-6 + 3 * 2^-24 * C, C the largest
+ * |coordinate| of the ARENA (not of the positions at build time): the last term covers the rounding of the traversals'
+ * fp32 slab arithmetic, which grows with the coordinates and not with the extent.  The rule for
+ * edited scenes follows: a refit (update, transform, moved lights) and a rebuild use the build's margin unchanged, and
+ * it is valid for every position they can be given, because a position outside the arena is refused.  To move a scene
+ * farther than its arena, create it at the new place.
  *
  * Refused with MCPT_E_INVALID and a message, before anything on the host or on any device is modified: a NULL scene
  * or NULL positions; count < 1, first < 0 or first + count > nfacets; a stats struct_size mismatch; a facet of the

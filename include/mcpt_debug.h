@@ -119,6 +119,11 @@ int mcpt_debug_bvh4_check_device(mcpt_scene* scene, int32_t device, int64_t out[
 // than the tree has is MCPT_E_INVALID).  Lets a test compare the nodes before and after an update.
 int mcpt_debug_bvh4_download(mcpt_scene* scene, int32_t device, int64_t counts[2], void* nodes, void* qnodes,
                              int32_t* leaf_facets, int64_t cap_nodes, int64_t cap_slots);
+// The trees mcpt_debug_bvh4_check walks, handed out: the host's 4-wide tree (collapse_bvh4 of the binary tree, or of
+// the light-only one) and its quantised form (quantize_bvh4), in mcpt_debug_bvh4_download's layout and with its
+// capacity rules.  Needs no device.  Lets a CPU test model the traversals' box tests on the very boxes a device gets.
+int mcpt_debug_bvh4_host(mcpt_scene* scene, int32_t light_only, int64_t counts[2], void* nodes, void* qnodes,
+                         int32_t* leaf_facets, int64_t cap_nodes, int64_t cap_slots);
 // mcpt_debug_bvh4_check_device's walk over the LIGHT-ONLY tree `device` holds (its nodes, quantized nodes and leaf
 // slots against the host positions; a leaf slot's vertices that differ from the host's count as errors).  The check of
 // the light tree's device-side refit (mcpt_scene_set_lights_movable, include/mcpt.h).

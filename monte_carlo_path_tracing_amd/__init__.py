@@ -273,7 +273,8 @@ DEBUG_EXPORTS = ["mcpt_debug_bvh4_check_device_light", "mcpt_debug_light_tables"
                  "mcpt_debug_set_collective_lib", "mcpt_debug_bvh8_check", "mcpt_debug_bvh4_check",
                  "mcpt_debug_adaptive_active", "mcpt_debug_bvh4_check_device", "mcpt_debug_bvh4_download",
                  "mcpt_debug_set_pick_table", "mcpt_debug_root_picks", "mcpt_debug_set_rebuild_leaf_max",
-                 "mcpt_debug_phong", "mcpt_debug_device_bytes_live", "mcpt_debug_prep_pick_counts"]  # include/mcpt_debug.h
+                 "mcpt_debug_phong", "mcpt_debug_device_bytes_live", "mcpt_debug_prep_pick_counts",
+                 "mcpt_debug_bvh4_host"]  # include/mcpt_debug.h
 
 
 def lib():
@@ -454,6 +455,7 @@ def lib():
                "mcpt_debug_set_rebuild_leaf_max": [I],
                "mcpt_debug_root_picks": [P, C.POINTER(Camera), C.POINTER(RenderOpts), ip, dp, ip],
                "mcpt_debug_bvh4_download": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C"), P, P, P, C.c_int64, C.c_int64],
+               "mcpt_debug_bvh4_host": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C"), P, P, P, C.c_int64, C.c_int64],
                "mcpt_debug_bvh4_check_device_light": [P, I, np.ctypeslib.ndpointer(np.int64, flags="C")],
                "mcpt_debug_light_tables": [P, I, C.c_char_p, P, C.c_int64, C.POINTER(C.c_int64)],
                "mcpt_debug_light_area_cum_bench": [P, I, I, C.POINTER(D)],
@@ -1877,6 +1879,19 @@ def debug_bvh4_download(scene, device=-1):
     _check(lib().mcpt_debug_bvh4_download(scene.h, int(device), counts, nodes.ctypes.data_as(C.c_void_p),
                                           qn.ctypes.data_as(C.c_void_p), lf.ctypes.data_as(C.c_void_p), nodes.shape[0],
                                           lf.shape[0]))
+    return nodes, qn, lf[:int(counts[1])]
+
+
+def debug_bvh4_host(scene, light_only=False):
+    """Diagnostics (host only, no GPU): the 4-wide tree debug_bvh4_check walks and its quantised form, in
+    debug_bvh4_download's layout: (nodes [BVH4_NODE], quantized nodes [BVH4_QNODE], facet of every leaf slot)."""
+    counts = np.zeros(2, np.int64)
+    lo = 1 if light_only else 0
+    _check(lib().mcpt_debug_bvh4_host(scene.h, lo, counts, None, None, None, 0, 0))
+    nodes, qn = np.zeros(int(counts[0]), BVH4_NODE), np.zeros(int(counts[0]), BVH4_QNODE)
+    lf = np.zeros(max(int(counts[1]), 1), np.int32)
+    _check(lib().mcpt_debug_bvh4_host(scene.h, lo, counts, nodes.ctypes.data_as(C.c_void_p), qn.ctypes.data_as(C.c_void_p),
+                                      lf.ctypes.data_as(C.c_void_p), nodes.shape[0], lf.shape[0]))
     return nodes, qn, lf[:int(counts[1])]
 
 

@@ -452,6 +452,14 @@ struct Builder {
 
 }  // namespace
 
+double box_margin(const double lo[3], const double hi[3]) {
+    double ext = 0, cmax = 0;
+    for (int c = 0; c < 3; c++) ext = std::max(ext, hi[c] - lo[c]);  // no facets (lo > hi): 0
+    for (int c = 0; c < 3; c++)
+        if (lo[c] <= hi[c]) cmax = std::max(cmax, std::max(std::fabs(lo[c] - ext), std::fabs(hi[c] + ext)));
+    return 1e-5 * ext + 1e-6 + kBoxMarginUlps * 0x1p-24 * cmax;
+}
+
 Bvh build_bvh(const HostScene& s, const std::vector<int32_t>& facets, int max_leaf) {
     Bvh bvh;
     Builder B;
@@ -469,9 +477,7 @@ Bvh build_bvh(const HostScene& s, const std::vector<int32_t>& facets, int max_le
         for (int c = 0; c < 3; c++) p.c[c] = 0.5 * (p.box.lo[c] + p.box.hi[c]);
         scene.grow(p.box);
     }
-    double ext = 0;
-    for (int c = 0; c < 3; c++) ext = std::max(ext, scene.hi[c] - scene.lo[c]);
-    B.margin = 1e-5 * ext + 1e-6;
+    B.margin = box_margin(scene.lo, scene.hi);
     BvhNode root{};
     for (int k = 0; k < 2; k++) {
         for (int c = 0; c < 3; c++) {
@@ -931,9 +937,7 @@ Bvh8 build_bvh8(const HostScene& s, const Bvh& b) {
     double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
     for (int32_t f : b.leaf_facets)
         for (int k = 0; k < 9; k++) lo[k % 3] = std::min(lo[k % 3], (double)s.pos[9 * (size_t)f + k]), hi[k % 3] = std::max(hi[k % 3], (double)s.pos[9 * (size_t)f + k]);
-    double ext = 0;
-    for (int c = 0; c < 3; c++) ext = std::max(ext, hi[c] - lo[c]);
-    B.margin = 1e-5 * ext + 1e-6;  // Builder::margin of the same facets
+    B.margin = box_margin(lo, hi);  // Builder::margin of the same facets
     B.out.nodes.resize(1);
     if (b.nodes.empty() || b.leaf_facets.empty()) {  // no facets: a root without children
         std::memset(&B.out.nodes[0], 0, sizeof(BvhNode8Q));

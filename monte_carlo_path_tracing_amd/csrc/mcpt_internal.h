@@ -56,6 +56,15 @@ struct Bvh {
 };
 Bvh build_bvh(const HostScene& s, const std::vector<int32_t>& facets, int max_leaf);
 
+// The margin every box of a tree over facets inside [lo, hi] is enlarged by: 1e-5 of the largest
+// axis extent `ext` + 1e-6, plus kBoxMarginUlps * 2^-24 * C for the traversals' fp32 slab arithmetic, whose absolute
+// error grows with the size of the coordinates and not with the scene's extent.  C bounds |coordinate| over the arena
+// of mcpt_scene_update ([lo - ext, hi + ext]), so the one value holds for every position an update, a transform, a
+// refit or a rebuild can put into the tree.  The only place the formula lives: both host builders, the scene's refit
+// margin (host and k_refit_level) and the rebuild use it.
+constexpr double kBoxMarginUlps = 3.0;
+double box_margin(const double lo[3], const double hi[3]);
+
 // 4-wide node (128 B, two cache lines): the four children's boxes as per-axis float4s, so a
 // node visit is 8 dwordx4 loads and four independent slab tests.  Children as in BvhNode;
 // unused slots hold kBvh4Empty.

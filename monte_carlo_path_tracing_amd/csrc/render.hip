@@ -138,7 +138,8 @@ __device__ inline void load_node(const BvhNode4* nd, float (&lo)[3][4], float (&
 //   t = fma(byte, 2^(ex - 127) * inv, fma(org, inv, -o * inv))
 // -- the same plane (org + byte * scale, quantize_bvh4 rounds it outward) with a few more fp32
 // roundings, each ~1 ulp of |plane - origin| * |inv|, far inside the boxes' 1e-5-of-the-scene
-// margins; 2 VALU per plane (v_cvt_f32_ubyteN + v_fma_f32) plus 2 per axis
+// margins, and the roundings of (float)o, o * inv and the byte decode, ~3 ulp of the COORDINATES, which
+// the margin's third term covers (box_margin); 2 VALU per plane (v_cvt_f32_ubyteN + v_fma_f32) plus 2 per axis
 // The planes come out as near (tn) and far (tf) per axis: the byte arrays are swapped by the sign of
 // the inverse direction (neg[a]), as m = scale * inv carries that sign and fma(q, m, b) is monotone
 // in q -- tn / tf are exactly the fminf / fmaxf of the two slab distances.
@@ -251,7 +252,7 @@ __host__ __device__ inline int tri_filter(float4 a4, float4 b4, float4 c4, const
 //    nodes), so the fp64 triangle tests run with few idle lanes; leaves travel on the stack as
 //    ~((first << kLeafBits) | count) (kLeafBits = 5: SAH leaves hold up to 16 triangles);
 //  * four slab tests per node visit as one FMA per plane (origin * inverse precomputed; the boxes'
-//    conservative margins absorb the extra rounding), hits ordered near-to-far by a 5-comparator
+//    conservative margins absorb the extra rounding: box_margin, derived in DESIGN.md 4.26), hits ordered near-to-far by a 5-comparator
 //    network, the nearest followed and the rest pushed far-first;
 //  * a short LDS stack of kLds entries per lane with a private (scratch) overflow up to kStack;
 //  * every triangle of a hit leaf gets the reference's fp64 Cramer test (Myobj.cpp:165-192) behind
@@ -7033,7 +7034,7 @@ static int finish_scene(HostScene&& hs, mcpt_scene** out) {
         sc->build_hi[i % 3] = std::max(sc->build_hi[i % 3], (double)sc->host.pos[i]);
     }
     for (int c = 0; c < 3; c++) sc->build_ext = std::max(sc->build_ext, sc->build_hi[c] - sc->build_lo[c]);
-    sc->margin = 1e-5 * sc->build_ext + 1e-6;
+    sc->margin = box_margin(sc->build_lo, sc->build_hi);
     *out = sc;
     return MCPT_OK;
 }

@@ -218,8 +218,8 @@ struct mcpt_scene {
     std::vector<int> comm_devices;  // distinct devices of the cached ncclCommInitAll communicators
     std::vector<void*> comms;
     std::mutex mu;
-    // mcpt_scene_update: the build's bounding box, largest axis extent and box margin (Builder::margin) stay the
-    // scene's for good; `updated` once a call succeeded (the 8-wide trees are then stale and refused); the refit
+    // mcpt_scene_update: the build's bounding box, largest axis extent and box margin (box_margin of that box: it
+    // covers every position of the arena) stay the scene's for good; `updated` once a call succeeded (the 8-wide trees are then stale and refused); the refit
     // index of `bvh` and the facet -> leaf-slot map, both built at the first update
     double build_lo[3] = {0, 0, 0}, build_hi[3] = {0, 0, 0}, build_ext = 0, margin = 0;
     bool updated = false;

@@ -303,6 +303,32 @@ int mcpt_debug_bvh4_download(mcpt_scene* sc, int32_t device, int64_t* counts, vo
     return MCPT_OK;
 }
 
+int mcpt_debug_bvh4_host(mcpt_scene* sc, int32_t light_only, int64_t* counts, void* nodes, void* qnodes, int32_t* leaf_facets,
+                         int64_t cap_nodes, int64_t cap_slots) {
+    if (!sc || !counts) {
+        set_error("invalid argument");
+        return MCPT_E_INVALID;
+    }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    if (int rs = host_sync(sc)) return rs;
+    const Bvh& bb = light_only ? sc->lbvh : sc->bvh;
+    const std::vector<BvhNode4> b4 = collapse_bvh4(bb);
+    counts[0] = (int64_t)b4.size();
+    counts[1] = (int64_t)bb.leaf_facets.size();
+    if (((nodes || qnodes) && cap_nodes < counts[0]) || (leaf_facets && cap_slots < counts[1])) {
+        set_error("mcpt_debug_bvh4_host: the tree has %lld nodes and %lld leaf slots, more than the buffers hold",
+                  (long long)counts[0], (long long)counts[1]);
+        return MCPT_E_INVALID;
+    }
+    if (nodes) std::memcpy(nodes, b4.data(), b4.size() * sizeof(BvhNode4));
+    if (qnodes) {
+        const std::vector<BvhNode4Q> q4 = quantize_bvh4(b4);
+        std::memcpy(qnodes, q4.data(), q4.size() * sizeof(BvhNode4Q));
+    }
+    if (leaf_facets) std::copy(bb.leaf_facets.begin(), bb.leaf_facets.end(), leaf_facets);
+    return MCPT_OK;
+}
+
 int mcpt_debug_bvh8_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
     if (!sc || !out) {
         set_error("invalid argument");

@@ -297,3 +297,262 @@ def swatch_owners(oscene, cam):
                 owner[i * cam.width + j] = mat[f]
                 xface[i * cam.width + j] = abs(un[f][0]) == 1.0 and un[f][1] == 0.0 and un[f][2] == 0.0
     return owner, xface
+
+
+# ---- traversal stress: a cluster that can sit far from the origin, and the ray families aimed at it ----
+# (tests/test_traversal_stress.py, tests/test_traversal_stress_cpu.py)
+class _ObjExact(gv.Obj):
+    """gv.Obj whose vertices are written with every digit (the float32 the loader makes of them is then the
+    float32 of the double computed here, at any offset and scale)"""
+
+    def write(self, path, mtllib):
+        with open(path, "w", newline="\n") as f:
+            f.write("mtllib %s\n" % mtllib)
+            for p in self.v:
+                f.write("v %.17g %.17g %.17g\n" % p)
+            for n in self.vn:
+                f.write("vn %.9g %.9g %.9g\n" % n)
+            for name, mtl, faces in self.groups:
+                f.write("o %s\nusemtl %s\n" % (name, mtl))
+                for tri in faces:
+                    f.write("f %s\n" % " ".join("%d//%d" % vn for vn in tri))
+
+
+STRESS_LATTICE = 64  # lattice coordinates: multiples of scale / 64
+# facets in file order: (group, number of triangles)
+STRESS_GROUPS = (("random", 1400), ("lattice", 500), ("coincident", 64), ("degenerate", 8), ("anchor", 2), ("floor", 2),
+                 ("light", 2))
+
+
+def stress_ranges():
+    """group -> (first facet, end facet) of ray_stress's scene"""
+    out, at = {}, 0
+    for name, n in STRESS_GROUPS:
+        out[name] = (at, at + n)
+        at += n
+    return out
+
+
+def ray_stress(outdir, offset=(0, 0, 0), scale=1.0, seed=5):
+    """About 2 000 triangles in a box of extent `scale` whose corner sits at offset * scale (offset in extents): a unit
+    cluster u in [0, 1]^3 written at scale * (u + offset).  In file order (STRESS_GROUPS):
+      * 1 400 random triangles, edge lengths log-uniform in 1e-4 .. 1e-1 of the extent;
+      * 250 axis-aligned quads on lattice coordinates (multiples of scale / 64, 1 .. 8 cells wide): shared planes, flat
+        boxes, edges lying on box faces; the quads in x-planes have no diffuse part (the reference's cosine-lobe frame
+        is 0 / 0 for a normal of exactly -e_x);
+      * 32 pairs of coincident triangles: 16 pairs on the lattice (y- and z-planes), 16 of random orientation, the odd
+        pairs' second copy with its vertices rotated (same triangle, another operation order);
+      * 8 zero-area facets: 4 with collinear vertices, 4 with a repeated vertex;
+      * an anchor quad across the bottom of the box (y = 0), a floor just above it (y = 2 / 64) and one light quad (y = 1, 0.6 extents wide, facing down)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    off = np.asarray(offset, np.float64)
+    obj, L = _ObjExact(), STRESS_LATTICE
+
+    def place(u):
+        return tuple(float(x) for x in scale * (np.asarray(u, np.float64) + off))
+
+    def tri(faces, pts, n):
+        ni = obj.normal(tuple(float(x) for x in n))
+        faces.append(tuple((obj.vert(place(p)), ni) for p in pts))
+
+    def geo_normal(p):
+        n = np.cross(np.subtract(p[1], p[0]), np.subtract(p[2], p[0]))
+        l = np.linalg.norm(n)
+        return n / l if l > 0 else np.array([0.0, 1.0, 0.0])
+
+    def random_tri(size):
+        m = 0.02 + size  # the triangle reaches at most `size` from c: it stays inside the unit box
+        c = rng.uniform(m, 1.0 - m, 3)
+        u = rng.normal(size=3)
+        u /= np.linalg.norm(u)
+        w = np.cross(u, rng.normal(size=3))
+        w /= np.linalg.norm(w)
+        return [c - 0.5 * size * u, c + 0.5 * size * u, c + size * (rng.uniform(-0.4, 0.4) * u + rng.uniform(0.3, 0.9) * w)]
+
+    def lattice_pts(axis, p, i, j, w, h):
+        o = [k for k in range(3) if k != axis]
+        pts = []
+        for a, b in ((i, j), (i + w, j), (i + w, j + h), (i, j + h)):
+            q = [0.0, 0.0, 0.0]
+            q[axis], q[o[0]], q[o[1]] = p / L, a / L, b / L
+            pts.append(q)
+        return pts
+
+    groups = {name: [] for name, _ in STRESS_GROUPS}
+    for _ in range(1400):
+        p = random_tri(10.0 ** rng.uniform(-4.0, -1.0))
+        tri(groups["random"], p, geo_normal(p))
+    lat_x, lat_yz = [], []
+    for k in range(250):
+        axis = k % 3
+        w, h = (int(x) for x in rng.choice([1, 2, 4, 8], 2))
+        q = lattice_pts(axis, int(rng.integers(6, L - 5)), int(rng.integers(2, L - 2 - w)), int(rng.integers(2, L - 2 - h)), w, h)
+        n = geo_normal(q[:3])
+        for t in ((q[0], q[1], q[2]), (q[0], q[2], q[3])):
+            tri(lat_x if axis == 0 else lat_yz, t, n)
+    # the loader keeps file order inside a group; x-plane quads come first ("mirror" has no diffuse part)
+    for k in range(32):
+        if k < 16:
+            q = lattice_pts(1 + k % 2, int(rng.integers(6, L - 5)), int(rng.integers(2, L - 12)), int(rng.integers(2, L - 12)),
+                            int(rng.integers(4, 9)), int(rng.integers(4, 9)))
+            p = [q[0], q[1], q[3]]
+        else:
+            p = random_tri(rng.uniform(0.05, 0.2))
+        n = geo_normal(p)
+        tri(groups["coincident"], p, n)
+        tri(groups["coincident"], p[1:] + p[:1] if k % 2 else p, n)
+    for k in range(8):
+        p = random_tri(0.05)
+        p = [p[0], p[1], 0.5 * (np.asarray(p[0]) + p[1])] if k < 4 else [p[0], p[0], p[1]]
+        tri(groups["degenerate"], p, (0.0, 1.0, 0.0))
+    # the floor is not the box's lowest face: the reference's grid loses rays that start on a minimum face of its box
+    # (its "crack"), and with them the oracle's frame; the anchor quad below spans the box and is seen from below only
+    for name, y, a, b in (("anchor", 0.0, 0.0, 1.0), ("floor", 2.0 / L, 1.0 / L, 1.0 - 1.0 / L)):
+        fl = [(a, y, a), (a, y, b), (b, y, b), (b, y, a)]  # (b - a) x (c - a) = +y
+        for t in ((fl[0], fl[1], fl[2]), (fl[0], fl[2], fl[3])):
+            tri(groups[name], t, (0.0, 1.0, 0.0))
+    lq = [(0.2, 1.0, 0.2), (0.8, 1.0, 0.2), (0.8, 1.0, 0.8), (0.2, 1.0, 0.8)]  # faces the floor
+    for t in ((lq[0], lq[1], lq[2]), (lq[0], lq[2], lq[3])):
+        tri(groups["light"], t, (0.0, -1.0, 0.0))
+    assert len(lat_x) + len(lat_yz) == 500
+    obj.groups.append(("random", "diffuse", groups["random"]))
+    obj.groups.append(("lattice_x", "mirror", lat_x))
+    obj.groups.append(("lattice_yz", "glossy", lat_yz))
+    for name in ("coincident", "degenerate", "anchor", "floor"):
+        obj.groups.append((name, "diffuse", groups[name]))
+    obj.groups.append(("light", "lamp", groups["light"]))
+    mtls = [("diffuse", (0.5, 0.5, 0.5), (0.0, 0.0, 0.0), 1.0), ("mirror", (0.0, 0.0, 0.0), (0.5, 0.5, 0.5), 50.0),
+            ("glossy", (0.1, 0.1, 0.1), (0.4, 0.4, 0.4), 50.0), ("lamp", (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.0)]
+    cam = (place((0.5, 0.95, 3.0)), place((0.5, 0.2, 0.5)))
+    # from 2.6 extents in front of the box, looking down at the floor through the cluster
+    return _write(outdir, "stress", obj, mtls, [("lamp", (40.0, 36.0, 30.0))], cam, "60.0")
+
+
+STRESS_FAMILIES = ("aimed", "secondary", "axis", "far", "scaled")
+STRESS_RAYS = 4096 + 37  # a partial block
+
+
+def stress_rays(arrays, family, seed=11):
+    """(origins, directions, excluded facet) of one ray family over the arrays of a loaded ray_stress scene (the
+    float32 positions the library holds: targets are points of THOSE triangles, computed in double):
+      aimed      at vertices, edge points and interior points, and points a relative 1e-15 / 1e-12 / 1e-9 off them,
+                 from origins inside the box 0.05 extents from the target;
+      secondary  origins on a facet (excluded), directions cosine-distributed about either side's normal -- and, for
+                 every other ray, aimed at another facet's vertex / edge / interior point as a shadow ray is;
+      axis       one or two direction components exactly 0.0 or -0.0, every origin coordinate a lattice coordinate,
+                 along lattice lines and inside lattice planes, at lattice vertices, edge and interior points;
+      far        the aimed targets from 1e2 and 1e4 extents outside the box;
+      scaled     the aimed rays with the direction multiplied by 1e-3 (first half) and 1e3 (second half).
+    The last ray of every family has a NaN direction."""
+    import numpy as np
+    rng = np.random.default_rng(seed + (0 if family == "scaled" else STRESS_FAMILIES.index(family)))
+    n, R = STRESS_RAYS, stress_ranges()
+    P = arrays["positions"].astype(np.float64).reshape(-1, 3, 3)
+    lo, hi = P.reshape(-1, 3).min(axis=0), P.reshape(-1, 3).max(axis=0)
+    ext = float((hi - lo).max())
+    cr = np.linalg.norm(np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0]), axis=1)
+    hittable = cr >= 4e-8  # |detA| = |ab x ac| cos >= 1e-8 from most directions of a unit ray
+
+    def ids(name, only=hittable):
+        a, b = R[name]
+        f = np.arange(a, b)
+        return f[only[a:b]]
+
+    rand_ok, lat, coin = ids("random"), ids("lattice"), ids("coincident")
+    if len(rand_ok) < 50:
+        rand_ok = lat
+
+    def pick_tris(m, p_coin=0.08, lattice_only=False):
+        u = rng.random(m)
+        t = rand_ok[rng.integers(0, len(rand_ok), m)]
+        t = np.where(u < 0.35, lat[rng.integers(0, len(lat), m)], t)
+        if lattice_only:
+            lc = coin[coin < R["coincident"][0] + 32]
+            t = lat[rng.integers(0, len(lat), m)]
+            return np.where(u < p_coin, lc[rng.integers(0, len(lc), m)], t)
+        t = np.where(u < p_coin, coin[rng.integers(0, len(coin), m)], t)
+        return np.where(u > 0.97, rng.integers(R["floor"][0], R["light"][1], m), t)
+
+    def targets(tri, perturb=True, eps=(0.0, 0.0, 1e-15, -1e-15, 1e-12, -1e-12, 1e-9, -1e-9)):
+        m = len(tri)
+        kind = rng.integers(0, 3, m)
+        w = rng.random((m, 3))
+        w[kind == 0] = np.eye(3)[rng.integers(0, 3, int((kind == 0).sum()))]  # a vertex
+        e = rng.integers(0, 3, m)
+        w[kind == 1, e[kind == 1]] = 0.0  # a point on an edge
+        if not perturb:  # lattice points: edge midpoints, the middle of the hypotenuse's neighbourhood
+            w[kind == 1] = np.where(w[kind == 1] > 0, 0.5, 0.0)
+            w[kind == 2] = np.array([0.5, 0.25, 0.25])
+        w /= w.sum(axis=1, keepdims=True)
+        tg = np.einsum("nk,nkc->nc", w, P[tri])
+        if perturb:
+            tg *= 1.0 + rng.choice(eps, (m, 1))
+        return tg
+
+    def unit(v):
+        return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+    def aimed(m, dist, inside):
+        tri = pick_tris(m)
+        tg = targets(tri)
+        d = unit(rng.normal(size=(m, 3)))
+        ro = tg + dist * ext * d
+        if inside:  # keep the origin inside the box: mirror the components that leave it
+            out = (ro < lo) | (ro > hi)
+            ro = np.where(out, tg - dist * ext * d, ro)
+            ro = np.clip(ro, lo, hi)
+        return ro, unit(tg - ro), np.where(rng.random(m) < 0.1, tri, -1)
+
+    if family in ("aimed", "scaled"):
+        ro, rd, ex = aimed(n, 0.05, True)
+        if family == "scaled":
+            rd = rd * np.where(np.arange(n) < n // 2, 1e-3, 1e3)[:, None]
+    elif family == "far":
+        ro, rd, ex = aimed(n, np.where(np.arange(n) % 2 == 0, 1e2, 1e4)[:, None], False)
+    elif family == "secondary":
+        src = pick_tris(n, p_coin=0.02)
+        w = rng.dirichlet(np.ones(3), n)
+        ro = np.einsum("nk,nkc->nc", w, P[src])
+        nrm = unit(np.cross(P[src, 1] - P[src, 0], P[src, 2] - P[src, 0])) * rng.choice([-1.0, 1.0], (n, 1))
+        a = unit(np.cross(nrm, unit(rng.normal(size=(n, 3)))))
+        b = np.cross(nrm, a)
+        u1, u2 = rng.random(n), rng.random(n)
+        r, ph = np.sqrt(u1), 2 * np.pi * u2
+        rd = (r * np.cos(ph))[:, None] * a + (r * np.sin(ph))[:, None] * b + np.sqrt(1 - u1)[:, None] * nrm
+        shadow = rng.random(n) < 0.5
+        # the nearest of four candidate targets, so that fewer of these rays end on an occluder
+        cand = np.stack([targets(pick_tris(n, p_coin=0.2), eps=(0.0, 0.0, 0.0, 1e-15, -1e-15, 1e-12, -1e-12)) for _ in range(4)])
+        tg = cand[np.argmin(np.linalg.norm(cand - ro, axis=2), axis=0), np.arange(n)]
+        rd = np.where(shadow[:, None], unit(tg - ro), rd)
+        ex = src
+    elif family == "axis":
+        tri = pick_tris(n, p_coin=0.1, lattice_only=True)
+        tg = targets(tri, perturb=False)
+        V = P[np.concatenate([lat, coin[coin < R["coincident"][0] + 32]])].reshape(-1, 3)  # lattice vertex coordinates
+        other = V[rng.integers(0, len(V), n)]
+        rows = np.arange(n)
+        line = rng.random(n) < 0.5
+        # along a lattice line, at a vertex: the origin is that vertex with one coordinate from another lattice vertex
+        tg[line] = P[tri[line], rng.integers(0, 3, int(line.sum()))]
+        ax = rng.integers(0, 3, n)
+        ro = tg.copy()
+        ro[rows[line], ax[line]] = other[rows[line], ax[line]]
+        same = line & (ro[rows, ax] == tg[rows, ax])
+        ro[rows[same], ax[same]] = V.min(axis=0)[ax[same]]  # the pick was the vertex's own coordinate: the lowest one
+        # inside the facet's lattice plane, at a vertex, an edge midpoint or an interior point: the origin is another
+        # lattice vertex moved into that plane
+        plane = np.argmin(P[tri].max(axis=1) - P[tri].min(axis=1), axis=1)
+        ro[~line] = other[~line]
+        ro[rows[~line], plane[~line]] = P[tri[~line], 0, plane[~line]]
+        d = tg - ro  # exact zeros where the coordinates are equal
+        nz = np.linalg.norm(d, axis=1) > 0
+        d[~nz] = (0.0, -1.0, 0.0)
+        rd = unit(d)
+        rd = np.where((rd == 0) & (rng.random((n, 3)) < 0.5), -0.0, rd)
+        assert ((rd == 0).sum(axis=1) >= 1).all()
+        ex = np.full(n, -1)
+    else:
+        raise ValueError(family)
+    rd[-1] = np.nan
+    return np.ascontiguousarray(ro), np.ascontiguousarray(rd), np.asarray(ex, np.int32)

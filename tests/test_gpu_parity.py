@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, SCENE_OBJ, SCENE_XML
+from bruteforce import brute_force
 import monte_carlo_path_tracing_amd as mcpt
 from monte_carlo_path_tracing_amd import rng
 from oracle import pyoracle as po
@@ -59,33 +60,9 @@ def test_primary_hit_map_vs_reference(scene):
 
 
 def brute_force_hits(scene_arrays, rin, light_only):
-    """Closest hit over ALL facets with the reference's fp64 Cramer rule (Myobj.cpp:165-192)."""
-    P = scene_arrays["positions"].astype(np.float64).reshape(-1, 3, 3)
-    a, b, c = P[:, 0], P[:, 1], P[:, 2]
-    is_light = np.zeros(len(P), bool)
-    is_light[scene_arrays["light_facet"]] = True
-
-    def det(x, y, z):
-        cr = np.stack([x[..., 1] * y[..., 2] - x[..., 2] * y[..., 1], x[..., 2] * y[..., 0] - x[..., 0] * y[..., 2],
-                       x[..., 0] * y[..., 1] - x[..., 1] * y[..., 0]], -1)
-        return ((0 + cr[..., 0] * z[..., 0]) + cr[..., 1] * z[..., 1]) + cr[..., 2] * z[..., 2]
-
-    out = np.full(len(rin), -1)
-    ab, ac = a - b, a - c
-    for r in range(len(rin)):
-        ro, rd, ex = rin[r, :3], np.broadcast_to(rin[r, 3:6], a.shape), int(rin[r, 6])
-        ar = a - ro
-        dA = det(ab, ac, rd)
-        with np.errstate(all="ignore"):
-            be, ga, t = det(ar, ac, rd) / dA, det(ab, ar, rd) / dA, det(ab, ac, ar) / dA
-        ok = (np.abs(dA) >= 1e-8) & ~((be < 0) | (ga < 0) | (be + ga > 1) | (t < 0) | (np.abs(t) < 1e-8))
-        if ex >= 0:
-            ok[ex] = False
-        if light_only:
-            ok &= is_light
-        if ok.any():
-            out[r] = int(np.argmin(np.where(ok, t, np.inf)))
-    return out
+    """Closest hit over ALL facets with the reference's fp64 Cramer rule (Myobj.cpp:165-192): the facets of
+    tests/bruteforce.py's brute_force for rays given as rows (origin, direction, excluded facet)."""
+    return brute_force(scene_arrays, rin[:, :3], rin[:, 3:6], rin[:, 6].astype(np.int64), light_only)[0].astype(np.int64)
 
 
 @pytest.mark.parametrize("light_only,name", [(False, "rays_hit.npy"), (True, "rays_lighthit.npy")])
