@@ -569,6 +569,24 @@ int mcpt_render_rays(mcpt_scene* scene, const mcpt_render_opts* opts, int32_t n,
 /* same with the three arrays in DEVICE memory (coarse-grained, on opts->device; see mcpt_render_device) */
 int mcpt_render_rays_device(mcpt_scene* scene, const mcpt_render_opts* opts, int32_t n, const double* dev_origin,
                             const double* dev_dir, double* dev_out_rgb, mcpt_stats* stats);
+/* The same radiance for a sparse set of a frame's pixels: ray r carries an explicit pixel id index[r].
+ * origin and dir are n*3 doubles read densely, index holds n ids, out_rgb is out_n*3 doubles.  Ray r ADDS
+ * sum_k L_k / spp into out_rgb[3*index[r]..], and sample k of ray r draws the counter-RNG numbers of (seed,
+ * pixel = index[r], sample = k): the n rays of a frame's pixels index[0..n) give those pixels of mcpt_render_rays over
+ * the whole frame, at the cost of n rays.  Nothing else in out_rgb is written.  Duplicate ids are allowed: each entry
+ * adds the same samples again.  A broken ray is a miss as above.  stats->camera_samples = n * (sample_end -
+ * sample_begin).  MCPT_E_INVALID before any device work: everything mcpt_render_rays refuses, a NULL index, out_n < 1
+ * or out_n > 2^28, and an id outside [0, out_n) (the message names the first such entry). */
+int mcpt_render_rays_indexed(mcpt_scene* scene, const mcpt_render_opts* opts, int32_t n, const int32_t* index,
+                             const double* origin, const double* dir, int32_t out_n, double* out_rgb, mcpt_stats* stats);
+/* same with the four arrays in DEVICE memory (coarse-grained, on opts->device; see mcpt_render_device).  The ids cannot
+ * be read before the run: the root kernel bound-checks every id before it forms an address from it, a ray whose id lies
+ * outside [0, out_n) traces nothing and adds nothing, and the call then returns MCPT_E_INVALID AFTER the run, with a
+ * message that says so -- the valid rays' sums have been added, nothing outside the out_n slots has been touched, and
+ * *stats is not written. */
+int mcpt_render_rays_indexed_device(mcpt_scene* scene, const mcpt_render_opts* opts, int32_t n, const int32_t* dev_index,
+                                    const double* dev_origin, const double* dev_dir, int32_t out_n, double* dev_out_rgb,
+                                    mcpt_stats* stats);
 /* The camera's height*width rays for sample index `sample`, row 0 = top image row, to host arrays (height*width*3
  * doubles each): origin = the pulled-back eye, dir = the unit direction through the pixel's centre (jitter = 0;
  * `seed` and `sample` are then unused) or through MCPT_RENDER_PIXEL_JITTER's offset for (seed, pixel, sample)
@@ -939,6 +957,22 @@ int mcpt_gradient_rays(const mcpt_camera* cam, int32_t stratum, int32_t a, int32
 /* same with origin and dir in DEVICE memory on `device` */
 int mcpt_gradient_rays_device(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device,
                               double* dev_origin, double* dev_dir);
+/* Host helper, no device work: the selected pixels of phase (a, b) in a width x height frame, as a list.  With
+ * hs' = a < height ? (height - a + stratum - 1) / stratum : 0 and ws' likewise from b and width (integer division),
+ * *count = hs' * ws' -- which may be 0, as for a 2 x 2 frame at stratum 3 with phase (2, 2) -- and entry r = I * ws' + J
+ * is pixel (stratum I + a) * width + stratum J + b: strictly increasing.  index may be NULL (the count only), else it
+ * takes *count entries.  MCPT_E_INVALID: a NULL count, width or height < 1 or a frame of more than 2^28 pixels, a
+ * stratum outside 1..8, a phase outside [0, stratum). */
+int mcpt_gradient_index(int32_t width, int32_t height, int32_t stratum, int32_t a, int32_t b, int32_t* count, int32_t* index);
+/* The gradient rays of the selected pixels alone, for mcpt_render_rays_indexed: mcpt_gradient_index's count entries of
+ * the index (count int32), the pulled-back eye as origin and the pixel's direction (count*3 doubles each) -- the rays
+ * mcpt_gradient_rays gives the selected pixels, bit for bit (the same device function).  With count == 0 the call
+ * succeeds and writes nothing.  The checks are mcpt_gradient_rays' own, and a NULL index. */
+int mcpt_gradient_rays_indexed(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device, int32_t* index,
+                               double* origin, double* dir);
+/* same with the three arrays in DEVICE memory on `device` */
+int mcpt_gradient_rays_indexed_device(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device,
+                                      int32_t* dev_index, double* dev_origin, double* dev_dir);
 /* Host arrays in, host array out (see `gradient` above).  device_seconds (device time of the kernel, HIP events) may be
  * NULL.  Refused with MCPT_E_INVALID before any device work: a NULL opts, a struct_size mismatch, a stratum, radius or
  * scale out of range, a phase outside [0, stratum), width or height < 1 or a frame of more than 2^28 pixels, a NULL

@@ -16,6 +16,7 @@ import os
 import numpy as np
 
 __all__ = ["Scene", "Camera", "Comm", "render", "render_device", "render_rays", "render_rays_device", "camera_rays", "RENDER_PIXEL_JITTER",
+           "render_rays_indexed", "render_rays_indexed_device", "gradient_index", "gradient_rays_indexed",
            "render_adaptive", "render_adaptive_device", "closest_hit", "light_prep", "primary_hits",
            "AovBuffers", "DenoiseOpts", "render_aovs", "render_aovs_device", "denoise", "denoise_device", "variance_from_noise",
            "TemporalOpts", "TemporalAccumulator", "temporal_accumulate", "temporal_accumulate_device", "camera_orbit",
@@ -243,6 +244,8 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_scene_counts", "mcpt_scene_accel_bytes", "mcpt_scene_arrays", "mcpt_scene_camera", "mcpt_scene_meshing", "mcpt_scene_grid_info",
            "mcpt_render_opts_init", "mcpt_render", "mcpt_render_device",
            "mcpt_render_rays", "mcpt_render_rays_device", "mcpt_camera_rays",
+           "mcpt_render_rays_indexed", "mcpt_render_rays_indexed_device", "mcpt_gradient_index", "mcpt_gradient_rays_indexed",
+           "mcpt_gradient_rays_indexed_device",
            "mcpt_adaptive_opts_init", "mcpt_render_adaptive", "mcpt_render_adaptive_device",
            "mcpt_render_aovs", "mcpt_render_aovs_device", "mcpt_denoise_opts_init", "mcpt_denoise", "mcpt_denoise_device",
            "mcpt_variance_from_noise", "mcpt_temporal_opts_init", "mcpt_temporal_accumulate",
@@ -385,6 +388,12 @@ def lib():
             L.mcpt_render_rays.argtypes = [P, C.POINTER(RenderOpts), I, P, P, P, C.POINTER(Stats)]
             L.mcpt_render_rays_device.argtypes = L.mcpt_render_rays.argtypes
             L.mcpt_camera_rays.argtypes = [C.POINTER(Camera), C.c_uint64, I, I, I, P, P]
+        if hasattr(L, "mcpt_render_rays_indexed"):  # and along rays that carry their pixel ids
+            L.mcpt_render_rays_indexed.argtypes = [P, C.POINTER(RenderOpts), I, P, P, P, I, P, C.POINTER(Stats)]
+            L.mcpt_render_rays_indexed_device.argtypes = L.mcpt_render_rays_indexed.argtypes
+            L.mcpt_gradient_index.argtypes = [I, I, I, I, I, C.POINTER(I), P]
+            L.mcpt_gradient_rays_indexed.argtypes = [C.POINTER(Camera), I, I, I, I, P, P, P]
+            L.mcpt_gradient_rays_indexed_device.argtypes = L.mcpt_gradient_rays_indexed.argtypes
         if hasattr(L, "mcpt_scene_update"):  # and the in-place geometry updates
             L.mcpt_update_stats_init.argtypes = [C.POINTER(UpdateStats)]
             L.mcpt_update_stats_init.restype = None
@@ -829,6 +838,39 @@ def render_rays_device(scene, n, origin_ptr, dir_ptr, spp, dev_ptr, mode="mis", 
     o = _opts(spp, mode, seed, sample_range, device, samples_per_launch, queue_factor, progress, "bvh", flags)
     opt = lambda p: None if p is None else C.c_void_p(int(p))
     _check(lib().mcpt_render_rays_device(scene.h, C.byref(o), int(n), opt(origin_ptr), opt(dir_ptr), opt(dev_ptr), C.byref(st)))
+    return st
+
+
+def render_rays_indexed(scene, index, origin, dir, out_n, spp, mode="mis", seed=DEFAULT_SEED, sample_range=None, out=None,
+                        device=None, samples_per_launch=0, queue_factor=0, progress=None, flags=0):
+    """mcpt_render_rays_indexed (include/mcpt.h): render_rays for a sparse set of a frame's pixels.  index holds n pixel
+    ids in [0, out_n), origin and dir are n x 3.  Returns (out_n x 3 fp64 radiance, Stats): ray r's sum is ADDED into
+    row index[r] of `out` (zeros if None) and nothing else is written; sample k of ray r draws the random numbers of
+    (seed, pixel index[r], sample k).  Duplicate ids add the same samples again.  Single device, BVH only."""
+    index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+    origin, dir = _d(origin, (-1, 3)), _d(dir, (-1, 3))
+    n = index.shape[0]
+    assert origin.shape == (n, 3) and dir.shape == (n, 3)
+    if out is None:
+        out = np.zeros((max(int(out_n), 0), 3))
+    assert out.dtype == np.float64 and out.flags.c_contiguous and out.shape == (max(int(out_n), 0), 3)
+    st = Stats()
+    o = _opts(spp, mode, seed, sample_range, device, samples_per_launch, queue_factor, progress, "bvh", flags)
+    _check(lib().mcpt_render_rays_indexed(scene.h, C.byref(o), n, index.ctypes.data, origin.ctypes.data, dir.ctypes.data,
+                                          int(out_n), out.ctypes.data, C.byref(st)))
+    return out, st
+
+
+def render_rays_indexed_device(scene, n, index_ptr, origin_ptr, dir_ptr, out_n, spp, dev_ptr, mode="mis", seed=DEFAULT_SEED,
+                               sample_range=None, device=None, samples_per_launch=0, queue_factor=0, progress=None, flags=0):
+    """render_rays_indexed over device buffers (n int32 ids, n*3 doubles each of origins and directions, out_n*3 doubles
+    at dev_ptr, e.g. torch CUDA tensors' data_ptr()): the radiance is accumulated into dev_ptr.  An id outside
+    [0, out_n) is found by the kernel: that ray adds nothing and the call raises after the run.  Returns the Stats."""
+    st = Stats()
+    o = _opts(spp, mode, seed, sample_range, device, samples_per_launch, queue_factor, progress, "bvh", flags)
+    opt = lambda p: None if p is None else C.c_void_p(int(p))
+    _check(lib().mcpt_render_rays_indexed_device(scene.h, C.byref(o), int(n), opt(index_ptr), opt(origin_ptr), opt(dir_ptr),
+                                                 int(out_n), opt(dev_ptr), C.byref(st)))
     return st
 
 
@@ -1385,6 +1427,26 @@ def gradient_rays(camera, stratum, a, b, device=None):
     _check(lib().mcpt_gradient_rays(C.byref(camera), int(stratum), int(a), int(b), -1 if device is None else int(device),
                                     origin.ctypes.data, dir.ctypes.data))
     return origin, dir
+
+
+def gradient_index(width, height, stratum, a, b):
+    """mcpt_gradient_index: the pixels (i, j) of a width x height frame with i mod stratum == a and j mod stratum == b as
+    an increasing int32 list of pixel ids i * width + j (possibly empty).  No device work."""
+    n = C.c_int32()
+    _check(lib().mcpt_gradient_index(int(width), int(height), int(stratum), int(a), int(b), C.byref(n), None))
+    index = np.zeros(max(n.value, 1), dtype=np.int32)
+    _check(lib().mcpt_gradient_index(int(width), int(height), int(stratum), int(a), int(b), C.byref(n), index.ctypes.data))
+    return index[:n.value]
+
+
+def gradient_rays_indexed(camera, stratum, a, b, device=None):
+    """mcpt_gradient_rays_indexed: (index, origin, dir) of the selected pixels alone -- gradient_index's ids and
+    gradient_rays' rays at them bit for bit, count and count x 3 -- what render_rays_indexed takes."""
+    n = len(gradient_index(camera.width, camera.height, stratum, a, b))
+    index, origin, dir = np.zeros(max(n, 1), dtype=np.int32), np.zeros((max(n, 1), 3)), np.zeros((max(n, 1), 3))
+    _check(lib().mcpt_gradient_rays_indexed(C.byref(camera), int(stratum), int(a), int(b), -1 if device is None else int(device),
+                                            index.ctypes.data, origin.ctypes.data, dir.ctypes.data))
+    return index[:n], origin[:n], dir[:n]
 
 
 def temporal_gradient(prev_raw, regrad, a, b, stratum=3, radius=1, scale=1.0, device=None):

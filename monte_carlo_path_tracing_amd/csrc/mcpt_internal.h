@@ -361,6 +361,10 @@ int temporal_upsample_enqueue(const mcpt_temporal_opts* tp, const mcpt_upsample_
 int camera_phase_rays_enqueue(const mcpt_camera* full_cam, int32_t factor, int32_t a, int32_t b, double* dOrigin, double* dDir);
 // the same for mcpt_gradient_rays_device
 int gradient_rays_enqueue(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, double* dOrigin, double* dDir);
+// the same for mcpt_gradient_rays_indexed_device; *count gets the number of entries, and with 0 entries
+// nothing is launched
+int gradient_rays_indexed_enqueue(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t* dIndex, double* dOrigin,
+                                  double* dDir, int32_t* count);
 
 // render.hip -- k_motion_aovs alone, on the primary-hit tables the scene's state on `device` holds from its last
 // mcpt_render_aovs[_device] call, which must have been for a W x H camera (the frame sequence calls it right after the

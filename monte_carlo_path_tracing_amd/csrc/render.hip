@@ -279,7 +279,9 @@ __host__ __device__ inline int tri_filter(float4 a4, float4 b4, float4 c4, const
 // kLazyBG: the running best keeps its leaf slot instead of (beta, gamma) -- 1 VGPR for 4 across the whole
 // traversal -- and the winner's (beta, gamma) are recomputed once at the end by the same operations on the same
 // triangle, so they are bit-identical (MCPT_RAYS_LAZY_BG, k_mis_rays)
-template <int kLds, bool kCount = false, int kTop = 0, bool kFilter = true, bool kLazyBG = false>
+// (kTag gives a kernel a copy of the traversal of its own, so that a second caller does not change how the first is
+// compiled: with one shared copy k_roots_rays went from 163 to 180 VGPRs)
+template <int kLds, bool kCount = false, int kTop = 0, bool kFilter = true, bool kLazyBG = false, int kTag = 0>
 __device__ inline Hit trace4_ww(const BvhNode4* __restrict__ nodes, const float4* __restrict__ leafv, d3 ro, d3 rd,
                                 int exclude, int* __restrict__ lds, int stride, unsigned* visits = nullptr,
                                 unsigned* tests = nullptr, const BvhNode4* top = nullptr, float tlimit0 = FLT_MAX,
@@ -1115,6 +1117,12 @@ struct RayRoots {
     int n;                 // supplied rays: their number (the "frame" is n x 1)
     int jitter;            // 1: the camera's rays through per-sample sub-pixel offsets (origin / dir unused)
 };
+// indexed rays (mcpt_render_rays_indexed): [n] pixel ids in device memory; ray r keys the RNG and the framebuffer by
+// index[r], which must lie in [0, nid).  Kept out of RayRoots so that the plain kernel's arguments stay what they were
+struct RayIds {
+    const int* index = nullptr;
+    int nid = 0;
+};
 
 // the camera ray of pixel p for sample k: through the pixel's centre, or (jitter) through the centre displaced by
 // (dy, dx) in [-0.5, 0.5)^2, drawn from the counter RNG's node 0 of (seed, p, k) -- node ids start at 1, so this
@@ -1149,9 +1157,18 @@ __device__ inline bool ray_ok(d3 ro, d3 rd) {
 #ifndef MCPT_RAY_ROOTS_PT
 #define MCPT_RAY_ROOTS_PT 4
 #endif
+// kIndexed (k_roots_rays_indexed): the roots run over the rr.n rays as before and root r reads ITS ray, densely;
+// from there on its pixel is the id index[r] -- entry_eval's RNG key, the emitter's framebuffer slot and q.pixel, by
+// which every later kernel keys its own -- so a sparse pixel set of a frame costs its own rays only.  An id outside
+// [0, nid) is checked before any address is formed from it: the root becomes a broken ray (a zero direction, which
+// traces nothing, adds nothing and draws nothing) and sets bit 1 of the stats word whose bit 0 is the queue overflow
+// (kStatBadId).
+constexpr unsigned long long kStatBadId = 2ull;
 constexpr int kRayRootsPT = MCPT_RAY_ROOTS_PT;
-__global__ __launch_bounds__(256) void k_roots_rays(Params P, CamFrame cam, RayRoots rr, int npx, int s0, long long rbase,
-                                                    int nroots, Queue q, int group, int nsamp) {
+template <bool kIndexed>
+__device__ __forceinline__ void roots_rays(const Params& P, const CamFrame& cam, const RayRoots& rr, int npx, int s0,
+                                           long long rbase, int nroots, const Queue& q, int group, int nsamp, const int* index,
+                                           int nid) {
     __shared__ int stack[kStack * 256];
     __shared__ unsigned s_w[kRayRootsPT][4];
     __shared__ unsigned s_base;
@@ -1181,8 +1198,16 @@ __global__ __launch_bounds__(256) void k_roots_rays(Params P, CamFrame cam, RayR
                 ro = mk3(rr.origin[3 * (size_t)p], rr.origin[3 * (size_t)p + 1], rr.origin[3 * (size_t)p + 2]);
                 rd = mk3(rr.dir[3 * (size_t)p], rr.dir[3 * (size_t)p + 1], rr.dir[3 * (size_t)p + 2]);
             }
+            if (kIndexed) {  // p was the ray's position; from here on it is the ray's id
+                p = index[p];
+                if ((unsigned)p >= (unsigned)nid) {  // a broken ray, of pixel 0: a miss adds nothing and draws nothing
+                    atomicOr((unsigned long long*)(P.stats + 4), kStatBadId);
+                    p = 0;
+                    rd = mk3(0, 0, 0);
+                }
+            }
             if (ray_ok(ro, rd)) {
-                h = trace4_ww<kStack>(P.S.bvh4, P.S.leaf_v, ro, rd, -1, stack + threadIdx.x, 256);
+                h = trace4_ww<kStack, false, 0, true, false, kIndexed ? 1 : 0>(P.S.bvh4, P.S.leaf_v, ro, rd, -1, stack + threadIdx.x, 256);
                 w = mul(rd, -1);
             }
             const Entry e = entry_eval(P, h.f >= 0, h.f, h.beta, h.gamma, w, p, s, 1);
@@ -1235,6 +1260,15 @@ __global__ __launch_bounds__(256) void k_roots_rays(Params P, CamFrame cam, RayR
     }
 }
 
+__global__ __launch_bounds__(256) void k_roots_rays(Params P, CamFrame cam, RayRoots rr, int npx, int s0, long long rbase,
+                                                    int nroots, Queue q, int group, int nsamp) {
+    roots_rays<false>(P, cam, rr, npx, s0, rbase, nroots, q, group, nsamp, nullptr, 0);
+}
+__global__ __launch_bounds__(256) void k_roots_rays_indexed(Params P, CamFrame cam, RayRoots rr, int npx, int s0, long long rbase,
+                                                            int nroots, Queue q, int group, int nsamp, RayIds ids) {
+    roots_rays<true>(P, cam, rr, npx, s0, rbase, nroots, q, group, nsamp, ids.index, ids.nid);
+}
+
 // mcpt_camera_rays: the rays k_roots_rays shades for sample k of every pixel (jitter) or the pixel-centre rays
 __global__ __launch_bounds__(256) void k_camera_rays(CamFrame cam, uint64_t seed, int k, int jitter, double* origin,
                                                      double* dir) {
@@ -1266,6 +1300,19 @@ __global__ __launch_bounds__(256) void k_gradient_rays(CamFrame cam, int s, int 
     if ((p / cam.W) % s == a && (p % cam.W) % s == b) rd = pixel_ray_dir(cam, 0, p, 0, false);
     origin[3 * (size_t)p] = cam.eye.x, origin[3 * (size_t)p + 1] = cam.eye.y, origin[3 * (size_t)p + 2] = cam.eye.z;
     dir[3 * (size_t)p] = rd.x, dir[3 * (size_t)p + 1] = rd.y, dir[3 * (size_t)p + 2] = rd.z;
+}
+
+// mcpt_gradient_rays_indexed: the selected pixels alone.  Entry r = I * ws + J of the hs x ws selection is pixel
+// p = (s I + a) W + s J + b: its id, the eye and the pixel-centre ray by the same function (k_gradient_rays' bits)
+__global__ __launch_bounds__(256) void k_gradient_rays_indexed(CamFrame cam, int s, int a, int b, int ws, int n, int* index,
+                                                               double* origin, double* dir) {
+    const int r = blockIdx.x * 256 + (int)threadIdx.x;
+    if (r >= n) return;
+    const int p = (s * (r / ws) + a) * cam.W + s * (r % ws) + b;
+    const d3 rd = pixel_ray_dir(cam, 0, p, 0, false);
+    index[r] = p;
+    origin[3 * (size_t)r] = cam.eye.x, origin[3 * (size_t)r + 1] = cam.eye.y, origin[3 * (size_t)r + 2] = cam.eye.z;
+    dir[3 * (size_t)r] = rd.x, dir[3 * (size_t)r + 1] = rd.y, dir[3 * (size_t)r + 2] = rd.z;
 }
 
 // moves nodes [sb, sb + m) of src to [db, db + m) of dst (every field a generation carries into the
@@ -5440,7 +5487,11 @@ int pick_table_min_samples() {
 struct RenderPlan {
     CamFrame cf{};  // the camera's frame (unused with caller-supplied rays)
     RayRoots rr{};  // where the roots' rays come from when ray_roots: the caller's rays, or the camera's jittered ones
-    int W = 0, H = 0, npx = 0, s0 = 0, s1 = 0;
+    RayIds ids{};   // the caller's rays carry pixel ids
+    // npx: the roots' enumeration (pixels of the frame, or rays) -- R, nact, target, cap, progress, camera_samples;
+    // nid: the id space, which bounds whatever a run indexes by q.pixel.  They differ only with indexed rays
+    // (ids.index: npx = rr.n rays, nid = ids.nid framebuffer slots; DESIGN.md §4.27 lists the uses)
+    int W = 0, H = 0, npx = 0, nid = 0, s0 = 0, s1 = 0;
     bool grid = false;        // MCPT_ACCEL_GRID
     bool ray_roots = false;   // k_roots_rays makes the roots: no per-pixel tables, no root caches
     bool needs_prep = false;  // the O(N_L) light prep runs: shade_with_mis, and shade() with the spherical sampler
@@ -5468,13 +5519,15 @@ struct RenderPlan {
 // validates the call and fills the plan.  rays != nullptr (mcpt_render_rays): the roots are the supplied rays, the
 // "frame" is rays->n x 1 and cam is unused; MCPT_RENDER_PIXEL_JITTER: the roots are the camera's jittered rays.
 int make_plan(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt_render_opts* o, bool adaptive,
-              const RayRoots* rays, RenderPlan* out) {
+              const RayRoots* rays, RenderPlan* out, const RayIds* ids = nullptr) {
     RenderPlan& p = *out;
     int rc;
     if ((rc = validate_render(o))) return rc;
     p.cf = rays ? CamFrame{} : cam_setup(*cam);
     p.W = rays ? rays->n : cam->width, p.H = rays ? 1 : cam->height, p.npx = p.W * p.H;
     p.rr = rays ? *rays : RayRoots{nullptr, nullptr, 0, (o->flags & MCPT_RENDER_PIXEL_JITTER) ? 1 : 0};
+    if (rays && ids) p.ids = *ids;
+    p.nid = p.ids.index ? p.ids.nid : p.npx;
     p.ray_roots = rays || p.rr.jitter;
     job_range(o, &p.s0, &p.s1);
     // MCPT_ACCEL_GRID: the reference's uniform grid over the scene and this camera's eye, n0 =
@@ -5673,7 +5726,7 @@ int bind_buffers(mcpt_scene* sc, DeviceState& D, const RenderPlan& p, const mcpt
         B.exact_list = (int*)D.exact.p;
         B.maybe_list = B.exact_list + cap + kExactHead;
 #if MCPT_BAND_DIAG
-        HIP_OK(hipMemset((double*)D.exact_scr.p + (size_t)exact_waves(D.d.NL) * ((D.d.NL + 63) & ~63) * 3 / 2, 0, 4ull * npx));
+        HIP_OK(hipMemset((double*)D.exact_scr.p + (size_t)exact_waves(D.d.NL) * ((D.d.NL + 63) & ~63) * 3 / 2, 0, 4ull * p.nid));
 #endif
         B.exact_scr = (double*)D.exact_scr.p;
         B.slack = (double*)D.slack.p;
@@ -5849,7 +5902,7 @@ struct WavefrontRun {
         HIP_OK(hipMemcpyAsync(D.pinned_count + 2, (char*)D.stats.p + 32, 8, hipMemcpyDeviceToHost, st));
         if (pl.stale) HIP_OK(hipMemcpyAsync(D.pinned_count + 16, T.ctrl, kCtrlBytes, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
-        if (*(unsigned long long*)(D.pinned_count + 2)) {
+        if (*(unsigned long long*)(D.pinned_count + 2) & 1ull) {  // (bit 1, kStatBadId, is the caller's to report)
             set_error("wavefront queue overflow (capacity %d); raise queue_factor", pl.cap);
             return MCPT_E_OVERFLOW;
         }
@@ -5904,7 +5957,10 @@ struct WavefrontRun {
     // appends the run's next m roots to cur (through node_entry): from the caller's / the jittered rays, or from the
     // per-pixel root table
     int refill_roots(int m) {
-        if (pl.ray_roots)
+        if (pl.ids.index)
+            hipLaunchKernelGGL(k_roots_rays_indexed, dim3((m + 256 * kRayRootsPT - 1) / (256 * kRayRootsPT)), dim3(256), 0, st, P,
+                               pl.cf, pl.rr, nact, a, rnext, m, *cur, std::max(1, nminor), b - a, pl.ids);
+        else if (pl.ray_roots)
             hipLaunchKernelGGL(k_roots_rays, dim3((m + 256 * kRayRootsPT - 1) / (256 * kRayRootsPT)), dim3(256), 0, st, P,
                                pl.cf, pl.rr, nact, a, rnext, m, *cur, std::max(1, nminor), b - a);
         else
@@ -6382,9 +6438,9 @@ int fill_stats(const RenderPlan& p, const Bound& B, DeviceState& D, const Counte
             hs[12], hs[13], hs[14], hs[15]);
     if (B.exact_scr) {
         const int nlp = (D.d.NL + 63) & ~63;
-        std::vector<int> pc(p.npx);
+        std::vector<int> pc(p.nid);
         HIP_OK(hipMemcpy(pc.data(), reinterpret_cast<int*>(B.exact_scr + (size_t)exact_waves(D.d.NL) * nlp * 3 / 2),
-                         4ull * p.npx, hipMemcpyDeviceToHost));
+                         4ull * p.nid, hipMemcpyDeviceToHost));
         long long tot = 0, distinct = 0, mx = 0;
         for (int v : pc) tot += v, distinct += v > 0, mx = std::max<long long>(mx, v);
         fprintf(stderr, "exact diag: roots %lld over %lld pixels (max %lld per pixel)\n", tot, distinct, mx);
@@ -6400,12 +6456,13 @@ int fill_stats(const RenderPlan& p, const Bound& B, DeviceState& D, const Counte
 // is the cap, the statistics are summed over the passes) -- and report.  With roots from rays (make_plan) the
 // per-pixel setup (primary hits, root table, root caches, RootLit pool) is skipped.
 int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, const mcpt_render_opts* o,
-                     double* dfb, mcpt_stats* stats, const AdaptiveRun* ad = nullptr, const RayRoots* rays = nullptr) {
+                     double* dfb, mcpt_stats* stats, const AdaptiveRun* ad = nullptr, const RayRoots* rays = nullptr,
+                     const RayIds* ids = nullptr) {
     RenderPlan pl;
     Bound B;
     Counters C;
     int rc;
-    if ((rc = make_plan(sc, D, cam, o, ad != nullptr, rays, &pl)) || (rc = bind_buffers(sc, D, pl, o, ad != nullptr, &B)))
+    if ((rc = make_plan(sc, D, cam, o, ad != nullptr, rays, &pl, ids)) || (rc = bind_buffers(sc, D, pl, o, ad != nullptr, &B)))
         return rc;
     const hipStream_t st = D.stream;
     HIP_OK(hipMemsetAsync(D.stats.p, 0, kStatBytes, st));
@@ -6422,7 +6479,17 @@ int render_on_device(mcpt_scene* sc, DeviceState& D, const mcpt_camera* cam, con
     fprintf(stderr, "adaptive diag: runs %d drain_ms %.3f adaptive_kernels_ms %.3f total_ms %.3f\n", C.diag_runs, C.diag_drain_ms,
             C.diag_kernel_ms, (double)ms);
 #endif
-    return stats ? fill_stats(pl, B, D, C, ms, stats) : MCPT_OK;
+    if (stats && (rc = fill_stats(pl, B, D, C, ms, stats))) return rc;
+    if (pl.ids.index) {  // a device call's ids cannot be read before the run: the root kernel's flag
+        unsigned long long flags = 0;
+        HIP_OK(hipMemcpy(&flags, (char*)D.stats.p + 32, 8, hipMemcpyDeviceToHost));
+        if (flags & kStatBadId) {
+            set_error("mcpt_render_rays_indexed_device: the index held an id outside [0, out_n = %d): found after the run; "
+                      "those rays traced nothing, every other ray's sum has been added", pl.ids.nid);
+            return MCPT_E_INVALID;
+        }
+    }
+    return MCPT_OK;
 }
 
 // mcpt_debug_root_picks: a render call's setup up to the root caches, then the roots' picks alone
@@ -7003,6 +7070,31 @@ int gradient_rays_enqueue(const mcpt_camera* cam, int32_t s, int32_t a, int32_t 
     return MCPT_OK;
 }
 
+// the selection of phase (a, b) in a W x H frame: hs x ws pixels (s I + a, s J + b), either of which may be 0
+void gradient_selection(int W, int H, int s, int a, int b, int* hs, int* ws) {
+    *hs = a < H ? (H - a + s - 1) / s : 0;
+    *ws = b < W ? (W - b + s - 1) / s : 0;
+}
+
+int gradient_rays_indexed_enqueue(const mcpt_camera* cam, int32_t s, int32_t a, int32_t b, int32_t* dIndex, double* dOrigin,
+                                  double* dDir, int32_t* count) {
+    int rc;
+    if (!dIndex) {
+        set_error("mcpt_gradient_rays_indexed: null argument: index");
+        return MCPT_E_INVALID;
+    }
+    if ((rc = gradient_rays_check(cam, s, a, b, dOrigin, dDir))) return rc;
+    int hs, ws;
+    gradient_selection(cam->width, cam->height, s, a, b, &hs, &ws);
+    const int n = hs * ws;
+    *count = n;
+    if (!n) return MCPT_OK;
+    const CamFrame cf = cam_setup(*cam);
+    hipLaunchKernelGGL(k_gradient_rays_indexed, dim3((n + 255) / 256), dim3(256), 0, 0, cf, s, a, b, ws, n, dIndex, dOrigin, dDir);
+    HIP_OK(hipGetLastError());
+    return MCPT_OK;
+}
+
 }  // namespace mcpt
 
 // ============================================================================================
@@ -7321,6 +7413,73 @@ int mcpt_render_rays(mcpt_scene* sc, const mcpt_render_opts* o, int32_t n, const
     return MCPT_OK;
 }
 
+// the checks of mcpt_render_rays_indexed[_device] that need no device: mcpt_render_rays' own, the index and out_n
+static int check_render_rays_indexed(mcpt_scene* sc, const mcpt_render_opts* o, int32_t n, const int32_t* index,
+                                     const double* origin, const double* dir, int32_t out_n, const double* out) {
+    int rc;
+    if ((rc = check_render_rays(sc, o, n, origin, dir, out))) return rc;
+    if (!index) {
+        set_error("mcpt_render_rays_indexed: null argument: index");
+        return MCPT_E_INVALID;
+    }
+    if (out_n < 1 || out_n > (1 << 28)) {
+        set_error("mcpt_render_rays_indexed: out_n = %d (must lie in 1..2^28)", out_n);
+        return MCPT_E_INVALID;
+    }
+    return MCPT_OK;
+}
+
+int mcpt_render_rays_indexed_device(mcpt_scene* sc, const mcpt_render_opts* o, int32_t n, const int32_t* dev_index,
+                                    const double* dev_origin, const double* dev_dir, int32_t out_n, double* dev_out,
+                                    mcpt_stats* stats) {
+    int rc;
+    if ((rc = check_render_rays_indexed(sc, o, n, dev_index, dev_origin, dev_dir, out_n, dev_out))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    if ((rc = get_device_state(sc, o->device, &D))) return rc;
+    if ((rc = check_device_buffer(dev_out, D->device)) || (rc = check_device_buffer(dev_origin, D->device, "dev_origin")) ||
+        (rc = check_device_buffer(dev_dir, D->device, "dev_dir")) || (rc = check_device_buffer(dev_index, D->device, "dev_index")))
+        return rc;
+    // the caller's buffers may still be written by work on other streams (e.g. torch's)
+    HIP_OK(hipDeviceSynchronize());
+    const RayRoots rr{dev_origin, dev_dir, n, 0};
+    const RayIds ids{dev_index, out_n};
+    mcpt_stats st{};
+    if ((rc = render_on_device(sc, *D, nullptr, o, dev_out, &st, nullptr, &rr, &ids))) return rc;
+    copy_stats(o, st, stats);
+    return MCPT_OK;
+}
+
+int mcpt_render_rays_indexed(mcpt_scene* sc, const mcpt_render_opts* o, int32_t n, const int32_t* index, const double* origin,
+                             const double* dir, int32_t out_n, double* out_rgb, mcpt_stats* stats) {
+    int rc;
+    if ((rc = check_render_rays_indexed(sc, o, n, index, origin, dir, out_n, out_rgb))) return rc;
+    for (int32_t r = 0; r < n; r++)
+        if (index[r] < 0 || index[r] >= out_n) {
+            set_error("mcpt_render_rays_indexed: index[%d] = %d is outside [0, out_n = %d)", r, index[r], out_n);
+            return MCPT_E_INVALID;
+        }
+    std::lock_guard<std::mutex> lk(sc->mu);
+    DeviceState* D;
+    if ((rc = get_device_state(sc, o->device, &D))) return rc;
+    const size_t bytes = 3 * (size_t)n * sizeof(double), obytes = 3 * (size_t)out_n * sizeof(double);
+    if ((rc = ensure(D->fb, obytes)) || (rc = ensure(D->ray_o, bytes)) || (rc = ensure(D->ray_d, bytes)) ||
+        (rc = ensure(D->ray_i, (size_t)n * sizeof(int32_t))))
+        return rc;
+    HIP_OK(hipMemcpyAsync(D->fb.p, out_rgb, obytes, hipMemcpyHostToDevice, D->stream));
+    HIP_OK(hipMemcpyAsync(D->ray_o.p, origin, bytes, hipMemcpyHostToDevice, D->stream));
+    HIP_OK(hipMemcpyAsync(D->ray_d.p, dir, bytes, hipMemcpyHostToDevice, D->stream));
+    HIP_OK(hipMemcpyAsync(D->ray_i.p, index, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, D->stream));
+    const RayRoots rr{(const double*)D->ray_o.p, (const double*)D->ray_d.p, n, 0};
+    const RayIds ids{(const int*)D->ray_i.p, out_n};
+    mcpt_stats st{};
+    if ((rc = render_on_device(sc, *D, nullptr, o, (double*)D->fb.p, &st, nullptr, &rr, &ids))) return rc;
+    HIP_OK(hipMemcpyAsync(out_rgb, D->fb.p, obytes, hipMemcpyDeviceToHost, D->stream));
+    HIP_OK(hipStreamSynchronize(D->stream));
+    copy_stats(o, st, stats);
+    return MCPT_OK;
+}
+
 int mcpt_camera_rays(const mcpt_camera* cam, uint64_t seed, int32_t sample, int32_t jitter, int32_t device, double* origin,
                      double* dir) {
     if (!cam || !origin || !dir) {
@@ -7458,6 +7617,94 @@ int mcpt_gradient_rays(const mcpt_camera* cam, int32_t stratum, int32_t a, int32
 int mcpt_gradient_rays_device(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device, double* dev_origin,
                               double* dev_dir) {
     return gradient_rays(cam, stratum, a, b, device, dev_origin, dev_dir, false);
+}
+
+int mcpt_gradient_index(int32_t width, int32_t height, int32_t s, int32_t a, int32_t b, int32_t* count, int32_t* index) {
+    if (!count) {
+        set_error("mcpt_gradient_index: null argument: count");
+        return MCPT_E_INVALID;
+    }
+    if (width < 1 || height < 1 || (long long)width * height > (1ll << 28)) {
+        set_error("mcpt_gradient_index: invalid frame size: width %d, height %d (a frame may hold 2^28 pixels)", width, height);
+        return MCPT_E_INVALID;
+    }
+    if (s < 1 || s > 8) {
+        set_error("mcpt_gradient_index: stratum %d is outside 1..8", s);
+        return MCPT_E_INVALID;
+    }
+    if (a < 0 || a >= s || b < 0 || b >= s) {
+        set_error("mcpt_gradient_index: invalid phase (%d, %d): both must lie in [0, stratum = %d)", a, b, s);
+        return MCPT_E_INVALID;
+    }
+    int hs, ws;
+    gradient_selection(width, height, s, a, b, &hs, &ws);
+    *count = hs * ws;
+    if (index)
+        for (int I = 0; I < hs; I++)
+            for (int J = 0; J < ws; J++) index[(size_t)I * ws + J] = (s * I + a) * width + s * J + b;
+    return MCPT_OK;
+}
+
+// both forms of mcpt_gradient_rays_indexed; host: index, origin and dir are host arrays
+static int gradient_rays_indexed(const mcpt_camera* cam, int32_t s, int32_t a, int32_t b, int32_t device, int32_t* index,
+                                 double* origin, double* dir, bool host) {
+    int rc;
+    if (!index) {  // (a host call's checks come before its device buffer exists)
+        set_error("mcpt_gradient_rays_indexed: null argument: index");
+        return MCPT_E_INVALID;
+    }
+    if ((rc = gradient_rays_check(cam, s, a, b, origin, dir))) return rc;
+    int hs, ws;
+    gradient_selection(cam->width, cam->height, s, a, b, &hs, &ws);
+    const size_t n = (size_t)hs * ws, bytes = 3 * n * sizeof(double);
+    int32_t count = 0;
+    if (!n) return MCPT_OK;
+    struct Restore {  // the caller's current device
+        int prev = -1;
+        ~Restore() {
+            if (prev >= 0) (void)hipSetDevice(prev);
+        }
+    } restore;
+    if (device >= 0) {
+        HIP_OK(hipGetDevice(&restore.prev));
+        HIP_OK(hipSetDevice(device));
+    }
+    if (!host) {
+        int cur = 0;
+        HIP_OK(hipGetDevice(&cur));
+        if ((rc = check_device_buffer(index, cur, "dev_index")) || (rc = check_device_buffer(origin, cur, "dev_origin")) ||
+            (rc = check_device_buffer(dir, cur, "dev_dir")))
+            return rc;
+        // the caller's arrays may still be in use by work on other streams (e.g. torch's)
+        HIP_OK(hipDeviceSynchronize());
+        if ((rc = gradient_rays_indexed_enqueue(cam, s, a, b, index, origin, dir, &count))) return rc;
+        HIP_OK(hipStreamSynchronize(nullptr));
+        return MCPT_OK;
+    }
+    struct Buf {
+        void* p = nullptr;
+        ~Buf() {
+            if (p) (void)hipFree(p);
+        }
+    } buf;
+    HIP_OK(hipMalloc(&buf.p, 2 * bytes + n * sizeof(int32_t)));
+    double* d = (double*)buf.p;
+    int32_t* di = (int32_t*)(d + 6 * n);
+    if ((rc = gradient_rays_indexed_enqueue(cam, s, a, b, di, d, d + 3 * n, &count))) return rc;
+    HIP_OK(hipMemcpy(origin, d, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dir, d + 3 * n, bytes, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(index, di, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+int mcpt_gradient_rays_indexed(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device, int32_t* index,
+                               double* origin, double* dir) {
+    return gradient_rays_indexed(cam, stratum, a, b, device, index, origin, dir, true);
+}
+
+int mcpt_gradient_rays_indexed_device(const mcpt_camera* cam, int32_t stratum, int32_t a, int32_t b, int32_t device,
+                                      int32_t* dev_index, double* dev_origin, double* dev_dir) {
+    return gradient_rays_indexed(cam, stratum, a, b, device, dev_index, dev_origin, dev_dir, false);
 }
 
 void mcpt_adaptive_opts_init(mcpt_adaptive_opts* a) {

@@ -143,6 +143,7 @@ struct DeviceState {
     int ad_last_list = -1, ad_last_n = 0;  // the last active list built (mcpt_debug_adaptive_active)
     DevBuf aov;  // mcpt_render_aovs: the four maps of a host call (10 doubles per pixel)
     DevBuf ray_o, ray_d;  // mcpt_render_rays: a host call's origins and directions
+    DevBuf ray_i;         // mcpt_render_rays_indexed: a host call's ids
     int spill_cap = 0;  // nodes the spill stack qs holds (grown on demand)
     bool bvh8_tried = false;  // ensure_bvh8 ran on this device
     DevBuf g_start, g_tri;  // the scene's uniform grid (MCPT_ACCEL_GRID), version grid_version
