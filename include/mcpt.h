@@ -540,6 +540,44 @@ int mcpt_scene_set_materials(mcpt_scene* scene, int32_t first_material, int32_t 
                              mcpt_relight_stats* stats);
 int mcpt_scene_light_groups(const mcpt_scene* scene, int32_t* group);
 
+/* Facet visibility: ranges of facets hidden and shown again in place.  No reference interface
+ * corresponds.  The rule: after a successful call the scene traces and renders as mcpt_scene_create of the current
+ * arrays WITHOUT the hidden facets would, with that scene's facet ids mapped back through the monotone old -> new index
+ * map -- mcpt_closest_hit and mcpt_primary_hits bit for bit, renders in every mode up to the order of the fp64 atomics.
+ *
+ * mcpt_scene_set_visible: facets [first, first + count) become invisible (visible == 0) or visible again (any other
+ * value).  No ray of any call hits a hidden facet -- camera rays, extension rays, the MIS light-visibility rays,
+ * mcpt_closest_hit, mcpt_primary_hits, the AOV and motion-AOV calls, mcpt_render_rays*, the adaptive render and every
+ * sequence -- so it occludes nothing and is never shaded.  Everything else about it stays: its index, mcpt_scene_counts,
+ * mcpt_scene_arrays and its material.  mcpt_scene_update[_device], mcpt_scene_transform, mcpt_scene_pose_save,
+ * mcpt_scene_rest_save and mcpt_scene_host_sync accept hidden facets and store their new values, which appear when the
+ * facet is shown.  Hiding a hidden facet or showing a visible one is accepted and does nothing to that facet.
+ *
+ * How: the facet arrays, the ids, the slot map and every tree's topology stay.  A hidden facet's leaf slots hold its own
+ * first vertex three times, which both triangle tests reject exactly (a zero determinant), and the boxes on its path are
+ * refit around those points; showing scatters the facet array's vertices back and refits again.  The host copy comes
+ * first (a per-facet byte and the host tree's boxes: a device state created later honours the mask), then every device
+ * state the handle has, each by one scatter kernel and the refit's per-level kernels on the state's stream, which is
+ * synchronised once.  Like mcpt_scene_update the call takes the scene's lock, syncs the host copy first if ranges are
+ * pending, and its first success marks the handle as updated (the 8-wide debug trees are refused afterwards).
+ * mcpt_scene_rebuild keeps every facet: a hidden one is placed at its point with collapsed slots.  `stats` (may be
+ * NULL) is filled as an update fills it.  With a communicator every rank must make the same call.
+ *
+ * Refused with MCPT_E_INVALID before anything is modified: a NULL scene; count <= 0 or a range outside the scene; a
+ * stats struct_size mismatch; a range that contains a light triangle, with or without mcpt_scene_set_lights_movable (the
+ * first one is named: hiding a light would change every light table; mcpt_scene_set_light_radiance with zeros switches
+ * a light off).  While any facet is hidden, MCPT_ACCEL_GRID, MCPT_HIT_GRID and mcpt_scene_meshing are refused with
+ * MCPT_E_INVALID: the reference grid's in-cell rule depends on the scene's box, so a grid without the facets would not
+ * be the reference's.
+ *
+ * mcpt_scene_visibility: visible[f] = 1 / 0 for every facet (nfacets bytes, may be NULL) and the number of hidden
+ * facets (may be NULL).  MCPT_E_INVALID: a NULL scene.
+ *
+ * Not covered: hiding lights; visibility per ray type (camera-only, shadow-only); a rebuild that drops hidden facets
+ * from the tree; changing the facet count; consistency across the ranks of a communicator. */
+int mcpt_scene_set_visible(mcpt_scene* scene, int32_t first, int32_t count, int32_t visible, mcpt_update_stats* stats);
+int mcpt_scene_visibility(const mcpt_scene* scene, uint8_t* visible, int32_t* hidden);
+
 /* main.cpp:547-588: render samples [sample_begin, sample_end) of an spp-sample frame and ADD
  * sum_k L_k * (1/spp) into out_rgb (caller-owned host buffer, height*width*3 doubles, row 0 =
  * top image row).  Devices: opts->device, or opts->devices / opts->comm (see mcpt_render_opts). */

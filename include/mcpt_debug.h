@@ -112,7 +112,10 @@ int mcpt_debug_bvh4_check(mcpt_scene* scene, int32_t light_only, int64_t out[6])
 // The same walk over what `device` (-1 = current) holds of the scene's main tree: its 4-wide nodes (leaf codes
 // unpacked), quantized nodes and leaf slots are downloaded and walked against the host positions; vertices of a leaf
 // slot or of the device's facet array that differ from the host positions count as errors too.  The check of the
-// device-side refit (mcpt_scene_update, include/mcpt.h).
+// device-side refit (mcpt_scene_update, include/mcpt.h).  A hidden facet (mcpt_scene_set_visible) is walked, here and
+// in mcpt_debug_bvh4_check, as the collapsed triangle its leaf slots hold -- its first vertex three times: a hidden
+// facet's slot that holds a real triangle and a visible facet's slot that is collapsed both count as errors, while the
+// device's facet array is compared with the stored values.  Unchanged when nothing is hidden.
 int mcpt_debug_bvh4_check_device(mcpt_scene* scene, int32_t device, int64_t out[6]);
 // Downloads that tree: counts = {nodes, leaf slots}; nodes (128 B each), qnodes (64 B each) and leaf_facets (the
 // facet of every slot) may each be NULL, else they hold at least cap_nodes / cap_slots entries (a smaller capacity

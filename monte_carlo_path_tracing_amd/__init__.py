@@ -269,6 +269,7 @@ EXPORTS = ["mcpt_version", "mcpt_last_error", "mcpt_scene_load", "mcpt_scene_cre
            "mcpt_scene_light_update_info",
            "mcpt_relight_stats_init", "mcpt_scene_set_light_radiance", "mcpt_scene_set_light_radiance_device",
            "mcpt_scene_set_materials", "mcpt_scene_light_groups",
+           "mcpt_scene_set_visible", "mcpt_scene_visibility",
            "mcpt_gradient_opts_init", "mcpt_gradient_phase", "mcpt_gradient_rays", "mcpt_gradient_rays_device",
            "mcpt_temporal_gradient", "mcpt_temporal_gradient_device", "mcpt_temporal_accumulate_antilag",
            "mcpt_temporal_accumulate_antilag_device", "mcpt_sequence_set_antilag", "mcpt_sequence_antilag_info"]
@@ -433,6 +434,9 @@ def lib():
             L.mcpt_scene_set_light_radiance_device.argtypes = [P, I, I, I, P, C.POINTER(RelightStats)]
             L.mcpt_scene_set_materials.argtypes = [P, I, I, P, C.POINTER(RelightStats)]
             L.mcpt_scene_light_groups.argtypes = [P, ip]
+        if hasattr(L, "mcpt_scene_set_visible"):  # and the facet visibility
+            L.mcpt_scene_set_visible.argtypes = [P, I, I, I, C.POINTER(UpdateStats)]
+            L.mcpt_scene_visibility.argtypes = [P, P, C.POINTER(C.c_int32)]
         if hasattr(L, "mcpt_temporal_gradient"):  # and the anti-lag by temporal gradients
             L.mcpt_gradient_opts_init.argtypes = [C.POINTER(GradientOpts)]
             L.mcpt_gradient_opts_init.restype = None
@@ -673,6 +677,37 @@ class Scene:
         c = C.c_double(0.0)
         _check(lib().mcpt_scene_tree_cost(self.h, -1 if device is None else int(device), C.byref(c)))
         return float(c.value)
+
+    def set_visible(self, first, count, visible=True):
+        """mcpt_scene_set_visible: facets [first, first + count) become invisible (visible=False) or visible again, on
+        the host copy and on every device the scene lives on.  No ray of any call hits a hidden facet; its index, its
+        rows of arrays() and its material stay, and update() / transform() of a hidden facet store values that appear
+        when it is shown.  Light triangles cannot be hidden; the grid modes are refused while anything is.  Returns
+        the stats dict of update()."""
+        st = UpdateStats()
+        lib().mcpt_update_stats_init(C.byref(st))
+        _check(lib().mcpt_scene_set_visible(self.h, int(first), int(count), 1 if visible else 0, C.byref(st)))
+        return st.as_dict()
+
+    def hide(self, first, count):
+        """set_visible(first, count, False)"""
+        return self.set_visible(first, count, False)
+
+    def show(self, first, count):
+        """set_visible(first, count, True)"""
+        return self.set_visible(first, count, True)
+
+    def visible(self):
+        """mcpt_scene_visibility: a bool per facet, False where it is hidden"""
+        v = np.zeros(max(self.nfacets, 1), np.uint8)
+        _check(lib().mcpt_scene_visibility(self.h, v.ctypes.data_as(C.c_void_p), None))
+        return v[:self.nfacets].astype(bool)
+
+    def hidden_count(self):
+        """mcpt_scene_visibility: how many facets are hidden"""
+        n = C.c_int32(0)
+        _check(lib().mcpt_scene_visibility(self.h, None, C.byref(n)))
+        return int(n.value)
 
     def arrays(self):
         F, M, NL = self.nfacets, self.nmaterials, self.nlights

@@ -722,7 +722,8 @@ void refit_bvh(Bvh& b, const BvhRefitIndex& ix, const HostScene& s, const std::v
         Box bx;
         for (int32_t j = ~nd.child[k]; j < ~nd.child[k] + nd.count[k]; j++)
             for (int v = 0; v < 3; v++) {
-                const float* p = &s.pos[9 * static_cast<size_t>(b.leaf_facets[j]) + 3 * v];
+                const int32_t f = b.leaf_facets[j];  // a hidden facet is its first vertex (its collapsed device slot)
+                const float* p = &s.pos[9 * static_cast<size_t>(f) + (s.is_hidden(f) ? 0 : 3 * v)];
                 const double d[3] = {p[0], p[1], p[2]};
                 bx.grow(d);
             }

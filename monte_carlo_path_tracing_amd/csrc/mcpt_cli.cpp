@@ -47,6 +47,11 @@
 //   of the full-size pixels and accumulates them in a full-size history (mcpt_sequence_create_temporal_upsampled): the
 //   same files and lines as the --upsample arm, the "upsampled" line carrying the frame's phase and the share of the
 //   pixels that were filled in.  Not with --history-clamp, --jitter, --grid or --adaptive.
+//               [--hide FIRST:COUNT[:FRAME]] [--show FIRST:COUNT[:FRAME]]
+//   --hide and --show (repeatable, with or without --frames and --device-sequence) make facets [FIRST, FIRST + COUNT)
+//   invisible or visible again in place (mcpt_scene_set_visible) before the frame with the 0-based index FRAME (default
+//   0), in command-line order, and print a "hid" / "showed" line with the call's statistics.  A range with a light
+//   triangle is refused with the library's message.  Not with --grid.
 //               [--move FIRST:COUNT:DX,DY,DZ]
 //   --move (with --frames N, with or without --device-sequence) animates facets [FIRST, FIRST + COUNT): before frame
 //   k >= 1 they are set to float(double(original) + k * (DX, DY, DZ)) by mcpt_scene_update (the BVH is refit in place, no
@@ -218,6 +223,40 @@ struct Mover {
         std::printf("  moved facets [%d, %d) by %d x (%g, %g, %g): %lld leaf slots, %lld nodes refit on %d levels, %.3f ms device\n",
                     first, first + count, k, d[0], d[1], d[2], (long long)us.leaf_slots, (long long)us.nodes_refit, us.levels,
                     us.device_seconds * 1e3);
+        return 0;
+    }
+};
+
+// --hide FIRST:COUNT[:FRAME] and --show FIRST:COUNT[:FRAME] (repeatable): before the frame with that 0-based index
+// (default 0, so it also works without --frames) facets [first, first + count) are hidden or shown again in place
+// (mcpt_scene_set_visible), in the order of the command line
+struct Visibility {
+    struct Edit {
+        int32_t first, count, frame, visible;
+    };
+    std::vector<Edit> edits;
+    bool parse(const char* arg, bool visible) {
+        Edit e{0, 0, 0, visible ? 1 : 0};
+        char tail = 0;
+        const int n = std::sscanf(arg, "%d:%d%c", &e.first, &e.count, &tail);
+        if (n == 3 && std::sscanf(arg, "%d:%d:%d%c", &e.first, &e.count, &e.frame, &tail) != 3) return false;
+        if (n < 2 || e.first < 0 || e.count < 1 || e.frame < 0) return false;
+        edits.push_back(e);
+        return true;
+    }
+    int apply(mcpt_scene* scene, int k) const {
+        for (const Edit& e : edits) {
+            if (e.frame != k) continue;
+            mcpt_update_stats us;
+            mcpt_update_stats_init(&us);
+            if (mcpt_scene_set_visible(scene, e.first, e.count, e.visible, &us) != MCPT_OK) {
+                std::fprintf(stderr, "--%s failed: %s\n", e.visible ? "show" : "hide", mcpt_last_error());
+                return 1;
+            }
+            std::printf("  %s facets [%d, %d): %lld leaf slots, %lld nodes refit on %d levels, %.3f ms device\n",
+                        e.visible ? "showed" : "hid", e.first, e.first + e.count, (long long)us.leaf_slots, (long long)us.nodes_refit,
+                        us.levels, us.device_seconds * 1e3);
+        }
         return 0;
     }
 };
@@ -409,6 +448,7 @@ struct SequenceArgs {
     Rebuilder* rebuild;  // --rebuild, or null
     Relighter* relight;  // --dim / --tint, or null
     int antilag;  // --antilag: the stratum, or 0
+    const Visibility* vis;  // --hide / --show, or null
 };
 
 void print_antilag(int stratum, int a, int b, double mean, double mx, double trace_seconds) {
@@ -476,6 +516,7 @@ int render_sequence(mcpt_scene* scene, const mcpt_camera& cam0, const SequenceAr
             std::fprintf(stderr, "--motion failed: %s\n", mcpt_last_error());
             return 1;
         }
+        if (a.vis && a.vis->apply(scene, k)) return 1;
         if (a.move && a.move->apply(scene, k)) return 1;
         if (a.rotate && a.rotate->apply(scene, k)) return 1;
         if (a.rebuild && a.rebuild->apply(scene, k)) return 1;
@@ -652,7 +693,7 @@ int render_sequence_device(mcpt_scene* scene, const mcpt_camera& cam0, const Seq
             rc = 1;
             break;
         }
-        if ((a.move && a.move->apply(scene, k)) || (a.rotate && a.rotate->apply(scene, k)) ||
+        if ((a.vis && a.vis->apply(scene, k)) || (a.move && a.move->apply(scene, k)) || (a.rotate && a.rotate->apply(scene, k)) ||
             (a.rebuild && a.rebuild->apply(scene, k)) || (a.relight && a.relight->apply(scene, k))) {
             rc = 1;
             break;
@@ -758,6 +799,7 @@ int main(int argc, char** argv) {
     bool rebuild_flag = false;
     Rebuilder rebuilder;
     Relighter relighter;
+    Visibility visibility;
     for (int a = 1; a < argc; a++) {
         auto next = [&]() -> const char* {
             if (a + 1 >= argc) {
@@ -859,6 +901,14 @@ int main(int argc, char** argv) {
                 return 2;
             }
         }
+        else if (!std::strcmp(argv[a], "--hide") || !std::strcmp(argv[a], "--show")) {
+            const char* opt = argv[a];
+            if (!visibility.parse(next(), !std::strcmp(opt, "--show"))) {
+                std::fprintf(stderr, "%s needs FIRST:COUNT[:FRAME] (a facet range and the 0-based frame it takes effect before), not %s\n",
+                             opt, argv[a]);
+                return 2;
+            }
+        }
         else if (!std::strcmp(argv[a], "--motion")) motion_flag = true;
         else if (!std::strcmp(argv[a], "--antilag")) antilag_flag = true;
         else if (!std::strcmp(argv[a], "--antilag-stratum")) antilag_stratum = std::atoi(next()), antilag_stratum_flag = true;
@@ -888,6 +938,19 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "--jitter traces its camera rays over the BVH; drop --grid\n");
             return 2;
         }
+    }
+    if (!visibility.edits.empty()) {  // refused before anything is loaded
+        if (grid) {
+            std::fprintf(stderr, "--hide and --show are not supported with --grid: the reference grid's in-cell rule depends on the "
+                                 "scene's box, so a grid without the hidden facets would not be the reference's; drop --grid\n");
+            return 2;
+        }
+        for (const Visibility::Edit& e : visibility.edits)
+            if (e.frame >= std::max(frames, 1)) {
+                std::fprintf(stderr, "--%s %d:%d:%d: frame %d is not one of the run's %d (0-based)\n", e.visible ? "show" : "hide", e.first,
+                             e.count, e.frame, e.frame, std::max(frames, 1));
+                return 2;
+            }
     }
     if (move_flag && frames == 0) {  // refused before anything is loaded
         std::fprintf(stderr, "--move moves facets between the frames of a sequence; add --frames N\n");
@@ -1046,7 +1109,7 @@ int main(int argc, char** argv) {
         const SequenceArgs sa{frames, spp, mode, flags, orbit, seed, progress, grid, denoise, out, hdr_out, aov_out,
                               move_flag ? &mover : nullptr, motion_flag, rotate_flag ? &rotator : nullptr,
                               rebuild_flag ? &rebuilder : nullptr, relight_flag ? &relighter : nullptr,
-                              antilag_flag ? antilag_stratum : 0};
+                              antilag_flag ? antilag_stratum : 0, visibility.edits.empty() ? nullptr : &visibility};
         if (clamp_flag && !history_clamp) {
             std::fprintf(stderr, "--clamp-radius and --clamp-alpha-fast need --history-clamp\n");
             return 2;
@@ -1057,6 +1120,7 @@ int main(int argc, char** argv) {
         mcpt_scene_destroy(scene);
         return rc;
     }
+    if (visibility.apply(scene, 0)) return 1;
     ad.max_spp = spp;
     const auto t0 = std::chrono::steady_clock::now();
     if ((adaptive ? render_adaptive(scene, cam, ad, mode, seed, progress, grid, flags, hdr, count, noise, &st)

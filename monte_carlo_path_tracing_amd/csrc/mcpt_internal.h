@@ -30,6 +30,9 @@ struct HostScene {
     std::vector<int32_t> group_start, group_count;
     bool has_cam = false;
     mcpt_camera cam{};
+    // mcpt_scene_set_visible: F bytes, 1 = hidden; empty until the handle's first call
+    std::vector<uint8_t> hidden;
+    bool is_hidden(int f) const { return !hidden.empty() && hidden[static_cast<size_t>(f)] != 0; }
 };
 
 // scene_io.cpp
@@ -137,6 +140,7 @@ BvhRefitIndex make_bvh_refit_index(const Bvh& b);
 void box_with_margin(const double lo[3], const double hi[3], double margin, float* flo, float* fhi);
 // every leaf holding one of `slots` gets the union of the FULL bounds of all its triangles (from s.pos), enlarged by
 // `margin`; every ancestor slot the union of its child node's two slot boxes.  Boxes off those paths are untouched.
+// A hidden facet (s.hidden, mcpt_scene_set_visible) counts as its first vertex alone.
 void refit_bvh(Bvh& b, const BvhRefitIndex& ix, const HostScene& s, const std::vector<int32_t>& slots, double margin);
 
 // scene_io.cpp -- Myobj::get_unique_normal_of_facet (Myobj.cpp:680-709) of facet f into s.unique_n
@@ -184,6 +188,7 @@ struct RefitDev {
     uint8_t* node_dirty;        // nnodes
     unsigned* counters;         // [0] offending values (refit_validate_enqueue), [1] nodes refit
     int32_t F, nslots, nnodes;
+    uint8_t* hidden;            // F bytes, 1 = hidden (mcpt_scene_set_visible); null until the state's first mask
 };
 // counts into r.counters[0] the non-finite values of dpos / dnrm (count * 9 floats each, dnrm may be null) and the
 // positions outside [lo, hi]
@@ -204,6 +209,12 @@ int transform_enqueue(const RefitDev& r, const float* rest_v, const float* rest_
 // k_refit_level alone over every level, deepest first, on the dirty bytes the state holds (r.counters[1] cleared
 // first, the dirty bytes after): the tail of refit_enqueue, and how a rebuilt tree gets its boxes
 int refit_levels_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, double margin, void* stream);
+
+// mcpt_scene_set_visible on one device state (r.hidden must be set): k_visibility_scatter gives facets
+// [first, first + count) their mask byte and, from tri_v, every leaf slot its collapsed (v0, v0, v0) or full form with
+// the dirty byte; then refit_levels_enqueue
+int visibility_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, int32_t first, int32_t count, int32_t visible,
+                       double margin, void* stream);
 
 // light_tables.hip -- the device side of a light move (mcpt_scene_set_lights_movable): the device
 // pointers of one device state's light tables (owned by scene_state.h's DeviceState; the layouts are get_device_state's)

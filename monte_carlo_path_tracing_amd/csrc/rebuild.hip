@@ -60,21 +60,25 @@ __device__ inline double wave_max(double v) {
     return v;
 }
 
-// the centre of the facet's box on each axis, in double (exact: a sum of two floats halved)
-__device__ inline void facet_centroid(const float4* __restrict__ tri_v, int f, double c[3]) {
-    const float4 a = tri_v[3 * (size_t)f], b = tri_v[3 * (size_t)f + 1], d = tri_v[3 * (size_t)f + 2];
+// the centre of the facet's box on each axis, in double (exact: a sum of two floats halved); a hidden facet
+// (mcpt_scene_set_visible; hidden may be null) is its first vertex, where its collapsed slot sits
+__device__ inline void facet_centroid(const float4* __restrict__ tri_v, const uint8_t* __restrict__ hidden, int f, double c[3]) {
+    const float4 a = tri_v[3 * (size_t)f];
+    const bool hid = hidden && hidden[f];
+    const float4 b = hid ? a : tri_v[3 * (size_t)f + 1], d = hid ? a : tri_v[3 * (size_t)f + 2];
     c[0] = 0.5 * ((double)fminf(fminf(a.x, b.x), d.x) + (double)fmaxf(fmaxf(a.x, b.x), d.x));
     c[1] = 0.5 * ((double)fminf(fminf(a.y, b.y), d.y) + (double)fmaxf(fmaxf(a.y, b.y), d.y));
     c[2] = 0.5 * ((double)fminf(fminf(a.z, b.z), d.z) + (double)fmaxf(fmaxf(a.z, b.z), d.z));
 }
 
 // part: six arrays of nb doubles (lo x y z, hi x y z)
-__global__ __launch_bounds__(kRbBlock) void k_rb_bounds(const float4* __restrict__ tri_v, int F, int nb, double* __restrict__ part) {
+__global__ __launch_bounds__(kRbBlock) void k_rb_bounds(const float4* __restrict__ tri_v, const uint8_t* __restrict__ hidden, int F, int nb,
+                                                        double* __restrict__ part) {
     __shared__ double s[6][kRbBlock / 64];
     double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
     for (int f = blockIdx.x * kRbBlock + threadIdx.x; f < F; f += nb * kRbBlock) {
         double c[3];
-        facet_centroid(tri_v, f, c);
+        facet_centroid(tri_v, hidden, f, c);
 #pragma unroll
         for (int a = 0; a < 3; a++) lo[a] = fmin(lo[a], c[a]), hi[a] = fmax(hi[a], c[a]);
     }
@@ -113,12 +117,13 @@ __device__ inline uint64_t spread3(uint64_t x) {
     return x;
 }
 
-__global__ __launch_bounds__(kRbBlock) void k_rb_morton(const float4* __restrict__ tri_v, int F, const double* __restrict__ bounds,
+__global__ __launch_bounds__(kRbBlock) void k_rb_morton(const float4* __restrict__ tri_v, const uint8_t* __restrict__ hidden, int F,
+                                                        const double* __restrict__ bounds,
                                                         uint64_t* __restrict__ keys, int32_t* __restrict__ vals) {
     const int f = blockIdx.x * kRbBlock + threadIdx.x;
     if (f >= F) return;
     double c[3];
-    facet_centroid(tri_v, f, c);
+    facet_centroid(tri_v, hidden, f, c);
     uint64_t q[3];
 #pragma unroll
     for (int a = 0; a < 3; a++) {
@@ -238,15 +243,17 @@ __global__ __launch_bounds__(kRbBlock) void k_rb_root(int32_t* node_b, int32_t* 
     if (blockIdx.x == 0 && threadIdx.x == 0) node_b[0] = 0, node_e[0] = F, above[0] = 0;
 }
 
-// slot s holds facet vals[s]
-__global__ __launch_bounds__(kRbBlock) void k_rb_leaves(const float4* __restrict__ tri_v, const int32_t* __restrict__ vals, int F,
+// slot s holds facet vals[s]; a hidden facet's slot is collapsed to its first vertex (k_visibility_scatter's form)
+__global__ __launch_bounds__(kRbBlock) void k_rb_leaves(const float4* __restrict__ tri_v, const uint8_t* __restrict__ hidden,
+                                                        const int32_t* __restrict__ vals, int F,
                                                         float4* __restrict__ leaf_v, int32_t* __restrict__ slot_start,
                                                         int32_t* __restrict__ slot_list, uint8_t* __restrict__ slot_dirty) {
     const int s = blockIdx.x * kRbBlock + threadIdx.x;
     if (s >= F) return;
     const int f = vals[s];
     float4 v0 = tri_v[3 * (size_t)f];
-    const float4 v1 = tri_v[3 * (size_t)f + 1], v2 = tri_v[3 * (size_t)f + 2];
+    const bool hid = hidden && hidden[f];
+    const float4 v1 = hid ? v0 : tri_v[3 * (size_t)f + 1], v2 = hid ? v0 : tri_v[3 * (size_t)f + 2];
     v0.w = __int_as_float(f);
     leaf_v[3 * (size_t)s] = v0;
     leaf_v[3 * (size_t)s + 1] = make_float4(v1.x, v1.y, v1.z, 0.f);
@@ -380,9 +387,9 @@ int rebuild_build(RebuildWork* w, RefitDev* out, int leaf_max, int stack_cap, do
     const float4* tri_v = reinterpret_cast<const float4*>(out->tri_v);
     const int fblocks = (F + kRbBlock - 1) / kRbBlock, nb = std::min(fblocks, kRbMaxPartials);
     double* bounds = w->part + 6 * (size_t)kRbMaxPartials;
-    hipLaunchKernelGGL(k_rb_bounds, dim3(nb), dim3(kRbBlock), 0, st, tri_v, F, nb, w->part);
+    hipLaunchKernelGGL(k_rb_bounds, dim3(nb), dim3(kRbBlock), 0, st, tri_v, out->hidden, F, nb, w->part);
     hipLaunchKernelGGL(k_rb_bounds_final, dim3(1), dim3(64), 0, st, w->part, nb, bounds);
-    hipLaunchKernelGGL(k_rb_morton, dim3(fblocks), dim3(kRbBlock), 0, st, tri_v, F, bounds, w->keys0, w->vals0);
+    hipLaunchKernelGGL(k_rb_morton, dim3(fblocks), dim3(kRbBlock), 0, st, tri_v, out->hidden, F, bounds, w->keys0, w->vals0);
     RB_HIP_OK(hipGetLastError());
     size_t tb = w->temp_bytes;
     RB_HIP_OK(rocprim::radix_sort_pairs(w->temp, tb, w->keys0, w->keys1, w->vals0, w->vals1, (size_t)F, 0, 63, st));
@@ -427,7 +434,8 @@ int rebuild_build(RebuildWork* w, RefitDev* out, int leaf_max, int stack_cap, do
         return MCPT_E_SCENE;
     }
     out->nnodes = lf.back();
-    hipLaunchKernelGGL(k_rb_leaves, dim3(fblocks), dim3(kRbBlock), 0, st, tri_v, w->vals1, F, reinterpret_cast<float4*>(out->leaf_v),
+    hipLaunchKernelGGL(k_rb_leaves, dim3(fblocks), dim3(kRbBlock), 0, st, tri_v, out->hidden, w->vals1, F,
+                       reinterpret_cast<float4*>(out->leaf_v),
                        const_cast<int32_t*>(out->slot_start), const_cast<int32_t*>(out->slot_list), out->slot_dirty);
     RB_HIP_OK(hipGetLastError());
     RB_HIP_OK(hipMemsetAsync(out->node_dirty, 0, (size_t)out->nnodes, st));

@@ -7,6 +7,8 @@
 //   k_transform_range (mcpt_scene_transform, §4.21) an affine map of a facet range of the rest pose into the staging
 //                     arrays, counting the same offenders; the host reads the count before the scatter is enqueued;
 //   k_refit_scatter   one thread per facet of the range: tri_v, tri_n, every leaf slot of the facet, its dirty byte;
+//   k_visibility_scatter (mcpt_scene_set_visible, §4.28) one thread per facet of the range: its mask byte and, from
+//                     tri_v, every leaf slot collapsed to the first vertex or restored, its dirty byte;
 //   k_refit_level     one launch per tree level, deepest first, one thread per node: a leaf child with a dirty slot
 //                     gets the union of the full bounds of all its triangles, enlarged by the build's margin; an
 //                     inner child whose node is dirty gets the union of that node's slot boxes; a node with a
@@ -93,7 +95,36 @@ __global__ __launch_bounds__(kRefitBlock) void k_refit_scatter(RefitDev r, int f
     tv[0] = v0;
     tv[1] = v1;
     tv[2] = v2;
+    // a hidden facet (mcpt_scene_set_visible) keeps its new values in tri_v; its slots hold the new v0 three times
+    const bool hid = r.hidden && r.hidden[f];
+    const float4 s1 = hid ? v0 : v1, s2 = hid ? v0 : v2;
     v0.w = __int_as_float(f);  // the facet id bits of the slot's first vertex
+    for (int q = r.slot_start[f]; q < r.slot_start[f + 1]; q++) {
+        const int s = r.slot_list[q];
+        float4* lv = reinterpret_cast<float4*>(r.leaf_v) + 3 * (size_t)s;
+        lv[0] = v0;
+        lv[1] = s1;
+        lv[2] = s2;
+        r.slot_dirty[s] = 1;
+    }
+}
+
+// mcpt_scene_set_visible (include/mcpt.h): one thread per facet of the range, from tri_v (three
+// consecutive float4 per lane).  A facet whose byte already says `hide` is left alone.  A hidden facet's slots hold its
+// first vertex three times (both triangle tests reject a zero determinant exactly), a visible one's its vertices; the
+// facet id bits stay in the first .w.  k_refit_level then shrinks or regrows the boxes from the slots as they are.
+__global__ __launch_bounds__(kRefitBlock) void k_visibility_scatter(RefitDev r, int first, int count, int hide) {
+    const int i = blockIdx.x * kRefitBlock + (int)threadIdx.x;
+    if (i >= count) return;
+    const int f = first + i;
+    if ((r.hidden[f] != 0) == (hide != 0)) return;
+    r.hidden[f] = hide ? 1 : 0;
+    const float4* tv = reinterpret_cast<const float4*>(r.tri_v) + 3 * (size_t)f;
+    float4 v0 = tv[0];
+    float4 v1 = tv[1], v2 = tv[2];
+    v0.w = 0.0f, v1.w = 0.0f, v2.w = 0.0f;
+    if (hide) v1 = v0, v2 = v0;
+    v0.w = __int_as_float(f);
     for (int q = r.slot_start[f]; q < r.slot_start[f + 1]; q++) {
         const int s = r.slot_list[q];
         float4* lv = reinterpret_cast<float4*>(r.leaf_v) + 3 * (size_t)s;
@@ -347,6 +378,18 @@ int refit_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, in
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(k_refit_scatter, dim3((count + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, r, first, count,
                        dpos, dnrm);
+    return refit_levels_enqueue(r, level_first, nlevels, margin, stream);
+}
+
+int visibility_enqueue(const RefitDev& r, const int32_t* level_first, int nlevels, int32_t first, int32_t count, int32_t visible,
+                       double margin, void* stream) {
+    if (first < 0 || count < 1 || (int64_t)first + count > r.F || !r.hidden) {
+        set_error("visibility: range or mask do not match the device state");
+        return MCPT_E_INVALID;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_visibility_scatter, dim3((count + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, st, r, first, count,
+                       visible ? 0 : 1);
     return refit_levels_enqueue(r, level_first, nlevels, margin, stream);
 }
 

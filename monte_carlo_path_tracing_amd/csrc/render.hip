@@ -4855,10 +4855,11 @@ std::vector<float4> leaf_vertices(const HostScene& s, const Bvh& b) {
     for (size_t q = 0; q < b.leaf_facets.size(); q++) {
         const int f = b.leaf_facets[q];
         for (int k = 0; k < 3; k++) {
+            const int kv = s.is_hidden(f) ? 0 : k;  // a hidden facet's slot: its first vertex three times (§4.28)
             float4 x;
-            x.x = s.pos[9 * f + 3 * k];
-            x.y = s.pos[9 * f + 3 * k + 1];
-            x.z = s.pos[9 * f + 3 * k + 2];
+            x.x = s.pos[9 * f + 3 * kv];
+            x.y = s.pos[9 * f + 3 * kv + 1];
+            x.z = s.pos[9 * f + 3 * kv + 2];
             int fb = f;
             float w;
             std::memcpy(&w, &fb, 4);
@@ -5325,6 +5326,7 @@ hipError_t launch_prep(int variant, const DScene& d, uint64_t seed, int n, const
 // render_multi calls it on the calling thread before its device workers start, so the workers only
 // find an up-to-date grid and read it)
 int ensure_host_grid(mcpt_scene* sc, const double eye[3], int n0) {
+    if (int rh = hidden_refused(sc, "MCPT_ACCEL_GRID / MCPT_HIT_GRID")) return rh;
     if (int rs = host_sync(sc)) return rs;  // the grid is built from host.pos (and a sync drops a stale grid)
     Grid& g = sc->grid;
     if (!g.ok || g.n0 != n0 || g.eye[0] != eye[0] || g.eye[1] != eye[1] || g.eye[2] != eye[2]) {
@@ -5379,6 +5381,12 @@ int mcpt::bvh8_refused(const mcpt_scene* sc) {
     if (!sc->updated) return MCPT_OK;
     set_error("the 8-wide trees are not refit by mcpt_scene_update: MCPT_DEBUG_RAYS_CW8, MCPT_DEBUG_HIT_CW8 and "
               "mcpt_debug_bvh8_check are refused for a scene handle after its first update");
+    return MCPT_E_INVALID;
+}
+int mcpt::hidden_refused(const mcpt_scene* sc, const char* what) {
+    if (sc->hidden_count == 0) return MCPT_OK;
+    set_error("%s is refused while facets are hidden (%d are; mcpt_scene_set_visible): the reference grid's in-cell rule "
+              "depends on the scene's box, so a grid without them would not be the reference's", what, sc->hidden_count);
     return MCPT_E_INVALID;
 }
 namespace {
@@ -7955,6 +7963,7 @@ int mcpt_scene_meshing(mcpt_scene* sc, const double eye[3], int32_t n0) {
         return MCPT_E_INVALID;
     }
     std::lock_guard<std::mutex> lk(sc->mu);
+    if (int rh = hidden_refused(sc, "mcpt_scene_meshing")) return rh;
     if (int rs = host_sync(sc)) return rs;
     sc->grid = build_grid(sc->host, eye, n0);
     sc->grid_version++;
@@ -7999,6 +8008,7 @@ int mcpt_closest_hit(mcpt_scene* sc, int32_t n, const double* ro, const double* 
     if ((rc = get_device_state(sc, -1, &D))) return rc;
     const bool grid = (flags & MCPT_HIT_GRID) != 0;
     if (grid) {
+        if ((rc = hidden_refused(sc, "MCPT_HIT_GRID"))) return rc;
         if (!sc->grid.ok) {
             set_error("MCPT_HIT_GRID: no grid (call mcpt_scene_meshing first)");
             return MCPT_E_INVALID;

@@ -1,6 +1,7 @@
 // Scene editing: everything that changes a loaded scene's geometry in place and keeps the host copy, the device
 // states and their trees in step -- mcpt_scene_update[_device], movable lights, mcpt_scene_pose_save / _rest_save,
-// mcpt_scene_transform with the lazily synced host copy, mcpt_scene_rebuild and mcpt_scene_tree_cost -- and what its
+// mcpt_scene_transform with the lazily synced host copy, mcpt_scene_rebuild and mcpt_scene_tree_cost, the facet
+// visibility of mcpt_scene_set_visible -- and what its
 // lights and surfaces look like: mcpt_scene_set_light_radiance[_device], mcpt_scene_set_materials (include/mcpt.h).
 // Host code only: the kernels are refit.hip's, light_tables.hip's and rebuild.hip's.  Locks are taken in the order
 // mu, host_mu, devs_mu; every function that visits device states leaves the caller's device current (DeviceRestore).
@@ -229,6 +230,19 @@ int mcpt::ensure_refit_state(mcpt_scene* sc, DeviceState& D) {
     if (D.refit.ready) return MCPT_OK;
     if (int rc = build_tree_refit(D, D.refit, D.d.bvh4, D.d.bvh4q, D.d.nbvh4, D.d.leaf_v, D.nslots, sc->slots, "")) return rc;
     D.refit.ready = true;
+    return ensure_hidden_state(sc, D);
+}
+// the state's copy of the handle's visibility mask, made from the host's bytes as they are -- a
+// state's slots were written under exactly that mask, by get_device_state or by the calls since -- and handed to the
+// refit state if there is one.  Nothing to do for a handle that never hid a facet: the pointer stays null.
+int mcpt::ensure_hidden_state(mcpt_scene* sc, DeviceState& D) {
+    const std::vector<uint8_t>& h = sc->host.hidden;
+    if (h.empty()) return MCPT_OK;
+    if (!D.hidden.p) {
+        if (int rc = ensure(D.hidden, h.size())) return rc;
+        HIP_OK(hipMemcpy(D.hidden.p, h.data(), h.size(), hipMemcpyHostToDevice));
+    }
+    if (D.refit.ready) D.refit.dev.hidden = (uint8_t*)D.hidden.p;
     return MCPT_OK;
 }
 
@@ -879,6 +893,84 @@ int mcpt_scene_host_sync(mcpt_scene* sc) {
     return host_sync(sc);
 }
 
+// ---- mcpt_scene_set_visible and mcpt_scene_visibility (include/mcpt.h; the kernel is refit.hip's) ----
+int mcpt_scene_set_visible(mcpt_scene* sc, int32_t first, int32_t count, int32_t visible, mcpt_update_stats* stats) {
+    static const char* who = "mcpt_scene_set_visible";
+    int rc;
+    if ((rc = refuse_null(who, sc))) return rc;
+    if (count < 1 || first < 0 || (int64_t)first + count > sc->host.F) {
+        set_error("%s: facets [%d, %lld) are not a non-empty range of the scene's %d facets", who, first, (long long)first + count,
+                  sc->host.F);
+        return MCPT_E_INVALID;
+    }
+    if ((rc = check_struct_size(stats, "mcpt_update_stats"))) return rc;
+    std::lock_guard<std::mutex> lk(sc->mu);
+    HostScene& hs = sc->host;
+    for (int f = first; f < first + count; f++)
+        if (hs.light_of[f] >= 0) {
+            set_error("%s: facet %d is a light triangle (light %d); lights cannot be hidden (mcpt_scene_set_light_radiance "
+                      "with zeros switches one off)", who, f, hs.light_of[f]);
+            return MCPT_E_INVALID;
+        }
+    if ((rc = host_sync(sc))) return rc;  // the host refit reads every triangle of a touched leaf
+    ensure_slot_map(sc, false);
+    if (hs.hidden.empty()) hs.hidden.assign((size_t)hs.F, 0);
+    // every state's mask and refit state while the host's bytes are still the ones its slots were written under
+    const std::vector<DeviceState*> devs = device_states(sc);
+    DeviceRestore back;
+    if (!devs.empty()) HIP_OK(hipGetDevice(&back.device));
+    for (DeviceState* D : devs) {
+        HIP_OK(hipSetDevice(D->device));
+        if ((rc = ensure_refit_state(sc, *D)) || (rc = ensure_hidden_state(sc, *D))) return rc;
+    }
+    // the host copy first: it stays the truth for device states made later and for the debug checks
+    const uint8_t hide = visible ? 0 : 1;
+    for (int f = first; f < first + count; f++) {
+        sc->hidden_count += (int32_t)hide - (int32_t)hs.hidden[f];
+        hs.hidden[f] = hide;
+    }
+    const std::vector<int32_t> slots(sc->slots.list.begin() + sc->slots.start[first], sc->slots.list.begin() + sc->slots.start[first + count]);
+    refit_bvh(sc->bvh, sc->slots.ix, hs, slots, sc->margin);
+    sc->grid.ok = false;  // refused while anything is hidden, rebuilt by the next grid-mode call after that
+    sc->updated = true;   // the 8-wide trees are stale from here on (bvh8_refused)
+    mcpt_update_stats st;
+    mcpt_update_stats_init(&st);
+    st.facets = count;
+    st.leaf_slots = (int64_t)slots.size();
+    for (DeviceState* D : devs) {
+        HIP_OK(hipSetDevice(D->device));
+        // work of other streams (the caller's, a frame sequence's) that still reads these arrays
+        HIP_OK(hipDeviceSynchronize());
+        HIP_OK(hipEventRecord(D->ev0, D->stream));
+        if ((rc = visibility_enqueue(D->refit.dev, D->refit.level_first.data(), (int)D->refit.level_first.size() - 1, first, count, visible,
+                                     sc->margin, D->stream)))
+            return rc;
+        HIP_OK(hipEventRecord(D->ev1, D->stream));
+        HIP_OK(hipStreamSynchronize(D->stream));
+        if (st.device_states++ == 0) {
+            float ms = 0;
+            unsigned n = 0;
+            HIP_OK(hipEventElapsedTime(&ms, D->ev0, D->ev1));
+            HIP_OK(hipMemcpy(&n, D->refit.dev.counters + 1, sizeof n, hipMemcpyDeviceToHost));
+            st.device_seconds = 1e-3 * ms;
+            st.nodes_refit = n;
+            st.levels = (int32_t)D->refit.level_first.size() - 1;
+        }
+    }
+    if (stats) *stats = st;
+    return MCPT_OK;
+}
+
+int mcpt_scene_visibility(const mcpt_scene* sc, uint8_t* visible, int32_t* hidden) {
+    if (int rn = refuse_null("mcpt_scene_visibility", sc)) return rn;
+    mcpt_scene* w = const_cast<mcpt_scene*>(sc);
+    std::lock_guard<std::mutex> lk(w->mu);
+    if (visible)
+        for (int f = 0; f < sc->host.F; f++) visible[f] = sc->host.is_hidden(f) ? 0 : 1;
+    if (hidden) *hidden = sc->hidden_count;
+    return MCPT_OK;
+}
+
 // ---- mcpt_scene_rebuild and mcpt_scene_tree_cost (include/mcpt.h; the kernels are rebuild.hip's) ----
 void mcpt_rebuild_stats_init(mcpt_rebuild_stats* st) { stats_init(st); }
 
@@ -918,6 +1010,9 @@ static int rebuild_state(mcpt_scene* sc, DeviceState& D, mcpt_rebuild_stats* st)
     r.slot_dirty = (uint8_t*)S.slot_dirty.p;
     r.node_dirty = (uint8_t*)S.node_dirty.p;
     r.counters = (unsigned*)D.rb_counters.p;
+    // hidden facets stay in the tree, at their points with collapsed slots; both sets carry the mask
+    if ((rc = ensure_hidden_state(sc, D))) return rc;
+    r.hidden = (uint8_t*)D.hidden.p;
     // work of other streams (the caller's, a frame sequence's) that still reads the arrays of the set built two
     // rebuilds ago, or writes tri_v
     HIP_OK(hipDeviceSynchronize());

@@ -153,6 +153,9 @@ struct DeviceState {
     // every level of the breadth-first 4-wide tree) and the staging copies of a host call's arrays
     TreeRefit refit;
     DevBuf up_pos, up_nrm;
+    // mcpt_scene_set_visible: the state's copy of host.hidden (F bytes), allocated with the refit state
+    // of a handle that has a mask or at the state's first visibility call; refit.dev.hidden points at it from then on
+    DevBuf hidden;
     // a light move on this device, built at the state's first one: the light tables' pointers for
     // light_tables.hip, a second TreeRefit over the light-only tree (lbvh4, lbvh4q, lleaf_v; tri_v / tri_n shared with
     // `refit`) with its own slot map, dirty bytes, counters and levels, a pinned copy of the by-value constants and
@@ -225,6 +228,8 @@ struct mcpt_scene {
     double build_lo[3] = {0, 0, 0}, build_hi[3] = {0, 0, 0}, build_ext = 0, margin = 0;
     bool updated = false;
     mcpt::SlotMap slots;
+    // mcpt_scene_set_visible: how many bytes of host.hidden are set
+    int32_t hidden_count = 0;
     // mcpt_scene_set_lights_movable: the switch, the numbers of the last successful update / transform
     // call, and the same index and slot map for `lbvh`, built at the first light move
     bool lights_movable = false;
@@ -268,6 +273,7 @@ int check_device_buffer(const void* p, int device, const char* name = "dev_out_r
 int prep_chunks(int NL);
 void ensure_bvh8_host(mcpt_scene* sc);
 int bvh8_refused(const mcpt_scene* sc);
+int hidden_refused(const mcpt_scene* sc, const char* what);  // the grid modes while facets are hidden (§4.28)
 extern std::atomic<int> g_rebuild_leaf_max;
 
 // a host array as a buffer of its own that D owns, even if the copy fails
@@ -291,6 +297,7 @@ std::vector<DeviceState*> device_states(mcpt_scene* sc);
 int host_sync(mcpt_scene* sc);
 void ensure_slot_map(mcpt_scene* sc, bool light_tree);
 int ensure_refit_state(mcpt_scene* sc, DeviceState& D);
+int ensure_hidden_state(mcpt_scene* sc, DeviceState& D);
 int ensure_light_tables(mcpt_scene* sc, DeviceState& D);
 int ensure_light_state(mcpt_scene* sc, DeviceState& D);
 

@@ -123,6 +123,15 @@ static void bvh4_walk(const std::vector<BvhNode4>& b4, const std::vector<BvhNode
     out[4] = bad;
     out[5] = maxd;
 }
+// the positions the trees are checked against: the host's, with a hidden facet (mcpt_scene_set_visible, DESIGN.md
+// §4.28) as the collapsed triangle its leaf slots hold -- its first vertex three times; the host's own when none is
+static std::vector<float> slot_positions(const HostScene& hs) {
+    std::vector<float> pos(hs.pos);
+    for (int f = 0; f < hs.F; f++)
+        if (hs.is_hidden(f))
+            for (int k = 1; k < 3; k++) std::copy_n(&hs.pos[9 * (size_t)f], 3, &pos[9 * (size_t)f + 3 * k]);
+    return pos;
+}
 int mcpt_debug_bvh4_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
     if (!sc || !out) {
         set_error("invalid argument");
@@ -132,7 +141,7 @@ int mcpt_debug_bvh4_check(mcpt_scene* sc, int32_t light_only, int64_t* out) {
     if (int rs = host_sync(sc)) return rs;
     const Bvh& bb = light_only ? sc->lbvh : sc->bvh;
     const std::vector<BvhNode4> b4 = collapse_bvh4(bb);
-    bvh4_walk(b4, quantize_bvh4(b4), bb.leaf_facets, sc->host.pos, out);
+    bvh4_walk(b4, quantize_bvh4(b4), bb.leaf_facets, slot_positions(sc->host), out);
     return MCPT_OK;
 }
 
@@ -182,17 +191,19 @@ static int bvh4_check_device(mcpt_scene* sc, int32_t device, bool light_only, in
     DeviceTree t;
     int rc;
     if ((rc = download_tree(sc, device, true, &t, light_only))) return rc;
-    const std::vector<float>& pos = sc->host.pos;
+    // a hidden facet's slot must hold its collapsed form and a visible facet's its triangle: either way round is an error
+    const std::vector<float> pos = slot_positions(sc->host);
     bvh4_walk(t.b4, t.q4, t.leaf_facets, pos, out);
-    // the device's own copies of the vertices against the host's
-    auto differs = [&](const float4* v, int f) {
+    // the device's own copies of the vertices against the host's: the slots against the slot form, the facet array
+    // against the stored values (a hidden facet keeps them)
+    auto differs = [&](const float4* v, const std::vector<float>& p, int f) {
         int64_t n = 0;
-        for (int k = 0; k < 3; k++) n += std::memcmp(&v[k].x, &pos[9 * (size_t)f + 3 * k], 12) != 0;
+        for (int k = 0; k < 3; k++) n += std::memcmp(&v[k].x, &p[9 * (size_t)f + 3 * k], 12) != 0;
         return n;
     };
     for (size_t q = 0; q < t.leaf_facets.size(); q++)
-        if (t.leaf_facets[q] >= 0 && t.leaf_facets[q] < sc->host.F) out[4] += differs(&t.leaf_v[3 * q], t.leaf_facets[q]);
-    for (int f = 0; f < sc->host.F; f++) out[4] += differs(&t.tri_v[3 * (size_t)f], f);
+        if (t.leaf_facets[q] >= 0 && t.leaf_facets[q] < sc->host.F) out[4] += differs(&t.leaf_v[3 * q], pos, t.leaf_facets[q]);
+    for (int f = 0; f < sc->host.F; f++) out[4] += differs(&t.tri_v[3 * (size_t)f], sc->host.pos, f);
     return MCPT_OK;
 }
 int mcpt_debug_light_tables(mcpt_scene* sc, int32_t device, const char* which, void* out, int64_t cap, int64_t* bytes) {
