@@ -497,19 +497,31 @@ __device__ inline double light_weight_bf(d3 p0, d3 p1, d3 p2, double lsum2, d3 x
 #ifndef MCPT_BAND_TAU
 #define MCPT_BAND_TAU 300.0
 #endif
+// Where survivor counts are reported (mcpt_light_prep: `flag` = kBandFlagCounts) tiny triangles are flagged with them
+// -- tau num - (4 - den) < kBandTiny, the same FMA and compare against another value.  The reference's sA carries
+// ~u / (shortest edge angle) <= u sqrt(2x) / num of rounding whatever the shape (the unit vectors' rounding, amplified
+// in the normalised cross products), so a well-shaped triangle below ~1e-5 rad has a reference sA that is mostly noise
+// and may come out negative: the reference then culls a light that this form keeps, and the counts differ (a tiny
+// distant light next to ordinary ones).  The flagged ones get the sliver's term and its test against
+// the reference's error, 2 w < 64 u t.  An unflagged triangle has x < tau num and num >= kBandTiny / tau, and is clear
+// of that test when sA >= num / 2 (den <= 4) exceeds 64 u sqrt(2 tau num) / num, i.e. num > (128 u sqrt(2 tau))^(2/3)
+// = 5.0e-9: kBandTiny >= 1.5e-6; 2^-19 = 1.9e-6.  The renderer reports no counts and keeps 4 (kBandFlag): its picks
+// among such lights are the per-chunk bound's.
+constexpr double kBandTiny = 0x1.0p-19;
+constexpr double kBandFlag = 4.0, kBandFlagCounts = 4.0 + kBandTiny;
 struct WeightBx {
     double w;     // weight (0 if culled)
     double num;   // |A.(B x C)|
     double den;   // 1 + A.B + B.C + C.A
     bool ok;      // survives the full stage
-    bool sliver;  // 4 - den > kBandTau num
+    bool sliver;  // kBandTau num + den < flag
 };
 template <bool kPrepBatch = false>
-__device__ inline WeightBx light_weight_bx(d3 p0, d3 p1, d3 p2, double lsum2, d3 x1) {
+__device__ inline WeightBx light_weight_bx(d3 p0, d3 p1, d3 p2, double lsum2, d3 x1, double flag = kBandFlag) {
     const SphEx e = sph_excess<kPrepBatch>(sub(p0, x1), sub(p1, x1), sub(p2, x1));
     const double w = e.half * lsum2;
     const bool good = e.edges_ok & (e.half > 0) & __builtin_amdgcn_class(w, 0x1e0);
-    return WeightBx{good ? w : 0.0, e.num, e.den, good, fma(MCPT_BAND_TAU, e.num, e.den) < 4.0};
+    return WeightBx{good ? w : 0.0, e.num, e.den, good, fma(MCPT_BAND_TAU, e.num, e.den) < flag};
 }
 // the sliver's error term (without the factor u lsum2 / 2 applied by the caller): sqrt(2x) / num,
 // x = 4 - den, from the hardware rsqrt / rcp estimates (~1e-7 relative), rounded up by 1% (a bound

@@ -1883,7 +1883,7 @@ __global__ __launch_bounds__(256) void k_prep(DScene S, uint64_t seed, int n, co
                 bool ok = false;
                 if (act) {
                     const PrepLight L = load_light(S, lj);
-                    const WeightBx r = light_weight_bx(L.p0, L.p1, L.p2, L.lsum2, x1);
+                    const WeightBx r = light_weight_bx(L.p0, L.p1, L.p2, L.lsum2, x1, exact_counts ? kBandFlagCounts : kBandFlag);
                     ok = r.ok;
                     w = r.w;
                     if (ok && r.sliver) {
@@ -2053,7 +2053,7 @@ __device__ inline double prep_weight_buf(__amdgpu_buffer_rsrc_t rw, int li, d3 x
                            mk3(u2d(d.x, d.y), u2d(d.z, d.w), u2d(e.x, e.y)), u2d(e.z, e.w), x1, ok);
 }
 // prep_weight_buf with the exact-pick bookkeeping (light_weight_bx); *lsum2 = the record's 2 sum L
-__device__ inline WeightBx prep_weight_buf_bx(__amdgpu_buffer_rsrc_t rw, int li, d3 x1, double* lsum2) {
+__device__ inline WeightBx prep_weight_buf_bx(__amdgpu_buffer_rsrc_t rw, int li, d3 x1, double* lsum2, double flag) {
     const v4u a = struct_load_b128(rw, li, 0, 0, 0);
     const v4u b = struct_load_b128(rw, li, 16, 0, 0);
     const v4u c = struct_load_b128(rw, li, 32, 0, 0);
@@ -2062,7 +2062,7 @@ __device__ inline WeightBx prep_weight_buf_bx(__amdgpu_buffer_rsrc_t rw, int li,
     *lsum2 = u2d(e.z, e.w);
     return light_weight_bx<true>(mk3(u2d(a.x, a.y), u2d(a.z, a.w), u2d(b.x, b.y)),
                                  mk3(u2d(b.z, b.w), u2d(c.x, c.y), u2d(c.z, c.w)),
-                                 mk3(u2d(d.x, d.y), u2d(d.z, d.w), u2d(e.x, e.y)), u2d(e.z, e.w), x1);
+                                 mk3(u2d(d.x, d.y), u2d(d.z, d.w), u2d(e.x, e.y)), u2d(e.z, e.w), x1, flag);
 }
 // fp32 records (MCPT_RENDER_PRECISION_FP32, LightF32): 10 floats at a 64-B stride (a record never
 // straddles a cache line), the same padding and sentinels as lt_w
@@ -2687,6 +2687,7 @@ __global__ __launch_bounds__(256, kMinWavesPerSimd) void k_prep_pk2(DScene S, ui
         int nbad = 0;
         double sacc = 0;  // flagged slivers' error terms (this lane's candidates)
         int ndeg = 0;     // near-degenerate slivers (this lane's)
+        const double flag = C.exact_counts ? kBandFlagCounts : kBandFlag;  // light_weight_bx: counts flag tiny triangles too
         const NodeF32 xf = node_f32(x1);
         // the stash rows follow the padded list: row b = the 64 weights of batch b, for the m first batches
         double* stash = reinterpret_cast<double*>(lst + 64 * nb);
@@ -2723,7 +2724,7 @@ __global__ __launch_bounds__(256, kMinWavesPerSimd) void k_prep_pk2(DScene S, ui
                 if (b0 + i < nb) {  // wave-uniform
                     const int k = 64 * (b0 + i) + lane;
                     double l2;
-                    const WeightBx r = prep_weight_buf_bx(rw, (int)lst[k], x1, &l2);  // w = 0 if culled
+                    const WeightBx r = prep_weight_buf_bx(rw, (int)lst[k], x1, &l2, flag);  // w = 0 if culled
                     if (kStash && b0 + i < m) stash[k] = r.ok ? r.w : -1.0;  // wave-uniform; read back by the pick
                     if (kBuild) {  // in-batch inclusive prefix, culled with the sign bit (PrepCache::w)
                         const double sc = wave_incl_scan(r.ok ? r.w : 0.0, lane);

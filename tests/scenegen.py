@@ -121,16 +121,11 @@ def sphere_mix(outdir):
     return _write(outdir, "sphmix", obj, mtls, lights, CAM)
 
 
-def slivers(outdir, strips=24):
-    """Lights seen nearly edge-on from the floor: vertical light blinds (planes x = const, split into
-    long thin triangles) standing on the floor region, whose planes pass through the floor points next
-    to them -- their spherical triangles are slivers (one vertex angle near pi), where the reference's
-    alpha + beta + gamma - pi is decided by the last bits of its acos; plus a panel tilted 2 degrees
-    off the vertical (near-grazing for the points below it)."""
-    obj, mtls = gv.Obj(), []
-    _floor(obj, mtls)
+def _blinds(obj, xs, strips):
+    """the faces of vertical light blinds in the planes x = xk (two thin layers each, facing +x and -x), `strips` long
+    thin quads high"""
     faces = []
-    for xk in (-1.2, -0.4, 0.4, 1.2):
+    for xk in xs:
         for side in (1.0, -1.0):  # two thin layers facing +x and -x
             x = xk + 0.002 * side
             n = obj.normal((side, 0.0, 0.0))
@@ -142,7 +137,31 @@ def slivers(outdir, strips=24):
                 if side < 0:
                     tri = [(a, c, b), (a, d, c)]
                 faces += [tuple((v, n) for v in t) for t in tri]
-    obj.groups.append(("blinds", "blinds", faces))
+    return faces
+
+
+def _tiny_lights(obj, mtls, lights, radii, places):
+    """8x4 sphere lights "tinyNN" of every radius at every (distance above the floor, azimuth)"""
+    k = 0
+    for r in radii:
+        for dist, az in places:
+            name = "tiny%02d" % k
+            c = (dist * 0.3 * math.cos(az), dist, dist * 0.3 * math.sin(az))
+            obj.sphere(name, name, c, r, 8, 4)
+            mtls.append((name, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.0))
+            lights.append((name, (4000.0, 3000.0, 2000.0)))
+            k += 1
+
+
+def slivers(outdir, strips=24):
+    """Lights seen nearly edge-on from the floor: vertical light blinds (planes x = const, split into
+    long thin triangles) standing on the floor region, whose planes pass through the floor points next
+    to them -- their spherical triangles are slivers (one vertex angle near pi), where the reference's
+    alpha + beta + gamma - pi is decided by the last bits of its acos; plus a panel tilted 2 degrees
+    off the vertical (near-grazing for the points below it)."""
+    obj, mtls = gv.Obj(), []
+    _floor(obj, mtls)
+    obj.groups.append(("blinds", "blinds", _blinds(obj, (-1.2, -0.4, 0.4, 1.2), strips)))
     faces = []
     t = math.radians(2.0)
     n = obj.normal((math.cos(t), math.sin(t), 0.0))
@@ -164,15 +183,7 @@ def tiny_far(outdir):
     obj, mtls = gv.Obj(), []
     _floor(obj, mtls)
     lights = []
-    k = 0
-    for r in (1e-2, 1e-3, 1e-4, 1e-6):
-        for dist, az in ((20.0, 0.3), (45.0, 1.9), (90.0, 4.0)):
-            name = "tiny%02d" % k
-            c = (dist * 0.3 * math.cos(az), dist, dist * 0.3 * math.sin(az))
-            obj.sphere(name, name, c, r, 8, 4)
-            mtls.append((name, (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.0))
-            lights.append((name, (4000.0, 3000.0, 2000.0)))
-            k += 1
+    _tiny_lights(obj, mtls, lights, (1e-2, 1e-3, 1e-4, 1e-6), ((20.0, 0.3), (45.0, 1.9), (90.0, 4.0)))
     obj.sphere("lamp", "lamp", (1.2, 2.2, -0.8), 0.25, 16, 8)
     mtls.append(("lamp", (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.0))
     lights.append(("lamp", (5.0, 5.0, 5.0)))
@@ -556,3 +567,57 @@ def stress_rays(arrays, family, seed=11):
         raise ValueError(family)
     rd[-1] = np.nan
     return np.ascontiguousarray(ro), np.ascontiguousarray(rd), np.asarray(ex, np.int32)
+
+
+# ---- light-prep stress: lights whose cull thresholds a shading point can sit on, at any place and size ----
+# (tests/prepcases.py, tests/test_prep_stress.py, tests/test_prep_stress_cpu.py)
+PREP_KINDS = ("plain", "hard", "few")
+PREP_PANEL = {"plain": (14, 13), "hard": (14, 13), "few": (5, 6)}  # quads of the light panel
+PREP_BLINDS, PREP_STRIPS = (-0.4, 1.2), 6
+# light triangles per kind: the panel, the 16 x 8 sphere, and for "hard" the blinds and four 8 x 4 tiny spheres
+PREP_NLIGHTS = {"plain": 2 * 14 * 13 + 224, "hard": 2 * 14 * 13 + 224 + len(PREP_BLINDS) * 2 * PREP_STRIPS * 2 + 4 * 48,
+                "few": 2 * 5 * 6}
+
+
+def prep_stress(outdir, offset=(0, 0, 0), scale=1.0, kind="plain"):
+    """The floor and block under lights, written at scale * (p + offset) with every digit (offset in units of the
+    scaled scene's own unit, as ray_stress's is; the scene is about 8 units wide), the XML camera moved with it.
+      plain  a down-facing light panel of 14 x 13 quads, tilted 0.1 in x (no light normal is an axis; its corners at
+             (+x, -z) and (-x, +z) belong to one triangle each), and a 16 x 8 sphere light low beside the block: 588
+             light triangles, 10 chunks; from the floor and the block's faces chunks lie above, below and across the
+             tangent plane;
+      hard   plain plus two of slivers' edge-on blinds and four of tiny_far's tiny distant lights;
+      few    the panel alone with 5 x 6 quads: 60 light triangles (k_prep_lane)."""
+    if kind not in PREP_KINDS:
+        raise ValueError(kind)
+    obj, mtls, lights = _ObjExact(), [], []
+    _floor(obj, mtls)
+    nx, nz = PREP_PANEL[kind]
+    faces = []
+    n = obj.normal(gv.norm((0.1, -1.0, 0.0)))
+    x0, x1, z0, z1 = -1.5, 1.5, -1.5, 1.5
+    for i in range(nx):
+        for k in range(nz):
+            xa, xb = x0 + (x1 - x0) * i / nx, x0 + (x1 - x0) * (i + 1) / nx
+            za, zb = z0 + (z1 - z0) * k / nz, z0 + (z1 - z0) * (k + 1) / nz
+            a, b = obj.vert((xa, 2.5 + 0.1 * xa, za)), obj.vert((xb, 2.5 + 0.1 * xb, za))
+            c, d = obj.vert((xb, 2.5 + 0.1 * xb, zb)), obj.vert((xa, 2.5 + 0.1 * xa, zb))
+            faces += [((a, n), (b, n), (c, n)), ((a, n), (c, n), (d, n))]  # facing the floor
+    obj.groups.append(("panel", "panel", faces))
+    mtls.append(("panel", (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.0))
+    lights.append(("panel", (2.0, 2.0, 2.0)))
+    if kind != "few":
+        obj.sphere("bulb", "bulb", (-1.2, 0.6, 0.5), 0.3, 16, 8)
+        mtls.append(("bulb", (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.0))
+        lights.append(("bulb", (20.0, 18.0, 15.0)))
+    if kind == "hard":
+        obj.groups.append(("blinds", "blinds", _blinds(obj, PREP_BLINDS, PREP_STRIPS)))
+        mtls.append(("blinds", (0.0, 0.0, 0.0), (0.0, 0.0, 0.0), 1.0))
+        lights.append(("blinds", (4.0, 4.0, 4.0)))
+        _tiny_lights(obj, mtls, lights, (1e-2, 1e-4), ((20.0, 0.3), (45.0, 1.9)))
+
+    def place(p):
+        return tuple(scale * (x + o) for x, o in zip(p, offset))
+
+    obj.v = [place(p) for p in obj.v]
+    return _write(outdir, "prep_" + kind, obj, mtls, lights, (place(CAM[0]), place(CAM[1])))
